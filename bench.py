@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — the hot path of PartitionedLS on MI355X, one BASELINE.json config per run (default C3, the headline).
 
-    python bench.py --gpus 1 --steps K --warmup W [--config C2|C3|C4|C5|L340]
+    python bench.py --gpus 1 --steps K --warmup W [--config C2|C3|C4|C5|L340] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one pass of the hot path over the synthetic problem, inputs resident in HBM when the timed region starts.
@@ -19,6 +19,10 @@ One "step" = one pass of the hot path over the synthetic problem, inputs residen
         value = fits/s over all ranks; the roofline object is the Gram kernel's fp64-MFMA fraction.
 Rank 0 prints ONE JSON line (DESIGN.md §6 defines `roofline` (the binding fp64 bound), `roofline_hbm` (measured bytes),
 `nominal_hbm` (SURVEY §8(d)'s byte model) and `cpu_baseline`).
+A plain run sets up, warms up, times the steps and prints that line; every figure in it comes from the timed steps.  --full adds the
+legs that take runs of their own: `host_inclusive` (C3 / C4), `bnb_hard` (C5) and `cpu_baseline` (Opt configs, with its comparison of
+sampled objectives against the oracle).  --dump-outputs DIR writes the model of the last timed step (what fit() would hand back) as
+float64 .npy files; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -61,6 +65,10 @@ def main():
     ap.add_argument("--cpu-patterns", type=int, default=32, help="patterns in the dense CPU baseline sample")
     ap.add_argument("--cpu-workers", type=int, default=0, help="worker processes of the CPU baselines (0 = min(16, cores))")
     ap.add_argument("--bnb-cap", type=int, default=200000, help="node cap of the C5 bnb_hard leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs outside the headline: host_inclusive, bnb_hard, cpu_baseline (each one still off with its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the model computed by the last timed step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     import numpy as np
@@ -117,7 +125,8 @@ def main():
         _, bpat = pls.dist.reduce_winner(ctx, bobj, bpat, device=red_dev, order_key=okey)
         a, b, t, opt, bi = ctx.opt_finish(bpat)
         return dict(npat=npat, local=g1 - g0, opt=opt, best_index=bi, unconv=unconv, t_gram=t_gram, t_prep=t_prep,
-                    t_sweep=t_sweep, t_calib=t_calib, t_finish=ctx.timing(L.T_FINISH), pivots=pivots, vetoes=vetoes)
+                    t_sweep=t_sweep, t_calib=t_calib, t_finish=ctx.timing(L.T_FINISH), pivots=pivots, vetoes=vetoes,
+                    model=dict(alpha=a, beta=b, t=t, opt=opt, best_index=bi))
 
     def bnb_pass(cap=None):
         ctx.opt_prepare_device(dX.data_ptr(), dy.data_ptr(), N, D, N, P, 0.0, L.OPT_FAITHFUL_INTERCEPT)
@@ -127,14 +136,15 @@ def main():
         else:                   # frontier batches dealt over the ranks, every node to the rank that holds its parent's tableau snapshot
             mu, pat, free, bounded = pls.dist.bnb_search_warm(ctx, K + 1, rank=rank, world=world, device=red_dev, max_nodes=cap)
         a, b, t, opt = ctx.bnb_leaf(pat, free)
-        return dict(opt=opt, nopen=bounded, seconds=time.perf_counter() - t0)
+        return dict(opt=opt, nopen=bounded, seconds=time.perf_counter() - t0, model=dict(alpha=a, beta=b, t=t, opt=opt))
 
     def alt_pass():
         ctx.opt_prepare_device(dX.data_ptr(), dy.data_ptr(), N, D, N, P, 0.0, L.OPT_FAITHFUL_INTERCEPT)
         t_gram, t_prep = ctx.timing(L.T_GRAM), ctx.timing(L.T_PREP)
         t0 = time.perf_counter()
         a, b, t, opt, iters = ctx.alt_prepared(alt_a0, alt_b0, eps=1e-6, T=200)
-        return dict(opt=opt, iters=iters, t_gram=t_gram, t_prep=t_prep, alt_ms=(time.perf_counter() - t0) * 1e3)
+        return dict(opt=opt, iters=iters, t_gram=t_gram, t_prep=t_prep, alt_ms=(time.perf_counter() - t0) * 1e3,
+                    model=dict(alpha=a, beta=b, t=t, opt=opt, iterations=iters))
 
     def step():
         if kind == "alt":
@@ -163,6 +173,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt[0])
     res = hist[-1]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, np)
     avg = lambda key: sum(h[key] for h in hist) / len(hist)
     Mp = D + 1
     out = {"metric": METRIC, "unit": "solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -268,7 +280,7 @@ def main():
         out["alt"] = {"iterations": res["iters"], "ms_per_iteration": avg("alt_ms") / max(1, res["iters"]), "opt": res["opt"],
                       "noise_floor": 0.1 * N ** 0.5}
 
-    if rank == 0 and world == 1 and args.config in ("C3", "C4") and not args.no_host_inclusive:
+    if args.full and rank == 0 and world == 1 and args.config in ("C3", "C4") and not args.no_host_inclusive:
         # What a caller with X in HOST memory sees (the reference's callers hold Julia arrays, Opt.jl:73 / Alt.jl:50): the same fit through
         # the host-pointer entry, X uploaded inside the call.  Never `value`.  Two cases: a FRESH array (pages the runtime has never
         # pinned: a new allocation per fit) and the same array again.
@@ -299,7 +311,7 @@ def main():
             "device_resident_ms": out["ms_per_step"], "opt": best[2],
             "note": "the same fit through the host-pointer entry (X uploaded inside the call, staged through page-locked buffers by 4 copier "
                     "threads): what a Julia caller sees; the link's ceiling on this box is 57 GB/s (tools/ubench/h2d_paths.hip).  Not `value`."}
-    if rank == 0 and kind == "bnb":
+    if args.full and rank == 0 and kind == "bnb":
         # BnB where it has to branch: target = intercept + noise (no feature carries signal), same X, same shape
         ctx.synth_device(seed, N, D, np.zeros(D), dX.data_ptr(), dy.data_ptr())
         torch.cuda.synchronize()
@@ -332,7 +344,7 @@ def main():
         t1 = time.perf_counter()                             # the host-driven form of the warm search (what N > 1 ranks run): native frontier,
         mu3, _, _, bounded3 = pls.dist.bnb_search_warm(ctx, K + 1, max_nodes=args.bnb_cap)     # snapshot slots through the C ABI, one rank
         out["bnb_hard"]["host_driven_warm_nodes_per_s"] = bounded3 / (time.perf_counter() - t1)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and kind != "alt":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and kind != "alt":
         # the sample of the CPU baseline: the GPU's winner + random patterns (reference indexing, K + 1 bits).  The device's answer for
         # every one of them — from the SWEEP's own per-pattern output (all_opt of a faithful enumeration: what ranks the patterns) and
         # from a single re-solve with the objective recomputed from the data (partls_opt_pattern) — is compared with the dense oracle:
@@ -354,6 +366,16 @@ def main():
     ctx.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, res, np):
+    """The model of the last timed step, every array as float64 (scalars as 0-d arrays): <name>.npy for fit(Opt) / fit(Alt),
+    bnb_<name>.npy for C5's fit(BnB).  A few KB at every config."""
+    os.makedirs(path, exist_ok=True)
+    models = [("", res["model"])] + ([("bnb_", res["bnb"]["model"])] if "bnb" in res else [])
+    for prefix, model in models:
+        for name, v in model.items():
+            np.save(os.path.join(path, prefix + name + ".npy"), np.asarray(v, dtype=np.float64))
 
 
 def ctx_leaf_opt(ctx, dX, dy, N, D, P, pat, free, L):

@@ -19,6 +19,7 @@ def _header_symbols():
 def test_header_symbols_are_exported(partls):
     syms = _header_symbols()
     assert len(syms) >= 15
+    partls.lowlevel.lib()     # the package's loader goes first: it puts torch's HIP runtime in place before the library binds one
     lib = C.CDLL(partls.library_path())
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/partls.h but not exported"
