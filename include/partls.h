@@ -70,25 +70,26 @@ partls_status partls_fit_opt(partls_ctx *ctx, const double *X, int64_t N, int64_
 /* ---- fit(Opt) on several GPUs of one node, inside the library  — the loop Opt.jl:85-94 has no loop-carried state ---------
  * One process, one host thread and one context per device.  Device r uploads rows [r N / R, (r+1) N / R) of X and y (1 / R of the PCIe
  * traffic each) and builds the Gram products of its block; their sum — ncclAllReduce(ncclSum) on (M+2)^2 doubles over xGMI — is the
- * problem every device then prepares.  Device r sweeps the Gray-index range [r * 2^K' / R, (r+1) * 2^K' / R) of the pattern space,
- * and the global lexicographic minimum
- * (objective, reference pattern index) — argmin's first-index rule, Opt.jl:96 — is taken with two RCCL all-reduces over xGMI:
- * ncclMin on the objective, then ncclMin on the index masked to the minimisers (RCCL has no MINLOC).  The key of the
- * visiting order rides in the first all-reduce; ranks that disagree on it fail with PARTLS_ERR_STATE instead of combining
- * shards that do not partition the pattern space.  The winner is re-solved on the first device; the passes over the data it needs
- * (refinement, objective, KKT check) run on every device's row block and are summed in rank order.
+ * problem every device then prepares.  Device r sweeps the Gray-index range [r * 2^K' / R, (r+1) * 2^K' / R) of the pattern space
+ * and leaves its winner and near ties in host memory; the first device merges them into the global lexicographic minimum
+ * (objective, reference pattern index) — argmin's first-index rule, Opt.jl:96 — and the near ties a single context would re-rank.
+ * Ranks that disagree on the key of the visiting order fail with PARTLS_ERR_STATE instead of combining shards that do not partition
+ * the pattern space.  The winner is re-solved on the first device; the passes over the data it needs (refinement, objective, KKT
+ * check) run on every device's row block and are summed in rank order.
  *   devices[ndev]: HIP device indices (devices == NULL: devices 0 .. ndev-1; ndev == 0: every visible device).
  *   A list that names one device more than once (rehearsal of the R-rank control flow on a one-GPU box) cannot form an RCCL
- *   communicator: its reduction runs through the host instead; everything else is the same code.
+ *   communicator: its Gram sum runs through the host instead; everything else is the same code.
  *   librccl.so.1 is loaded when the first communicator is needed (PARTLS_RCCL_LIB overrides the name), never for partls_fit_opt.
- * partls_fit_opt_multi: arguments and outputs exactly as partls_fit_opt (all_opt: the shards' entries merged).
+ * partls_fit_opt_multi: arguments and outputs exactly as partls_fit_opt (all_opt: the shards' entries merged, with
+ * PARTLS_ERR_ILL_CONDITIONED too).
  * partls_multi_context: the context of rank r (rank 0 holds the winner's problem after a fit: partls_opt_finish /
  * partls_opt_pattern on it rebuild the models of returnAllSolutions, Opt.jl:99-101).  A partls_multi is not thread-safe. */
 typedef struct partls_multi partls_multi;
 partls_status partls_multi_create(const int *devices, int ndev, partls_multi **out);
 void          partls_multi_destroy(partls_multi *mc);
 int           partls_multi_size(const partls_multi *mc);                 /* number of ranks (0 for NULL)                  */
-int           partls_multi_uses_rccl(const partls_multi *mc);            /* 1: reductions over RCCL, 0: host (see above)   */
+int           partls_multi_uses_rccl(const partls_multi *mc);            /* 1: Gram products of row-sharded fits summed over
+                                                                            RCCL, 0: through the host (see above)          */
 partls_ctx   *partls_multi_context(partls_multi *mc, int rank);          /* NULL when out of range                         */
 partls_status partls_fit_opt_multi(partls_multi *mc, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
                                    const int64_t *P, int64_t K, int64_t ldP, double eta, uint32_t flags,
@@ -97,17 +98,17 @@ partls_status partls_fit_opt_multi(partls_multi *mc, const double *X, int64_t N,
  * Same handle, same row-sharded upload and Gram sum as partls_fit_opt_multi.  Every rank thread runs the same best-first frontier
  * (partls_frontier_*): per round the batch * R most promising nodes are dealt — a node goes to the rank that holds its parent's tableau
  * snapshot (warm start), the surplus and the cold nodes to the least loaded ranks —, every rank bounds its share on its own GPU, and ONE
- * all-gather of (bound, branch, snapshot slot) per round — ncclAllGather over xGMI; host memory for a device list with duplicates —
- * carries the incumbent, so that all ranks prune, branch and count snapshot references identically.  The incumbent's model is built on
- * the first device (partls_bnb_leaf, data passes over every rank's row block).  Outputs as partls_fit_bnb; *nopen = nodes bounded by
+ * exchange of (bound, branch, snapshot slot) per round through host memory carries the incumbent, so that all ranks prune, branch
+ * and count snapshot references identically.  The incumbent's model is built on the first device (partls_bnb_leaf, data passes over
+ * every rank's row block).  Outputs as partls_fit_bnb; *nopen = nodes bounded by
  * all ranks (not a parity quantity: the search order differs from the reference's depth-first recursion). */
 partls_status partls_fit_bnb_multi(partls_multi *mc, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
                                    const int64_t *P, int64_t K, int64_t ldP, double eta,
                                    double *alpha, double *beta, double *t, double *opt, int64_t *nopen);
 /* Robustness of the rank threads (both fits): every phase ends in a rendezvous at which the ranks agree to go on or to leave together; a
  * rank that cannot keep the protocol, or does not reach a rendezvous within PARTLS_MULTI_TIMEOUT_S seconds (default 3600), fails the
- * fit with PARTLS_ERR_STATE instead of hanging it; a failed RCCL enqueue aborts the communicators (ncclCommAbort) and the handle
- * reduces through host memory from then on (partls_multi_uses_rccl turns 0). */
+ * fit with PARTLS_ERR_STATE instead of hanging it; a failed enqueue of the Gram sum aborts the communicators (ncclCommAbort) and the
+ * handle sums through host memory from then on (partls_multi_uses_rccl turns 0). */
 /* per-rank HIP-event time (ms) of stage `which` in the last partls_fit_opt_multi */
 partls_status partls_multi_get_timing(const partls_multi *mc, int rank, int which, double *ms);
 

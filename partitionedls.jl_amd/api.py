@@ -347,10 +347,10 @@ class Frontier:
 
 
 class MultiContext:
-    """Owner of a partls_multi: fit(Opt) sharded over several GPUs of one node inside the library (one host thread and one
-    context per device, RCCL min-reduce; include/partls.h: partls_fit_opt_multi).  devices: None = every visible device, an int
-    n = devices 0..n-1, or a list of device indices (a list naming a device twice rehearses the R-rank control flow on one GPU:
-    its reduction then runs through the host)."""
+    """Owner of a partls_multi: fit(Opt) and fit(BnB) sharded over several GPUs of one node inside the library (one host thread and
+    one context per device; include/partls.h: partls_fit_opt_multi, partls_fit_bnb_multi).  devices: None = every visible device, an
+    int n = devices 0..n-1, or a list of device indices (a list naming a device twice rehearses the R-rank control flow on one GPU:
+    the Gram sum of its row blocks then runs through the host instead of RCCL)."""
 
     def __init__(self, devices=None):
         self._h = C.c_void_p()
@@ -562,7 +562,7 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
     explicit starting point alpha0[M+1], beta0[K+1];  Opt: returnAllSolutions.
     faithful_intercept=True enumerates the reference's 2^(K+1) patterns instead of 2^K with a free intercept
     (same optimum).  Opt / BnB, devices=... (None | count | list of device indices): the enumeration / the frontier search is sharded
-    over those GPUs inside the library (partls_fit_opt_multi: RCCL min-reduce; partls_fit_bnb_multi: one all-gather per round), as the
+    over those GPUs inside the library (partls_fit_opt_multi, partls_fit_bnb_multi: the ranks' results meet in host memory), as the
     Julia drop-in does on a multi-GPU node.  nnlsalg is accepted for signature parity; the device solver is an exact active-set method.
     on_ill_conditioned: what to do when the returned model fails the data-space KKT check (status 9: X beyond the fp64 Gram form;
     the reference's QR-based NNLS still returns a model there, and the Julia patch reroutes to it): "warn" (default) returns the best

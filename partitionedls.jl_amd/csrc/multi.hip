@@ -4,24 +4,24 @@
 // Opt: the loop of the reference, Opt.jl:85-94, has no loop-carried state: the 2^K' sign patterns are sharded over the devices by
 // Gray-index range, exactly as partitionedls.jl_amd/dist.py does across processes — here inside one process, one host thread
 // and one partls_ctx per device, so that a Julia `fit(Opt, X, y, P)` uses the whole node without any glue on its side.
-// The winner is the lexicographic minimum (objective, reference pattern index) — argmin's first-index rule, Opt.jl:96 — taken
-// with two RCCL all-reduces (ncclMin on the objective, ncclMin on the index masked to the minimisers): 24 + 8 bytes over xGMI,
-// latency-bound; the shards' near ties (<= 4 candidates of 16 bytes per rank) are handed to rank 0 so that the finish re-ranks the
-// set a single context would.
+// Every rank publishes its winner and near ties (<= 4 candidates of 16 bytes) in host memory; after the agreement rendezvous rank 0
+// merges them (partls_opt_merge_candidates): the lexicographic minimum (objective, reference pattern index) — argmin's first-index
+// rule, Opt.jl:96 — and the near ties a single context would re-rank in its finish.
 // BnB: the subtrees below two open nodes are independent given the incumbent (BnB.jl:94-132); every rank thread runs the same
 // native frontier (frontier.h), bounds its share of every round on its own GPU (warm-started from the parent's tableau snapshot,
-// which lives on the rank that bounded the parent), and ONE all-gather of (bound, branch, slot) per round — ncclAllGather over
-// xGMI — carries the incumbent.
-// RCCL is loaded on first use (573 MB on disk: a single-GPU fit never pays for it).
+// which lives on the rank that bounded the parent), and ONE exchange of (bound, branch, slot) per round through host memory
+// carries the incumbent.
+// The one exchange of device data is the sum of the row blocks' Gram products (gram_rendezvous): ncclAllReduce over xGMI when the
+// devices are distinct, host memory otherwise.  RCCL is loaded on first use (573 MB on disk: a single-GPU fit never pays for it).
 //
 // PROTOCOL.  A fit is a fixed sequence of phases; every phase ends in a rendezvous (HostBarrier) at which the ranks publish their
 // status, and after which ALL of them either go on or leave — a rank that failed joins the rendezvous it owes from its error path,
-// so nobody is ever left waiting, and no collective is entered unless every rank has just agreed to enter it.  Between such an
-// agreement and the enqueue of the collective there is no fallible host allocation (buffers are sized before the threads start).
+// so nobody is ever left waiting, and the Gram collective is entered only when every rank has just agreed to enter it.  Between such
+// an agreement and the enqueue of the collective there is no fallible host allocation (buffers are sized before the threads start).
 // A rank that cannot keep the protocol (an exception on its thread, a rendezvous that times out: PARTLS_MULTI_TIMEOUT_S, default
 // 3600 s) POISONS the barrier: every other rank's next rendezvous fails at once and the fit returns PARTLS_ERR_STATE instead of
 // hanging.  A failed RCCL enqueue aborts every communicator of the handle (ncclCommAbort releases the ranks already inside the
-// collective); the handle then reduces through host memory for the rest of its life.
+// collective); the handle then sums the Gram products through host memory for the rest of its life.
 #include "ctx.h"
 #include "frontier.h"
 #include <new>
@@ -49,7 +49,6 @@ struct Rccl {
     ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
     ncclResult_t (*CommAbort)(ncclComm_t) = nullptr;
     ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
     const char *(*GetErrorString)(ncclResult_t) = nullptr;
     std::string error;
 };
@@ -71,9 +70,8 @@ Rccl &rccl()
         r.CommDestroy = reinterpret_cast<decltype(r.CommDestroy)>(dlsym(r.handle, "ncclCommDestroy"));
         r.CommAbort = reinterpret_cast<decltype(r.CommAbort)>(dlsym(r.handle, "ncclCommAbort"));
         r.AllReduce = reinterpret_cast<decltype(r.AllReduce)>(dlsym(r.handle, "ncclAllReduce"));
-        r.AllGather = reinterpret_cast<decltype(r.AllGather)>(dlsym(r.handle, "ncclAllGather"));
         r.GetErrorString = reinterpret_cast<decltype(r.GetErrorString)>(dlsym(r.handle, "ncclGetErrorString"));
-        if (!r.CommInitAll || !r.CommDestroy || !r.AllReduce || !r.AllGather || !r.GetErrorString) r.error = "librccl.so.1 lacks ncclCommInitAll / ncclAllReduce / ncclAllGather";
+        if (!r.CommInitAll || !r.CommDestroy || !r.AllReduce || !r.GetErrorString) r.error = "librccl.so.1 lacks ncclCommInitAll / ncclAllReduce";
     });
     return r;
 }
@@ -104,9 +102,7 @@ struct HostBarrier {
     void reset() { std::lock_guard<std::mutex> lk(m); waiting = 0; broken = false; }
 };
 
-constexpr int64_t NO_CANDIDATE = (int64_t)1 << 62;
-
-// CRC-32 of the group -> Gray-bit assignment: exact in a double (it rides in the objective all-reduce)
+// CRC-32 of the group -> Gray-bit assignment: rank 0 checks that every rank's is the same before it combines the shards
 double order_key(const int64_t *gbit, int kb)
 {
     uint32_t crc = 0xFFFFFFFFu;
@@ -129,18 +125,15 @@ struct partls_multi {
     bool use_rccl = false;
     std::mutex comm_mutex;                   // abort_rccl
     std::vector<ncclComm_t> comms;
-    std::vector<DevBuf> red;                 // per rank: [objective, key, -key | index] on its device
     HostBarrier bar;
     // per-call exchange between the rank threads
     std::vector<partls_status> st;
     std::vector<std::string> msg;
     std::vector<char> secondary;             // the rank's status only says "another rank failed": report that rank's instead
-    std::vector<double> obj, key;
-    std::vector<int64_t> pat, unconv;
+    std::vector<double> key;
+    std::vector<int64_t> unconv;
     std::vector<Cand> cand;                  // every rank's winner + near ties of its shard (partls_opt_candidates)
     std::vector<std::vector<double>> all_opt;
-    double win_obj = 0.0;
-    int64_t win_pat = -1;
     std::vector<std::vector<double>> t_ms;
     // row-sharded fits: did rank r get as far as the Gram rendezvous (a rank that failed earlier joins it from its error path), the
     // status of its part of the exchange, and the host images of the partial Gram products of the host-reduced mode (sized before the
@@ -149,18 +142,15 @@ struct partls_multi {
     std::vector<std::vector<double>> gram_img, gram_sum;
     bool shard_rows = false;
     bool replicate = false;                  // PARTLS_MULTI_REPLICATE (read at create): every rank uploads all of X (A/B tests)
-    // BnB: the per-round exchange of (bound, branch, slot).  Host mode: xbuf[parity][rank * stride ...] (written before the round's
-    // rendezvous, read after it; two parities so that a fast rank's next round cannot overwrite what a slow one still reads).
-    // RCCL mode: per-rank device buffers [send | recv] and pinned host images of both.
+    // BnB: the per-round exchange of (bound, branch, slot): xbuf[parity][rank * stride ...] (written before the round's rendezvous, read
+    // after it; two parities so that a fast rank's next round cannot overwrite what a slow one still reads)
     std::vector<double> xbuf[2];
     size_t xstride = 0;
-    std::vector<DevBuf> xdev;
-    std::vector<PinnedDoubles> xpin;
     int64_t bnb_nodes = 0;
     // fault injection (tests): PARTLS_MULTI_FAULT="rank:stage[:vanish]", read at create.  Stage 1: before the upload, 2: inside the Gram
-    // exchange, 3: after the sweep / before the search, 4: in the reduction / the second search round, 5: rank 0's finish.  Default: the
-    // rank FAILS there (error status, protocol kept); "vanish" (stages 1, 3, 4): it leaves its thread without a word — the bounded
-    // rendezvous must catch it.
+    // exchange, 3: after the sweep / before the search, 4: after the sweeps' agreement / the second search round, 5: rank 0's finish.
+    // Default: the rank FAILS there (error status, protocol kept); "vanish" (stages 1, 3, 4): it leaves its thread without a word — the
+    // bounded rendezvous must catch it.
     int fault_rank = -1, fault_stage = 0;
     bool fault_vanish = false;
 };
@@ -307,58 +297,6 @@ partls_status prepare_rank(partls_multi *mc, int r, const FitArgs &a, uint32_t f
     return st;
 }
 
-// lexicographic minimum over the ranks through RCCL: every rank ends with the same (objective, pattern).  Both collectives are
-// enqueued whatever happens in between (the other ranks enqueue theirs); errors are reported afterwards.
-partls_status reduce_rccl(partls_multi *mc, int r, double obj, int64_t pat, double key, double *gobj, int64_t *gpat, bool *enqueue_failed)
-{
-    Rccl &R = rccl();
-    partls_ctx *c = mc->ctx[(size_t)r];
-    double *d = mc->red[(size_t)r].as<double>();
-    const double h[3] = {pat >= 0 ? obj : INFINITY, key, -key};
-    double g[3] = {INFINITY, 0.0, 0.0};
-    partls_status st = PARTLS_OK;
-    auto hipok = [&](hipError_t e, const char *what) { if (e != hipSuccess && st == PARTLS_OK) { set_error("%s failed on rank %d: %s", what, r, hipGetErrorString(e)); st = PARTLS_ERR_HIP; } };
-    hipok(hipMemcpyAsync(d, h, sizeof(h), hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync");
-    ncclResult_t e = R.AllReduce(d, d, 3, ncclDouble, ncclMin, mc->comms[(size_t)r], c->stream);
-    if (e != ncclSuccess) { if (st == PARTLS_OK) { set_error("ncclAllReduce(min objective) failed on rank %d: %s", r, R.GetErrorString(e)); st = PARTLS_ERR_HIP; } *enqueue_failed = true; return st; }
-    hipok(hipMemcpyAsync(g, d, sizeof(g), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
-    hipok(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
-    int64_t idx = (st == PARTLS_OK && pat >= 0 && obj == g[0]) ? pat : NO_CANDIDATE, gidx = NO_CANDIDATE;
-    int64_t *di = reinterpret_cast<int64_t *>(d + 4);
-    hipok(hipMemcpyAsync(di, &idx, sizeof(idx), hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync");
-    e = R.AllReduce(di, di, 1, ncclInt64, ncclMin, mc->comms[(size_t)r], c->stream);
-    if (e != ncclSuccess) { if (st == PARTLS_OK) { set_error("ncclAllReduce(min index) failed on rank %d: %s", r, R.GetErrorString(e)); st = PARTLS_ERR_HIP; } *enqueue_failed = true; return st; }
-    hipok(hipMemcpyAsync(&gidx, di, sizeof(gidx), hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
-    hipok(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
-    if (st != PARTLS_OK) return st;
-    if (g[1] != -g[2]) {
-        set_error("partls_fit_opt_multi: the ranks visit the patterns in different orders (bit-order keys differ), their Gray-index "
-                  "ranges do not partition the pattern space");
-        return PARTLS_ERR_STATE;
-    }
-    *gobj = g[0];
-    *gpat = gidx == NO_CANDIDATE ? -1 : gidx;
-    return PARTLS_OK;
-}
-
-// the same reduction from the host slots every rank filled before the agreement rendezvous (device list with duplicates, or a handle
-// whose communicators were aborted): no further rendezvous needed — the slots are rewritten by the next fit only
-partls_status reduce_host(partls_multi *mc, double *gobj, int64_t *gpat)
-{
-    double bo = INFINITY;
-    int64_t bp = NO_CANDIDATE;
-    bool same = true;
-    for (int q = 0; q < mc->ndev; ++q) {
-        same = same && mc->key[(size_t)q] == mc->key[0];
-        if (mc->pat[(size_t)q] < 0) continue;
-        if (mc->obj[(size_t)q] < bo || (mc->obj[(size_t)q] == bo && mc->pat[(size_t)q] < bp)) { bo = mc->obj[(size_t)q]; bp = mc->pat[(size_t)q]; }
-    }
-    if (!same) { set_error("partls_fit_opt_multi: the ranks visit the patterns in different orders (bit-order keys differ)"); return PARTLS_ERR_STATE; }
-    *gobj = bo;
-    *gpat = bp == NO_CANDIDATE ? -1 : bp;
-    return PARTLS_OK;
-}
-
 void rank_opt(partls_multi *mc, int r, const FitArgs &a)
 {
     partls_ctx *c = mc->ctx[(size_t)r];
@@ -367,8 +305,8 @@ void rank_opt(partls_multi *mc, int r, const FitArgs &a)
     partls_status st = prepare_rank(mc, r, a, a.flags);
     if (mc->bar.is_broken()) return;
     // ---- phase 2: visiting order and the sweep of this rank's shard ---------------------------------------------------------------
-    double bobj = INFINITY, key = 0.0;
-    int64_t bpat = -1, unconv = 0;
+    double key = 0.0;
+    int64_t unconv = 0;
     if (st == PARTLS_OK) {
         const int flt = fault_at(mc, r, 3);
         if (flt == 2) throw Vanish();
@@ -382,64 +320,57 @@ void rank_opt(partls_multi *mc, int r, const FitArgs &a)
             key = order_key(gbit, c->kbits);
             const int64_t g0 = (int64_t)(((__int128)r * npat) / R), g1 = (int64_t)(((__int128)(r + 1) * npat) / R);
             double *ao = a.all_opt ? mc->all_opt[(size_t)r].data() : nullptr;      // this rank's image of all_opt (NaN outside its shard), merged by the caller
-            st = partls_opt_sweep(c, g0, g1, &bobj, &bpat, ao, &unconv);
+            st = partls_opt_sweep(c, g0, g1, nullptr, nullptr, ao, &unconv);
         }
     }
-    note(mc, r, st);
-    mc->unconv[(size_t)r] = unconv;
-    mc->obj[(size_t)r] = bpat >= 0 ? bobj : INFINITY;
-    mc->pat[(size_t)r] = bpat;
-    mc->key[(size_t)r] = key;
+    // this shard's winner (first) and near ties, read by rank 0 after the rendezvous
     Cand &cd = mc->cand[(size_t)r];
     cd.n = 0;
     if (st == PARTLS_OK) {
         int64_t n = 0;
-        if (partls_opt_candidates(c, 4, cd.obj, cd.pat, &n) == PARTLS_OK) cd.n = (int)n;
+        st = partls_opt_candidates(c, 4, cd.obj, cd.pat, &n);
+        cd.n = (int)n;
     }
+    note(mc, r, st);
+    mc->unconv[(size_t)r] = unconv;
+    mc->key[(size_t)r] = key;
     for (int w = 0; w < PARTLS_T_COUNT; ++w) mc->t_ms[(size_t)r][(size_t)w] = c->ms[w];
-    // agree on the outcome so far BEFORE any collective: a rank that failed must not leave the others waiting inside RCCL
+    // agree on the outcome of the sweeps: after this rendezvous only rank 0 works on
     if (!mc->bar.wait()) { lost(mc, r); return; }
     if (any_failed(mc)) return;
-    // ---- phase 3: the global lexicographic minimum ----------------------------------------------------------------------------------
-    double gobj = INFINITY;
-    int64_t gpat = -1;
-    const bool with_rccl = mc->use_rccl;
-    bool enqueue_failed = false;
     const int flt4 = fault_at(mc, r, 4);
     if (flt4 == 2) throw Vanish();
-    st = with_rccl ? reduce_rccl(mc, r, bobj, bpat, key, &gobj, &gpat, &enqueue_failed) : reduce_host(mc, &gobj, &gpat);
-    if (flt4 == 1 && st == PARTLS_OK) { set_error("injected fault (stage 4) on rank %d", r); st = PARTLS_ERR_HIP; }
-    if (enqueue_failed) abort_rccl(mc);                      // the ranks inside the collective are released; all of them fail below
-    note(mc, r, st);
-    if (with_rccl) {                                         // did the collectives work everywhere?
-        if (!mc->bar.wait()) { lost(mc, r); return; }
-        if (any_failed(mc)) return;
-    } else if (st != PARTLS_OK) return;                      // (host mode: every rank computed the same thing from the same slots)
+    if (flt4 == 1) { set_error("injected fault (stage 4) on rank %d", r); fail(mc, r, PARTLS_ERR_HIP); return; }
     if (r != 0) return;
-    // ---- phase 4: the winner, on the first device ------------------------------------------------------------------------------------
-    mc->win_obj = gobj;
-    mc->win_pat = gpat;
-    if (gpat < 0) { set_error("sweep produced no candidate"); fail(mc, 0, PARTLS_ERR_NOT_CONVERGED); return; }
-    // near ties of EVERY shard: rank 0 re-ranks the set a single context would have had (Opt.jl:90,96)
+    // ---- phase 3: the winner, on the first device ------------------------------------------------------------------------------------
+    for (int q = 1; q < R; ++q)
+        if (mc->key[(size_t)q] != mc->key[0]) {
+            set_error("partls_fit_opt_multi: the ranks visit the patterns in different orders (bit-order keys differ), their Gray-index "
+                      "ranges do not partition the pattern space");
+            fail(mc, 0, PARTLS_ERR_STATE);
+            return;
+        }
+    // near ties of EVERY shard: rank 0 re-ranks the set a single context would have had (Opt.jl:90,96).  Every list starts with its
+    // shard's winner, so the merged winner is the lexicographic minimum (objective, reference pattern index) over all shards.
     double co[4 * 64]; int64_t cp[4 * 64];
     int64_t nc = 0;
     for (int q = 0; q < R; ++q) for (int i = 0; i < mc->cand[(size_t)q].n; ++i) { co[nc] = mc->cand[(size_t)q].obj[i]; cp[nc] = mc->cand[(size_t)q].pat[i]; ++nc; }
-    double mo = INFINITY; int64_t mp = -1;
-    st = partls_opt_merge_candidates(c, nc, co, cp, &mo, &mp);
-    if (st == PARTLS_OK && mp != gpat) { set_error("internal: the merged candidate lists name pattern %lld, the reduction %lld", (long long)mp, (long long)gpat); st = PARTLS_ERR_STATE; }
+    int64_t win = -1;
+    st = partls_opt_merge_candidates(c, nc, co, cp, nullptr, &win);
     if (st != PARTLS_OK) { fail(mc, 0, st); return; }
+    if (win < 0) { set_error("sweep produced no candidate"); fail(mc, 0, PARTLS_ERR_NOT_CONVERGED); return; }
     // the winner is re-solved on the first device; its passes over the data (refinement, objective, KKT check) cover every rank's
     // row block: rank 0's thread drives the other devices' streams as well (every rank has finished its sweep: rendezvous above)
     if (mc->shard_rows) c->peers.assign(mc->ctx.begin() + 1, mc->ctx.end());
     if (fault_at(mc, 0, 5) == 1) { set_error("injected fault (stage 5) on rank 0"); fail(mc, 0, PARTLS_ERR_HIP); return; }
-    st = partls_opt_finish(c, gpat, a.alpha, a.beta, a.t, a.opt, a.best_index);
+    st = partls_opt_finish(c, win, a.alpha, a.beta, a.t, a.opt, a.best_index);
     mc->t_ms[0][PARTLS_T_FINISH] = c->ms[PARTLS_T_FINISH];
     if (st != PARTLS_OK) fail(mc, 0, st);
 }
 
 // fit(BnB) over the ranks: every rank thread runs the same frontier; per round it bounds its share on its own GPU (warm-started from
-// the parent's snapshot, which it holds), one all-gather of (bound, branch, slot) shares the results — and with them the incumbent —
-// and every rank prunes, branches and counts snapshot references identically (frontier.h).  BnB.jl:94-132.
+// the parent's snapshot, which it holds), one exchange of (bound, branch, slot) through host memory shares the results — and with
+// them the incumbent — and every rank prunes, branches and counts snapshot references identically (frontier.h).  BnB.jl:94-132.
 void rank_bnb(partls_multi *mc, int r, const FitArgs &a)
 {
     partls_ctx *c = mc->ctx[(size_t)r];
@@ -484,9 +415,10 @@ void rank_bnb(partls_multi *mc, int r, const FitArgs &a)
         if (flt == 1 && round == 1) { set_error("injected fault (stage 4) on rank %d", r); st = PARTLS_ERR_HIP; }
         if (st == PARTLS_OK && mine > 0) st = partls_bnb_bound_snap(c, mine, bp.data(), bf.data(), src.data(), dst.data(), lb.data(), br.data());
         note(mc, r, st);
-        // publish: status and results in this round's parity slots (host mode: that IS the exchange)
+        // publish: status and results in this round's parity slots — that IS the exchange.  The status is the rank's recorded one, so
+        // that a failure noted after the previous exchange (the snapshot release below) stops every rank here too.
         double *slot = mc->xbuf[round & 1].data() + (size_t)r * stride;
-        slot[0] = st == PARTLS_OK ? 0.0 : 1.0; slot[1] = (double)total; slot[2] = (double)mine;
+        slot[0] = mc->st[(size_t)r] == PARTLS_OK ? 0.0 : 1.0; slot[1] = (double)total; slot[2] = (double)mine;
         for (int64_t i = 0; i < mine; ++i) { slot[4 + i] = lb[(size_t)i]; slot[4 + batch + i] = (double)br[(size_t)i]; slot[4 + 2 * batch + i] = (double)dst[(size_t)i]; }
         f.prefetch();                                           // the next round's pops, while the slower ranks finish this one
         if (!mc->bar.wait()) { lost(mc, r); return; }
@@ -496,43 +428,14 @@ void rank_bnb(partls_multi *mc, int r, const FitArgs &a)
             ok = ok && sq[0] == 0.0;
             same = same && sq[1] == (double)total && sq[2] == (double)per_rank[(size_t)q];
         }
-        if (!ok) { if (st == PARTLS_OK) { set_error("partls_fit_bnb_multi: another rank failed in round %u of the search", round); fail(mc, r, PARTLS_ERR_STATE, true); } return; }
+        if (!ok) { if (mc->st[(size_t)r] == PARTLS_OK) { set_error("partls_fit_bnb_multi: another rank failed in round %u of the search", round); fail(mc, r, PARTLS_ERR_STATE, true); } return; }
         if (!same) { set_error("partls_fit_bnb_multi: the ranks' frontiers disagree in round %u (internal error)", round); fail(mc, r, PARTLS_ERR_STATE); return; }
         if (total == 0) break;                                  // the same decision on every rank
         const double *xsrc = mc->xbuf[round & 1].data();
-        if (mc->use_rccl) {
-            // the exchange proper: ncclAllGather over xGMI of [lb | branch | slot] (3 x per doubles per rank, per = the largest share)
-            Rccl &Rc = rccl();
-            int64_t per = 0;
-            for (int q = 0; q < R; ++q) per = std::max<int64_t>(per, per_rank[(size_t)q]);
-            const size_t cnt = (size_t)3 * per;
-            double *hs = mc->xpin[(size_t)r].data(), *hr = hs + (size_t)3 * batch;
-            for (int64_t i = 0; i < mine; ++i) { hs[i] = lb[(size_t)i]; hs[per + i] = (double)br[(size_t)i]; hs[2 * per + i] = (double)dst[(size_t)i]; }
-            double *ds = mc->xdev[(size_t)r].as<double>(), *dr = ds + (size_t)3 * batch;
-            partls_status xs = PARTLS_OK;
-            bool enqueue_failed = false;
-            if (hipMemcpyAsync(ds, hs, cnt * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) xs = PARTLS_ERR_HIP;
-            const ncclResult_t e = Rc.AllGather(ds, dr, cnt, ncclDouble, mc->comms[(size_t)r], c->stream);
-            if (e != ncclSuccess) { set_error("ncclAllGather(bounds of round %u) failed on rank %d: %s", round, r, Rc.GetErrorString(e)); xs = PARTLS_ERR_HIP; enqueue_failed = true; }
-            else if (hipMemcpyAsync(hr, dr, cnt * R * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-                if (xs == PARTLS_OK) set_error("rank %d: copy of the gathered bounds failed", r);
-                xs = PARTLS_ERR_HIP;
-            }
-            if (enqueue_failed) abort_rccl(mc);
-            note(mc, r, xs);
-            if (!mc->bar.wait()) { lost(mc, r); return; }
-            if (any_failed(mc)) return;
-            int64_t j = 0;
-            for (int q = 0; q < R; ++q) {
-                const double *g = hr + (size_t)q * cnt;
-                for (int64_t i = 0; i < per_rank[(size_t)q]; ++i, ++j) { glb[(size_t)j] = g[i]; gbr[(size_t)j] = (int32_t)g[per + i]; gdst[(size_t)j] = (int32_t)g[2 * per + i]; }
-            }
-        } else {
-            int64_t j = 0;
-            for (int q = 0; q < R; ++q) {
-                const double *g = xsrc + (size_t)q * stride + 4;
-                for (int64_t i = 0; i < per_rank[(size_t)q]; ++i, ++j) { glb[(size_t)j] = g[i]; gbr[(size_t)j] = (int32_t)g[batch + i]; gdst[(size_t)j] = (int32_t)g[2 * batch + i]; }
-            }
+        int64_t j = 0;
+        for (int q = 0; q < R; ++q) {
+            const double *g = xsrc + (size_t)q * stride + 4;
+            for (int64_t i = 0; i < per_rank[(size_t)q]; ++i, ++j) { glb[(size_t)j] = g[i]; gbr[(size_t)j] = (int32_t)g[batch + i]; gdst[(size_t)j] = (int32_t)g[2 * batch + i]; }
         }
         f.ingest(glb.data(), gbr.data(), gdst.data());
         if (!f.dead.empty()) {
@@ -588,12 +491,6 @@ partls_status run_fit(partls_multi *mc, const FitArgs &a)
         const size_t batch = (size_t)std::max(1, mc->ctx[0]->knobs.bnb_batch);
         mc->xstride = 4 + 3 * batch;
         for (int p = 0; p < 2; ++p) mc->xbuf[p].assign(mc->xstride * (size_t)R, 0.0);
-        if (mc->use_rccl)
-            for (int r = 0; r < R; ++r) {
-                PARTLS_HIP_CHECK(hipSetDevice(mc->devices[(size_t)r]));
-                PARTLS_HIP_CHECK(mc->xdev[(size_t)r].ensure((size_t)3 * batch * (R + 1) * sizeof(double)));
-                PARTLS_HIP_CHECK(mc->xpin[(size_t)r].resize((size_t)3 * batch * (R + 1)));
-            }
     }
     std::vector<std::thread> th;
     th.reserve((size_t)R);
@@ -643,8 +540,7 @@ try {
     mc->st.assign((size_t)ndev, PARTLS_OK); mc->msg.assign((size_t)ndev, std::string());
     for (std::string &m : mc->msg) m.reserve(600);               // set_error's buffer is 512 bytes: fail() never allocates
     mc->secondary.assign((size_t)ndev, 0);
-    mc->obj.assign((size_t)ndev, 0.0); mc->key.assign((size_t)ndev, 0.0);
-    mc->pat.assign((size_t)ndev, -1); mc->unconv.assign((size_t)ndev, 0);
+    mc->key.assign((size_t)ndev, 0.0); mc->unconv.assign((size_t)ndev, 0);
     mc->cand.assign((size_t)ndev, Cand());
     mc->all_opt.resize((size_t)ndev);
     mc->replicate = getenv("PARTLS_MULTI_REPLICATE") != nullptr;
@@ -658,19 +554,11 @@ try {
     mc->gram_img.resize((size_t)ndev); mc->gram_sum.resize((size_t)ndev);
     mc->t_ms.assign((size_t)ndev, std::vector<double>((size_t)PARTLS_T_COUNT, 0.0));
     mc->bar.n = ndev;
-    mc->red.resize((size_t)ndev);
-    mc->xdev.resize((size_t)ndev);
-    mc->xpin.resize((size_t)ndev);
     for (int r = 0; r < ndev; ++r) {
         partls_ctx *c = nullptr;
         partls_status st = partls_create(mc->devices[(size_t)r], &c);
         if (st != PARTLS_OK) { partls_multi_destroy(mc); return st; }
         mc->ctx.push_back(c);
-        if (hipSetDevice(mc->devices[(size_t)r]) != hipSuccess || mc->red[(size_t)r].ensure(8 * sizeof(double)) != hipSuccess) {
-            set_error("partls_multi_create: device buffer allocation failed on device %d", mc->devices[(size_t)r]);
-            partls_multi_destroy(mc);
-            return PARTLS_ERR_HIP;
-        }
     }
     if (distinct) {
         Rccl &R = rccl();
@@ -700,8 +588,6 @@ void partls_multi_destroy(partls_multi *mc)
         for (size_t r = 0; r < mc->ctx.size(); ++r)
             if (mc->ctx[r] && mc->ctx[r]->stream && hipSetDevice(mc->devices[r]) == hipSuccess) (void)hipStreamSynchronize(mc->ctx[r]->stream);
         for (ncclComm_t cm : mc->comms) if (cm) (void)rccl().CommDestroy(cm);
-        for (size_t r = 0; r < mc->red.size(); ++r)
-            if (hipSetDevice(mc->devices[r]) == hipSuccess) { mc->red[r].release(); if (r < mc->xdev.size()) mc->xdev[r].release(); if (r < mc->xpin.size()) mc->xpin[r].release(); }
     }
     for (partls_ctx *c : mc->ctx) partls_destroy(c);
     delete mc;
@@ -730,20 +616,18 @@ try {
     if (all_opt) flags |= PARTLS_OPT_FAITHFUL_INTERCEPT;
     const FitArgs a{0, X, N, M, ldX, y, P, K, ldP, eta, flags, alpha, beta, t, opt, best_index, all_opt, nullptr};
     const int R = mc->ndev;
-    partls_status st = run_fit(mc, a);
-    if (st != PARTLS_OK) {
-        for (auto &v : mc->all_opt) std::vector<double>().swap(v);
-        return st;
-    }
-    if (all_opt) {                                           // every pattern belongs to exactly one shard: the others hold NaN there
+    const partls_status st = run_fit(mc, a);
+    // status 9 leaves the model in the outputs: all_opt is filled as well, as partls_fit_opt's sweep fills it before the finish
+    if (all_opt && (st == PARTLS_OK || st == PARTLS_ERR_ILL_CONDITIONED)) {   // every pattern belongs to exactly one shard: the others hold NaN there
         const size_t np = (size_t)1 << (K + 1);
         std::memcpy(all_opt, mc->all_opt[0].data(), np * sizeof(double));
         for (int r = 1; r < R; ++r) {
             const double *src = mc->all_opt[(size_t)r].data();
             for (size_t i = 0; i < np; ++i) if (src[i] == src[i]) all_opt[i] = src[i];
         }
-        for (auto &v : mc->all_opt) std::vector<double>().swap(v);
     }
+    for (auto &v : mc->all_opt) std::vector<double>().swap(v);
+    if (st != PARTLS_OK) return st;
     int64_t unconv = 0;
     for (int r = 0; r < R; ++r) unconv += mc->unconv[(size_t)r];
     if (unconv) { set_error("%lld subproblems hit the pivot cap", (long long)unconv); return PARTLS_ERR_NOT_CONVERGED; }

@@ -1,9 +1,10 @@
 """GPU tests of the in-library multi-device fit(Opt) (include/partls.h: partls_fit_opt_multi; Opt.jl:85-96 sharded).
 
-A one-GPU box can exercise both halves of the design: one rank through the real RCCL communicator (ncclCommInitAll +
-two ncclAllReduce(min)), and R ranks — R host threads, R contexts, R Gray-index shards — that all sit on device 0, whose
-reduction runs through the host because RCCL refuses a communicator with a duplicated device.  Both must reproduce the
-single-context fit: winner, objective, model, and the merged all_opt."""
+A one-GPU box can exercise the design: one rank with a real RCCL communicator (ncclCommInitAll; the Gram sum of a row-sharded
+fit is its one collective), and R ranks — R host threads, R contexts, R Gray-index shards — that all sit on device 0, whose
+Gram sum runs through the host because RCCL refuses a communicator with a duplicated device.  Every configuration takes the
+winner from the shards' candidate lists in host memory.  Both must reproduce the single-context fit: winner, objective, model,
+and the merged all_opt."""
 import ctypes as C
 
 import numpy as np
@@ -87,6 +88,35 @@ def test_fit_api_with_devices(partls, oracle):
     sols = list(r3.solutions)
     assert len(sols) == 1 << (P.shape[1] + 1)
     np.testing.assert_allclose([s[0] for s in sols], ref["all_opt"], rtol=1e-9, atol=1e-9)
+
+
+def test_ill_conditioned_fit_still_merges_all_opt(partls):
+    """Status 9 (PARTLS_ERR_ILL_CONDITIONED) leaves the best Gram-form model in the outputs, and all_opt with it: the shards' images are
+    merged as on success, as partls_fit_opt's sweep fills all_opt before its finish (fit(Opt, devices=..., returnAllSolutions=True))."""
+    L = partls.lowlevel
+    rng = np.random.default_rng(42)                                           # cond(X) ~ 7e7 (tests/test_gpu_edge.py, noise 1e-7)
+    N, D, K = 2000, 24, 4
+    X = rng.standard_normal((N, 6)) @ rng.standard_normal((6, D)) + 1e-7 * rng.standard_normal((N, D))
+    grp = np.arange(D) % K
+    P = np.zeros((D, K), dtype=np.int64); P[np.arange(D), grp] = 1
+    y = X @ (rng.random(D) * np.array([1., -2, 3, -1])[grp]) + 0.3 + 0.05 * rng.standard_normal(N)
+    ctx = partls.Context(0)
+    try:
+        ctx.opt_prepare(X, y, P, 0.0, L.OPT_FAITHFUL_INTERCEPT)
+        _, _, allopt1, _ = ctx.opt_sweep(0, -1, want_all=True)
+    finally:
+        ctx.close()
+    mc = partls.MultiContext([0, 0])
+    mc.tolerate_ill = True
+    try:
+        a, b, t, opt, bi, allopt = mc.fit_opt(X, y, P, want_all=True)
+        assert mc.last_ill
+        assert not np.isnan(allopt).any()                                     # every pattern was visited by exactly one shard
+        # the Gram form at this conditioning carries ~1e-7 of relative error in the objectives, and the row-sharded Gram sum rounds
+        # differently from the single context's: the two agree to that level, not to round-off
+        np.testing.assert_allclose(allopt, allopt1, rtol=1e-6)
+    finally:
+        mc.close()
 
 
 def test_exact_tie_across_ranks_keeps_the_first_index(partls):
@@ -266,7 +296,7 @@ def _branching(seed=7, N=400, D=36, K=6):
 
 @pytest.mark.parametrize("devices", [[0], [0, 0], [0, 0, 0]])
 def test_fit_bnb_multi_equals_the_single_context_search_and_the_oracle(partls, oracle, monkeypatch, devices):
-    """partls_fit_bnb_multi: one rank through the real RCCL communicator (ncclAllGather per round), 2 / 3 rank threads on device 0
+    """partls_fit_bnb_multi: one rank with the real RCCL communicator, 2 / 3 rank threads on device 0; every round's exchange goes
     through host memory — same optimum and model as partls_fit_bnb, as the oracle's depth-first recursion (BnB.jl:94-132) and as Opt.
     Small batches, so that the search takes many rounds and the dealing (owner first, surplus cold) is exercised."""
     monkeypatch.setenv("PARTLS_BNB_BATCH", "8")
@@ -354,7 +384,7 @@ def test_a_rank_that_fails_at_any_stage_fails_the_fit_and_nobody_hangs(partls, o
         mc.close()
 
 
-@pytest.mark.parametrize("alg,stage", [("opt", 1), ("opt", 3), ("bnb", 3), ("bnb", 4)])   # (opt, 4: nothing is owed after the agreement in host mode)
+@pytest.mark.parametrize("alg,stage", [("opt", 1), ("opt", 3), ("bnb", 3), ("bnb", 4)])   # (opt, 4: nothing is owed after the agreement)
 def test_a_rank_that_vanishes_is_caught_by_the_bounded_rendezvous(partls, monkeypatch, alg, stage):
     """The rank thread simply returns (what a protocol bug would look like): the others wait PARTLS_MULTI_TIMEOUT_S at their rendezvous,
     then the fit fails with PARTLS_ERR_STATE instead of hanging; a later fit on the same handle works (the barrier is reset)."""
