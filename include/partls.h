@@ -62,7 +62,8 @@ void          partls_destroy(partls_ctx *ctx);
  *   *best_index = the reference's 0-based pattern index b (bit k = sign of group k+1, bit K = intercept sign; in
  *   free-intercept mode bit K is set from the sign of the fitted intercept).
  *   all_opt: optional (may be NULL); needs PARTLS_OPT_FAITHFUL_INTERCEPT; 2^(K+1) doubles, all_opt[b] = optval of pattern b
- *   (Opt.jl:90) computed from the Gram form.  Models of individual patterns: partls_opt_pattern(). */
+ *   (Opt.jl:90) computed from the Gram form.  Models of every pattern: partls_opt_models(); of one pattern, refined in data space:
+ *   partls_opt_finish() / partls_opt_pattern(). */
 partls_status partls_fit_opt(partls_ctx *ctx, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
                              const int64_t *P, int64_t K, int64_t ldP, double eta, uint32_t flags,
                              double *alpha, double *beta, double *t, double *opt, int64_t *best_index, double *all_opt);
@@ -143,8 +144,31 @@ partls_status partls_opt_candidates(const partls_ctx *ctx, int64_t capacity, dou
 partls_status partls_opt_merge_candidates(partls_ctx *ctx, int64_t count, const double *obj, const int64_t *pattern,
                                           double *win_obj, int64_t *win_pattern);
 /* raw NNLS solution of one pattern b (reference indexing, K+1 bits): raw_alpha[M+1] >= 0 as nonneg_lsq returns it at
- * Opt.jl:89, and its optval (Opt.jl:90).  Needs a prepared context. */
+ * Opt.jl:89, and its optval (Opt.jl:90).  Needs a prepared context.  Every pattern at once: partls_opt_models. */
 partls_status partls_opt_pattern(partls_ctx *ctx, int64_t pattern, double *raw_alpha, double *optval);
+/* Models of a Gray-index range straight from the sweep (Opt.jl:87-101 without one solve per pattern).
+ * The range [g_begin, g_end) is the one partls_opt_sweep takes: the context's own visiting order, g_end = -1 = to the end.
+ * Row i (0 <= i < g_end - g_begin) describes Gray index g_begin + i; every array is column-major with one pattern per column
+ * (leading dimensions >= M+1, M, K: Julia passes an M x B matrix as it is):
+ *   pattern[i]                          reference index b of that pattern (required)
+ *   optval[i]                           Opt.jl:90 in the Gram form, = all_opt[b] of a plain sweep (optional)
+ *   raw_alpha[i * ld_raw + m], m <= M   nonneg_lsq's alpha (Opt.jl:89), as partls_opt_pattern returns it (optional)
+ *   alpha[i * ld_alpha + m], beta[i * ld_beta + k], t[i]
+ *                                       cleanupResult(Opt, ...) (Opt.jl:34-44), as partls_opt_finish returns it (optional; all three or none)
+ *   *n_unconverged, *n_vetoes           patterns of the range that hit the pivot cap / entering pivots refused by the
+ *                                       leave-one-out rule (optional)
+ * Accuracy: these are the Gram-form solutions that rank all_opt, not refined in data space as partls_opt_finish's are ("Every pattern's model").
+ * With *n_vetoes > 0 the data has (nearly) dependent columns and the Gram form carries no guarantee: use partls_opt_finish per pattern.
+ * A pattern that hit the pivot cap gets NaN in its optval and model rows. The caller re-solves it with partls_opt_finish.
+ * The range is processed in pieces whose device buffers stay below PARTLS_OPT_MODELS_PIECE_BYTES; a range whose buffers fit is one piece
+ * on the chain plan of partls_opt_sweep for the same range.  To spread one export over several devices, give each device's context a
+ * disjoint Gray range of the same prepared problem (equal visiting order: compare partls_opt_bit_order).
+ * Needs a context prepared with PARTLS_OPT_FAITHFUL_INTERCEPT (else PARTLS_ERR_STATE). Leaves the state of the last
+ * partls_opt_sweep untouched: winner, near ties, exported winner row, candidates, pivot and veto counters. */
+#define PARTLS_OPT_MODELS_PIECE_BYTES (1ULL << 30)   /* 1 GiB */
+partls_status partls_opt_models(partls_ctx *ctx, int64_t g_begin, int64_t g_end, int64_t *pattern, double *optval,
+                                double *raw_alpha, int64_t ld_raw, double *alpha, int64_t ld_alpha,
+                                double *beta, int64_t ld_beta, double *t, int64_t *n_unconverged, int64_t *n_vetoes);
 /* visiting order of the sweep: gbit[k] = Gray-index bit that carries group k (K' entries; identity unless calibrated);
  * flip_cost (optional, K' doubles): measured cost of a flip of group k in pivot equivalents (pivots + weighted block pivots and
  * extra KKT scans; exact counts, no timing), -1 when the calibration did not run (sweeps too short

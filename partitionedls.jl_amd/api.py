@@ -189,6 +189,27 @@ class Context:
         _check(L.lib().partls_opt_pattern(self._h, int(pattern), _dp(ra), C.byref(o)))
         return ra, o.value
 
+    def opt_models(self, g_begin=0, g_end=-1, raw=False):
+        """Models of the Gray-index range [g_begin, g_end) straight from the sweep (partls_opt_models), rows in visiting order:
+        dict of numpy arrays pattern[B] (reference index b), opt[B], alpha[B, M], beta[B, K], t[B] (cleanupResult), raw_alpha[B, M+1]
+        when raw=True, and the counts n_unconverged (those rows are NaN) and n_vetoes.  Gram-form models (not refined in data space)."""
+        N, M, K = self._shape
+        B = max(0, (self.num_patterns() if g_end < 0 else int(g_end)) - int(g_begin))
+        pat = np.zeros(B, dtype=np.int64)
+        opt = np.zeros(B)
+        a = np.zeros((B, M))
+        b = np.zeros((B, K))
+        t = np.zeros(B)
+        ra = np.zeros((B, M + 1)) if raw else None
+        nu = C.c_int64()
+        nv = C.c_int64()
+        _check(L.lib().partls_opt_models(self._h, int(g_begin), int(g_end), _ip(pat), _dp(opt), _dp(ra) if raw else None, M + 1,
+                                         _dp(a), M, _dp(b), K, _dp(t), C.byref(nu), C.byref(nv)))
+        out = dict(pattern=pat, opt=opt, alpha=a, beta=b, t=t, n_unconverged=nu.value, n_vetoes=nv.value)
+        if raw:
+            out["raw_alpha"] = ra
+        return out
+
     def alt_prepared(self, alpha0, beta0, eps=1e-6, T=100):
         """Alt on a context prepared with OPT_FAITHFUL_INTERCEPT (e.g. device-resident inputs)."""
         N, M, K = self._shape
@@ -552,6 +573,47 @@ class _Solutions:
 
     def __iter__(self):
         return (self[b] for b in range(len(self)))
+
+    def blocks(self, chunk=1 << 18):
+        """Every pattern's model in bulk, in the sweep's visiting order: a generator of (b, opt, alpha, beta, t) blocks of at most `chunk`
+        patterns (b: reference indices; alpha[len(b), M], beta[len(b), K]).  The models come straight from the sweep kernels
+        (partls_opt_models): the Gram-form solutions that rank opt, not refined in data space as self[b]'s are.  A pattern that hit the
+        pivot cap is solved once more on its own (opt_finish).  With refused dependent columns (n_vetoes > 0) the Gram form carries no
+        guarantee: the block is rebuilt pattern by pattern through self[b] instead, with a warning."""
+        ctx = self._context()
+        npat = len(self)
+        warned = False
+        for g0 in range(0, npat, int(chunk)):
+            r = ctx.opt_models(g0, min(npat, g0 + int(chunk)))
+            b, opt, a, bt, t = r["pattern"], r["opt"], r["alpha"], r["beta"], r["t"]
+            if r["n_vetoes"] > 0:
+                if not warned:
+                    warnings.warn("partitionedls: the sweep refused dependent columns (%d leave-one-out vetoes): the Gram-form models carry no "
+                                  "guarantee, every model is rebuilt on its own (slow)" % r["n_vetoes"], IllConditionedWarning, stacklevel=2)
+                    warned = True
+                redo = np.arange(len(b))
+            else:
+                redo = np.flatnonzero(np.isnan(opt))
+            for i in redo:
+                o, model = self[int(b[i])]
+                opt[i], a[i], bt[i], t[i] = o, model.α, model.β, model.t
+            yield b, opt, a, bt, t
+
+    def arrays(self, chunk=1 << 18):
+        """(opt[2^(K+1)], alpha[2^(K+1), M], beta[2^(K+1), K], t[2^(K+1)]) indexed by the reference pattern b — every model at once,
+        from blocks(chunk) (see there for accuracy and fallbacks)."""
+        _, M, K = self._context()._shape
+        npat = len(self)
+        opt = np.empty(npat)
+        alpha = np.empty((npat, M))
+        beta = np.empty((npat, K))
+        t = np.empty(npat)
+        for b, o, a, bt, tt in self.blocks(chunk):
+            opt[b] = o
+            alpha[b] = a
+            beta[b] = bt
+            t[b] = tt
+        return opt, alpha, beta, t
 
 
 def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="nnls", returnAllSolutions=False, rng=None,

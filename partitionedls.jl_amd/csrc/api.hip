@@ -255,14 +255,15 @@ static bool opt_range_ok(const partls_ctx *c, const char *who)
     return false;
 }
 
-static hipError_t launch_any_sweep(partls_ctx *c, SweepParams &p, int grid)
+// models: the export instantiation of the chain-mode kernel (partls_opt_models; see launch_sweep_blk in common.h)
+static hipError_t launch_any_sweep(partls_ctx *c, SweepParams &p, int grid, bool models = false)
 {
     if (c->use_reg) {
         p.T0 = c->T0reg.as<double>();
-        return launch_sweep_blk(p, c->T, grid, c->stream);
+        return launch_sweep_blk(p, c->T, grid, c->stream, models);
     }
     p.T0 = c->Tfull.as<double>();
-    return c->knobs.eager_generic ? launch_sweep_generic(p, grid, c->stream) : launch_sweep_lazy(p, grid, c->stream);
+    return c->knobs.eager_generic ? launch_sweep_generic(p, grid, c->stream, models) : launch_sweep_lazy(p, grid, c->stream, models);
 }
 
 void opt_codes(const partls_ctx *c, uint64_t pattern, std::vector<int8_t> &codes)
@@ -921,13 +922,13 @@ void partls_destroy(partls_ctx *c)
                           &c->T0reg, &c->scratch, &c->bestObj, &c->bestPat, &c->counters, &c->allOpt, &c->wdev, &c->partial,
                           &c->yhatD, &c->gD, &c->nodeCode, &c->nodeSol, &c->nodeObj, &c->gridCtr,
                           &c->predX, &c->predY, &c->nodeTab, &c->nodeBasic, &c->altA, &c->altGA, &c->altHg,
-                          &c->nodePiv, &c->maskInt, &c->allOptRef, &c->bnbIn, &c->bnbOut, &c->altGersh};
+                          &c->nodePiv, &c->maskInt, &c->allOptRef, &c->bnbIn, &c->bnbOut, &c->altGersh, &c->mdlRows, &c->mdlOut, &c->mdlCtr};
         for (DevBuf *b : bufs) b->release();
         for (void *q : c->bnbChunks) (void)hipFree(q);
         c->bnbChunks.clear();
         c->hG.release();
         c->bnbHostIn.release(); c->bnbHostOut.release();
-        c->hScale.release(); c->hPart.release(); c->hGpart.release(); c->sweepOut.release(); c->nodeOut.release(); c->exportSol.release();
+        c->hScale.release(); c->hPart.release(); c->hGpart.release(); c->sweepOut.release(); c->nodeOut.release(); c->exportSol.release(); c->mdlStage.release();
         for (int i = 0; i < 8; ++i) { if (c->upPin[i]) (void)hipHostFree(c->upPin[i]); if (c->upEvent[i]) (void)hipEventDestroy(c->upEvent[i]); }
         for (int t = 0; t < 4; ++t) if (c->upStream[t]) (void)hipStreamDestroy(c->upStream[t]);
         if (c->hTab) (void)hipHostFree(c->hTab);
@@ -1062,28 +1063,10 @@ static int64_t reference_pattern(const partls_ctx *c, int64_t q)
     return (int64_t)r;
 }
 
-partls_status partls_opt_sweep(partls_ctx *c, int64_t g_begin, int64_t g_end, double *best_obj, int64_t *best_pattern,
-                               double *all_opt, int64_t *n_unconverged)
-try {
-    if (!c || !c->prepared) { set_error("partls_opt_sweep: context not prepared"); return PARTLS_ERR_STATE; }
-    if (!opt_range_ok(c, "partls_opt_sweep")) return PARTLS_ERR_UNSUPPORTED;
-    const int64_t npat = (int64_t)1 << c->kbits;
-    if (g_end < 0) g_end = npat;
-    if (g_begin < 0 || g_begin > g_end || g_end > npat) { set_error("bad Gray-index range [%lld,%lld)", (long long)g_begin, (long long)g_end); return PARTLS_ERR_BAD_ARG; }
-    if (all_opt && !c->faithful) { set_error("all_opt needs PARTLS_OPT_FAITHFUL_INTERCEPT"); return PARTLS_ERR_BAD_ARG; }
-    PARTLS_HIP_CHECK(hipSetDevice(c->device));
-    if (g_begin == g_end) {
-        if (best_obj) *best_obj = INFINITY;
-        if (best_pattern) *best_pattern = -1;
-        if (n_unconverged) *n_unconverged = 0;
-        return PARTLS_OK;
-    }
-    if (!c->order_ready) {
-        partls_status st = calibrate_bit_order(c);
-        if (st != PARTLS_OK) return st;
-    }
-    const int n = c->n, ld = n + 1;
-    const int64_t total = g_end - g_begin;
+// Chain length and grid of a sweep over `total` Gray indices (partls_opt_sweep; partls_opt_models per piece: the same plan for the same
+// range, so its rows carry the objectives all_opt gets).  false (error set): the range needs more than 2^31 chains.
+static bool sweep_plan(partls_ctx *c, int64_t total, int64_t *chain_len_out, int *grid_out, const char *who)
+{
     // Chain length.  A chain start costs ~8 patterns' pivots, so chains should be long (~1024 patterns), but the register kernel runs ONE
     // chain per CU at a time and the chains of a range take almost equally long: the sweep lasts ceil(chains / CUs) chain times, and a
     // chain count that is not a multiple of the CU count pays for the whole last round (measured on C3, 256 CUs: 1024 chains of 1024
@@ -1121,9 +1104,39 @@ try {
     }
     if (chain_len < 1) chain_len = 1;
     const int64_t nchains = (total + chain_len - 1) / chain_len;
-    if (nchains >= (1LL << 31) || chain_len >= (1LL << 31)) { set_error("partls_opt_sweep: more than 2^31 chains in one call; split the Gray-index range"); return PARTLS_ERR_UNSUPPORTED; }
+    if (nchains >= (1LL << 31) || chain_len >= (1LL << 31)) { set_error("%s: more than 2^31 chains in one call; split the Gray-index range", who); return false; }
     int grid = (int)std::min<int64_t>(nchains, c->knobs.grid > 0 ? c->knobs.grid : (c->use_reg ? 4096 : 1024));
     if (grid < 1) grid = 1;
+    *chain_len_out = chain_len;
+    *grid_out = grid;
+    return true;
+}
+
+partls_status partls_opt_sweep(partls_ctx *c, int64_t g_begin, int64_t g_end, double *best_obj, int64_t *best_pattern,
+                               double *all_opt, int64_t *n_unconverged)
+try {
+    if (!c || !c->prepared) { set_error("partls_opt_sweep: context not prepared"); return PARTLS_ERR_STATE; }
+    if (!opt_range_ok(c, "partls_opt_sweep")) return PARTLS_ERR_UNSUPPORTED;
+    const int64_t npat = (int64_t)1 << c->kbits;
+    if (g_end < 0) g_end = npat;
+    if (g_begin < 0 || g_begin > g_end || g_end > npat) { set_error("bad Gray-index range [%lld,%lld)", (long long)g_begin, (long long)g_end); return PARTLS_ERR_BAD_ARG; }
+    if (all_opt && !c->faithful) { set_error("all_opt needs PARTLS_OPT_FAITHFUL_INTERCEPT"); return PARTLS_ERR_BAD_ARG; }
+    PARTLS_HIP_CHECK(hipSetDevice(c->device));
+    if (g_begin == g_end) {
+        if (best_obj) *best_obj = INFINITY;
+        if (best_pattern) *best_pattern = -1;
+        if (n_unconverged) *n_unconverged = 0;
+        return PARTLS_OK;
+    }
+    if (!c->order_ready) {
+        partls_status st = calibrate_bit_order(c);
+        if (st != PARTLS_OK) return st;
+    }
+    const int n = c->n, ld = n + 1;
+    const int64_t total = g_end - g_begin;
+    int64_t chain_len = 0;
+    int grid = 0;
+    if (!sweep_plan(c, total, &chain_len, &grid, "partls_opt_sweep")) return PARTLS_ERR_UNSUPPORTED;
 
     // one output block on the device, one copy back: [counters (4 x 8 B) | best objective (grid) | best pattern (grid) | runner-up
     // objective (grid) | runner-up pattern (grid)]
@@ -1374,6 +1387,128 @@ try {
             raw_alpha[m] = a > 0.0 ? a : 0.0;
         }
     if (unconv) { set_error("pattern solve hit the pivot cap"); return PARTLS_ERR_NOT_CONVERGED; }
+    return PARTLS_OK;
+}
+catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
+catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+
+// Models of a Gray-index range straight from the sweep (include/partls.h).  The range is cut into pieces whose device buffers (scaled
+// rows, objectives, cleaned outputs) stay below PARTLS_OPT_MODELS_PIECE_BYTES; each piece is one sweep with the export instantiation of the
+// kernel, on the chain plan partls_opt_sweep would choose for it, then one launch of the cleanup kernel (models.hip), then one copy back
+// through page-locked staging.  Nothing of the last partls_opt_sweep's state is touched: the counters and per-workgroup results of the
+// export go to a block of their own (mdlCtr), the winner's row of bestSol stays.
+static void par_rows(int64_t rows, size_t row_bytes, const std::function<void(int64_t, int64_t)> &fn)
+{
+    // the host copy out of the staging buffer: one core moves ~10 GB/s, a piece at C3 is ~1 GB
+    const int nt = (size_t)rows * row_bytes < ((size_t)32 << 20) ? 1 : 8;
+    if (nt == 1) { fn(0, rows); return; }
+    std::vector<std::thread> th;
+    const int64_t per = (rows + nt - 1) / nt;
+    try {
+        for (int i = 1; i < nt; ++i) {
+            const int64_t r0 = std::min<int64_t>(rows, i * per), r1 = std::min<int64_t>(rows, r0 + per);
+            th.emplace_back(fn, r0, r1);
+        }
+    } catch (...) {                                          // out of threads: the caller's thread takes the rest
+        const int64_t done_from = (int64_t)(th.size() + 1) * per;
+        fn(std::min<int64_t>(rows, done_from), rows);
+    }
+    fn(0, std::min<int64_t>(rows, per));
+    for (std::thread &t : th) t.join();
+}
+
+static void copy_rows(double *dst, int64_t ld_dst, const double *src, int64_t width, int64_t rows)
+{
+    if (!dst || width <= 0) return;
+    par_rows(rows, (size_t)width * sizeof(double), [&](int64_t r0, int64_t r1) {
+        if (ld_dst == width) std::memcpy(dst + (size_t)r0 * width, src + (size_t)r0 * width, (size_t)(r1 - r0) * width * sizeof(double));
+        else for (int64_t r = r0; r < r1; ++r) std::memcpy(dst + (size_t)r * ld_dst, src + (size_t)r * width, (size_t)width * sizeof(double));
+    });
+}
+
+partls_status partls_opt_models(partls_ctx *c, int64_t g_begin, int64_t g_end, int64_t *pattern, double *optval, double *raw_alpha,
+                                int64_t ld_raw, double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t,
+                                int64_t *n_unconverged, int64_t *n_vetoes)
+try {
+    if (!c || !c->prepared) { set_error("partls_opt_models: context not prepared"); return PARTLS_ERR_STATE; }
+    if (!c->faithful) { set_error("partls_opt_models needs a context prepared with PARTLS_OPT_FAITHFUL_INTERCEPT"); return PARTLS_ERR_STATE; }
+    if (!opt_range_ok(c, "partls_opt_models")) return PARTLS_ERR_UNSUPPORTED;
+    const int64_t npat = (int64_t)1 << c->kbits, M = c->M, K = c->K;
+    if (g_end < 0) g_end = npat;
+    if (g_begin < 0 || g_begin > g_end || g_end > npat) { set_error("partls_opt_models: bad Gray-index range [%lld,%lld)", (long long)g_begin, (long long)g_end); return PARTLS_ERR_BAD_ARG; }
+    if (!pattern) { set_error("partls_opt_models: pattern is NULL"); return PARTLS_ERR_BAD_ARG; }
+    if ((alpha || beta || t) && !(alpha && beta && t)) { set_error("partls_opt_models: alpha, beta and t go together (all three or none)"); return PARTLS_ERR_BAD_ARG; }
+    if ((raw_alpha && ld_raw < M + 1) || (alpha && (ld_alpha < M || ld_beta < K))) { set_error("partls_opt_models: leading dimension too small"); return PARTLS_ERR_BAD_ARG; }
+    if (n_unconverged) *n_unconverged = 0;
+    if (n_vetoes) *n_vetoes = 0;
+    PARTLS_HIP_CHECK(hipSetDevice(c->device));
+    if (g_begin == g_end) return PARTLS_OK;
+    if (!c->order_ready) {
+        partls_status st = calibrate_bit_order(c);
+        if (st != PARTLS_OK) return st;
+    }
+    const int n = c->n, ld = n + 1;
+    const int64_t total = g_end - g_begin;
+    const size_t out_w = 3 + (size_t)M + (size_t)K;                 // cleaned output per pattern: pattern, optval, t, alpha, beta
+    const size_t per_pat = (size_t)n + 1 + out_w;                     // + the scaled row (raw alpha in place) and its objective
+    const int64_t cap = std::max<int64_t>(1, (int64_t)(PARTLS_OPT_MODELS_PIECE_BYTES / (per_pat * sizeof(double))));
+    const int64_t npieces = (total + cap - 1) / cap;
+    const int64_t piece = (total + npieces - 1) / npieces;            // equal pieces: no short tail piece of cold chain starts
+    PARTLS_HIP_CHECK(c->mdlRows.ensure((size_t)piece * (n + 1) * sizeof(double)));
+    PARTLS_HIP_CHECK(c->mdlOut.ensure((size_t)piece * out_w * sizeof(double)));
+    const size_t stage_words = 4 + (size_t)piece * (out_w + (raw_alpha ? (size_t)n : 0));
+    PARTLS_HIP_CHECK(c->mdlStage.resize(stage_words));
+    if (!c->use_reg) c->coop_state_valid = false;                    // the global-memory kernels overwrite the shared tableau scratch
+    unsigned long long unconv = 0, vetoes = 0;
+    for (int64_t p0 = g_begin; p0 < g_end; p0 += piece) {
+        const int64_t cnt = std::min<int64_t>(piece, g_end - p0);
+        int64_t chain_len = 0;
+        int grid = 0;
+        if (!sweep_plan(c, cnt, &chain_len, &grid, "partls_opt_models")) return PARTLS_ERR_UNSUPPORTED;
+        // [counters (4 x 8 B) | best objective (grid) | best pattern (grid)]: what the kernel reports per workgroup, unused here
+        PARTLS_HIP_CHECK(c->mdlCtr.ensure(sizeof(double) * (4 + 2 * (size_t)grid)));
+        PARTLS_HIP_CHECK(hipMemsetAsync(c->mdlCtr.p, 0, 4 * sizeof(unsigned long long), c->stream));
+        if (!c->use_reg) PARTLS_HIP_CHECK(c->scratch.ensure((size_t)grid * ld * ld * sizeof(double)));
+        else PARTLS_HIP_CHECK(c->scratch.ensure(64 * sizeof(double)));
+        double *rows = c->mdlRows.as<double>(), *obj = rows + (size_t)cnt * n, *out = c->mdlOut.as<double>();
+        SweepParams p{};
+        p.n = n; p.kbits = c->kbits;
+        p.mask = c->order_identity ? c->maskTabP : c->maskInt.as<uint64_t>();
+        p.scratch = c->scratch.as<double>();
+        p.g_begin = p0; p.g_end = p0 + cnt; p.chain_len = chain_len;
+        p.tol = c->tol; p.piv_eps = 1e-11; p.max_rounds = 20 * (n + 1);
+        p.best_obj = c->mdlCtr.as<double>() + 4; p.best_pat = reinterpret_cast<int64_t *>(c->mdlCtr.as<double>() + 4 + grid);
+        p.n_unconverged = c->mdlCtr.as<unsigned long long>();
+        p.n_pivots = c->mdlCtr.as<unsigned long long>() + 1;
+        p.n_vetoes = c->mdlCtr.as<unsigned long long>() + 2;
+        for (int k = 0; k < 40; ++k) p.rbit.gbit[k] = (uint8_t)k;
+        if (!c->order_identity) for (int k = 0; k < c->kbits; ++k) p.rbit.gbit[c->order.gbit[k]] = (uint8_t)k;
+        p.node_sol = rows; p.node_obj2 = obj; p.node_ld = n;
+        PARTLS_HIP_CHECK(launch_any_sweep(c, p, grid, /*models=*/true));
+        PARTLS_HIP_CHECK(launch_models_cleanup(rows, obj, p0, cnt, (int)M, (int)K, c->kbits, c->order, c->order_identity, c->permP,
+                                               c->scale.as<double>(), c->maskAugD.as<uint64_t>(), raw_alpha != nullptr, out, c->stream));
+        double *st = c->mdlStage.data();
+        PARTLS_HIP_CHECK(hipMemcpyAsync(st, c->mdlCtr.p, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(st + 4, out, (size_t)cnt * out_w * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (raw_alpha) PARTLS_HIP_CHECK(hipMemcpyAsync(st + 4 + (size_t)cnt * out_w, rows, (size_t)cnt * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        unsigned long long cn[3];
+        std::memcpy(cn, st, sizeof(cn));
+        unconv += cn[0];
+        vetoes += cn[2];
+        const double *o = st + 4;
+        const size_t r = (size_t)(p0 - g_begin);
+        std::memcpy(pattern + r, o, (size_t)cnt * sizeof(int64_t));
+        if (optval) std::memcpy(optval + r, o + cnt, (size_t)cnt * sizeof(double));
+        if (t) std::memcpy(t + r, o + 2 * cnt, (size_t)cnt * sizeof(double));
+        if (alpha) {
+            copy_rows(alpha + r * ld_alpha, ld_alpha, o + 3 * cnt, M, cnt);
+            copy_rows(beta + r * ld_beta, ld_beta, o + 3 * cnt + (size_t)cnt * M, K, cnt);
+        }
+        if (raw_alpha) copy_rows(raw_alpha + r * ld_raw, ld_raw, o + (size_t)cnt * out_w, M + 1, cnt);
+    }
+    if (n_unconverged) *n_unconverged = (int64_t)unconv;
+    if (n_vetoes) *n_vetoes = (int64_t)vetoes;
     return PARTLS_OK;
 }
 catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }

@@ -103,9 +103,12 @@ __device__ __forceinline__ bool ref_index_less(unsigned long long a, unsigned lo
     return top >= 0 && !((a >> at) & 1ULL);
 }
 
-hipError_t launch_sweep_generic(const SweepParams &p, int grid, hipStream_t s);   // tableau in global memory, every block applied at once
-hipError_t launch_sweep_lazy(const SweepParams &p, int grid, hipStream_t s);      // ... updates deferred (sweep_lazy.hip): the n > 320 path
-hipError_t launch_sweep_blk(const SweepParams &p, int T, int grid, hipStream_t s);
+// models = true (chain mode only, partls_opt_models): the export instantiation of the kernel — every pattern's scaled solution goes to
+// row g - g_begin of node_sol (leading dimension node_ld) and its objective (sqrt of the corner, all_opt's value) to node_obj2[g - g_begin];
+// NaN in both for a pattern that hit the pivot cap.  best_sol is not written.
+hipError_t launch_sweep_generic(const SweepParams &p, int grid, hipStream_t s, bool models = false);   // tableau in global memory, every block applied at once
+hipError_t launch_sweep_lazy(const SweepParams &p, int grid, hipStream_t s, bool models = false);      // ... updates deferred (sweep_lazy.hip): the n > 320 path
+hipError_t launch_sweep_blk(const SweepParams &p, int T, int grid, hipStream_t s, bool models = false);
 hipError_t launch_sweep_coop(const SweepParams &p, int nwg, hipStream_t s);   // one node, many workgroups (n > 320)
 bool       sweep_reg_supported(int n);
 int        sweep_reg_tiles(int n);
@@ -130,6 +133,13 @@ hipError_t launch_prep(const double *G, int ldg, int M, double eta, const uint64
 int        walk_flipped_bit(int chain, int step, int kbits, int seg_len, int nseg);
 hipError_t launch_walk_codes(const uint64_t *mask, int n, int kbits, int chains, int L, int seg_len, int nseg, int8_t *codes, hipStream_t s);
 hipError_t launch_pattern_gather(const double *in, int64_t npat, int kbits, const BitOrder &order, double *out, hipStream_t s);
+
+// partls_opt_models (models.hip): the sweep's scaled solutions of Gray indices [g0, g0 + cnt) -> reference pattern, raw alpha (in place
+// over the solution rows, ld n = M + 1), cleanupResult's alpha / beta / t; out = [pattern (cnt int64) | optval (cnt) | t (cnt) |
+// alpha (cnt x M) | beta (cnt x K)].  A row whose objective is NaN (pivot cap) gets NaN everywhere.
+hipError_t launch_models_cleanup(double *sol, const double *obj, int64_t g0, int64_t cnt, int M, int K, int kbits, const BitOrder &order,
+                                 bool order_identity, const int *perm, const double *scale, const uint64_t *mask_aug, bool want_raw,
+                                 double *out, hipStream_t s);
 
 // BnB node batches (misc.hip): per-variable constraint codes of the nodes (pat, free) and (bound, branch) from their solutions
 hipError_t launch_bnb_codes(const uint64_t *mask_tab, int n, const uint64_t *pat, const uint64_t *free_, int cnt, int8_t *codes, hipStream_t s);

@@ -121,6 +121,9 @@ struct partls_ctx {
     partls::PinnedDoubles hPart, hGpart;           // host staging of a data pass (page-locked like every device -> host destination of a fit: a pageable
                                                    // one costs 17-30 us of runtime staging per copy and blocks the caller — a third of a C2-sized fit's host time)
     partls::PinnedDoubles sweepOut, nodeOut, exportSol;   // ... of a sweep's per-workgroup results, of a node batch, of the sweep's solution of its winner
+    // partls_opt_models: one piece's scaled rows + objectives, its cleaned outputs, the export's own counters, and their page-locked staging
+    partls::DevBuf mdlRows, mdlOut, mdlCtr;
+    partls::PinnedDoubles mdlStage;
     // called between the Gram build and the tableau preparation (partls_fit_opt_multi: the Gram products of the row blocks are summed)
     std::function<partls_status(partls_ctx *)> gram_hook;
     partls::PinnedDoubles bnbHostIn, bnbHostOut;   // page-locked staging of a node batch (8-byte words): the two copies of a round cost ~10 us each instead of ~25 pageable

@@ -284,7 +284,11 @@ __device__ __forceinline__ int panel_block(double *P, double *Z, double *U, doub
 
 // NODE: node mode (Alt alpha-steps, BnB bounds: one subproblem per chain, free / zero groups) is a separate instantiation, so
 // that the chain-mode sweep carries neither the node pointers nor the per-thread `free` flag through its loops.
-template <int T, int H, bool NODE, int W = 2>
+// MODELS (chain mode only, partls_opt_models): every finished pattern leaves its scaled solution (basic ? q : 0, node_sol's format) in
+// row g - g_begin of p.node_sol (leading dimension p.node_ld) and sqrt(obj2) in p.node_obj2[g - g_begin]; a pattern that hit the pivot
+// cap leaves NaN in both.  The row follows from the chain and pattern counters alone (no live register beyond the default build's); the
+// export instantiation writes no best_sol.  A separate instantiation: the default ones keep their code.
+template <int T, int H, bool NODE, int W = 2, bool MODELS = false>
 __device__ __forceinline__ void sweep_body(const SweepParams &p)
 {
     using L = Half<T, H, W>;
@@ -385,6 +389,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
             blocked = false;
             int ninf_best = n + 1, patience = 3, rounds = 0;
             bool progress = false;                                    // did the previous round change the basis?
+            [[maybe_unused]] const unsigned nunconv0 = nunconv;      // MODELS: did this pattern hit the pivot cap?
             for (;;) {
                 // ---- KKT scan of the rhs column (registers) ------------------------------------------------------------
                 // a column rejected as dependent is only dependent on the basis it was tested against (Lawson–Hanson
@@ -565,7 +570,13 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                 }
             }
             if (p.all_opt && tid == THREADS - 1) p.all_opt[pat] = sqrt(obj2);
-            if constexpr (!NODE && (W == 1 || (PARTLS_EXPORT_BIG && T <= EXPORT_MAXT))) {
+            if constexpr (MODELS) {
+                const size_t row = (size_t)chain * (size_t)clen + (size_t)gi;
+                const bool capped = nunconv != nunconv0;
+                if (has_var) p.node_sol[row * p.node_ld + tid] = capped ? __builtin_nan("") : (basic ? q : 0.0);
+                if (tid == THREADS - 1) p.node_obj2[row] = capped ? __builtin_nan("") : sqrt(obj2);
+            }
+            if constexpr (!NODE && !MODELS && (W == 1 || (PARTLS_EXPORT_BIG && T <= EXPORT_MAXT))) {
                 // (round 3: 256-thread kernel only — in the 512-thread kernel the two extra live registers moved 8 spills and cost 1.8 % of the
                 // C3 sweep.  Round 4: the spills turned out to be hoisted address offsets and are gone; -DPARTLS_EXPORT_BIG=1 measures it again)
                 // the workgroup's best pattern so far leaves its solution behind (rhs column of the basic variables, as node mode's
@@ -641,21 +652,21 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
 // are computed from LDS words or kernel arguments that are identical for all 512 threads — never from a half's own registers —
 // so both instantiations execute the same barrier sequence: per scan 1, per block 2 + m (the m panel steps; idle waves only
 // count them).  Any edit that makes a barrier conditional on per-half or per-wave data deadlocks the CU.
-template <int T, bool NODE>
+template <int T, bool NODE, bool MODELS = false>
 __global__ __launch_bounds__(THREADS, 2) void sweep_blk_kernel(SweepParams p)
 {
     const int half = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
-    if (half == 0) sweep_body<T, 0, NODE>(p);
-    else sweep_body<T, 1, NODE>(p);
+    if (half == 0) sweep_body<T, 0, NODE, 2, MODELS>(p);
+    else sweep_body<T, 1, NODE, 2, MODELS>(p);
 }
 
 #ifndef PARTLS_SMALL_OCC
 #define PARTLS_SMALL_OCC(T) ((T) <= 8 ? 3 : 2)          // waves per SIMD = workgroups per CU the allocator is asked to leave room for
 #endif
-template <int T, bool NODE>
+template <int T, bool NODE, bool MODELS = false>
 __global__ __launch_bounds__(256, PARTLS_SMALL_OCC(T)) void sweep_small_kernel(SweepParams p)
 {
-    sweep_body<T, 0, NODE, 1>(p);
+    sweep_body<T, 0, NODE, 1, MODELS>(p);
 }
 
 // Tfull ((n+1)^2) -> tile-cyclic initial state: [slot = tri(gamma) + rho][256 = a + 16 b], then q0[16 T], then the corner
@@ -697,13 +708,15 @@ hipError_t launch_layout_reg(const double *Tfull, int n, int T, double *T0reg, h
 }
 
 template <int T>
-static hipError_t launch_blk_T(const SweepParams &p, int grid, hipStream_t s)
+static hipError_t launch_blk_T(const SweepParams &p, int grid, hipStream_t s, bool models)
 {
     if constexpr (T <= blk::MAXT_S) {                        // small tableau: 256-thread workgroups, several per CU
         if (p.node_code) hipLaunchKernelGGL((blk::sweep_small_kernel<T, true>), dim3(grid), dim3(256), 0, s, p);
+        else if (models) hipLaunchKernelGGL((blk::sweep_small_kernel<T, false, true>), dim3(grid), dim3(256), 0, s, p);
         else hipLaunchKernelGGL((blk::sweep_small_kernel<T, false>), dim3(grid), dim3(256), 0, s, p);
     } else {
         if (p.node_code) hipLaunchKernelGGL((blk::sweep_blk_kernel<T, true>), dim3(grid), dim3(blk::THREADS), 0, s, p);     // ~100 KB of static LDS
+        else if (models) hipLaunchKernelGGL((blk::sweep_blk_kernel<T, false, true>), dim3(grid), dim3(blk::THREADS), 0, s, p);
         else hipLaunchKernelGGL((blk::sweep_blk_kernel<T, false>), dim3(grid), dim3(blk::THREADS), 0, s, p);
     }
     return hipGetLastError();
@@ -745,13 +758,13 @@ int sweep_reg_concurrency_query(int T)
     }
 }
 
-hipError_t launch_sweep_blk(const SweepParams &p, int T, int grid, hipStream_t s)
+hipError_t launch_sweep_blk(const SweepParams &p, int T, int grid, hipStream_t s, bool models)
 {
     switch (T) {
 #ifdef PARTLS_ONLY_T
-        case PARTLS_ONLY_T: return launch_blk_T<PARTLS_ONLY_T>(p, grid, s);
+        case PARTLS_ONLY_T: return launch_blk_T<PARTLS_ONLY_T>(p, grid, s, models);
 #else
-#define PARTLS_L(i) case i + 1: return launch_blk_T<i + 1>(p, grid, s);
+#define PARTLS_L(i) case i + 1: return launch_blk_T<i + 1>(p, grid, s, models);
         PARTLS_CASES(PARTLS_L)
 #undef PARTLS_L
 #endif

@@ -32,6 +32,9 @@ __device__ __forceinline__ int sign_of_var(uint64_t m, uint64_t pat)
     return 2 * __popcll(m & pat) - __popcll(m);
 }
 
+// MODELS (chain mode, partls_opt_models): every finished pattern leaves its scaled solution in row g - g_begin of p.node_sol and its
+// objective in p.node_obj2 (NaN for a pattern that hit the pivot cap), as sweep_blk.hip's export instantiation does
+template <bool MODELS>
 __global__ __launch_bounds__(GEN_THREADS) void sweep_generic_kernel(SweepParams p, int mb)
 {
     const int n = p.n, ld = n + 1;
@@ -76,6 +79,7 @@ __global__ __launch_bounds__(GEN_THREADS) void sweep_generic_kernel(SweepParams 
             __syncthreads();
             int ninf_best = n + 1, patience = 3, rounds = 0;
             bool progress = false;
+            [[maybe_unused]] const unsigned long long nunconv0 = nunconv;   // MODELS: did this pattern hit the pivot cap?
             for (;;) {
                 if (progress) {                                    // rejections hold for the basis they were tested against only
                     for (int i = tid; i < n; i += GEN_THREADS) s_blocked[i] = 0;
@@ -138,6 +142,13 @@ __global__ __launch_bounds__(GEN_THREADS) void sweep_generic_kernel(SweepParams 
             const double obj2 = T[(size_t)n * ld + n];
             const double obj = sqrt(obj2 > 0.0 ? obj2 : 0.0);
             if (p.all_opt && tid == 0) p.all_opt[pat] = obj;
+            if constexpr (MODELS) {
+                const size_t row = (size_t)(g - p.g_begin);
+                const bool capped = nunconv != nunconv0;
+                for (int i = tid; i < n; i += GEN_THREADS)
+                    p.node_sol[row * p.node_ld + i] = capped ? __builtin_nan("") : (s_basic[i] ? T[(size_t)i * ld + n] : 0.0);
+                if (tid == 0) p.node_obj2[row] = capped ? __builtin_nan("") : obj;
+            }
             if (obj < best_obj || (obj == best_obj && best_pat >= 0 && ref_index_less(pat, (unsigned long long)best_pat, p.rbit.gbit))) {
                 second_obj = best_obj; second_pat = best_pat;
                 best_obj = obj; best_pat = (long long)pat;
@@ -148,7 +159,7 @@ __global__ __launch_bounds__(GEN_THREADS) void sweep_generic_kernel(SweepParams 
             }
             __syncthreads();
         }
-        if (p.node_sol) {
+        if (!MODELS && p.node_sol) {
             for (int i = tid; i < n; i += GEN_THREADS)
                 p.node_sol[(size_t)chain * p.node_ld + i] = s_basic[i] ? T[(size_t)i * ld + n] : 0.0;
             if (tid == 0) p.node_obj2[chain] = T[(size_t)n * ld + n];
@@ -164,16 +175,22 @@ __global__ __launch_bounds__(GEN_THREADS) void sweep_generic_kernel(SweepParams 
     }
 }
 
-hipError_t launch_sweep_generic(const SweepParams &p, int grid, hipStream_t s)
+template <bool MODELS>
+static hipError_t launch_generic(const SweepParams &p, int grid, hipStream_t s)
 {
     const int ld = p.n + 1;
     int mb = gj_block_size(ld, (size_t)136 * 1024);
     const size_t shmem = (size_t)2 * mb * ld * sizeof(double) + (3 * GJ_MB + GEN_THREADS / 64) * sizeof(double) + 2 * (size_t)p.n + 16;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&sweep_generic_kernel),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&sweep_generic_kernel<MODELS>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sweep_generic_kernel, dim3(grid), dim3(GEN_THREADS), shmem, s, p, mb);
+    hipLaunchKernelGGL(sweep_generic_kernel<MODELS>, dim3(grid), dim3(GEN_THREADS), shmem, s, p, mb);
     return hipGetLastError();
+}
+
+hipError_t launch_sweep_generic(const SweepParams &p, int grid, hipStream_t s, bool models)
+{
+    return (models && !p.node_code) ? launch_generic<true>(p, grid, s) : launch_generic<false>(p, grid, s);
 }
 
 }  // namespace partls

@@ -441,7 +441,9 @@ __device__ __forceinline__ int lz_panel_stepwise(double *__restrict__ Pn, double
     return __popc(accm);
 }
 
-template <int NT, bool NODE>
+// MODELS (chain mode, partls_opt_models): every finished pattern leaves its scaled solution in row g - g_begin of p.node_sol and its
+// objective in p.node_obj2 (NaN for a pattern that hit the pivot cap), as sweep_blk.hip's export instantiation does; no best_sol
+template <int NT, bool NODE, bool MODELS = false>
 __global__ __launch_bounds__(NT) void sweep_lazy_kernel(SweepParams p, int mb, int rows)
 {
     const int n = p.n, ld = n + 1;
@@ -522,6 +524,7 @@ __global__ __launch_bounds__(NT) void sweep_lazy_kernel(SweepParams p, int mb, i
             __syncthreads();
             int ninf_best = n + 1, patience = 3, rounds = 0;
             bool progress = false;
+            [[maybe_unused]] const unsigned long long nunconv0 = nunconv;   // MODELS: did this pattern hit the pivot cap?
             for (;;) {
                 if (progress) {                                    // rejections hold for the basis they were tested against only
                     for (int i = tid; i < n; i += NT) s_blocked[i] = 0;
@@ -736,13 +739,19 @@ __global__ __launch_bounds__(NT) void sweep_lazy_kernel(SweepParams p, int mb, i
             const double obj2 = qs[n];
             const double obj = sqrt(obj2 > 0.0 ? obj2 : 0.0);
             if (p.all_opt && tid == 0) p.all_opt[pat] = obj;
+            if constexpr (MODELS) {
+                const size_t row = (size_t)(g - p.g_begin);
+                const bool capped = nunconv != nunconv0;
+                for (int i = tid; i < n; i += NT) p.node_sol[row * p.node_ld + i] = capped ? __builtin_nan("") : (s_basic[i] ? qs[i] : 0.0);
+                if (tid == 0) p.node_obj2[row] = capped ? __builtin_nan("") : obj;
+            }
             if (obj < best_obj || (obj == best_obj && best_pat >= 0 && ref_index_less(pat, (unsigned long long)best_pat, p.rbit.gbit))) {
                 second_obj = best_obj; second_pat = best_pat;
                 best_obj = obj; best_pat = (long long)pat;
             } else if (obj < second_obj) { second_obj = obj; second_pat = (long long)pat; }
             // the workgroup's best pattern so far leaves its solution behind (as sweep_blk.hip's 256-thread kernel does): the host takes
             // the winner's from here instead of solving that pattern again — at n > 320 a 1.2 ms solve on the many-workgroup kernel
-            if (p.best_sol && !code && obj2 < wg_best2) {
+            if (!MODELS && p.best_sol && !code && obj2 < wg_best2) {
                 wg_best2 = obj2;
                 for (int i = tid; i < n; i += NT) p.best_sol[(size_t)blockIdx.x * p.node_ld + i] = s_basic[i] ? qs[i] : 0.0;
             }
@@ -752,7 +761,7 @@ __global__ __launch_bounds__(NT) void sweep_lazy_kernel(SweepParams p, int mb, i
             }
             __syncthreads();
         }
-        if (p.node_sol) {
+        if (!MODELS && p.node_sol) {
             for (int i = tid; i < n; i += NT)
                 p.node_sol[(size_t)chain * p.node_ld + i] = s_basic[i] ? qs[i] : 0.0;
             if (tid == 0) p.node_obj2[chain] = qs[n];
@@ -807,9 +816,13 @@ bool lazy_plan(int ld, int *mb_out, int *rows_out, size_t *shmem_out)
 }
 
 template <int NT>
-static hipError_t launch_lazy_nt(const SweepParams &p, int grid, int mb, int rows, size_t shmem, hipStream_t s)
+static hipError_t launch_lazy_nt(const SweepParams &p, int grid, int mb, int rows, size_t shmem, hipStream_t s, bool models)
 {
-    if (p.node_code) {
+    if (models && !p.node_code) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&sweep_lazy_kernel<NT, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((sweep_lazy_kernel<NT, false, true>), dim3(grid), dim3(NT), shmem, s, p, mb, rows);
+    } else if (p.node_code) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&sweep_lazy_kernel<NT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((sweep_lazy_kernel<NT, true>), dim3(grid), dim3(NT), shmem, s, p, mb, rows);
@@ -822,12 +835,12 @@ static hipError_t launch_lazy_nt(const SweepParams &p, int grid, int mb, int row
 }
 
 // one thread per tableau row in the panel: 512 threads up to n = 511 (half the waves at every barrier of the m panel steps), 1024 beyond
-hipError_t launch_sweep_lazy(const SweepParams &p, int grid, hipStream_t s)
+hipError_t launch_sweep_lazy(const SweepParams &p, int grid, hipStream_t s, bool models)
 {
     int mb = 0, rows = 0;
     size_t shmem = 0;
     if (!lazy_plan(p.n + 1, &mb, &rows, &shmem)) return hipErrorInvalidValue;
-    return p.n + 1 <= 512 ? launch_lazy_nt<512>(p, grid, mb, rows, shmem, s) : launch_lazy_nt<1024>(p, grid, mb, rows, shmem, s);
+    return p.n + 1 <= 512 ? launch_lazy_nt<512>(p, grid, mb, rows, shmem, s, models) : launch_lazy_nt<1024>(p, grid, mb, rows, shmem, s, models);
 }
 
 }  // namespace partls
