@@ -1221,10 +1221,10 @@ try {
         if (bpat < 0 || bo[(size_t)i] < bobj || (bo[(size_t)i] == bobj && bp[(size_t)i] < bpat)) { bobj = bo[(size_t)i]; bpat = bp[(size_t)i]; best_wg = i; }
     }
     if (p.best_sol) c->export_wg = best_wg;                 // row of bestSol that holds the winner's solution (valid while near_for == winner)
-    // Near ties.  The tracked objective^2 carries the Gram form's absolute error (~eps * y'y times the pivots of the chain), so two
-    // patterns closer than that can come out in the wrong order relative to the reference, which computes every objective from the
-    // data (Opt.jl:90).  Candidates within that error of the winner — each workgroup reports its minimum and its runner-up — are
-    // remembered (at most 3, best first); partls_opt_finish re-ranks them with the objective from the data.
+    // Near ties.  The tracked objective^2 carries the Gram form's absolute error (a few eps * y'y, growing about as the square root
+    // of the chain length: DESIGN.md §3), so two patterns closer than that can come out in the wrong order relative to the reference,
+    // which computes every objective from the data (Opt.jl:90).  Candidates within that error of the winner — each workgroup reports its
+    // minimum and its runner-up — are remembered (at most 3, best first); partls_opt_finish re-ranks them with the objective from the data.
     c->near_pat.clear();
     c->cand.clear();
     c->near_for = bpat;
