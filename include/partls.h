@@ -180,6 +180,35 @@ partls_status partls_opt_bit_order(partls_ctx *ctx, int64_t *gbit, double *flip_
 /* number of subproblems one full sweep solves (2^K or 2^(K+1)) for the prepared problem */
 int64_t       partls_opt_num_patterns(const partls_ctx *ctx);
 
+/* ---- cross-validation of fit(Opt) over folds x an η grid, and the full-data regularisation path, in one call ------------------------
+ * The reference's MLJ model PartLS exposes η (PartitionedLS.jl:290-297); it can only be chosen on held-out rows.  Inputs as
+ * partls_opt_prepare (x_on_device: X, y are DEVICE pointers), plus
+ *   fold_ptr[F+1]: fold boundaries, 0 = fold_ptr[0] < ... < fold_ptr[F] = N; fold f = rows [fold_ptr[f], fold_ptr[f+1]).  F = 0
+ *                  (fold_ptr may be NULL): no CV, the path only.  F = 1 is an error.
+ *   eta[E]:        E >= 1 values, each finite and >= 0;   flags: those of partls_fit_opt (no all_opt).
+ * Problems: B = (F+1) E, indexed q = f E + e.  Problem (f < F, e) is fit(Opt, X[train_f], y[train_f], P; η = eta[e]) with train_f = every
+ * row outside fold f in its original order (the η rows are not rescaled by the training size: regularizeProblem, PartitionedLS.jl:108-123).
+ * Problem (F, e) is the fit on all rows (the regularisation path).  Outputs, column q of each (caller-allocated, column-major):
+ *   alpha[q * ld_alpha + m] (ld_alpha >= M), beta[q * ld_beta + k] (ld_beta >= K), t[q], opt[q], best_index[q]: as partls_fit_opt;
+ *   heldout_sse[q]: sum over the rows i of fold f of (predict(model, x_i) - y_i)^2 (PartitionedLS.jl:132), from the data; NaN for f = F;
+ *   status[q]: 0, PARTLS_ERR_ILL_CONDITIONED (the model as fit() returns it, see there) or PARTLS_ERR_NOT_CONVERGED (NaN outputs,
+ *              best_index -1).
+ * Any other failure (bad arguments, NaN/Inf data, HIP errors) fails the whole call and writes no output.
+ * Accuracy: every problem's model is the refined, KKT-checked model partls_opt_finish returns for a single fit; the Gram products of a
+ * training set are the sum of its folds' (fixed order), so an objective can differ from a single fit's by the Gram form's own rounding
+ * and a winner within the near-tie window (1e-13 y'y on obj^2) may be the other pattern of the tie.  Bitwise reproducible.
+ * The visiting order of the sweep is calibrated once, on the full-data problem at eta[0], and shared by every problem.  Register-kernel
+ * problems (n <= 288) are swept together in launches of up to 65535 problems; larger ones, PARTLS_OPT_GENERIC_KERNEL and the
+ * PARTLS_CV_SERIAL=1 knob (read at partls_create) sweep one problem after another.
+ * Context state afterwards: it keeps the upload of X (host inputs) but holds no prepared problem (a staged call must prepare again);
+ * partls_get_timing gives the phases of the whole call (GRAM: fold Grams + combine, PREP, SWEEP: sums over the batch, FINISH: host wall time of
+ * the per-problem finishes, held-out passes included). */
+partls_status partls_cv_opt(partls_ctx *ctx, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
+                            const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F,
+                            const double *eta, int64_t E, uint32_t flags,
+                            double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t, double *opt,
+                            int64_t *best_index, double *heldout_sse, int32_t *status);
+
 /* ---- fit(Alt, X, y, P; η, ϵ, T)  — replaces Alt.jl:50-124 ------------------------------------------------------------
  * alpha0[M+1], beta0[K+1]: the random initial point the Julia shim draws exactly as Alt.jl:58-66 does.
  * Outputs as Alt.jl:119: alpha[M], beta[K], *t = β[end]*α[end], *opt, *iters = completed iterations. */

@@ -210,6 +210,39 @@ class Context:
             out["raw_alpha"] = ra
         return out
 
+    def cv_opt(self, X, y, P, fold_ptr, etas, flags=0, device_ptrs=None):
+        """partls_cv_opt: fit(Opt) on every (fold, η) training set and on all rows, in one call.  X, y: host arrays, or
+        device_ptrs=(dX_ptr, dy_ptr, N, ldX) for device-resident inputs (X then ignored; pass X=None).  fold_ptr: F+1 boundaries (None or
+        [] for the path only).  Returns a dict of column-major results, one problem per column, q = f * E + e: alpha (M x B), beta (K x B),
+        t, opt, best_index, heldout_sse, status (all length B)."""
+        P = np.asfortranarray(P, dtype=np.int64)
+        M, K = P.shape
+        if device_ptrs is None:
+            X = np.asfortranarray(X, dtype=np.float64)
+            y = np.ascontiguousarray(y, dtype=np.float64)
+            N, M2 = X.shape
+            if M2 != M:
+                raise ValueError("DimensionMismatch: X is %s, P is %s" % (X.shape, P.shape))
+            xp, yp, ldX, on_dev = X.ctypes.data, y.ctypes.data, N, 0
+        else:
+            dX, dy, N, ldX = device_ptrs
+            xp, yp, on_dev = C.c_void_p(dX), C.c_void_p(dy), 1
+        fp = np.ascontiguousarray([] if fold_ptr is None else fold_ptr, dtype=np.int64)
+        F = max(len(fp) - 1, 0)
+        et = np.ascontiguousarray(np.atleast_1d(etas), dtype=np.float64)
+        E = len(et)
+        B = (F + 1) * max(E, 1)
+        alpha = np.zeros((M, B), order="F")
+        beta = np.zeros((K, B), order="F")
+        t = np.zeros(B); opt = np.zeros(B); sse = np.zeros(B)
+        bi = np.zeros(B, dtype=np.int64)
+        stat = np.zeros(B, dtype=np.int32)
+        self.generation += 1
+        _check(L.lib().partls_cv_opt(self._h, xp, int(N), int(M), int(ldX), yp, on_dev, P.ctypes.data, K, M, _ip(fp) if F else None, F,
+                                     _dp(et), E, int(flags), _dp(alpha), M, _dp(beta), K, _dp(t), _dp(opt), _ip(bi), _dp(sse),
+                                     stat.ctypes.data_as(C.POINTER(C.c_int32))))
+        return dict(alpha=alpha, beta=beta, t=t, opt=opt, best_index=bi, heldout_sse=sse, status=stat, F=F, E=E)
+
     def alt_prepared(self, alpha0, beta0, eps=1e-6, T=100):
         """Alt on a context prepared with OPT_FAITHFUL_INTERCEPT (e.g. device-resident inputs)."""
         N, M, K = self._shape
@@ -713,6 +746,112 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
                                     _dp(a), _dp(b), C.byref(t), C.byref(o), C.byref(no)))
         return PartLSFitResult(a, b, t.value, Pout), None, report(ctx, opt=o.value, nopen=no.value)
     raise TypeError("fit: first argument must be Opt, Alt or BnB")
+
+
+def cv_folds(N, nfolds=5, shuffle=False, rng=None):
+    """Folds of cross_validate: (fold_ptr[F+1], perm[N]).  Fold sizes are numpy.array_split's (the first N % F folds one row longer);
+    fold f is rows fold_ptr[f]:fold_ptr[f+1] of the data permuted by perm (the identity without shuffle; with shuffle, a permutation drawn
+    from rng: None, an int seed or a numpy Generator).  nfolds = 0 or None: no folds (fold_ptr = [0]).  nfolds = 1, a negative count and
+    nfolds > N are errors (ValueError)."""
+    N = int(N)
+    if N < 1:
+        raise ValueError("cv_folds: need N >= 1 rows")
+    if nfolds is None or int(nfolds) == 0:
+        return np.array([0], dtype=np.int64), np.arange(N, dtype=np.int64)
+    F = int(nfolds)
+    if F == 1 or F < 0:
+        raise ValueError("cv_folds: nfolds must be 0 (no folds) or >= 2, got %d" % F)
+    if F > N:
+        raise ValueError("cv_folds: %d folds for %d rows" % (F, N))
+    sizes = np.array([len(a) for a in np.array_split(np.arange(N), F)], dtype=np.int64)
+    fold_ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    if shuffle:
+        gen = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(None if rng is None else int(rng))
+        perm = gen.permutation(N).astype(np.int64)
+    else:
+        perm = np.arange(N, dtype=np.int64)
+    return fold_ptr, perm
+
+
+@dataclass
+class CVResult:
+    """What cross_validate returns.  sse / mse: F x E held-out sums / means of squared errors; mse_mean[e] = sum_f sse[f, e] / N (pooled);
+    best_eta: argmin of mse_mean over the η values whose problems all succeeded (first on ties); models[f][e] the training fits, path[e]
+    the full-data fits, model = path at best_eta; status[f][e] (F+1 rows: the last is the path) and ill_conditioned (status 9)."""
+    etas: np.ndarray
+    folds: list
+    fold_ptr: np.ndarray
+    perm: np.ndarray
+    sse: np.ndarray
+    mse: np.ndarray
+    mse_mean: np.ndarray
+    best_eta: float
+    best_index_eta: int
+    models: list
+    path: list
+    model: object
+    opt: np.ndarray
+    best_index: np.ndarray
+    status: np.ndarray
+    ill_conditioned: np.ndarray
+
+
+def cross_validate(alg, X, y, P, *, η=None, eta=None, nfolds=5, shuffle=False, rng=None, faithful_intercept=False, device=0,
+                   on_ill_conditioned="warn", generic_kernel=False):
+    """K-fold cross-validation of fit(Opt) over an η grid, plus the full-data path, in one device call (partls_cv_opt).
+
+    η/eta: the grid (default [0.0]); nfolds: F (0: the path only); shuffle / rng: rows permuted on the host first (CVResult.perm).
+    Problem (f, e) is fit(Opt, X[train_f], y[train_f], P; η = η[e]) with train_f every row outside fold f in order.
+    on_ill_conditioned: "warn" (default) keeps status-9 models and warns once, "raise" raises PartlsError(9)."""
+    if alg is not Opt:
+        raise TypeError("cross_validate: only Opt is supported")
+    if on_ill_conditioned not in ("warn", "raise"):
+        raise ValueError('on_ill_conditioned must be "warn" or "raise"')
+    grid = [0.0] if (η is None and eta is None) else (η if η is not None else eta)
+    etas = np.ascontiguousarray(np.atleast_1d(np.asarray(grid, dtype=np.float64)))
+    Xf, yf, Pf = _marshal(X, y, P)
+    N, M = Xf.shape
+    fold_ptr, perm = cv_folds(N, nfolds, shuffle, rng)
+    if shuffle:
+        Xf = np.asfortranarray(Xf[perm])
+        yf = np.ascontiguousarray(yf[perm])
+    F = len(fold_ptr) - 1
+    E = len(etas)
+    flags = (L.OPT_FAITHFUL_INTERCEPT if faithful_intercept else 0) | (L.OPT_GENERIC_KERNEL if generic_kernel else 0)
+    ctx = default_context(device)
+    r = ctx.cv_opt(Xf, yf, Pf, fold_ptr if F else None, etas, flags)
+    st = r["status"].reshape(F + 1, E)
+    if on_ill_conditioned == "raise" and np.any(st == L.ERR_ILL_CONDITIONED):
+        raise PartlsError(L.ERR_ILL_CONDITIONED, "a cross-validation problem failed its data-space KKT check")
+    if np.any(st == L.ERR_ILL_CONDITIONED):
+        warnings.warn("partitionedls: %d cross-validation problem(s) failed the data-space KKT check (X too ill-conditioned for the fp64 "
+                      "Gram form); their models are the best Gram-form ones" % int(np.sum(st == L.ERR_ILL_CONDITIONED)),
+                      IllConditionedWarning, stacklevel=2)
+    Pout = np.array(Pf, dtype=np.int64, order="C")
+
+    def model(q):
+        if r["status"][q] == L.ERR_NOT_CONVERGED:
+            return None
+        return PartLSFitResult(r["alpha"][:, q].copy(), r["beta"][:, q].copy(), float(r["t"][q]), Pout)
+
+    models = [[model(f * E + e) for e in range(E)] for f in range(F)]
+    path = [model(F * E + e) for e in range(E)]
+    sse = r["heldout_sse"].reshape(F + 1, E)[:F].copy()
+    sizes = np.diff(fold_ptr).astype(np.float64)
+    mse = sse / sizes[:, None] if F else sse
+    mse_mean = sse.sum(axis=0) / N if F else np.full(E, np.nan)
+    failed = np.any(st == L.ERR_NOT_CONVERGED, axis=0)
+    cand = np.where(failed | np.isnan(mse_mean), np.inf, mse_mean)
+    if F and np.isfinite(cand).any():
+        be = int(np.argmin(cand))
+    else:
+        be = 0 if not failed[0] else -1
+    best_eta = float(etas[be]) if be >= 0 else float("nan")
+    folds = [perm[fold_ptr[f]:fold_ptr[f + 1]] for f in range(F)]
+    return CVResult(etas=etas, folds=folds, fold_ptr=fold_ptr, perm=perm, sse=sse, mse=mse, mse_mean=mse_mean, best_eta=best_eta,
+                    best_index_eta=be, models=models, path=path, model=path[be] if be >= 0 else None,
+                    opt=r["opt"].reshape(F + 1, E).copy(), best_index=r["best_index"].reshape(F + 1, E).copy(), status=st.copy(),
+                    ill_conditioned=(st == L.ERR_ILL_CONDITIONED))
 
 
 def predict(*args, device=0):

@@ -49,7 +49,7 @@ partls_status check_common(partls_ctx *c, const void *X, int64_t N, int64_t M, i
     return PARTLS_OK;
 }
 
-static partls_status load_partition(partls_ctx *c, const int64_t *P, int64_t M, int64_t K, int64_t ldP)
+partls_status load_partition(partls_ctx *c, const int64_t *P, int64_t M, int64_t K, int64_t ldP)
 {
     c->P.assign((size_t)M * K, 0);
     c->mask_aug.assign((size_t)M + 2, 0);
@@ -83,7 +83,7 @@ namespace {
 constexpr int UP_T = 4;
 constexpr size_t UP_BUF = (size_t)8 << 20;
 }
-static partls_status upload_matrix(partls_ctx *c, double *dst, const double *X, int64_t N, int64_t M, int64_t ldX)
+partls_status upload_matrix(partls_ctx *c, double *dst, const double *X, int64_t N, int64_t M, int64_t ldX)
 {
     const size_t bytes = (size_t)N * M * sizeof(double);
     if (bytes < ((size_t)8 << 20) || c->knobs.no_staged_upload) {
@@ -191,7 +191,15 @@ partls_status ctx_prepare(partls_ctx *c, const double *X, int64_t N, int64_t M, 
     t_end(c, PARTLS_T_GRAM);
     // rows of X sharded over several devices: the Gram products of the blocks are summed here (partls_fit_opt_multi, multi.hip)
     if (c->gram_hook) { st = c->gram_hook(c); if (st != PARTLS_OK) return st; }
+    return ctx_prepare_tableau(c);
+}
 
+partls_status ctx_prepare_tableau(partls_ctx *c)
+{
+    const int64_t M = c->M, K = c->K;
+    const double eta = c->eta;
+    const bool faithful = c->faithful;
+    const uint32_t flags = c->flags;
     // tableau variables, grouped by partition (stable sort on the lowest group a variable belongs to) so that the
     // variables one Gray-code flip touches sit in as few 16-wide tile columns as possible
     c->n = faithful ? (int)M + 1 : (int)M;
@@ -892,6 +900,7 @@ try {
     c->knobs.alt_trace = getenv("PARTLS_ALT_TRACE") != nullptr;
     c->knobs.alt_always_check = getenv("PARTLS_ALT_ALWAYS_CHECK") != nullptr;
     c->knobs.print_stamps = getenv("PARTLS_PRINT_STAMPS") != nullptr;
+    c->knobs.cv_serial = getenv("PARTLS_CV_SERIAL") != nullptr && strcmp(getenv("PARTLS_CV_SERIAL"), "0") != 0;
     // a failure below must not leak the context (or the objects already created)
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     for (int w = 0; w < PARTLS_T_COUNT && e == hipSuccess; ++w) {
@@ -912,6 +921,10 @@ catch (...) { partls::set_error("internal error: an exception reached the C ABI"
 void partls_destroy(partls_ctx *c)
 {
     if (!c) return;
+    partls_destroy(c->cv_work);                           // partls_cv_opt's internal contexts (NULL when it never ran)
+    for (partls_ctx *v : c->cv_view) partls_destroy(v);
+    c->cv_work = nullptr;
+    c->cv_view.clear();
     // At process exit the HIP runtime (or a profiler layered on it) may already be torn down when a late destructor gets
     // here: touch the device only while the runtime still answers, otherwise just drop the host object.
     int ndev = 0;
@@ -922,13 +935,15 @@ void partls_destroy(partls_ctx *c)
                           &c->T0reg, &c->scratch, &c->bestObj, &c->bestPat, &c->counters, &c->allOpt, &c->wdev, &c->partial,
                           &c->yhatD, &c->gD, &c->nodeCode, &c->nodeSol, &c->nodeObj, &c->gridCtr,
                           &c->predX, &c->predY, &c->nodeTab, &c->nodeBasic, &c->altA, &c->altGA, &c->altHg,
-                          &c->nodePiv, &c->maskInt, &c->allOptRef, &c->bnbIn, &c->bnbOut, &c->altGersh, &c->mdlRows, &c->mdlOut, &c->mdlCtr};
+                          &c->nodePiv, &c->maskInt, &c->allOptRef, &c->bnbIn, &c->bnbOut, &c->altGersh, &c->mdlRows, &c->mdlOut, &c->mdlCtr,
+                          &c->cvG, &c->cvBatch, &c->cvEta};
         for (DevBuf *b : bufs) b->release();
         for (void *q : c->bnbChunks) (void)hipFree(q);
         c->bnbChunks.clear();
         c->hG.release();
         c->bnbHostIn.release(); c->bnbHostOut.release();
         c->hScale.release(); c->hPart.release(); c->hGpart.release(); c->sweepOut.release(); c->nodeOut.release(); c->exportSol.release(); c->mdlStage.release();
+        c->cvHost.release(); c->cvHostG.release();
         for (int i = 0; i < 8; ++i) { if (c->upPin[i]) (void)hipHostFree(c->upPin[i]); if (c->upEvent[i]) (void)hipEventDestroy(c->upEvent[i]); }
         for (int t = 0; t < 4; ++t) if (c->upStream[t]) (void)hipStreamDestroy(c->upStream[t]);
         if (c->hTab) (void)hipHostFree(c->hTab);
@@ -952,6 +967,8 @@ catch (...) { partls::set_error("internal error: an exception reached the C ABI"
 
 int64_t partls_opt_num_patterns(const partls_ctx *c) { return (c && c->prepared && c->kbits <= 40) ? ((int64_t)1 << c->kbits) : 0; }
 
+}  // extern "C": the Opt sweep's C++ helpers that cv.hip shares (ctx.h)
+
 // Which group sits on which bit of the Gray index.  Bit b flips in 2^-(b+1) of all transitions and a flip exchanges roughly the
 // variables of its group that carry signal, so the cheap groups belong on the fast bits: on C3 the reference's order (group k on
 // bit k) costs 16.9 M pivots / 74.9 ms, the measured-cost order 13.2 M / 51.0 ms for the same 2^20 subproblems.  The cost of a flip
@@ -960,7 +977,7 @@ int64_t partls_opt_num_patterns(const partls_ctx *c) { return (c && c->prepared 
 // exactly as in the sweep); pivots per flip are averaged per group.  Wall time = one chain = (8 + K'/2) patterns' worth, paid once
 // per prepare and only when the sweep is long enough to repay it.  Deterministic (fixed walks, no atomics in the solves), so every
 // rank of a sharded sweep derives the same order from the same data; dist.py cross-checks that before trusting the shards.
-static partls_status calibrate_bit_order(partls_ctx *c)
+partls_status partls::calibrate_bit_order(partls_ctx *c)
 {
     const int kb = c->kbits, n = c->n;
     c->order_ready = true;
@@ -1055,7 +1072,7 @@ static partls_status calibrate_bit_order(partls_ctx *c)
 }
 
 // internal pattern (group k on bit gbit[k]) -> the reference's pattern index (group k on bit k)
-static int64_t reference_pattern(const partls_ctx *c, int64_t q)
+int64_t partls::reference_pattern(const partls_ctx *c, int64_t q)
 {
     if (q < 0 || c->order_identity) return q;
     uint64_t r = 0;
@@ -1065,7 +1082,7 @@ static int64_t reference_pattern(const partls_ctx *c, int64_t q)
 
 // Chain length and grid of a sweep over `total` Gray indices (partls_opt_sweep; partls_opt_models per piece: the same plan for the same
 // range, so its rows carry the objectives all_opt gets).  false (error set): the range needs more than 2^31 chains.
-static bool sweep_plan(partls_ctx *c, int64_t total, int64_t *chain_len_out, int *grid_out, const char *who)
+bool partls::sweep_plan(partls_ctx *c, int64_t total, int64_t *chain_len_out, int *grid_out, const char *who)
 {
     // Chain length.  A chain start costs ~8 patterns' pivots, so chains should be long (~1024 patterns), but the register kernel runs ONE
     // chain per CU at a time and the chains of a range take almost equally long: the sweep lasts ceil(chains / CUs) chain times, and a
@@ -1111,6 +1128,59 @@ static bool sweep_plan(partls_ctx *c, int64_t total, int64_t *chain_len_out, int
     *grid_out = grid;
     return true;
 }
+
+// The host half of a sweep: counters, winner and near ties from the per-workgroup block the kernel left (sweep_out = [counters (4 x 8 B) |
+// best objective (grid) | best pattern (grid) | runner-up objective (grid) | runner-up pattern (grid)], patterns in the internal bit order).
+// Installs what partls_opt_finish reads: export_wg (has_sol: the kernel wrote bestSol), near_for, near_pat, cand.  partls_opt_sweep and the
+// batched sweep of partls_cv_opt (cv.hip, one block per problem) share it.
+void partls::install_sweep_result(partls_ctx *c, const double *sweep_out, int grid, bool has_sol, double *bobj_out, int64_t *bpat_out)
+{
+    unsigned long long cnt[3] = {0, 0, 0};
+    std::memcpy(cnt, sweep_out, sizeof(cnt));
+    std::vector<double> bo((size_t)grid);
+    std::vector<int64_t> bp((size_t)grid);
+    std::memcpy(bo.data(), sweep_out + 4, (size_t)grid * sizeof(double));
+    std::memcpy(bp.data(), sweep_out + 4 + grid, (size_t)grid * sizeof(int64_t));
+    c->last_pivots = cnt[1];
+    c->last_vetoes = cnt[2];
+    c->sweep_vetoes = cnt[2];
+    c->export_wg = -1;
+    double bobj = INFINITY;
+    int64_t bpat = -1;
+    int best_wg = -1;
+    for (int i = 0; i < grid; ++i) {                     // argmin with first-index tie-break (Opt.jl:96)
+        if (bp[(size_t)i] < 0) continue;
+        bp[(size_t)i] = reference_pattern(c, bp[(size_t)i]);
+        if (bpat < 0 || bo[(size_t)i] < bobj || (bo[(size_t)i] == bobj && bp[(size_t)i] < bpat)) { bobj = bo[(size_t)i]; bpat = bp[(size_t)i]; best_wg = i; }
+    }
+    if (has_sol) c->export_wg = best_wg;                 // row of bestSol that holds the winner's solution (valid while near_for == winner)
+    // Near ties.  The tracked objective^2 carries the Gram form's absolute error (a few eps * y'y, growing about as the square root
+    // of the chain length: DESIGN.md §3), so two patterns closer than that can come out in the wrong order relative to the reference,
+    // which computes every objective from the data (Opt.jl:90).  Candidates within that error of the winner — each workgroup reports its
+    // minimum and its runner-up — are remembered (at most 3, best first); partls_opt_finish re-ranks them with the objective from the data.
+    c->near_pat.clear();
+    c->cand.clear();
+    c->near_for = bpat;
+    if (bpat >= 0) {
+        const double yy = h_reg(c, (int)c->M + 1, (int)c->M + 1);
+        const double lim2 = bobj * bobj + c->knobs.near_tie_rel * (yy > 0.0 ? yy : 0.0);
+        std::vector<std::pair<double, int64_t>> cand;
+        const double *so = sweep_out + 4 + 2 * (size_t)grid;
+        const int64_t *sp = reinterpret_cast<const int64_t *>(sweep_out + 4 + 3 * (size_t)grid);
+        for (int i = 0; i < grid; ++i) {
+            if (bp[(size_t)i] >= 0 && bp[(size_t)i] != bpat && bo[(size_t)i] * bo[(size_t)i] <= lim2) cand.emplace_back(bo[(size_t)i], bp[(size_t)i]);
+            if (sp[i] >= 0 && so[i] * so[i] <= lim2) { const int64_t r = reference_pattern(c, sp[i]); if (r != bpat) cand.emplace_back(so[i], r); }
+        }
+        std::sort(cand.begin(), cand.end());
+        cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
+        c->cand.emplace_back(bobj, bpat);
+        for (size_t i = 0; i < cand.size() && c->near_pat.size() < 3; ++i) { c->near_pat.push_back(cand[i].second); c->cand.push_back(cand[i]); }
+    }
+    *bobj_out = bobj;
+    *bpat_out = bpat;
+}
+
+extern "C" {
 
 partls_status partls_opt_sweep(partls_ctx *c, int64_t g_begin, int64_t g_end, double *best_obj, int64_t *best_pattern,
                                double *all_opt, int64_t *n_unconverged)
@@ -1179,8 +1249,6 @@ try {
     PARTLS_HIP_CHECK(launch_any_sweep(c, p, grid));
     t_end(c, PARTLS_T_SWEEP);
 
-    std::vector<double> bo((size_t)grid);
-    std::vector<int64_t> bp((size_t)grid);
     unsigned long long cnt[3] = {0, 0, 0};
     PARTLS_HIP_CHECK(c->sweepOut.resize(sweep_words));
     const double *sweep_out = c->sweepOut.data();
@@ -1198,11 +1266,6 @@ try {
     PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
     t_collect(c);
     std::memcpy(cnt, sweep_out, sizeof(cnt));
-    std::memcpy(bo.data(), sweep_out + 4, (size_t)grid * sizeof(double));
-    std::memcpy(bp.data(), sweep_out + 4 + grid, (size_t)grid * sizeof(int64_t));
-    c->last_pivots = cnt[1];
-    c->last_vetoes = cnt[2];
-    c->sweep_vetoes = cnt[2];
     if (c->knobs.print_stamps) {                         // diagnostic build (-DPARTLS_STAMPS): phase shares of workgroup 0
         double st[32] = {0};
         if (hipMemcpy(st, c->scratch.p, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess)
@@ -1214,35 +1277,7 @@ try {
     }
     double bobj = INFINITY;
     int64_t bpat = -1;
-    int best_wg = -1;
-    for (int i = 0; i < grid; ++i) {                     // argmin with first-index tie-break (Opt.jl:96)
-        if (bp[(size_t)i] < 0) continue;
-        bp[(size_t)i] = reference_pattern(c, bp[(size_t)i]);
-        if (bpat < 0 || bo[(size_t)i] < bobj || (bo[(size_t)i] == bobj && bp[(size_t)i] < bpat)) { bobj = bo[(size_t)i]; bpat = bp[(size_t)i]; best_wg = i; }
-    }
-    if (p.best_sol) c->export_wg = best_wg;                 // row of bestSol that holds the winner's solution (valid while near_for == winner)
-    // Near ties.  The tracked objective^2 carries the Gram form's absolute error (a few eps * y'y, growing about as the square root
-    // of the chain length: DESIGN.md §3), so two patterns closer than that can come out in the wrong order relative to the reference,
-    // which computes every objective from the data (Opt.jl:90).  Candidates within that error of the winner — each workgroup reports its
-    // minimum and its runner-up — are remembered (at most 3, best first); partls_opt_finish re-ranks them with the objective from the data.
-    c->near_pat.clear();
-    c->cand.clear();
-    c->near_for = bpat;
-    if (bpat >= 0) {
-        const double yy = h_reg(c, (int)c->M + 1, (int)c->M + 1);
-        const double lim2 = bobj * bobj + c->knobs.near_tie_rel * (yy > 0.0 ? yy : 0.0);
-        std::vector<std::pair<double, int64_t>> cand;
-        const double *so = sweep_out + 4 + 2 * (size_t)grid;
-        const int64_t *sp = reinterpret_cast<const int64_t *>(sweep_out + 4 + 3 * (size_t)grid);
-        for (int i = 0; i < grid; ++i) {
-            if (bp[(size_t)i] >= 0 && bp[(size_t)i] != bpat && bo[(size_t)i] * bo[(size_t)i] <= lim2) cand.emplace_back(bo[(size_t)i], bp[(size_t)i]);
-            if (sp[i] >= 0 && so[i] * so[i] <= lim2) { const int64_t r = reference_pattern(c, sp[i]); if (r != bpat) cand.emplace_back(so[i], r); }
-        }
-        std::sort(cand.begin(), cand.end());
-        cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
-        c->cand.emplace_back(bobj, bpat);
-        for (size_t i = 0; i < cand.size() && c->near_pat.size() < 3; ++i) { c->near_pat.push_back(cand[i].second); c->cand.push_back(cand[i]); }
-    }
+    install_sweep_result(c, sweep_out, grid, p.best_sol != nullptr, &bobj, &bpat);
     if (best_obj) *best_obj = bobj;
     if (best_pattern) *best_pattern = bpat;
     if (n_unconverged) *n_unconverged = (int64_t)cnt[0];

@@ -84,6 +84,12 @@ struct SweepParams {
     int coop_fault;              // test hook (PARTLS_COOP_FAULT): the grid barrier expects this many arrivals too many, i.e. it can
                                  // only time out — exercises the abort word and the host's one-workgroup fallback.  77 in a launch of the deferred-update
                                  // kernel (PARTLS_LZ_FAULT): workgroup 0's first two-phase panel never publishes its progress word
+    // Batched chain-mode sweep (partls_cv_opt, cv.hip): the BATCH instantiation of the register kernels runs one problem per blockIdx.y.
+    // Problem q starts from T0 + q * batch_t0 with tolerance batch_tol[q]; best_obj, best_pat, second_obj, second_pat and the three
+    // counters are offset by q * batch_out 8-byte words, best_sol by q * gridDim.x rows of node_ld.  mask, rbit and the chain plan are
+    // the batch's.  Not read by any other instantiation.
+    int64_t batch_t0, batch_out;
+    const double *batch_tol;
 };
 
 // launchers (each returns hipError_t of the launch)
@@ -109,6 +115,10 @@ __device__ __forceinline__ bool ref_index_less(unsigned long long a, unsigned lo
 hipError_t launch_sweep_generic(const SweepParams &p, int grid, hipStream_t s, bool models = false);   // tableau in global memory, every block applied at once
 hipError_t launch_sweep_lazy(const SweepParams &p, int grid, hipStream_t s, bool models = false);      // ... updates deferred (sweep_lazy.hip): the n > 320 path
 hipError_t launch_sweep_blk(const SweepParams &p, int T, int grid, hipStream_t s, bool models = false);
+// the BATCH instantiation (chain mode, no export): grid x batch workgroups, problem q = blockIdx.y (see SweepParams::batch_t0)
+hipError_t launch_sweep_blk_batch(const SweepParams &p, int T, int grid, int batch, hipStream_t s);
+// layout_reg of `batch` stacked problems: Tfull + q * (n+1)^2 -> T0reg + q * sweep_reg_t0_doubles(T)
+hipError_t launch_layout_reg_batch(const double *Tfull, int n, int T, int batch, double *T0reg, hipStream_t s);
 hipError_t launch_sweep_coop(const SweepParams &p, int nwg, hipStream_t s);   // one node, many workgroups (n > 320)
 bool       sweep_reg_supported(int n);
 int        sweep_reg_tiles(int n);
@@ -128,6 +138,12 @@ hipError_t launch_gram(const double *X, int64_t N, int64_t M, int64_t ldX, const
 // perm[i] = augmented-Gram index of tableau variable i (variables are grouped by partition so a flip touches few tiles)
 hipError_t launch_prep(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, int free_intercept,
                        const int *perm, double *scale, double *Tfull, int n, hipStream_t s);
+// the same for `batch` problems at once (partls_cv_opt): slot q = blockIdx.y holds problem q0 + q, which reads the Gram
+// G + ((q0 + q) / E) * gstride with eta[(q0 + q) % E] (device array); writes scale + q * n, Tfull + q * (n+1)^2 and
+// tol[q] = tol_rel * sqrt(max(y'y, 0)) (1e-300 when that is not > 0)
+hipError_t launch_prep_batch(const double *G, int64_t gstride, int E, int64_t q0, const double *eta, int ldg, int M, const uint64_t *mask_aug,
+                             int free_intercept, const int *perm, double tol_rel, double *scale, double *Tfull, double *tol, int n,
+                             int batch, hipStream_t s);
 
 // bit-order calibration (misc.hip): node codes of the calibration walks, and all_opt from internal to reference pattern order
 int        walk_flipped_bit(int chain, int step, int kbits, int seg_len, int nseg);

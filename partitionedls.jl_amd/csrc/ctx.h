@@ -80,6 +80,7 @@ struct partls_knobs {
                                  // PARTLS_ERR_ILL_CONDITIONED instead of PARTLS_OK (see kkt_says_ill_conditioned, api.hip)
     double near_tie_rel = 1e-13; // PARTLS_NEAR_TIE_REL (tests): width of the near-tie window of the sweep, in units of y'y on the objective^2
     double cal_wb = 1.0, cal_ws = 1.0;  // PARTLS_CAL_WB / PARTLS_CAL_WS: multipliers of the block / scan weights of the bit-order cost model (experiments)
+    bool cv_serial = false;      // PARTLS_CV_SERIAL: partls_cv_opt sweeps its problems one after another through partls_opt_sweep (A/B tests, timing)
     int bit_order = 0;           // PARTLS_BIT_ORDER: 0 automatic (calibrate when the sweep is long enough to repay it), "identity" = 1
                                  // (group k on Gray bit k), "calibrate" = 2 (always measure; small problems in the tests)
 };
@@ -167,6 +168,14 @@ struct partls_ctx {
     int8_t *hBasic = nullptr;
     size_t hTabDoubles = 0;
     bool tab_valid = false, tab_full = false;
+    // partls_cv_opt (cv.hip): internal same-device contexts, created on first use and destroyed with this one.  cv_work holds one problem
+    // at a time for the finish (its G, tableau, winner); cv_view[g] is a view of the rows of fold g (dX, dy, N, ldX into this context's
+    // upload) — the peers of cv_work's data passes and the target of the held-out residual.  cvG: fold Grams, then the combined Grams;
+    // cvBatch: stacked per-problem state of a chunk (scale, Tfull, T0reg, tolerances, sweep results); cvHost: their host copies.
+    partls_ctx *cv_work = nullptr;
+    std::vector<partls_ctx *> cv_view;
+    partls::DevBuf cvG, cvBatch, cvEta;
+    partls::PinnedDoubles cvHost, cvHostG;
 };
 
 namespace partls {
@@ -178,6 +187,17 @@ void t_collect(partls_ctx *c);
 // Upload (or adopt) X, y; build the Gram products; lay the tableau out.  faithful = intercept is a regular variable.
 partls_status ctx_prepare(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
                           const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags);
+// The second half of ctx_prepare: from the Gram products in c->G (c->M, K, eta, flags, faithful and the partition already set) to the
+// tableau, the host copies and the tolerance.  partls_cv_opt calls it on a context whose G it filled itself.
+partls_status ctx_prepare_tableau(partls_ctx *c);
+partls_status load_partition(partls_ctx *c, const int64_t *P, int64_t M, int64_t K, int64_t ldP);
+// host X (N x M, ldX) -> packed device image (ld N) on c->stream, staged through page-locked buffers when large
+partls_status upload_matrix(partls_ctx *c, double *dst, const double *X, int64_t N, int64_t M, int64_t ldX);
+// the Opt sweep's pieces that partls_cv_opt shares (api.hip)
+partls_status calibrate_bit_order(partls_ctx *c);
+bool sweep_plan(partls_ctx *c, int64_t total, int64_t *chain_len_out, int *grid_out, const char *who);
+int64_t reference_pattern(const partls_ctx *c, int64_t q);
+void install_sweep_result(partls_ctx *c, const double *sweep_out, int grid, bool has_sol, double *bobj_out, int64_t *bpat_out);
 
 // Solve a batch of `cnt` independent subproblems ("nodes") from the fresh tableau.  codes[i * n + v] is the constraint on
 // tableau variable v in node i: +1 (w >= 0), -1 (w <= 0), 0 (w = 0), 2 (free) — see SweepParams::node_code.  sols: cnt x n

@@ -1,0 +1,396 @@
+// cv.hip — partls_cv_opt (include/partls.h): K-fold cross-validation of fit(Opt) over an η grid, and the full-data regularisation
+// path, in one call.  X goes up once; every fold's Gram products are built once (one launch_gram per row slice) and combined into the
+// training Gram of every fold (the sum of the other folds') and of all rows; the (F+1) x E problems are prepared in one batched launch
+// and swept in one launch of the BATCH instantiation of the register kernels (blockIdx.y = problem).  Each problem is then finished as
+// partls_opt_finish finishes a single fit (near-tie re-rank from the data, refinement, KKT check, cleanupResult), on an internal working
+// context whose data passes cover exactly its training rows (row-block views of the folds as its peers).  DESIGN.md §4.6.
+#include "ctx.h"
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <algorithm>
+
+namespace partls {
+
+// out[f] = sum over the folds g != f of Gf[g], g ascending (f < F); out[F] = sum over every fold.  nf = max(F, 1) fold Grams at stride gs.
+// A fixed order and no atomics: bitwise reproducible.
+__global__ __launch_bounds__(256) void fold_gram_combine_kernel(const double *__restrict__ Gf, int nf, int F, int64_t gs, int64_t cnt,
+                                                                double *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cnt) return;
+    const int f = blockIdx.y;
+    double s = 0.0;
+    for (int g = 0; g < nf; ++g)
+        if (f == F || g != f) s += Gf[(int64_t)g * gs + i];
+    out[(int64_t)f * gs + i] = s;
+}
+
+static hipError_t launch_fold_gram_combine(const double *Gf, int nf, int F, int64_t gs, double *out, hipStream_t s)
+{
+    const int64_t cnt = gs;
+    hipLaunchKernelGGL(fold_gram_combine_kernel, dim3((unsigned)((cnt + 255) / 256), F + 1), dim3(256), 0, s, Gf, nf, F, gs, cnt, out);
+    return hipGetLastError();
+}
+
+static partls_status make_internal(partls_ctx *c, partls_ctx **slot)
+{
+    if (*slot) return PARTLS_OK;
+    partls_status st = partls_create(c->device, slot);
+    if (st != PARTLS_OK) return st;
+    (*slot)->knobs = c->knobs;
+    return PARTLS_OK;
+}
+
+// the working context sees the training rows of problem fold f (f == F: all rows): its own rows are the first training fold, the
+// other training folds are its peers (data_pass, api.hip, sums context then peers in order)
+static void point_rows(partls_ctx *c, partls_ctx *W, const int64_t *fold_ptr, int64_t F, int64_t f)
+{
+    W->peers.clear();
+    W->ldX = c->ldX;
+    if (f == F) { W->dX = c->dX; W->dy = c->dy; W->N = c->N; return; }
+    bool first = true;
+    for (int64_t g = 0; g < F; ++g) {
+        if (g == f) continue;
+        if (first) {
+            W->dX = c->dX + fold_ptr[g]; W->dy = c->dy + fold_ptr[g]; W->N = fold_ptr[g + 1] - fold_ptr[g];
+            first = false;
+        } else {
+            W->peers.push_back(c->cv_view[(size_t)g]);
+        }
+    }
+}
+
+// what the caller gets per problem (host staging; nothing reaches the caller's arrays before the whole call has succeeded)
+struct CvOut {
+    std::vector<double> alpha, beta, t, opt, sse;
+    std::vector<int64_t> best;
+    std::vector<int32_t> status;
+};
+
+// Finish problem q on W (prepared state already installed): the tested single-fit finish, then the held-out SSE on fold f's rows.
+static partls_status finish_one(partls_ctx *c, partls_ctx *W, const int64_t *fold_ptr, int64_t F, int64_t f, int64_t q, int64_t bpat,
+                                int64_t unconv, CvOut &o)
+{
+    const int64_t M = c->M, K = c->K;
+    double *a = o.alpha.data() + (size_t)q * M, *b = o.beta.data() + (size_t)q * K;
+    partls_status st = PARTLS_ERR_NOT_CONVERGED;
+    if (bpat >= 0) {
+        point_rows(c, W, fold_ptr, F, f);
+        st = partls_opt_finish(W, bpat, a, b, &o.t[(size_t)q], &o.opt[(size_t)q], &o.best[(size_t)q]);
+        W->peers.clear();
+        if (st == PARTLS_OK && unconv) st = PARTLS_ERR_NOT_CONVERGED;
+    }
+    if (st != PARTLS_OK && st != PARTLS_ERR_ILL_CONDITIONED && st != PARTLS_ERR_NOT_CONVERGED) return st;
+    o.status[(size_t)q] = (int32_t)st;
+    if (st == PARTLS_ERR_NOT_CONVERGED) {
+        std::fill(a, a + M, NAN);
+        std::fill(b, b + K, NAN);
+        o.t[(size_t)q] = NAN; o.opt[(size_t)q] = NAN; o.best[(size_t)q] = -1; o.sse[(size_t)q] = NAN;
+        return PARTLS_OK;
+    }
+    o.sse[(size_t)q] = NAN;
+    if (f < F) {
+        // predict (PartitionedLS.jl:132): yhat = X (P .* alpha) beta .+ t, i.e. w_m = alpha_m sum_k P[m,k] beta_k, on fold f's rows
+        std::vector<double> w((size_t)M + 1, 0.0);
+        for (int64_t m = 0; m < M; ++m) {
+            double s = 0.0;
+            for (int64_t k = 0; k < K; ++k) if (c->cv_work->P[(size_t)m + (size_t)k * M]) s += b[k];
+            w[(size_t)m] = a[m] * s;
+        }
+        w[(size_t)M] = o.t[(size_t)q];
+        partls_ctx *v = c->cv_view[(size_t)f];
+        double s2 = 0.0;
+        const partls_status ds = data_pass(v, w, true, false, &s2, nullptr, {});
+        if (ds != PARTLS_OK) return ds;
+        o.sse[(size_t)q] = s2;
+    }
+    return PARTLS_OK;
+}
+
+static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
+                            const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F, const double *eta, int64_t E,
+                            uint32_t flags, CvOut &o)
+{
+    const int64_t B = (F + 1) * E;
+    const int nf = F > 0 ? (int)F : 1;
+    const bool faithful = (flags & PARTLS_OPT_FAITHFUL_INTERCEPT) != 0;
+    for (int w = 0; w < PARTLS_T_COUNT; ++w) c->ms[w] = 0.0;
+    PARTLS_HIP_CHECK(hipSetDevice(c->device));
+    // this context keeps the upload and the Gram products; it holds no prepared problem afterwards
+    c->prepared = false;
+    c->peers.clear();
+    c->near_for = -1; c->near_pat.clear(); c->cand.clear();
+    c->last_upload_ms = 0.0; c->last_upload_bytes = 0.0;
+    c->N = N; c->M = M; c->K = K; c->flags = flags; c->faithful = faithful;
+
+    // ---- one upload
+    if (x_on_device) {
+        c->dX = X; c->dy = y; c->ldX = ldX;
+    } else {
+        PARTLS_HIP_CHECK(c->ownX.ensure((size_t)N * M * sizeof(double)));
+        PARTLS_HIP_CHECK(c->ownY.ensure((size_t)N * sizeof(double)));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(c->ownY.p, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        const auto u0 = std::chrono::steady_clock::now();
+        partls_status st = upload_matrix(c, c->ownX.as<double>(), X, N, M, ldX);
+        if (st != PARTLS_OK) return st;
+        c->last_upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+        c->last_upload_bytes = (double)N * (double)M * sizeof(double);
+        c->dX = c->ownX.as<double>(); c->dy = c->ownY.as<double>(); c->ldX = N;
+    }
+
+    // ---- internal contexts: the working context and one row view per fold
+    partls_status st = make_internal(c, &c->cv_work);
+    if (st != PARTLS_OK) return st;
+    partls_ctx *W = c->cv_work;
+    W->knobs = c->knobs;
+    if (c->cv_view.size() < (size_t)F) c->cv_view.resize((size_t)F, nullptr);
+    for (int64_t g = 0; g < F; ++g) {
+        st = make_internal(c, &c->cv_view[(size_t)g]);
+        if (st != PARTLS_OK) return st;
+        partls_ctx *v = c->cv_view[(size_t)g];
+        v->dX = c->dX + fold_ptr[g]; v->dy = c->dy + fold_ptr[g]; v->ldX = c->ldX;
+        v->N = fold_ptr[g + 1] - fold_ptr[g]; v->M = M; v->K = K;
+        v->peers.clear();
+    }
+
+    // ---- one Gram launch per fold (row slice X + fold_ptr[g], y + fold_ptr[g], ldX unchanged), then the combine
+    int ldg = 0, chunks = 0;
+    size_t slabd = 0;
+    for (int g = 0; g < nf; ++g) {
+        const int64_t n_g = F > 0 ? fold_ptr[g + 1] - fold_ptr[g] : N;
+        slabd = std::max(slabd, gram_slab_doubles(n_g, M, c->knobs.gram_S, c->knobs.gram_cr, &chunks, &ldg));
+    }
+    c->ldg = ldg;
+    const int64_t gs = (int64_t)ldg * ldg;
+    PARTLS_HIP_CHECK(c->slab.ensure(slabd * sizeof(double)));
+    PARTLS_HIP_CHECK(c->cvG.ensure((size_t)(nf + F + 1) * gs * sizeof(double)));
+    double *Gf = c->cvG.as<double>(), *Gc = Gf + (size_t)nf * gs;
+    t_begin(c, PARTLS_T_GRAM);
+    for (int g = 0; g < nf; ++g) {
+        const int64_t r0 = F > 0 ? fold_ptr[g] : 0, n_g = F > 0 ? fold_ptr[g + 1] - fold_ptr[g] : N;
+        int ch = 0, ld2 = 0;
+        (void)gram_slab_doubles(n_g, M, c->knobs.gram_S, c->knobs.gram_cr, &ch, &ld2);
+        PARTLS_HIP_CHECK(launch_gram(c->dX + r0, n_g, M, c->ldX, c->dy + r0, c->slab.as<double>(), ch, ldg, c->knobs.gram_S, c->knobs.gram_cr,
+                                     Gf + (size_t)g * gs, c->stream));
+    }
+    PARTLS_HIP_CHECK(launch_fold_gram_combine(Gf, nf, (int)F, gs, Gc, c->stream));
+    t_end(c, PARTLS_T_GRAM);
+    PARTLS_HIP_CHECK(c->cvHostG.resize((size_t)(F + 1) * gs));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->cvHostG.data(), Gc, (size_t)(F + 1) * gs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    t_collect(c);
+    // NaN / Inf in [X y]: the diagonal of the all-rows Gram is non-finite (ctx_prepare's test; a sum of the folds' non-negative diagonals)
+    const double *Gall = c->cvHostG.data() + (size_t)F * gs;
+    for (int64_t i = 0; i < M + 2; ++i) {
+        if (i == M) continue;
+        if (!std::isfinite(Gall[(size_t)i * ldg + i])) { set_error("partls_cv_opt: X or y contains NaN/Inf (or overflows in X'X)"); return PARTLS_ERR_NONFINITE; }
+    }
+
+    // ---- the working context: the problem's shape, partition and Gram; prepared first for the full-data problem at eta[0], on which the
+    // visiting order of the whole batch is calibrated (the rule of a single fit decides whether that pays)
+    W->prepared = false;
+    W->peers.clear();
+    W->near_for = -1; W->near_pat.clear(); W->cand.clear();
+    W->sweep_vetoes = 0;
+    W->coop_state_valid = false;
+    W->order_ready = false; W->order_identity = true; W->flip_cost.clear();
+    W->gram_hook = nullptr;
+    st = load_partition(W, P, M, K, ldP);
+    if (st != PARTLS_OK) return st;
+    W->M = M; W->K = K; W->flags = flags; W->faithful = faithful;
+    W->ldg = ldg; W->chunks = chunks;
+    PARTLS_HIP_CHECK(W->G.ensure((size_t)gs * sizeof(double)));
+    auto load_problem_gram = [&](int64_t f) -> partls_status {
+        PARTLS_HIP_CHECK(hipMemcpyAsync(W->G.p, Gc + (size_t)f * gs, (size_t)gs * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+        return PARTLS_OK;
+    };
+    st = load_problem_gram(F);
+    if (st != PARTLS_OK) return st;
+    W->eta = eta[0];
+    point_rows(c, W, fold_ptr, F, F);
+    st = ctx_prepare_tableau(W);
+    if (st != PARTLS_OK) return st;
+    W->peers.clear();
+    if ((int64_t)W->kbits > 40) { set_error("partls_cv_opt: %d sign bits: the enumeration is out of range (K <= 39)", W->kbits); return PARTLS_ERR_UNSUPPORTED; }
+    st = calibrate_bit_order(W);
+    if (st != PARTLS_OK) return st;
+    c->ms[PARTLS_T_CALIB] = W->ms[PARTLS_T_CALIB];
+    const int n = W->n;
+    const int64_t npat = (int64_t)1 << W->kbits;
+
+    double ms_prep = 0.0, ms_sweep = 0.0, ms_finish = 0.0;
+    // ---- every problem on its own through the existing launchers: n > 288, PARTLS_OPT_GENERIC_KERNEL, PARTLS_CV_SERIAL
+    if (!W->use_reg || c->knobs.cv_serial) {
+        for (int64_t q = 0; q < B; ++q) {
+            const int64_t f = q / E, e = q % E;
+            st = load_problem_gram(f);
+            if (st != PARTLS_OK) return st;
+            W->eta = eta[e];
+            st = ctx_prepare_tableau(W);
+            if (st != PARTLS_OK) return st;
+            ms_prep += W->ms[PARTLS_T_PREP];
+            double bobj = 0.0;
+            int64_t bpat = -1, unconv = 0;
+            st = partls_opt_sweep(W, 0, -1, &bobj, &bpat, nullptr, &unconv);
+            if (st != PARTLS_OK) return st;
+            ms_sweep += W->ms[PARTLS_T_SWEEP];
+            const auto f0 = std::chrono::steady_clock::now();
+            st = finish_one(c, W, fold_ptr, F, f, q, bpat, unconv, o);
+            if (st != PARTLS_OK) return st;
+            ms_finish += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
+        }
+        c->ms[PARTLS_T_PREP] = ms_prep; c->ms[PARTLS_T_SWEEP] = ms_sweep; c->ms[PARTLS_T_FINISH] = ms_finish;
+        return PARTLS_OK;
+    }
+
+    // ---- batched: chunks of problems whose stacked tableaux stay below PARTLS_OPT_MODELS_PIECE_BYTES and whose count fits gridDim.y
+    const int T = W->T;
+    const size_t t0d = sweep_reg_t0_doubles(T), tfd = (size_t)(n + 1) * (n + 1);
+    const size_t tab_bytes = (tfd + t0d + (size_t)n + 1) * sizeof(double);
+    const int64_t bc_max = std::max<int64_t>(1, std::min<int64_t>(65535, (int64_t)(PARTLS_OPT_MODELS_PIECE_BYTES / tab_bytes)));
+    const bool want_sol = (sweep_reg_small(T) || sweep_reg_exports(T)) && !c->knobs.no_export;
+    PARTLS_HIP_CHECK(c->cvEta.ensure((size_t)E * sizeof(double)));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->cvEta.p, eta, (size_t)E * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    PARTLS_HIP_CHECK(c->scratch.ensure(64 * sizeof(double)));
+    BitOrder rbit;
+    for (int k = 0; k < 40; ++k) rbit.gbit[k] = (uint8_t)k;
+    if (!W->order_identity) for (int k = 0; k < W->kbits; ++k) rbit.gbit[W->order.gbit[k]] = (uint8_t)k;
+    hipEvent_t ev[4];
+    for (int i = 0; i < 4; ++i) PARTLS_HIP_CHECK(hipEventCreate(&ev[i]));
+    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; ++i) (void)hipEventDestroy(e[i]); } } evg{ev};
+    for (int64_t q0 = 0; q0 < B; q0 += bc_max) {
+        const int bc = (int)std::min<int64_t>(bc_max, B - q0);
+        int64_t chain_len = 0;
+        int grid_all = 0;
+        if (!sweep_plan(W, npat * bc, &chain_len, &grid_all, "partls_cv_opt")) return PARTLS_ERR_UNSUPPORTED;
+        const int64_t nch = (npat + chain_len - 1) / chain_len;
+        const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(nch, (grid_all + bc - 1) / bc));
+        const size_t out_w = 4 + 4 * (size_t)gx;
+        // [scale (bc x n) | Tfull (bc x (n+1)^2) | T0reg (bc x t0d) | tol (bc) | sweep blocks (bc x out_w) | best_sol (bc x gx x n)]
+        const size_t o_scale = 0, o_tf = o_scale + (size_t)bc * n, o_t0 = o_tf + (size_t)bc * tfd, o_tol = o_t0 + (size_t)bc * t0d,
+                     o_out = o_tol + (size_t)bc, o_sol = o_out + (size_t)bc * out_w, words = o_sol + (want_sol ? (size_t)bc * gx * n : 0);
+        PARTLS_HIP_CHECK(c->cvBatch.ensure(words * sizeof(double)));
+        double *base = c->cvBatch.as<double>();
+        PARTLS_HIP_CHECK(hipEventRecord(ev[0], c->stream));
+        PARTLS_HIP_CHECK(launch_prep_batch(Gc, gs, (int)E, q0, c->cvEta.as<double>(), ldg, (int)M, W->maskAugD.as<uint64_t>(), faithful ? 0 : 1,
+                                           W->permP, c->knobs.tol_rel, base + o_scale, base + o_tf, base + o_tol, n, bc, c->stream));
+        PARTLS_HIP_CHECK(launch_layout_reg_batch(base + o_tf, n, T, bc, base + o_t0, c->stream));
+        PARTLS_HIP_CHECK(hipMemsetAsync(base + o_out, 0, (size_t)bc * out_w * sizeof(double), c->stream));
+        PARTLS_HIP_CHECK(hipEventRecord(ev[1], c->stream));
+        SweepParams p{};
+        p.n = n; p.kbits = W->kbits;
+        p.mask = W->order_identity ? W->maskTabP : W->maskInt.as<uint64_t>();
+        p.T0 = base + o_t0;
+        p.scratch = c->scratch.as<double>();
+        p.g_begin = 0; p.g_end = npat; p.chain_len = chain_len;
+        p.tol = 0.0; p.piv_eps = 1e-11; p.max_rounds = 20 * (n + 1);
+        double *ob = base + o_out;
+        p.n_unconverged = reinterpret_cast<unsigned long long *>(ob);
+        p.n_pivots = reinterpret_cast<unsigned long long *>(ob) + 1;
+        p.n_vetoes = reinterpret_cast<unsigned long long *>(ob) + 2;
+        p.best_obj = ob + 4; p.best_pat = reinterpret_cast<int64_t *>(ob + 4 + gx);
+        p.second_obj = ob + 4 + 2 * (size_t)gx; p.second_pat = reinterpret_cast<int64_t *>(ob + 4 + 3 * (size_t)gx);
+        p.rbit = rbit;
+        if (want_sol) { p.best_sol = base + o_sol; p.node_ld = n; }
+        p.batch_t0 = (int64_t)t0d; p.batch_out = (int64_t)out_w; p.batch_tol = base + o_tol;
+        PARTLS_HIP_CHECK(launch_sweep_blk_batch(p, T, gx, bc, c->stream));
+        PARTLS_HIP_CHECK(hipEventRecord(ev[2], c->stream));
+        // host copies: scale, tolerances, sweep blocks
+        const size_t hw = (size_t)bc * n + (size_t)bc + (size_t)bc * out_w;
+        PARTLS_HIP_CHECK(c->cvHost.resize(hw));
+        double *h = c->cvHost.data();
+        PARTLS_HIP_CHECK(hipMemcpyAsync(h, base + o_scale, (size_t)bc * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(h + (size_t)bc * n, base + o_tol, ((size_t)bc + (size_t)bc * out_w) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        float f01 = 0.f, f12 = 0.f;
+        if (hipEventElapsedTime(&f01, ev[0], ev[1]) == hipSuccess) ms_prep += f01;
+        if (hipEventElapsedTime(&f12, ev[1], ev[2]) == hipSuccess) ms_sweep += f12;
+        const double *hscale = h, *htol = h + (size_t)bc * n, *hout = htol + bc;
+        const auto f0 = std::chrono::steady_clock::now();
+        for (int j = 0; j < bc; ++j) {
+            const int64_t q = q0 + j, f = q / E, e = q % E;
+            // install problem q's prepared state on the working context: what ctx_prepare_tableau would have left (the batched kernels
+            // compute the same entries) and what partls_opt_sweep would have left (winner, near ties, the winner's exported solution)
+            W->eta = eta[e];
+            std::memcpy(W->hG.data(), c->cvHostG.data() + (size_t)f * gs, (size_t)gs * sizeof(double));
+            std::memcpy(W->hScale.data(), hscale + (size_t)j * n, (size_t)n * sizeof(double));
+            W->tol = htol[j];
+            PARTLS_HIP_CHECK(hipMemcpyAsync(W->G.p, Gc + (size_t)f * gs, (size_t)gs * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+            PARTLS_HIP_CHECK(hipMemcpyAsync(W->scale.p, base + o_scale + (size_t)j * n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+            PARTLS_HIP_CHECK(hipMemcpyAsync(W->Tfull.p, base + o_tf + (size_t)j * tfd, tfd * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+            PARTLS_HIP_CHECK(hipMemcpyAsync(W->T0reg.p, base + o_t0 + (size_t)j * t0d, t0d * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+            if (want_sol) {
+                PARTLS_HIP_CHECK(W->bestSol.ensure((size_t)gx * n * sizeof(double)));
+                PARTLS_HIP_CHECK(hipMemcpyAsync(W->bestSol.p, base + o_sol + (size_t)j * gx * n, (size_t)gx * n * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+            }
+            W->coop_state_valid = false;
+            W->tab_valid = false;
+            W->prepared = true;
+            double bobj = 0.0;
+            int64_t bpat = -1;
+            const double *blk = hout + (size_t)j * out_w;
+            install_sweep_result(W, blk, gx, want_sol, &bobj, &bpat);
+            unsigned long long unconv = 0;
+            std::memcpy(&unconv, blk, sizeof(unconv));
+            st = finish_one(c, W, fold_ptr, F, f, q, bpat, (int64_t)unconv, o);
+            if (st != PARTLS_OK) return st;
+        }
+        ms_finish += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
+    }
+    c->ms[PARTLS_T_PREP] = ms_prep; c->ms[PARTLS_T_SWEEP] = ms_sweep; c->ms[PARTLS_T_FINISH] = ms_finish;
+    return PARTLS_OK;
+}
+
+}  // namespace partls
+
+using namespace partls;
+
+partls_status partls_cv_opt(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
+                            const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F,
+                            const double *eta, int64_t E, uint32_t flags,
+                            double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t, double *opt,
+                            int64_t *best_index, double *heldout_sse, int32_t *status)
+try {
+    partls_status st = check_common(c, X, N, M, ldX, P, K, ldP);
+    if (st != PARTLS_OK) return st;
+    if (!y) { set_error("partls_cv_opt: y is NULL"); return PARTLS_ERR_BAD_ARG; }
+    if (F < 0 || F == 1) { set_error("partls_cv_opt: F = %lld folds (need F = 0 for the path only, or F >= 2)", (long long)F); return PARTLS_ERR_BAD_ARG; }
+    if (F > 0) {
+        if (!fold_ptr) { set_error("partls_cv_opt: fold_ptr is NULL"); return PARTLS_ERR_BAD_ARG; }
+        if (F > N) { set_error("partls_cv_opt: F = %lld folds for N = %lld rows", (long long)F, (long long)N); return PARTLS_ERR_BAD_ARG; }
+        if (fold_ptr[0] != 0 || fold_ptr[F] != N) { set_error("partls_cv_opt: fold_ptr must start at 0 and end at N"); return PARTLS_ERR_BAD_ARG; }
+        for (int64_t g = 0; g < F; ++g)
+            if (!(fold_ptr[g] < fold_ptr[g + 1])) { set_error("partls_cv_opt: fold_ptr must be strictly increasing (fold %lld)", (long long)g); return PARTLS_ERR_BAD_ARG; }
+    }
+    if (E < 1 || !eta) { set_error("partls_cv_opt: need E >= 1 eta values"); return PARTLS_ERR_BAD_ARG; }
+    for (int64_t e = 0; e < E; ++e)
+        if (!(eta[e] >= 0.0) || !std::isfinite(eta[e])) { set_error("partls_cv_opt: eta[%lld] = %g must be finite and >= 0", (long long)e, eta[e]); return PARTLS_ERR_BAD_ARG; }
+    if (!alpha || !beta || !t || !opt || !best_index || !heldout_sse || !status) { set_error("partls_cv_opt: NULL output"); return PARTLS_ERR_BAD_ARG; }
+    if (ld_alpha < M || ld_beta < K) { set_error("partls_cv_opt: leading dimension of alpha / beta too small"); return PARTLS_ERR_BAD_ARG; }
+    if ((F + 1) > ((int64_t)1 << 40) / E) { set_error("partls_cv_opt: too many problems"); return PARTLS_ERR_BAD_ARG; }
+    if ((flags & PARTLS_OPT_FAITHFUL_INTERCEPT ? K + 1 : K) > 40) {
+        set_error("partls_cv_opt: K = %lld: the enumeration of fit(Opt) is out of range (K <= 39)", (long long)K);
+        return PARTLS_ERR_UNSUPPORTED;
+    }
+    const int64_t B = (F + 1) * E;
+    CvOut o;
+    o.alpha.assign((size_t)B * M, 0.0); o.beta.assign((size_t)B * K, 0.0);
+    o.t.assign((size_t)B, 0.0); o.opt.assign((size_t)B, 0.0); o.sse.assign((size_t)B, NAN);
+    o.best.assign((size_t)B, -1); o.status.assign((size_t)B, 0);
+    st = cv_run(c, X, N, M, ldX, y, x_on_device, P, K, ldP, fold_ptr, F, eta, E, flags, o);
+    if (st != PARTLS_OK) return st;
+    for (int64_t q = 0; q < B; ++q) {
+        std::memcpy(alpha + q * ld_alpha, o.alpha.data() + (size_t)q * M, (size_t)M * sizeof(double));
+        std::memcpy(beta + q * ld_beta, o.beta.data() + (size_t)q * K, (size_t)K * sizeof(double));
+    }
+    std::memcpy(t, o.t.data(), (size_t)B * sizeof(double));
+    std::memcpy(opt, o.opt.data(), (size_t)B * sizeof(double));
+    std::memcpy(best_index, o.best.data(), (size_t)B * sizeof(int64_t));
+    std::memcpy(heldout_sse, o.sse.data(), (size_t)B * sizeof(double));
+    std::memcpy(status, o.status.data(), (size_t)B * sizeof(int32_t));
+    set_error("");
+    return PARTLS_OK;
+}
+catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
+catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }

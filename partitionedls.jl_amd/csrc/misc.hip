@@ -126,6 +126,63 @@ hipError_t launch_prep(const double *G, int ldg, int M, double eta, const uint64
     return hipGetLastError();
 }
 
+// Batched preparation (partls_cv_opt): problem q = q0 + blockIdx.y reads the Gram G + (q / E) * gstride with eta[q % E] and writes slot
+// blockIdx.y of the outputs; the same entries as above.
+// Launched twice: scale (+ the tolerance from the problem's own y'y) first, then the tableau that reads it.
+__global__ void prep_scale_batch_kernel(const double *__restrict__ G, int64_t gstride, int E, int64_t q0, const double *__restrict__ eta, int ldg, int M,
+                                        const uint64_t *__restrict__ mask_aug, int free_intercept, const int *__restrict__ perm, int n,
+                                        double tol_rel, double *__restrict__ scale, double *__restrict__ tol)
+{
+    const int q = blockIdx.y;
+    const int64_t qq = q0 + q;
+    const double *Gq = G + (qq / E) * gstride;
+    const double e = eta[qq % E];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const double yy = Gq[(size_t)(M + 1) * ldg + (M + 1)];
+        const double t = tol_rel * sqrt(yy > 0.0 ? yy : 0.0);
+        tol[q] = t > 0.0 ? t : 1e-300;
+    }
+    if (i >= n) return;
+    const double d = base_entry(Gq, ldg, M, e, mask_aug, free_intercept, perm, n, i, i);
+    const double ref = Gq[(size_t)perm[i] * ldg + perm[i]];
+    scale[(int64_t)q * n + i] = (d > 0.0 && d > 1e-14 * fabs(ref)) ? 1.0 / sqrt(d) : 0.0;
+}
+
+__global__ void prep_tableau_batch_kernel(const double *__restrict__ G, int64_t gstride, int E, int64_t q0, const double *__restrict__ eta, int ldg,
+                                          int M, const uint64_t *__restrict__ mask_aug, int free_intercept, const int *__restrict__ perm,
+                                          int n, const double *__restrict__ scale, double *__restrict__ Tfull)
+{
+    const int q = blockIdx.y;
+    const int64_t qq = q0 + q;
+    const double *Gq = G + (qq / E) * gstride;
+    const double e = eta[qq % E];
+    const double *sq = scale + (int64_t)q * n;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int ld = n + 1;
+    if (idx >= ld * ld) return;
+    const int i = idx / ld, j = idx % ld;
+    const double si = (i < n) ? sq[i] : 1.0, sj = (j < n) ? sq[j] : 1.0;
+    double v = base_entry(Gq, ldg, M, e, mask_aug, free_intercept, perm, n, i, j) * si * sj;
+    if (i == j && i < n && si == 0.0) v = 1.0;
+    Tfull[(int64_t)q * ld * ld + idx] = v;
+}
+
+hipError_t launch_prep_batch(const double *G, int64_t gstride, int E, int64_t q0, const double *eta, int ldg, int M, const uint64_t *mask_aug,
+                             int free_intercept, const int *perm, double tol_rel, double *scale, double *Tfull, double *tol, int n,
+                             int batch, hipStream_t s)
+{
+    if (batch < 1 || batch > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(prep_scale_batch_kernel, dim3((n + 255) / 256, batch), dim3(256), 0, s, G, gstride, E, q0, eta, ldg, M, mask_aug,
+                       free_intercept, perm, n, tol_rel, scale, tol);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int tot = (n + 1) * (n + 1);
+    hipLaunchKernelGGL(prep_tableau_batch_kernel, dim3((tot + 255) / 256, batch), dim3(256), 0, s, G, gstride, E, q0, eta, ldg, M, mask_aug,
+                       free_intercept, perm, n, scale, Tfull);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Bit-order calibration of the Opt sweep (api.hip: calibrate_bit_order).  Bit b of the Gray index flips in 2^-(b+1) of all
 // transitions, so which group sits on which bit decides how many variables the sweep exchanges: measured on C3, the same 2^20

@@ -652,9 +652,27 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
 // are computed from LDS words or kernel arguments that are identical for all 512 threads — never from a half's own registers —
 // so both instantiations execute the same barrier sequence: per scan 1, per block 2 + m (the m panel steps; idle waves only
 // count them).  Any edit that makes a barrier conditional on per-half or per-wave data deadlocks the CU.
-template <int T, bool NODE, bool MODELS = false>
+// BATCH (chain mode only, partls_cv_opt): blockIdx.y selects one problem of a stacked batch; its tableau, tolerance and result slots
+// replace the launch's before the body runs (SweepParams::batch_t0).  A separate instantiation: the default ones keep their code.
+__device__ __forceinline__ void batch_select(SweepParams &p)
+{
+    const int64_t q = blockIdx.y;
+    p.T0 += q * p.batch_t0;
+    p.tol = p.batch_tol[q];
+    const int64_t o = q * p.batch_out;
+    p.best_obj += o;
+    p.best_pat += o;
+    if (p.second_obj) { p.second_obj += o; p.second_pat += o; }
+    if (p.n_unconverged) p.n_unconverged += o;
+    if (p.n_pivots) p.n_pivots += o;
+    if (p.n_vetoes) p.n_vetoes += o;
+    if (p.best_sol) p.best_sol += q * (int64_t)gridDim.x * p.node_ld;
+}
+
+template <int T, bool NODE, bool MODELS = false, bool BATCH = false>
 __global__ __launch_bounds__(THREADS, 2) void sweep_blk_kernel(SweepParams p)
 {
+    if constexpr (BATCH) batch_select(p);
     const int half = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
     if (half == 0) sweep_body<T, 0, NODE, 2, MODELS>(p);
     else sweep_body<T, 1, NODE, 2, MODELS>(p);
@@ -663,9 +681,10 @@ __global__ __launch_bounds__(THREADS, 2) void sweep_blk_kernel(SweepParams p)
 #ifndef PARTLS_SMALL_OCC
 #define PARTLS_SMALL_OCC(T) ((T) <= 8 ? 3 : 2)          // waves per SIMD = workgroups per CU the allocator is asked to leave room for
 #endif
-template <int T, bool NODE, bool MODELS = false>
+template <int T, bool NODE, bool MODELS = false, bool BATCH = false>
 __global__ __launch_bounds__(256, PARTLS_SMALL_OCC(T)) void sweep_small_kernel(SweepParams p)
 {
+    if constexpr (BATCH) batch_select(p);
     sweep_body<T, 0, NODE, 1, MODELS>(p);
 }
 
@@ -692,6 +711,31 @@ __global__ void layout_reg_kernel(const double *__restrict__ Tfull, int n, int T
     }
 }
 
+__global__ void layout_reg_batch_kernel(const double *__restrict__ Tfull, int n, int T, double *__restrict__ out)
+{
+    const int64_t q = blockIdx.y;
+    const int ns = T * (T + 1) / 2;
+    const int tot = ns * 256 + 16 * T + 1;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= tot) return;
+    const int ld = n + 1;
+    const double *Tq = Tfull + q * (int64_t)ld * ld;
+    double *oq = out + q * (int64_t)(ns * 256 + 16 * T + 8);
+    if (idx < ns * 256) {
+        const int s = idx >> 8, t8 = idx & 255, a = t8 & 15, b = t8 >> 4;
+        int gam = 0;
+        while ((gam + 1) * (gam + 2) / 2 <= s) ++gam;
+        const int rho = s - gam * (gam + 1) / 2;
+        const int i = 16 * rho + a, j = 16 * gam + b;
+        oq[idx] = (i < n && j < n) ? Tq[(size_t)i * ld + j] : ((i == j) ? 1.0 : 0.0);
+    } else if (idx < ns * 256 + 16 * T) {
+        const int v = idx - ns * 256;
+        oq[idx] = (v < n) ? Tq[(size_t)v * ld + n] : 0.0;
+    } else {
+        oq[idx] = Tq[(size_t)n * ld + n];
+    }
+}
+
 }  // namespace blk
 
 bool sweep_reg_supported(int n) { return n >= 1 && n <= 16 * blk::MAXT; }
@@ -705,6 +749,36 @@ hipError_t launch_layout_reg(const double *Tfull, int n, int T, double *T0reg, h
     const int tot = T * (T + 1) / 2 * 256 + 16 * T + 1;
     hipLaunchKernelGGL(blk::layout_reg_kernel, dim3((tot + 255) / 256), dim3(256), 0, s, Tfull, n, T, T0reg);
     return hipGetLastError();
+}
+
+hipError_t launch_layout_reg_batch(const double *Tfull, int n, int T, int batch, double *T0reg, hipStream_t s)
+{
+    const int tot = T * (T + 1) / 2 * 256 + 16 * T + 1;
+    hipLaunchKernelGGL(blk::layout_reg_batch_kernel, dim3((tot + 255) / 256, batch), dim3(256), 0, s, Tfull, n, T, T0reg);
+    return hipGetLastError();
+}
+
+template <int T>
+static hipError_t launch_blk_batch_T(const SweepParams &p, int grid, int batch, hipStream_t s)
+{
+    if constexpr (T <= blk::MAXT_S) hipLaunchKernelGGL((blk::sweep_small_kernel<T, false, false, true>), dim3(grid, batch), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((blk::sweep_blk_kernel<T, false, false, true>), dim3(grid, batch), dim3(blk::THREADS), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_sweep_blk_batch(const SweepParams &p, int T, int grid, int batch, hipStream_t s)
+{
+    if (p.node_code || batch < 1 || batch > 65535) return hipErrorInvalidValue;
+    switch (T) {
+#ifdef PARTLS_ONLY_T
+        case PARTLS_ONLY_T: return launch_blk_batch_T<PARTLS_ONLY_T>(p, grid, batch, s);
+#else
+#define PARTLS_L(i) case i + 1: return launch_blk_batch_T<i + 1>(p, grid, batch, s);
+        PARTLS_CASES(PARTLS_L)
+#undef PARTLS_L
+#endif
+        default: return hipErrorInvalidValue;
+    }
 }
 
 template <int T>
