@@ -312,6 +312,9 @@ partls_status partls_get_pivots(const partls_ctx *ctx, int64_t *pivots);
 /* entering pivots the last partls_opt_sweep refused under the leave-one-out dependence rule (0 on well-conditioned data; a
  * large count says the data are rank deficient on the unit-diagonal scale — see DESIGN.md §4, numerical notes) */
 partls_status partls_get_vetoes(const partls_ctx *ctx, int64_t *vetoes);
+/* pivot blocks the cooperative kernel (one node on a global-memory tableau, n > 288) exchanged in the last single-node solve; 0 when
+ * that solve ran on another kernel — including the one-workgroup retry after a grid-barrier timeout on a crowded device */
+partls_status partls_get_blocks(const partls_ctx *ctx, int64_t *blocks);
 /* data-space KKT violation of the model the last partls_opt_finish / partls_bnb_leaf (hence fit(Opt), fit(BnB)) returned: the largest
  * of |x_m'r| (passive or free variable), f_m x_m'r (variable at its bound) and -f_m w_m / max|w| over every variable, r = yo - Xo w
  * computed from the data, in units of ||x_m|| ||y||.  <= 3e-15 on data the Gram form resolves; above 1e-12 (PARTLS_KKT_TOL) the call

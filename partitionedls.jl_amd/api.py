@@ -329,6 +329,12 @@ class Context:
         _check(L.lib().partls_get_vetoes(self._h, C.byref(n)))
         return n.value
 
+    def blocks(self):
+        """pivot blocks of the cooperative kernel in the last single-node solve (0: the solve ran on another kernel)"""
+        n = C.c_int64()
+        _check(L.lib().partls_get_blocks(self._h, C.byref(n)))
+        return n.value
+
     def kkt_violation(self):
         """data-space KKT violation of the last finished winner (include/partls.h: partls_get_kkt_violation)"""
         v = C.c_double()

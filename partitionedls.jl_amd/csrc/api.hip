@@ -1707,6 +1707,15 @@ try {
 catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
 catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
 
+partls_status partls_get_blocks(const partls_ctx *c, int64_t *blocks)
+try {
+    if (!c || !blocks) { set_error("partls_get_blocks: bad argument"); return PARTLS_ERR_BAD_ARG; }
+    *blocks = (int64_t)c->last_blocks;
+    return PARTLS_OK;
+}
+catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
+catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+
 partls_status partls_opt_bit_order(partls_ctx *c, int64_t *gbit, double *flip_cost)
 try {
     if (!c || !c->prepared) { set_error("partls_opt_bit_order: context not prepared"); return PARTLS_ERR_STATE; }

@@ -106,37 +106,15 @@ def _bnb_problem():
 
 
 def _oracle_bound_fn(X, y, P):
-    """(pats, frees) -> (lb, branch): BnB.jl:69-92,107,117 restated with the oracle's dense NNLS on [Xp Xm]."""
-    import numpy as np
-    from oracle import oracle as O
-    N, M = X.shape
-    K = P.shape[1]
-    Xo = np.column_stack([X, np.ones(N)])
-    groups = [np.nonzero(P[:, k])[0] for k in range(K)] + [np.array([M])]
+    """(pats, frees) -> (lb, branch): BnB.jl:69-92,107,117 through the shared per-node reference (tests/bnb_reference.py)."""
+    from bnb_reference import NodeReference
+    ref = NodeReference(X, y, P)
 
     def bound(pats, frees):
-        lbs, brs = [], []
-        for pat, free in zip(pats.tolist(), frees.tolist()):
-            cols, owner, sign = [], [], []
-            state = np.zeros(M + 1, dtype=int)                    # bit 0: alpha >= 0 present, bit 1: alpha <= 0 present
-            for k, g in enumerate(groups):
-                if not (free >> k) & 1:
-                    state[g] |= 1 if (pat >> k) & 1 else 2
-            for m in range(M + 1):
-                if not state[m] & 2:
-                    cols.append(Xo[:, m]); owner.append(m); sign.append(1.0)
-                if not state[m] & 1:
-                    cols.append(-Xo[:, m]); owner.append(m); sign.append(-1.0)
-            A = np.column_stack(cols) if cols else np.zeros((N, 1))
-            x, rn, mode, _ = O.nnls(A, y)
-            w = np.zeros(M + 1)
-            for xi, m, sg in zip(x, owner, sign):
-                w[m] += sg * xi
-            nu = [float(np.clip(w[g], 0, None).sum() * np.clip(-w[g], 0, None).sum()) if (free >> k) & 1 else 0.0
-                  for k, g in enumerate(groups)]
-            kb = int(np.argmax(nu))
-            lbs.append(rn); brs.append(kb if nu[kb] > 0 else -1)
-        return np.array(lbs), np.array(brs, dtype=np.int32)
+        r = ref.nodes(pats, frees)
+        if not r["certified"].all():
+            raise RuntimeError("the node reference could not certify nodes %s" % r["certified"].nonzero()[0].tolist())
+        return r["lb"], r["branch"]
     return bound
 
 

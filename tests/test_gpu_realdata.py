@@ -22,6 +22,8 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from bnb_reference import ld_data_objective as _ld_data_objective
+
 U = 2.0 ** -53                     # unit round-off of fp64
 NEAR_TIE_REL = 1e-13               # ctx.h: default width of the sweep's near-tie window, in units of y'y on obj^2
 
@@ -102,17 +104,6 @@ def _frac(x):
 
 def _exact(Z, i, j):
     return sum((Fraction(float(a)) * Fraction(float(b)) for a, b in zip(Z[:, i], Z[:, j])), Fraction(0))
-
-
-def _ld_data_objective(X, y, w, t, block=32):
-    """||y - X w - t|| in long double, X in column blocks (memory stays at one block of long doubles)."""
-    r = y.astype(np.longdouble) - np.longdouble(t)
-    for j0 in range(0, X.shape[1], block):
-        j1 = min(X.shape[1], j0 + block)
-        nz = np.flatnonzero(w[j0:j1])
-        if len(nz):
-            r -= X[:, j0 + nz].astype(np.longdouble) @ w[j0:j1][nz].astype(np.longdouble)
-    return float(np.sqrt(np.dot(r, r)))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
