@@ -127,6 +127,23 @@ partls_status partls_multi_get_timing(const partls_multi *mc, int rank, int whic
  * finish:   solves the given pattern once more on its own, computes opt from the data, normalises (cleanupResult). */
 partls_status partls_opt_prepare(partls_ctx *ctx, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
                                  int x_on_device, const int64_t *P, int64_t K, int64_t ldP, double eta, uint32_t flags);
+/* ---- sample weights: the same prepare for the weighted problem (MLJ's supports_weights, scikit-learn's sample_weight) ---------------
+ *   minimise  sum_i w_i (x_i' (P .* α) β + t - y_i)^2  +  the η rows of regularizeProblem (PartitionedLS.jl:108-123, NOT weighted)
+ * over the same feasible set and sign patterns.  w[N]: every w_i finite and >= 0, sum w_i > 0; a row with w_i = 0 acts as an absent row
+ * (its X and y must still be finite).  w follows x_on_device: a host array, or a DEVICE array that stays owned by the caller and must
+ * stay valid while the context holds this problem.  w == NULL is exactly partls_opt_prepare.
+ * Errors (found before anything else is written; the context is left unprepared): NaN / Inf in w -> PARTLS_ERR_NONFINITE; a negative
+ * weight or sum w_i = 0 -> PARTLS_ERR_BAD_ARG; a context of a partls_multi -> PARTLS_ERR_UNSUPPORTED (multi-GPU fits are unweighted).
+ * Every staged call on the problem is then weighted — partls_opt_sweep, _finish, _pattern, _candidates, _merge_candidates, _models,
+ * _bit_order, partls_alt_prepared, partls_bnb_prepared, partls_bnb_bound(_snap), partls_bnb_leaf, partls_bnb_search — with "sum over
+ * rows" read as "weighted sum over rows" in every output: opt, all_opt, best_index, the near-tie window (1e-13 of y'Wy on obj^2),
+ * the data-space KKT check and PARTLS_ERR_ILL_CONDITIONED.  partls_predict is unchanged (weights do not enter a prediction).
+ * A weighted fit(Opt) is this + partls_opt_sweep + partls_opt_finish; a weighted fit(Alt) is
+ * partls_opt_prepare_weighted(..., PARTLS_OPT_FAITHFUL_INTERCEPT) + partls_alt_prepared, a weighted fit(BnB) the same prepare +
+ * partls_bnb_prepared.  The next plain prepare (or fit) on the context is unweighted again.  DESIGN.md §4.7. */
+partls_status partls_opt_prepare_weighted(partls_ctx *ctx, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
+                                          const double *w, int x_on_device, const int64_t *P, int64_t K, int64_t ldP, double eta,
+                                          uint32_t flags);
 partls_status partls_opt_sweep(partls_ctx *ctx, int64_t g_begin, int64_t g_end,
                                double *best_obj, int64_t *best_pattern, double *all_opt, int64_t *n_unconverged);
 partls_status partls_opt_finish(partls_ctx *ctx, int64_t pattern,
@@ -208,6 +225,15 @@ partls_status partls_cv_opt(partls_ctx *ctx, const double *X, int64_t N, int64_t
                             const double *eta, int64_t E, uint32_t flags,
                             double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t, double *opt,
                             int64_t *best_index, double *heldout_sse, int32_t *status);
+/* The same with sample weights w[N] (rules and errors of partls_opt_prepare_weighted; w follows x_on_device; w == NULL is exactly
+ * partls_cv_opt): problem (f, e) is the weighted fit on the training rows of fold f with their weights, and
+ * heldout_sse[q] = sum over the rows i of fold f of w_i (predict(model, x_i) - y_i)^2.  A fold whose training rows weigh 0 in total
+ * fails the call with PARTLS_ERR_BAD_ARG. */
+partls_status partls_cv_opt_weighted(partls_ctx *ctx, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
+                                     const double *w, int x_on_device, const int64_t *P, int64_t K, int64_t ldP,
+                                     const int64_t *fold_ptr, int64_t F, const double *eta, int64_t E, uint32_t flags,
+                                     double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t, double *opt,
+                                     int64_t *best_index, double *heldout_sse, int32_t *status);
 
 /* ---- fit(Alt, X, y, P; η, ϵ, T)  — replaces Alt.jl:50-124 ------------------------------------------------------------
  * alpha0[M+1], beta0[K+1]: the random initial point the Julia shim draws exactly as Alt.jl:58-66 does.

@@ -37,6 +37,8 @@ SYMBOLS = [
     ("partls_multi_get_timing", C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp]),
     ("partls_opt_prepare", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, C.c_int, C.c_void_p, _i64, _i64,
                                      C.c_double, C.c_uint32]),
+    ("partls_opt_prepare_weighted", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                              _i64, _i64, C.c_double, C.c_uint32]),
     ("partls_opt_sweep", C.c_int, [C.c_void_p, _i64, _i64, _dp, _ip, _dp, _ip]),
     ("partls_opt_finish", C.c_int, [C.c_void_p, _i64, _dp, _dp, _dp, _dp, _ip]),
     ("partls_opt_candidates", C.c_int, [C.c_void_p, _i64, _dp, _ip, _ip]),
@@ -45,6 +47,9 @@ SYMBOLS = [
     ("partls_opt_models", C.c_int, [C.c_void_p, _i64, _i64, _ip, _dp, _dp, _i64, _dp, _i64, _dp, _i64, _dp, _ip, _ip]),
     ("partls_cv_opt", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, C.c_int, C.c_void_p, _i64, _i64, _ip, _i64,
                                 _dp, _i64, C.c_uint32, _dp, _i64, _dp, _i64, _dp, _dp, _ip, _dp, C.POINTER(C.c_int32)]),
+    ("partls_cv_opt_weighted", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64,
+                                         _i64, _ip, _i64, _dp, _i64, C.c_uint32, _dp, _i64, _dp, _i64, _dp, _dp, _ip, _dp,
+                                         C.POINTER(C.c_int32)]),
     ("partls_opt_num_patterns", _i64, [C.c_void_p]),
     ("partls_opt_bit_order", C.c_int, [C.c_void_p, _ip, _dp]),
     ("partls_fit_alt", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, C.c_void_p, _i64, _i64, C.c_double,

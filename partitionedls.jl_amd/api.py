@@ -113,24 +113,37 @@ class Context:
             pass
 
     # ---- staged Opt path -------------------------------------------------------------------------------------------
-    def opt_prepare(self, X, y, P, eta=0.0, flags=0):
-        """X, y: host arrays (float64, any layout; copied F-contiguous)."""
+    def opt_prepare(self, X, y, P, eta=0.0, flags=0, weights=None):
+        """X, y: host arrays (float64, any layout; copied F-contiguous).  weights: optional per-row sample weights (host, length N):
+        partls_opt_prepare_weighted, after which every staged call on the problem is weighted."""
         X = np.asfortranarray(X, dtype=np.float64)
         y = np.ascontiguousarray(y, dtype=np.float64)
         P = np.asfortranarray(P, dtype=np.int64)
         N, M = X.shape
         self._shape = (N, M, P.shape[1])
         self.generation += 1
-        _check(L.lib().partls_opt_prepare(self._h, X.ctypes.data, N, M, N, y.ctypes.data, 0, P.ctypes.data, P.shape[1],
-                                          P.shape[0], float(eta), int(flags)))
+        if weights is None:
+            _check(L.lib().partls_opt_prepare(self._h, X.ctypes.data, N, M, N, y.ctypes.data, 0, P.ctypes.data, P.shape[1],
+                                              P.shape[0], float(eta), int(flags)))
+        else:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            if w.shape != (N,):
+                raise ValueError("weights: expected shape (%d,), got %s" % (N, w.shape))
+            _check(L.lib().partls_opt_prepare_weighted(self._h, X.ctypes.data, N, M, N, y.ctypes.data, w.ctypes.data, 0, P.ctypes.data,
+                                                       P.shape[1], P.shape[0], float(eta), int(flags)))
 
-    def opt_prepare_device(self, dX_ptr, dy_ptr, N, M, ldX, P, eta=0.0, flags=0):
-        """dX_ptr, dy_ptr: raw device addresses (e.g. torch tensor .data_ptr()) that stay owned by the caller."""
+    def opt_prepare_device(self, dX_ptr, dy_ptr, N, M, ldX, P, eta=0.0, flags=0, dw_ptr=None):
+        """dX_ptr, dy_ptr (and dw_ptr, optional per-row sample weights, N doubles): raw device addresses (e.g. torch tensor
+        .data_ptr()) that stay owned by the caller."""
         P = np.asfortranarray(P, dtype=np.int64)
         self._shape = (N, M, P.shape[1])
         self.generation += 1
-        _check(L.lib().partls_opt_prepare(self._h, C.c_void_p(dX_ptr), N, M, ldX, C.c_void_p(dy_ptr), 1, P.ctypes.data,
-                                          P.shape[1], P.shape[0], float(eta), int(flags)))
+        if dw_ptr is None:
+            _check(L.lib().partls_opt_prepare(self._h, C.c_void_p(dX_ptr), N, M, ldX, C.c_void_p(dy_ptr), 1, P.ctypes.data,
+                                              P.shape[1], P.shape[0], float(eta), int(flags)))
+        else:
+            _check(L.lib().partls_opt_prepare_weighted(self._h, C.c_void_p(dX_ptr), N, M, ldX, C.c_void_p(dy_ptr), C.c_void_p(dw_ptr), 1,
+                                                       P.ctypes.data, P.shape[1], P.shape[0], float(eta), int(flags)))
 
     def num_patterns(self):
         return int(L.lib().partls_opt_num_patterns(self._h))
@@ -210,13 +223,15 @@ class Context:
             out["raw_alpha"] = ra
         return out
 
-    def cv_opt(self, X, y, P, fold_ptr, etas, flags=0, device_ptrs=None):
+    def cv_opt(self, X, y, P, fold_ptr, etas, flags=0, device_ptrs=None, weights=None):
         """partls_cv_opt: fit(Opt) on every (fold, η) training set and on all rows, in one call.  X, y: host arrays, or
-        device_ptrs=(dX_ptr, dy_ptr, N, ldX) for device-resident inputs (X then ignored; pass X=None).  fold_ptr: F+1 boundaries (None or
-        [] for the path only).  Returns a dict of column-major results, one problem per column, q = f * E + e: alpha (M x B), beta (K x B),
+        device_ptrs=(dX_ptr, dy_ptr, N, ldX[, dw_ptr]) for device-resident inputs (X then ignored; pass X=None).  fold_ptr: F+1 boundaries
+        (None or [] for the path only).  weights (host inputs) / dw_ptr (device inputs): optional per-row sample weights
+        (partls_cv_opt_weighted).  Returns a dict of column-major results, one problem per column, q = f * E + e: alpha (M x B), beta (K x B),
         t, opt, best_index, heldout_sse, status (all length B)."""
         P = np.asfortranarray(P, dtype=np.int64)
         M, K = P.shape
+        wp = None
         if device_ptrs is None:
             X = np.asfortranarray(X, dtype=np.float64)
             y = np.ascontiguousarray(y, dtype=np.float64)
@@ -224,9 +239,18 @@ class Context:
             if M2 != M:
                 raise ValueError("DimensionMismatch: X is %s, P is %s" % (X.shape, P.shape))
             xp, yp, ldX, on_dev = X.ctypes.data, y.ctypes.data, N, 0
+            if weights is not None:
+                w = np.ascontiguousarray(weights, dtype=np.float64)
+                if w.shape != (N,):
+                    raise ValueError("weights: expected shape (%d,), got %s" % (N, w.shape))
+                wp = w.ctypes.data
         else:
-            dX, dy, N, ldX = device_ptrs
+            if weights is not None:
+                raise ValueError("cv_opt: device inputs take their weights as the fifth entry of device_ptrs")
+            dX, dy, N, ldX = device_ptrs[:4]
             xp, yp, on_dev = C.c_void_p(dX), C.c_void_p(dy), 1
+            if len(device_ptrs) > 4 and device_ptrs[4] is not None:
+                wp = C.c_void_p(device_ptrs[4])
         fp = np.ascontiguousarray([] if fold_ptr is None else fold_ptr, dtype=np.int64)
         F = max(len(fp) - 1, 0)
         et = np.ascontiguousarray(np.atleast_1d(etas), dtype=np.float64)
@@ -238,9 +262,14 @@ class Context:
         bi = np.zeros(B, dtype=np.int64)
         stat = np.zeros(B, dtype=np.int32)
         self.generation += 1
-        _check(L.lib().partls_cv_opt(self._h, xp, int(N), int(M), int(ldX), yp, on_dev, P.ctypes.data, K, M, _ip(fp) if F else None, F,
-                                     _dp(et), E, int(flags), _dp(alpha), M, _dp(beta), K, _dp(t), _dp(opt), _ip(bi), _dp(sse),
-                                     stat.ctypes.data_as(C.POINTER(C.c_int32))))
+        if wp is None:
+            _check(L.lib().partls_cv_opt(self._h, xp, int(N), int(M), int(ldX), yp, on_dev, P.ctypes.data, K, M, _ip(fp) if F else None, F,
+                                         _dp(et), E, int(flags), _dp(alpha), M, _dp(beta), K, _dp(t), _dp(opt), _ip(bi), _dp(sse),
+                                         stat.ctypes.data_as(C.POINTER(C.c_int32))))
+        else:
+            _check(L.lib().partls_cv_opt_weighted(self._h, xp, int(N), int(M), int(ldX), yp, wp, on_dev, P.ctypes.data, K, M,
+                                                  _ip(fp) if F else None, F, _dp(et), E, int(flags), _dp(alpha), M, _dp(beta), K, _dp(t),
+                                                  _dp(opt), _ip(bi), _dp(sse), stat.ctypes.data_as(C.POINTER(C.c_int32))))
         return dict(alpha=alpha, beta=beta, t=t, opt=opt, best_index=bi, heldout_sse=sse, status=stat, F=F, E=E)
 
     def alt_prepared(self, alpha0, beta0, eps=1e-6, T=100):
@@ -583,6 +612,26 @@ def _marshal(X, y, P):
             np.asfortranarray(P, dtype=np.int64))
 
 
+def _weights(weights, N, who):
+    """sample weights of fit / cross_validate, checked on the host before any device work: 1-D, length N, floating, finite, >= 0,
+    sum > 0 (ValueError otherwise) -> contiguous float64, or None"""
+    if weights is None:
+        return None
+    w = np.asarray(weights)
+    if w.ndim != 1 or w.shape[0] != N:
+        raise ValueError("%s: weights must be a vector of length N = %d, got shape %s" % (who, N, w.shape))
+    if not np.issubdtype(w.dtype, np.floating):
+        raise ValueError("%s: weights must be floating point, got %s" % (who, w.dtype))
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if not np.all(np.isfinite(w)):
+        raise ValueError("%s: weights must be finite" % who)
+    if np.any(w < 0):
+        raise ValueError("%s: weights must be >= 0" % who)
+    if not w.sum() > 0:
+        raise ValueError("%s: the weights sum to 0" % who)
+    return w
+
+
 class _Solutions:
     """returnAllSolutions (Opt.jl:99-101): element b is (opt_b, PartLSFitResult_b); models are rebuilt on demand from the context
     that holds the fitted problem.  They stay valid whatever is fitted afterwards, as in the reference: when a later fit has taken
@@ -598,9 +647,10 @@ class _Solutions:
 
     def _context(self):
         if self._owner.generation != self._gen:        # the shared context now holds another problem
-            Xf, yf, Pf, eta, flags, device = self._problem
+            Xf, yf, Pf, eta, flags, device = self._problem[:6]
+            w = self._problem[6] if len(self._problem) > 6 else None         # sample weights of a weighted fit
             self._ctx = self._owner = Context(device)
-            self._ctx.opt_prepare(Xf, yf, Pf, eta, flags)
+            self._ctx.opt_prepare(Xf, yf, Pf, eta, flags, weights=w)
             self._gen = self._ctx.generation
         return self._ctx
 
@@ -656,7 +706,8 @@ class _Solutions:
 
 
 def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="nnls", returnAllSolutions=False, rng=None,
-        alpha0=None, beta0=None, device=0, devices=None, faithful_intercept=False, generic_kernel=False, on_ill_conditioned="warn"):
+        alpha0=None, beta0=None, device=0, devices=None, faithful_intercept=False, generic_kernel=False, on_ill_conditioned="warn",
+        weights=None):
     """fit(::Type{Opt|Alt|BnB}, X, y, P; η, ...) -> (PartLSFitResult, None, Report)   [Opt.jl:73, Alt.jl:50, BnB.jl:30]
 
     η/eta: regularisation (default 0.0);  Alt: ϵ/eps (1e-6), T (100), rng (None | int seed | numpy Generator) or an
@@ -669,6 +720,9 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
     the reference's QR-based NNLS still returns a model there, and the Julia patch reroutes to it): "warn" (default) returns the best
     Gram-form model with report.ill_conditioned = True and report.kkt_violation set, and emits IllConditionedWarning; "raise" raises
     PartlsError(status 9).
+    weights: optional per-row sample weights w[N] (floating, finite, >= 0, sum > 0): the data term becomes sum_i w_i r_i^2 (the η rows
+    stay unweighted) and report.opt its square root with the η rows; a row of weight 0 acts as an absent row.  Single device only
+    (NotImplementedError with devices=).  DESIGN.md §4.7.
     """
     if alg not in (Opt, Alt, BnB):
         raise TypeError("fit: first argument must be Opt, Alt or BnB")
@@ -681,6 +735,9 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
     Xf, yf, Pf = _marshal(X, y, P)
     N, M = Xf.shape
     K = Pf.shape[1]
+    wf = _weights(weights, N, "fit")
+    if wf is not None and devices is not None:
+        raise NotImplementedError("fit: sample weights are not supported on several devices (devices=)")
     ctx = default_context(device)
     ctx.tolerate_ill = on_ill_conditioned == "warn"
     ctx.last_ill = False
@@ -710,14 +767,14 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
                 c0._shape = (N, M, K)
                 return model, None, report(mc, solutions=_Solutions(c0, allopt, Pout, (Xf, yf, Pf, eta_v, flags, mc.devices[0])))
             return model, None, report(mc, opt=opt, best_index=bi)
-        ctx.opt_prepare(Xf, yf, Pf, eta_v, flags)
+        ctx.opt_prepare(Xf, yf, Pf, eta_v, flags, weights=wf)
         bobj, bpat, allopt, unconv = ctx.opt_sweep(0, -1, want_all=returnAllSolutions)
         if unconv:
             raise PartlsError(L.ERR_NOT_CONVERGED, f"{unconv} subproblems hit the pivot cap")
         a, b, t, opt, bi = ctx.opt_finish(bpat)
         model = PartLSFitResult(a, b, t, Pout)
         if returnAllSolutions:
-            return model, None, report(ctx, solutions=_Solutions(ctx, allopt, Pout, (Xf, yf, Pf, eta_v, flags, device)))
+            return model, None, report(ctx, solutions=_Solutions(ctx, allopt, Pout, (Xf, yf, Pf, eta_v, flags, device, wf)))
         return model, None, report(ctx, opt=opt, best_index=bi)
     if alg is Alt:
         if alpha0 is None or beta0 is None:
@@ -733,6 +790,10 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
         b0 = np.ascontiguousarray(beta0, dtype=np.float64)
         if a0.shape != (M + 1,) or b0.shape != (K + 1,):
             raise ValueError("alpha0 must have M+1 and beta0 K+1 entries")
+        if wf is not None:                                # partls_fit_alt = prepare (faithful) + partls_alt_prepared
+            ctx.opt_prepare(Xf, yf, Pf, eta_v, L.OPT_FAITHFUL_INTERCEPT, weights=wf)
+            a, b, t, o, it = ctx.alt_prepared(a0, b0, eps_v, int(T))
+            return PartLSFitResult(a, b, t, Pout), None, report(ctx, opt=o, iters=it)
         a = np.zeros(M); b = np.zeros(K)
         t = C.c_double(); o = C.c_double(); it = C.c_int64()
         ctx.generation += 1
@@ -745,6 +806,10 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
             mc.tolerate_ill = ctx.tolerate_ill
             a, b, t, opt, nopen = mc.fit_bnb(Xf, yf, Pf, eta_v)
             return PartLSFitResult(a, b, t, Pout), None, report(mc, opt=opt, nopen=nopen)
+        if wf is not None:                                # partls_fit_bnb = prepare (faithful) + partls_bnb_prepared
+            ctx.opt_prepare(Xf, yf, Pf, eta_v, L.OPT_FAITHFUL_INTERCEPT, weights=wf)
+            a, b, t, o, no = ctx.bnb_prepared()
+            return PartLSFitResult(a, b, t, Pout), None, report(ctx, opt=o, nopen=no)
         a = np.zeros(M); b = np.zeros(K)
         t = C.c_double(); o = C.c_double(); no = C.c_int64()
         ctx.generation += 1
@@ -782,6 +847,7 @@ def cv_folds(N, nfolds=5, shuffle=False, rng=None):
 @dataclass
 class CVResult:
     """What cross_validate returns.  sse / mse: F x E held-out sums / means of squared errors; mse_mean[e] = sum_f sse[f, e] / N (pooled);
+    with sample weights, sse is weighted and the means divide by the weight of the fold / of all rows instead of the row counts;
     best_eta: argmin of mse_mean over the η values whose problems all succeeded (first on ties); models[f][e] the training fits, path[e]
     the full-data fits, model = path at best_eta; status[f][e] (F+1 rows: the last is the path) and ill_conditioned (status 9)."""
     etas: np.ndarray
@@ -803,12 +869,14 @@ class CVResult:
 
 
 def cross_validate(alg, X, y, P, *, η=None, eta=None, nfolds=5, shuffle=False, rng=None, faithful_intercept=False, device=0,
-                   on_ill_conditioned="warn", generic_kernel=False):
+                   on_ill_conditioned="warn", generic_kernel=False, weights=None):
     """K-fold cross-validation of fit(Opt) over an η grid, plus the full-data path, in one device call (partls_cv_opt).
 
     η/eta: the grid (default [0.0]); nfolds: F (0: the path only); shuffle / rng: rows permuted on the host first (CVResult.perm).
     Problem (f, e) is fit(Opt, X[train_f], y[train_f], P; η = η[e]) with train_f every row outside fold f in order.
-    on_ill_conditioned: "warn" (default) keeps status-9 models and warns once, "raise" raises PartlsError(9)."""
+    on_ill_conditioned: "warn" (default) keeps status-9 models and warns once, "raise" raises PartlsError(9).
+    weights: optional per-row sample weights (as fit; permuted with the rows by shuffle): problem (f, e) is the weighted fit on train_f,
+    sse[f, e] = sum over fold f of w_i r_i^2, mse[f, e] = sse[f, e] / (weight of fold f), mse_mean[e] = sum_f sse[f, e] / sum_i w_i."""
     if alg is not Opt:
         raise TypeError("cross_validate: only Opt is supported")
     if on_ill_conditioned not in ("warn", "raise"):
@@ -817,15 +885,22 @@ def cross_validate(alg, X, y, P, *, η=None, eta=None, nfolds=5, shuffle=False, 
     etas = np.ascontiguousarray(np.atleast_1d(np.asarray(grid, dtype=np.float64)))
     Xf, yf, Pf = _marshal(X, y, P)
     N, M = Xf.shape
+    wf = _weights(weights, N, "cross_validate")
     fold_ptr, perm = cv_folds(N, nfolds, shuffle, rng)
     if shuffle:
         Xf = np.asfortranarray(Xf[perm])
         yf = np.ascontiguousarray(yf[perm])
+        if wf is not None:
+            wf = np.ascontiguousarray(wf[perm])
+    if wf is not None and len(fold_ptr) > 1:
+        pos = np.add.reduceat((wf > 0).astype(np.int64), fold_ptr[:-1])
+        if np.any(pos == pos.sum()):
+            raise ValueError("cross_validate: the training rows of some fold have zero total weight")
     F = len(fold_ptr) - 1
     E = len(etas)
     flags = (L.OPT_FAITHFUL_INTERCEPT if faithful_intercept else 0) | (L.OPT_GENERIC_KERNEL if generic_kernel else 0)
     ctx = default_context(device)
-    r = ctx.cv_opt(Xf, yf, Pf, fold_ptr if F else None, etas, flags)
+    r = ctx.cv_opt(Xf, yf, Pf, fold_ptr if F else None, etas, flags, weights=wf)
     st = r["status"].reshape(F + 1, E)
     if on_ill_conditioned == "raise" and np.any(st == L.ERR_ILL_CONDITIONED):
         raise PartlsError(L.ERR_ILL_CONDITIONED, "a cross-validation problem failed its data-space KKT check")
@@ -843,9 +918,14 @@ def cross_validate(alg, X, y, P, *, η=None, eta=None, nfolds=5, shuffle=False, 
     models = [[model(f * E + e) for e in range(E)] for f in range(F)]
     path = [model(F * E + e) for e in range(E)]
     sse = r["heldout_sse"].reshape(F + 1, E)[:F].copy()
-    sizes = np.diff(fold_ptr).astype(np.float64)
-    mse = sse / sizes[:, None] if F else sse
-    mse_mean = sse.sum(axis=0) / N if F else np.full(E, np.nan)
+    if wf is None:
+        sizes, total = np.diff(fold_ptr).astype(np.float64), N
+    else:
+        sizes = np.array([wf[fold_ptr[f]:fold_ptr[f + 1]].sum() for f in range(F)])
+        total = wf.sum()
+    with np.errstate(divide="ignore", invalid="ignore"):          # a held-out fold of weight 0 has no mean (NaN)
+        mse = sse / sizes[:, None] if F else sse
+    mse_mean = sse.sum(axis=0) / total if F else np.full(E, np.nan)
     failed = np.any(st == L.ERR_NOT_CONVERGED, axis=0)
     cand = np.where(failed | np.isnan(mse_mean), np.inf, mse_mean)
     if F and np.isfinite(cand).any():

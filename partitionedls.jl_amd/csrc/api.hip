@@ -148,8 +148,39 @@ partls_status upload_matrix(partls_ctx *c, double *dst, const double *X, int64_t
     return PARTLS_OK;                                    // every copier has synchronised its stream: the image is complete for c->stream
 }
 
+partls_status prepare_weights(partls_ctx *c, const double *w, int64_t N, int on_device)
+{
+    c->dw = nullptr; c->ds = nullptr;
+    const double *dw = w;
+    if (!on_device) {
+        PARTLS_HIP_CHECK(c->ownW.ensure((size_t)N * sizeof(double)));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(c->ownW.p, w, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        dw = c->ownW.as<double>();
+    }
+    const int nb = weight_prep_blocks(N);
+    PARTLS_HIP_CHECK(c->ownS.ensure((size_t)N * sizeof(double)));
+    PARTLS_HIP_CHECK(c->wPart.ensure((size_t)3 * nb * sizeof(double)));
+    PARTLS_HIP_CHECK(c->hPart.resize((size_t)3 * nb));
+    PARTLS_HIP_CHECK(launch_weight_prep(dw, N, c->ownS.as<double>(), c->wPart.as<double>(), c->stream));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->hPart.data(), c->wPart.p, (size_t)3 * nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    bool neg = false, bad = false;
+    double sum = 0.0;
+    for (int b = 0; b < nb; ++b) {
+        neg = neg || c->hPart[(size_t)3 * b] != 0.0;
+        bad = bad || c->hPart[(size_t)3 * b + 1] != 0.0;
+        sum += c->hPart[(size_t)3 * b + 2];
+    }
+    if (bad) { set_error("the sample weights contain NaN/Inf"); return PARTLS_ERR_NONFINITE; }
+    if (neg) { set_error("a sample weight is negative"); return PARTLS_ERR_BAD_ARG; }
+    if (!(sum > 0.0)) { set_error("the sample weights sum to 0"); return PARTLS_ERR_BAD_ARG; }
+    if (!std::isfinite(sum)) { set_error("the sum of the sample weights overflows"); return PARTLS_ERR_NONFINITE; }
+    c->dw = dw; c->ds = c->ownS.as<double>();
+    return PARTLS_OK;
+}
+
 partls_status ctx_prepare(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
-                          const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags)
+                          const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags, const double *w)
 {
     partls_status st = check_common(c, X, N, M, ldX, P, K, ldP);
     if (st != PARTLS_OK) return st;
@@ -162,7 +193,13 @@ partls_status ctx_prepare(partls_ctx *c, const double *X, int64_t N, int64_t M, 
     c->sweep_vetoes = 0;
     c->coop_state_valid = false;
     c->order_ready = false; c->order_identity = true; c->flip_cost.clear(); c->ms[PARTLS_T_CALIB] = 0.0;
+    c->dw = nullptr; c->ds = nullptr;
     PARTLS_HIP_CHECK(hipSetDevice(c->device));
+    if (w) {
+        if (c->multi_rank) { set_error("sample weights: a context of a partls_multi is not supported (multi-GPU fits are unweighted)"); return PARTLS_ERR_UNSUPPORTED; }
+        st = prepare_weights(c, w, N, x_on_device);
+        if (st != PARTLS_OK) return st;
+    }
     st = load_partition(c, P, M, K, ldP);
     if (st != PARTLS_OK) return st;
     c->N = N; c->M = M; c->K = K; c->eta = eta; c->flags = flags; c->faithful = faithful;
@@ -187,7 +224,7 @@ partls_status ctx_prepare(partls_ctx *c, const double *X, int64_t N, int64_t M, 
     PARTLS_HIP_CHECK(c->G.ensure((size_t)c->ldg * c->ldg * sizeof(double)));
     t_begin(c, PARTLS_T_GRAM);
     PARTLS_HIP_CHECK(launch_gram(c->dX, N, M, c->ldX, c->dy, c->slab.as<double>(), c->chunks, c->ldg, c->knobs.gram_S, c->knobs.gram_cr,
-                                 c->G.as<double>(), c->stream));
+                                 c->G.as<double>(), c->stream, c->ds));
     t_end(c, PARTLS_T_GRAM);
     // rows of X sharded over several devices: the Gram products of the blocks are summed here (partls_fit_opt_multi, multi.hip)
     if (c->gram_hook) { st = c->gram_hook(c); if (st != PARTLS_OK) return st; }
@@ -421,7 +458,7 @@ void unscale_solution(const partls_ctx *c, const double *sol, std::vector<double
 
 // One pass over the DATA of the prepared problem — all of it: this context's rows and, when the rows of X are sharded over several
 // devices (partls_fit_opt_multi), those its peers hold:  *obj2 = sum_i (Xo w - y)_i^2  (without the eta rows) and, optionally,
-// g = Xo'(y - Xo w) over [features, intercept].  The kernels of every device are queued first (one host thread drives them all), the
+// g = Xo'(y - Xo w) over [features, intercept].  With sample weights (q->dw) the rows are weighted: sum_i w_i r_i^2 and Xo' W r.  The kernels of every device are queued first (one host thread drives them all), the
 // caller's `overlap` work runs on the host meanwhile, then the partial sums are added in a fixed order (context, then peers; slices in
 // order): run-to-run reproducible.
 partls_status data_pass(partls_ctx *c, const std::vector<double> &w, bool want_obj, bool want_grad, double *obj2, std::vector<double> *g,
@@ -446,9 +483,9 @@ partls_status data_pass(partls_ctx *c, const std::vector<double> &w, bool want_o
             PARTLS_HIP_CHECK(q->hGpart.resize((size_t)xr * (M + 1)));
         }
         PARTLS_HIP_CHECK(launch_residual(q->dX, N, M, q->ldX, want_obj ? q->dy : nullptr, q->wdev.as<double>(), w[(size_t)M],
-                                         want_obj ? q->partial.as<double>() : nullptr, nb, yhat, q->stream));
+                                         want_obj ? q->partial.as<double>() : nullptr, nb, yhat, q->stream, q->dw));
         if (want_grad) {
-            PARTLS_HIP_CHECK(launch_xtr(q->dX, N, M, q->ldX, q->dy, yhat, q->gD.as<double>(), q->stream));
+            PARTLS_HIP_CHECK(launch_xtr(q->dX, N, M, q->ldX, q->dy, yhat, q->gD.as<double>(), q->stream, q->dw));
             PARTLS_HIP_CHECK(hipMemcpyAsync(q->hGpart.data(), q->gD.p, q->hGpart.size() * sizeof(double), hipMemcpyDeviceToHost, q->stream));
         }
         if (want_obj) PARTLS_HIP_CHECK(hipMemcpyAsync(q->hPart.data(), q->partial.p, nb * sizeof(double), hipMemcpyDeviceToHost, q->stream));
@@ -849,7 +886,7 @@ using namespace partls;
 
 extern "C" {
 
-int partls_version(void) { return 100; }
+int partls_version(void) { return 101; }
 const char *partls_last_error(void) { return g_err; }
 
 int partls_device_count(void)
@@ -936,7 +973,7 @@ void partls_destroy(partls_ctx *c)
                           &c->yhatD, &c->gD, &c->nodeCode, &c->nodeSol, &c->nodeObj, &c->gridCtr,
                           &c->predX, &c->predY, &c->nodeTab, &c->nodeBasic, &c->altA, &c->altGA, &c->altHg,
                           &c->nodePiv, &c->maskInt, &c->allOptRef, &c->bnbIn, &c->bnbOut, &c->altGersh, &c->mdlRows, &c->mdlOut, &c->mdlCtr,
-                          &c->cvG, &c->cvBatch, &c->cvEta};
+                          &c->cvG, &c->cvBatch, &c->cvEta, &c->ownW, &c->ownS, &c->wPart};
         for (DevBuf *b : bufs) b->release();
         for (void *q : c->bnbChunks) (void)hipFree(q);
         c->bnbChunks.clear();
@@ -961,6 +998,15 @@ partls_status partls_opt_prepare(partls_ctx *c, const double *X, int64_t N, int6
                                  int x_on_device, const int64_t *P, int64_t K, int64_t ldP, double eta, uint32_t flags)
 try {
     return ctx_prepare(c, X, N, M, ldX, y, x_on_device, P, K, ldP, eta, (flags & PARTLS_OPT_FAITHFUL_INTERCEPT) != 0, flags);
+}
+catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
+catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+
+partls_status partls_opt_prepare_weighted(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
+                                          const double *w, int x_on_device, const int64_t *P, int64_t K, int64_t ldP, double eta,
+                                          uint32_t flags)
+try {
+    return ctx_prepare(c, X, N, M, ldX, y, x_on_device, P, K, ldP, eta, (flags & PARTLS_OPT_FAITHFUL_INTERCEPT) != 0, flags, w);
 }
 catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
 catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }

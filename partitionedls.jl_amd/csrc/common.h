@@ -130,9 +130,14 @@ hipError_t launch_layout_reg(const double *Tfull, int n, int T, double *T0reg, h
 
 // gram build: G_aug = Z'Z with Z = [X 1 y]  (n_aug = M + 2), full symmetric, ld = ldg (multiple of 64)
 // (gram_S / gram_cr: tuning overrides read once at partls_create, 0 = automatic)
+// sw (optional, device, N): s = sqrt(w) of the sample weights -> G_aug = Z~'Z~ with Z~ = diag(s) [X 1 y]
 size_t     gram_slab_doubles(int64_t N, int64_t M, int gram_S, int gram_cr, int *chunks_out, int *ldg_out);
 hipError_t launch_gram(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, double *slab, int chunks,
-                       int ldg, int gram_S, int gram_cr, double *G, hipStream_t s);
+                       int ldg, int gram_S, int gram_cr, double *G, hipStream_t s, const double *sw = nullptr);
+// sample weights (misc.hip): s[i] = sqrt(w[i]) and, per block b of weight_prep_blocks(N), part[3 b ..] = (any w < 0, any non-finite w,
+// sum of w) — the host adds the blocks in index order
+int        weight_prep_blocks(int64_t N);
+hipError_t launch_weight_prep(const double *w, int64_t N, double *s, double *part, hipStream_t st);
 
 // tableau prep: B = regularised (and, free-intercept mode, intercept-eliminated) Gram; Tfull = unit-diagonal scaled
 // perm[i] = augmented-Gram index of tableau variable i (variables are grouped by partition so a flip touches few tiles)
@@ -167,13 +172,14 @@ hipError_t launch_gersh(const double *Tfull, int n, double *out, hipStream_t s);
 // beta-step system of fit(Alt): Hg[k * (Kp + 1) + k2] = H[k][k2] (k2 < Kp), g[k] (k2 = Kp); GA is (M + 1) x Kp scratch
 hipError_t launch_alt_beta_system(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, const double *a, int Kp,
                                   double *GA, double *Hg, hipStream_t s);
+// wt (optional, device, N): sample weights -> sum_i wt[i] (...)^2
 hipError_t launch_residual(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w, double t,
-                           double *partial, int nblocks, double *yhat, hipStream_t s);
-// g[0..M] = Xo' (y - yhat): the gradient pass of the data-space refinement
+                           double *partial, int nblocks, double *yhat, hipStream_t s, const double *wt = nullptr);
+// g[0..M] = Xo' (y - yhat): the gradient pass of the data-space refinement (wt: Xo' W (y - yhat))
 // gpart: xtr_slices(N) x (M + 1) partial sums; g[m] = sum over the slices in order
 int        xtr_slices(int64_t N);
 hipError_t launch_xtr(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *yhat, double *gpart,
-                      hipStream_t s);
+                      hipStream_t s, const double *wt = nullptr);
 hipError_t launch_synth(uint64_t seed, int64_t N, int64_t D, const double *wstar_dev, double *X, double *y, hipStream_t s);
 
 // host-side mirror of the device generator (synth.hip); also used by partls_synth_truth

@@ -101,6 +101,12 @@ struct partls_ctx {
     bool faithful = false;                         // intercept is a sign-constrained tableau variable (2^(K+1) patterns)
     const double *dX = nullptr, *dy = nullptr;     // device views (owned copies below, or the caller's)
     partls::DevBuf ownX, ownY;
+    // sample weights of the prepared problem (partls_opt_prepare_weighted / partls_cv_opt_weighted; nullptr: unweighted): dw = w (the
+    // caller's device array, or ownW, the upload of a host one), ds = sqrt(w) (ownS, written by weight_prep_kernel).  Every Gram build
+    // and every data pass (data_pass) of the problem reads them; a plain prepare clears them.  DESIGN.md §4.7.
+    const double *dw = nullptr, *ds = nullptr;
+    partls::DevBuf ownW, ownS, wPart;
+    bool multi_rank = false;                       // this context belongs to a partls_multi (weighted prepares are refused)
     std::vector<int64_t> P;                        // M x K compact
     std::vector<uint64_t> mask_aug;                // M + 2: features, intercept (bit K), y (0)
     std::vector<uint64_t> pack;                    // staging of the one upload of masks and permutation
@@ -185,8 +191,12 @@ void t_end(partls_ctx *c, int w);
 void t_collect(partls_ctx *c);
 
 // Upload (or adopt) X, y; build the Gram products; lay the tableau out.  faithful = intercept is a regular variable.
+// w (optional): sample weights, a device pointer when x_on_device (see prepare_weights)
 partls_status ctx_prepare(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
-                          const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags);
+                          const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags, const double *w = nullptr);
+// Sample weights w[N] (host, or device when on_device) -> c->dw, c->ds after one weight_prep_kernel pass, or the status of the first
+// failed check: NaN / Inf -> PARTLS_ERR_NONFINITE; a negative weight or a sum that is not > 0 -> PARTLS_ERR_BAD_ARG.
+partls_status prepare_weights(partls_ctx *c, const double *w, int64_t N, int on_device);
 // The second half of ctx_prepare: from the Gram products in c->G (c->M, K, eta, flags, faithful and the partition already set) to the
 // tableau, the host copies and the tolerance.  partls_cv_opt calls it on a context whose G it filled itself.
 partls_status ctx_prepare_tableau(partls_ctx *c);

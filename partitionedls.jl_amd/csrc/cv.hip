@@ -48,12 +48,13 @@ static void point_rows(partls_ctx *c, partls_ctx *W, const int64_t *fold_ptr, in
 {
     W->peers.clear();
     W->ldX = c->ldX;
-    if (f == F) { W->dX = c->dX; W->dy = c->dy; W->N = c->N; return; }
+    if (f == F) { W->dX = c->dX; W->dy = c->dy; W->dw = c->dw; W->ds = c->ds; W->N = c->N; return; }
     bool first = true;
     for (int64_t g = 0; g < F; ++g) {
         if (g == f) continue;
         if (first) {
             W->dX = c->dX + fold_ptr[g]; W->dy = c->dy + fold_ptr[g]; W->N = fold_ptr[g + 1] - fold_ptr[g];
+            W->dw = c->dw ? c->dw + fold_ptr[g] : nullptr; W->ds = c->ds ? c->ds + fold_ptr[g] : nullptr;
             first = false;
         } else {
             W->peers.push_back(c->cv_view[(size_t)g]);
@@ -108,9 +109,9 @@ static partls_status finish_one(partls_ctx *c, partls_ctx *W, const int64_t *fol
     return PARTLS_OK;
 }
 
-static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
-                            const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F, const double *eta, int64_t E,
-                            uint32_t flags, CvOut &o)
+static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w,
+                            int x_on_device, const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F, const double *eta,
+                            int64_t E, uint32_t flags, CvOut &o)
 {
     const int64_t B = (F + 1) * E;
     const int nf = F > 0 ? (int)F : 1;
@@ -123,6 +124,13 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
     c->near_for = -1; c->near_pat.clear(); c->cand.clear();
     c->last_upload_ms = 0.0; c->last_upload_bytes = 0.0;
     c->N = N; c->M = M; c->K = K; c->flags = flags; c->faithful = faithful;
+    c->dw = nullptr; c->ds = nullptr;
+    // ---- sample weights (partls_cv_opt_weighted): checked and square-rooted before anything else; every fold Gram and every data pass
+    // (finish, held-out SSE) then reads its rows' slice of them
+    if (w) {
+        partls_status ws = prepare_weights(c, w, N, x_on_device);
+        if (ws != PARTLS_OK) return ws;
+    }
 
     // ---- one upload
     if (x_on_device) {
@@ -150,6 +158,7 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
         if (st != PARTLS_OK) return st;
         partls_ctx *v = c->cv_view[(size_t)g];
         v->dX = c->dX + fold_ptr[g]; v->dy = c->dy + fold_ptr[g]; v->ldX = c->ldX;
+        v->dw = c->dw ? c->dw + fold_ptr[g] : nullptr; v->ds = c->ds ? c->ds + fold_ptr[g] : nullptr;
         v->N = fold_ptr[g + 1] - fold_ptr[g]; v->M = M; v->K = K;
         v->peers.clear();
     }
@@ -172,7 +181,7 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
         int ch = 0, ld2 = 0;
         (void)gram_slab_doubles(n_g, M, c->knobs.gram_S, c->knobs.gram_cr, &ch, &ld2);
         PARTLS_HIP_CHECK(launch_gram(c->dX + r0, n_g, M, c->ldX, c->dy + r0, c->slab.as<double>(), ch, ldg, c->knobs.gram_S, c->knobs.gram_cr,
-                                     Gf + (size_t)g * gs, c->stream));
+                                     Gf + (size_t)g * gs, c->stream, c->ds ? c->ds + r0 : nullptr));
     }
     PARTLS_HIP_CHECK(launch_fold_gram_combine(Gf, nf, (int)F, gs, Gc, c->stream));
     t_end(c, PARTLS_T_GRAM);
@@ -186,6 +195,13 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
         if (i == M) continue;
         if (!std::isfinite(Gall[(size_t)i * ldg + i])) { set_error("partls_cv_opt: X or y contains NaN/Inf (or overflows in X'X)"); return PARTLS_ERR_NONFINITE; }
     }
+    // weighted: every training set needs weight (its ones-column entry is sum_i s_i^2 over its rows)
+    if (c->ds)
+        for (int64_t f = 0; f < F; ++f)
+            if (!(c->cvHostG[(size_t)f * gs + (size_t)M * ldg + M] > 0.0)) {
+                set_error("partls_cv_opt_weighted: the training rows of fold %lld have zero total weight", (long long)f);
+                return PARTLS_ERR_BAD_ARG;
+            }
 
     // ---- the working context: the problem's shape, partition and Gram; prepared first for the full-data problem at eta[0], on which the
     // visiting order of the whole batch is calibrated (the rule of a single fit decides whether that pays)
@@ -346,12 +362,12 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
 
 using namespace partls;
 
-partls_status partls_cv_opt(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
-                            const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F,
+static partls_status cv_opt(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w,
+                            int x_on_device, const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F,
                             const double *eta, int64_t E, uint32_t flags,
                             double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t, double *opt,
                             int64_t *best_index, double *heldout_sse, int32_t *status)
-try {
+{
     partls_status st = check_common(c, X, N, M, ldX, P, K, ldP);
     if (st != PARTLS_OK) return st;
     if (!y) { set_error("partls_cv_opt: y is NULL"); return PARTLS_ERR_BAD_ARG; }
@@ -378,7 +394,7 @@ try {
     o.alpha.assign((size_t)B * M, 0.0); o.beta.assign((size_t)B * K, 0.0);
     o.t.assign((size_t)B, 0.0); o.opt.assign((size_t)B, 0.0); o.sse.assign((size_t)B, NAN);
     o.best.assign((size_t)B, -1); o.status.assign((size_t)B, 0);
-    st = cv_run(c, X, N, M, ldX, y, x_on_device, P, K, ldP, fold_ptr, F, eta, E, flags, o);
+    st = cv_run(c, X, N, M, ldX, y, w, x_on_device, P, K, ldP, fold_ptr, F, eta, E, flags, o);
     if (st != PARTLS_OK) return st;
     for (int64_t q = 0; q < B; ++q) {
         std::memcpy(alpha + q * ld_alpha, o.alpha.data() + (size_t)q * M, (size_t)M * sizeof(double));
@@ -391,6 +407,28 @@ try {
     std::memcpy(status, o.status.data(), (size_t)B * sizeof(int32_t));
     set_error("");
     return PARTLS_OK;
+}
+
+partls_status partls_cv_opt(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
+                            const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F,
+                            const double *eta, int64_t E, uint32_t flags,
+                            double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t, double *opt,
+                            int64_t *best_index, double *heldout_sse, int32_t *status)
+try {
+    return cv_opt(c, X, N, M, ldX, y, nullptr, x_on_device, P, K, ldP, fold_ptr, F, eta, E, flags, alpha, ld_alpha, beta, ld_beta, t, opt,
+                  best_index, heldout_sse, status);
+}
+catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
+catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+
+partls_status partls_cv_opt_weighted(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w,
+                                     int x_on_device, const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F,
+                                     const double *eta, int64_t E, uint32_t flags,
+                                     double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t, double *opt,
+                                     int64_t *best_index, double *heldout_sse, int32_t *status)
+try {
+    return cv_opt(c, X, N, M, ldX, y, w, x_on_device, P, K, ldP, fold_ptr, F, eta, E, flags, alpha, ld_alpha, beta, ld_beta, t, opt,
+                  best_index, heldout_sse, status);
 }
 catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
 catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }

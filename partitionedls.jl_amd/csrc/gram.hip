@@ -160,10 +160,16 @@ __device__ __forceinline__ void full_panel(const double *sA, const double *sB, i
 // (independent, unconditional global loads) while the MFMAs of the current one run from LDS.
 __host__ __device__ constexpr size_t slice_doubles(int np, int nt) { return (size_t)np * GT * GT + 2 * ((size_t)nt * GT + 2); }
 
-template <bool EA, bool EB, bool DIAG>
+// WT (sample weights): every staged sample is scaled by s_i = sqrt(w_i) (`sw`, precomputed by weight_prep_kernel), so
+// the result is the Gram of Z~ = S [X 1 y], S = diag(s).  The scaling must be symmetric: on a diagonal tile the A fragment of block r and
+// the B fragment of block c are the same LDS words (diag_panel).  The ones column stages s_i, y stages s_i y_i, and the corner sums of
+// tile (0, 0) are formed from those same scaled values.  s of panel p + 1 is one more per-lane register, loaded behind the last store
+// that reads it (the last slot of the phase).  WT = false compiles to the unweighted kernel unchanged.
+template <bool WT, bool EA, bool EB, bool DIAG>
 __device__ __forceinline__ void gram_body(const double *__restrict__ X, int64_t N, int M, int64_t ldX,
                                           const double *__restrict__ y, double *__restrict__ slab, int np, int nt, int pair,
-                                          int chunk_rows, int S, int I, int J, int xg, int sl, double *sA, double *sB, double *sV)
+                                          int chunk_rows, int S, int I, int J, int xg, int sl, double *sA, double *sB, double *sV,
+                                          const double *__restrict__ sw)
 {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     double4_t acc[8];
@@ -186,6 +192,7 @@ __device__ __forceinline__ void gram_body(const double *__restrict__ X, int64_t 
     // separates the reads of a buffer from its refill and the stores from their reads.  Everything inside a phase is branch-free: a
     // panel that does not exist is "loaded" from a clamped valid address with its row predicate false (zeros reach the LDS).
     double va[NL], vb[DIAG ? 1 : NL], vy = 0.0;        // raw values of panel p + 1 (+ y for the diagonal tiles)
+    double vs = 1.0;                                   // WT: s of this lane's sample of panel p + 1
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     struct Panel { const double *Xrow; const double *yrow; unsigned lane_off, rowoff; bool rv; };
     int64_t chunk = xg + (int64_t)8 * sl;
@@ -203,6 +210,7 @@ __device__ __forceinline__ void gram_body(const double *__restrict__ X, int64_t 
         P.Xrow = X + row0; P.yrow = y + row0;
         return P;
     };
+    auto s_of = [&](const Panel &P) { return sw[(P.yrow - y) + P.rowoff]; };   // WT: s of this lane's sample of panel P
     auto advance = [&]() {                              // step (chunk, kb) to this workgroup's next panel
         if (++kb == kb_per_chunk) { kb = 0; chunk += cstride; }
         live = live && chunk < nchunks && (chunk * chunk_rows + (int64_t)kb * GK) < N;
@@ -216,16 +224,27 @@ __device__ __forceinline__ void gram_body(const double *__restrict__ X, int64_t 
     auto store_slot = [&](int buf, bool rv, int g) {
         const int i = g & (NL - 1);
         const int c = i * (NWV * CPW) + wave * CPW + csub;
-        if (g < NL) (sA + buf * (GT * GLD))[c * GLD + smp] = z_value<EA>(va[i], rv, M, I * GT + c);
-        else if constexpr (!DIAG) (sB + buf * (GT * GLD))[c * GLD + smp] = z_value<EB>(vb[i], rv, M, J * GT + c);
+        if constexpr (WT) {
+            if (g < NL) (sA + buf * (GT * GLD))[c * GLD + smp] = z_value<EA>(va[i], rv, M, I * GT + c) * vs;
+            else if constexpr (!DIAG) (sB + buf * (GT * GLD))[c * GLD + smp] = z_value<EB>(vb[i], rv, M, J * GT + c) * vs;
+        } else {
+            if (g < NL) (sA + buf * (GT * GLD))[c * GLD + smp] = z_value<EA>(va[i], rv, M, I * GT + c);
+            else if constexpr (!DIAG) (sB + buf * (GT * GLD))[c * GLD + smp] = z_value<EB>(vb[i], rv, M, J * GT + c);
+        }
     };
     auto store_virtual = [&](int buf, bool rv) {        // diagonal tiles: [valid, y] of the panel, and the corner sums of tile (0, 0)
         if constexpr (DIAG) {
             if (vloader) {
-                const double one = rv ? 1.0 : 0.0, yv = rv ? vy : 0.0;
                 double *dV = sV + buf * (2 * GK);
-                dV[smp] = one; dV[GK + smp] = yv;
-                if (corner) { c11 += one; c1y += yv; cyy = fma(yv, yv, cyy); }
+                if constexpr (WT) {                     // [s, s y]; corner sums s^2, s (s y), (s y)^2 of the staged values
+                    const double one = rv ? vs : 0.0, yv = rv ? vs * vy : 0.0;
+                    dV[smp] = one; dV[GK + smp] = yv;
+                    if (corner) { c11 = fma(one, one, c11); c1y = fma(one, yv, c1y); cyy = fma(yv, yv, cyy); }
+                } else {
+                    const double one = rv ? 1.0 : 0.0, yv = rv ? vy : 0.0;
+                    dV[smp] = one; dV[GK + smp] = yv;
+                    if (corner) { c11 += one; c1y += yv; cyy = fma(yv, yv, cyy); }
+                }
             }
         }
     };
@@ -237,6 +256,7 @@ __device__ __forceinline__ void gram_body(const double *__restrict__ X, int64_t 
 #pragma unroll
     for (int g = 0; g < NSLOT; ++g) load_slot(P, g);
     if constexpr (DIAG) { if (vloader) vy = P.yrow[P.rowoff]; }
+    if constexpr (WT) vs = s_of(P);
 #pragma unroll
     for (int g = 0; g < NSLOT; ++g) store_slot(0, P.rv, g);
     store_virtual(0, P.rv);
@@ -246,6 +266,7 @@ __device__ __forceinline__ void gram_body(const double *__restrict__ X, int64_t 
 #pragma unroll
     for (int g = 0; g < NSLOT; ++g) load_slot(P, g);
     if constexpr (DIAG) { if (vloader) vy = P.yrow[P.rowoff]; }
+    if constexpr (WT) vs = s_of(P);
     __syncthreads();
     int buf = 0;
     while (cur) {
@@ -259,6 +280,7 @@ __device__ __forceinline__ void gram_body(const double *__restrict__ X, int64_t 
             if (DIAG && g == 0) { store_virtual(buf ^ 1, rv1); if (vloader) vy = P2.yrow[P2.rowoff]; }
             store_slot(buf ^ 1, rv1, g);
             load_slot(P2, g);
+            if constexpr (WT) { if (g == NSLOT - 1) vs = s_of(P2); }     // the last store of panel p + 1 is behind us
             __builtin_amdgcn_sched_barrier(0);
         };
         if constexpr (DIAG) {
@@ -318,10 +340,11 @@ __device__ __forceinline__ void gram_body(const double *__restrict__ X, int64_t 
     }
 }
 
+template <bool WT>
 __global__ __launch_bounds__(64 * NWV, 4) void gram_kernel(      // 4 waves per SIMD (HIP: the second argument counts waves per EU): <= 128 VGPRs
 const double *__restrict__ X, int64_t N, int M, int64_t ldX,
                                                    const double *__restrict__ y, double *__restrict__ slab,
-                                                   int chunk_rows, int S, int np)
+                                                   int chunk_rows, int S, int np, const double *__restrict__ sw)
 {
     __shared__ double sA[2 * GT * GLD];              // [2 buffers][128 columns][GLD]
     __shared__ double sB[2 * GT * GLD];
@@ -336,11 +359,11 @@ const double *__restrict__ X, int64_t N, int M, int64_t ldX,
     const bool ragged = (M % GT) != 0;
     const bool ea = ragged && I == nt - 1, eb = ragged && J == nt - 1;
     if (I == J) {
-        if (ea) gram_body<true, true, true>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV);
-        else gram_body<false, false, true>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV);
+        if (ea) gram_body<WT, true, true, true>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV, sw);
+        else gram_body<WT, false, false, true>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV, sw);
     } else {
-        if (eb) gram_body<false, true, false>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV);
-        else gram_body<false, false, false>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV);
+        if (eb) gram_body<WT, false, true, false>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV, sw);
+        else gram_body<WT, false, false, false>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV, sw);
     }
 }
 
@@ -440,12 +463,13 @@ size_t gram_slab_doubles(int64_t N, int64_t M, int gram_S, int gram_cr, int *chu
 }
 
 hipError_t launch_gram(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, double *slab, int chunks,
-                       int ldg, int gram_S, int gram_cr, double *G, hipStream_t s)
+                       int ldg, int gram_S, int gram_cr, double *G, hipStream_t s, const double *sw)
 {
     int ldg2, S, cr, np, nt;
     gram_plan(N, M, gram_S, gram_cr, &ldg2, &S, &cr, &np, &nt);
     if (ldX >= ((int64_t)1 << 30)) return hipErrorInvalidValue;          // 32-bit per-lane element offsets (see z_load)
-    hipLaunchKernelGGL(gram_kernel, dim3(8 * S * np), dim3(64 * NWV), 0, s, X, N, (int)M, ldX, y, slab, cr, S, np);
+    if (sw) hipLaunchKernelGGL(gram_kernel<true>, dim3(8 * S * np), dim3(64 * NWV), 0, s, X, N, (int)M, ldX, y, slab, cr, S, np, sw);
+    else hipLaunchKernelGGL(gram_kernel<false>, dim3(8 * S * np), dim3(64 * NWV), 0, s, X, N, (int)M, ldX, y, slab, cr, S, np, sw);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int tot = ldg * ldg;

@@ -415,11 +415,15 @@ hipError_t launch_alt_beta_system(const double *G, int ldg, int M, double eta, c
 // ---------------------------------------------------------------------------------------------------------------------
 // Residual from the data (Opt.jl:90 / predict PartitionedLS.jl:132-134): one coalesced pass over column-major X.
 //   partial[b] = sum over the block's rows of (sum_m X[i,m] w[m] + t - y[i])^2 ;  yhat (optional) = X w + t
+// WT (sample weights): row i contributes wt[i] r_i^2, accumulated as fma(wt_i r_i, r_i, acc) — the unweighted order
+// with one exact factor when wt_i = 1.
 // Blocks are summed on the host in index order (reproducible).
 // ---------------------------------------------------------------------------------------------------------------------
+template <bool WT>
 __global__ __launch_bounds__(256) void residual_kernel(const double *__restrict__ X, int64_t N, int64_t M, int64_t ldX,
                                                        const double *__restrict__ y, const double *__restrict__ w, double t,
-                                                       double *__restrict__ partial, double *__restrict__ yhat)
+                                                       double *__restrict__ partial, double *__restrict__ yhat,
+                                                       const double *__restrict__ wt)
 {
     extern __shared__ double sw[];                       // w staged once per block
     for (int64_t m = threadIdx.x; m < M; m += blockDim.x) sw[m] = w[m];
@@ -437,7 +441,11 @@ __global__ __launch_bounds__(256) void residual_kernel(const double *__restrict_
         for (; m < M; ++m) a0 = fma(X[i + m * ldX], sw[m], a0);
         const double p = ((a0 + a1) + (a2 + a3)) + t;
         if (yhat) yhat[i] = p;
-        if (y) { const double r = p - y[i]; acc2 = fma(r, r, acc2); }
+        if (y) {
+            const double r = p - y[i];
+            if constexpr (WT) acc2 = fma(wt[i] * r, r, acc2);
+            else acc2 = fma(r, r, acc2);
+        }
     }
     __shared__ double red[256];
     red[threadIdx.x] = acc2;
@@ -450,10 +458,14 @@ __global__ __launch_bounds__(256) void residual_kernel(const double *__restrict_
 }
 
 hipError_t launch_residual(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w, double t,
-                           double *partial, int nblocks, double *yhat, hipStream_t s)
+                           double *partial, int nblocks, double *yhat, hipStream_t s, const double *wt)
 {
-    hipLaunchKernelGGL(residual_kernel, dim3(nblocks), dim3(256), (size_t)M * sizeof(double), s, X, N, M, ldX, y, w, t,
-                       partial, yhat);
+    if (wt && y)
+        hipLaunchKernelGGL(residual_kernel<true>, dim3(nblocks), dim3(256), (size_t)M * sizeof(double), s, X, N, M, ldX, y, w, t,
+                           partial, yhat, wt);
+    else
+        hipLaunchKernelGGL(residual_kernel<false>, dim3(nblocks), dim3(256), (size_t)M * sizeof(double), s, X, N, M, ldX, y, w, t,
+                           partial, yhat, nullptr);
     return hipGetLastError();
 }
 
@@ -463,10 +475,12 @@ hipError_t launch_residual(const double *X, int64_t N, int64_t M, int64_t ldX, c
 // loads of X in flight per thread, coalesced along the column, fixed-order block reduction; the XTR_R partial sums of a column are
 // added in slice order by the caller (reproducible).  One workgroup per whole column (round 1) left each CU with a handful of loads
 // in flight: 100 us for 205 MB at C3.
+// WT (sample weights): the residual of row i enters as wt[i] (y_i - yhat_i), i.e. g = Xo' W (y - yhat).
 // ---------------------------------------------------------------------------------------------------------------------
+template <bool WT>
 __global__ __launch_bounds__(256) void xtr_kernel(const double *__restrict__ X, int64_t N, int64_t M, int64_t ldX,
                                                   const double *__restrict__ y, const double *__restrict__ yhat,
-                                                  double *__restrict__ gpart, int R)
+                                                  double *__restrict__ gpart, int R, const double *__restrict__ wt)
 {
     const int64_t m = blockIdx.x;
     const int r = blockIdx.y;
@@ -478,13 +492,19 @@ __global__ __launch_bounds__(256) void xtr_kernel(const double *__restrict__ X, 
         for (; i + 768 < r1; i += 1024) {
             double x[4], d[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { x[u] = col[i + 256 * u]; d[u] = y[i + 256 * u] - yhat[i + 256 * u]; }
+            for (int u = 0; u < 4; ++u) {
+                x[u] = col[i + 256 * u];
+                if constexpr (WT) d[u] = wt[i + 256 * u] * (y[i + 256 * u] - yhat[i + 256 * u]);
+                else d[u] = y[i + 256 * u] - yhat[i + 256 * u];
+            }
 #pragma unroll
             for (int u = 0; u < 4; ++u) acc[u] = fma(x[u], d[u], acc[u]);
         }
-        for (; i < r1; i += 256) acc[0] = fma(col[i], y[i] - yhat[i], acc[0]);
+        if constexpr (WT) for (; i < r1; i += 256) acc[0] = fma(col[i], wt[i] * (y[i] - yhat[i]), acc[0]);
+        else for (; i < r1; i += 256) acc[0] = fma(col[i], y[i] - yhat[i], acc[0]);
     } else {
-        for (; i < r1; i += 256) acc[0] += y[i] - yhat[i];
+        if constexpr (WT) for (; i < r1; i += 256) acc[0] += wt[i] * (y[i] - yhat[i]);
+        else for (; i < r1; i += 256) acc[0] += y[i] - yhat[i];
     }
     __shared__ double red[256];
     red[threadIdx.x] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
@@ -505,10 +525,55 @@ int xtr_slices(int64_t N)
 }
 
 hipError_t launch_xtr(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *yhat, double *gpart,
-                      hipStream_t s)
+                      hipStream_t s, const double *wt)
 {
     const int R = xtr_slices(N);
-    hipLaunchKernelGGL(xtr_kernel, dim3((unsigned)(M + 1), (unsigned)R), dim3(256), 0, s, X, N, M, ldX, y, yhat, gpart, R);
+    if (wt) hipLaunchKernelGGL(xtr_kernel<true>, dim3((unsigned)(M + 1), (unsigned)R), dim3(256), 0, s, X, N, M, ldX, y, yhat, gpart, R, wt);
+    else hipLaunchKernelGGL(xtr_kernel<false>, dim3((unsigned)(M + 1), (unsigned)R), dim3(256), 0, s, X, N, M, ldX, y, yhat, gpart, R, wt);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Sample weights: one pass over w[N] on the device, for host and device weights alike.  Writes s = sqrt(w) (what the
+// Gram kernel stages; sqrt is correctly rounded, so sqrt(1) = 1 and sqrt(4) = 2 exactly) and, per block b, three partials:
+//   part[3b] = 1 if some w_i < 0,   part[3b + 1] = 1 if some w_i is NaN / Inf,   part[3b + 2] = sum of the block's w_i
+// (grid-stride rows, fixed-order tree over the block).  The host adds the blocks in index order and turns them into a status.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void weight_prep_kernel(const double *__restrict__ w, int64_t N, double *__restrict__ s,
+                                                          double *__restrict__ part)
+{
+    __shared__ double red[3][256];
+    double neg = 0.0, bad = 0.0, sum = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+        const double v = w[i];
+        const bool fin = isfinite(v);
+        if (!fin) bad = 1.0;
+        if (v < 0.0) neg = 1.0;
+        sum += fin ? v : 0.0;
+        s[i] = (fin && v >= 0.0) ? sqrt(v) : 0.0;
+    }
+    red[0][threadIdx.x] = neg; red[1][threadIdx.x] = bad; red[2][threadIdx.x] = sum;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+            red[0][threadIdx.x] = fmax(red[0][threadIdx.x], red[0][threadIdx.x + h]);
+            red[1][threadIdx.x] = fmax(red[1][threadIdx.x], red[1][threadIdx.x + h]);
+            red[2][threadIdx.x] += red[2][threadIdx.x + h];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { part[3 * blockIdx.x] = red[0][0]; part[3 * blockIdx.x + 1] = red[1][0]; part[3 * blockIdx.x + 2] = red[2][0]; }
+}
+
+int weight_prep_blocks(int64_t N)
+{
+    const int64_t b = (N + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
+}
+
+hipError_t launch_weight_prep(const double *w, int64_t N, double *s, double *part, hipStream_t st)
+{
+    hipLaunchKernelGGL(weight_prep_kernel, dim3(weight_prep_blocks(N)), dim3(256), 0, st, w, N, s, part);
     return hipGetLastError();
 }
 

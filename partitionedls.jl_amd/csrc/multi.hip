@@ -558,6 +558,7 @@ try {
         partls_ctx *c = nullptr;
         partls_status st = partls_create(mc->devices[(size_t)r], &c);
         if (st != PARTLS_OK) { partls_multi_destroy(mc); return st; }
+        c->multi_rank = true;
         mc->ctx.push_back(c);
     }
     if (distinct) {
