@@ -347,6 +347,18 @@ partls_status partls_get_blocks(const partls_ctx *ctx, int64_t *blocks);
  * returns PARTLS_ERR_ILL_CONDITIONED (see there).  min_pivot (optional): the smallest leave-one-out pivot of that model's basis on the
  * unit-diagonal scale, a lower bound of 1 / cond(G_BB) (0 when unknown). */
 partls_status partls_get_kkt_violation(const partls_ctx *ctx, double *violation, double *min_pivot);
+/* debugging / tests: the sweep kernel the prepared problem runs on (partls_opt_sweep, partls_opt_models, the node solves of
+ * partls_bnb_bound* / fit(Alt) / partls_opt_finish) and its tile count T = ceil(n / 16) on the register kernels (0 on the global-memory
+ * kernels).  After a partls_cv_opt (which leaves no prepared problem on ctx): the route of that call's problems, which are swept in one
+ * batched launch on the register kernels unless PARTLS_CV_SERIAL is set.  Read-only: the prepare decides it from n, the flags and the
+ * knobs read at partls_create.  PARTLS_ERR_STATE when neither holds. */
+typedef enum {
+    PARTLS_ROUTE_REG_256 = 1,   /* register-resident tableau, 256-thread workgroups (T <= 10)                            */
+    PARTLS_ROUTE_REG_512 = 2,   /* register-resident tableau, 512-thread workgroups (T = 11 .. 18; 19, 20: PARTLS_REG_MAXT) */
+    PARTLS_ROUTE_DEFERRED = 3,  /* global-memory tableau, deferred updates (n > 288, PARTLS_OPT_GENERIC_KERNEL)          */
+    PARTLS_ROUTE_EAGER = 4      /* global-memory tableau, every block applied at once (PARTLS_EAGER_GENERIC)             */
+} partls_route;
+partls_status partls_get_sweep_route(const partls_ctx *ctx, int *kernel, int *tiles);
 /* distinct subproblems the last partls_opt_finish solved and compared on the data objective (1: the sweep recorded no near tie) */
 partls_status partls_get_near_ties(const partls_ctx *ctx, int64_t *evaluated);
 /* debugging / tests: copy the Gram products of the prepared problem to the host: G ((M+2) x (M+2), column-major,

@@ -11,6 +11,7 @@ OK, ERR_BAD_ARG, ERR_BAD_PARTITION, ERR_NONFINITE, ERR_NO_DEVICE, ERR_HIP, ERR_N
 OPT_FAITHFUL_INTERCEPT = 1
 OPT_GENERIC_KERNEL = 2
 T_GRAM, T_PREP, T_SWEEP, T_FINISH, T_CALIB = range(5)
+ROUTE_REG_256, ROUTE_REG_512, ROUTE_DEFERRED, ROUTE_EAGER = range(1, 5)
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -84,6 +85,7 @@ SYMBOLS = [
     ("partls_get_blocks", C.c_int, [C.c_void_p, _ip]),
     ("partls_get_kkt_violation", C.c_int, [C.c_void_p, _dp, _dp]),
     ("partls_get_near_ties", C.c_int, [C.c_void_p, _ip]),
+    ("partls_get_sweep_route", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 ]
 
 _lib = None

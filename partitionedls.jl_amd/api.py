@@ -364,6 +364,13 @@ class Context:
         _check(L.lib().partls_get_blocks(self._h, C.byref(n)))
         return n.value
 
+    def sweep_route(self):
+        """(kernel, T): the sweep kernel of the prepared problem (or of the last cv_opt's problems) — L.ROUTE_REG_256, ROUTE_REG_512,
+        ROUTE_DEFERRED or ROUTE_EAGER — and its tile count on the register kernels, 0 otherwise (include/partls.h: partls_get_sweep_route)"""
+        k = C.c_int(); t = C.c_int()
+        _check(L.lib().partls_get_sweep_route(self._h, C.byref(k), C.byref(t)))
+        return k.value, t.value
+
     def kkt_violation(self):
         """data-space KKT violation of the last finished winner (include/partls.h: partls_get_kkt_violation)"""
         v = C.c_double()

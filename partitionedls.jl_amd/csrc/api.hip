@@ -1762,6 +1762,19 @@ try {
 catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
 catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
 
+partls_status partls_get_sweep_route(const partls_ctx *c, int *kernel, int *tiles)
+try {
+    if (!c || !kernel || !tiles) { set_error("partls_get_sweep_route: bad argument"); return PARTLS_ERR_BAD_ARG; }
+    // partls_cv_opt prepares its problems on the working context (cv.hip), which carries this context's knobs
+    const partls_ctx *p = c->prepared ? c : (c->cv_work && c->cv_work->prepared ? c->cv_work : nullptr);
+    if (!p) { set_error("partls_get_sweep_route: context not prepared"); return PARTLS_ERR_STATE; }
+    *kernel = p->use_reg ? (sweep_reg_small(p->T) ? PARTLS_ROUTE_REG_256 : PARTLS_ROUTE_REG_512)
+                         : (p->knobs.eager_generic ? PARTLS_ROUTE_EAGER : PARTLS_ROUTE_DEFERRED);
+    *tiles = p->use_reg ? p->T : 0;
+    return PARTLS_OK;
+}
+catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+
 partls_status partls_opt_bit_order(partls_ctx *c, int64_t *gbit, double *flip_cost)
 try {
     if (!c || !c->prepared) { set_error("partls_opt_bit_order: context not prepared"); return PARTLS_ERR_STATE; }

@@ -154,28 +154,28 @@ def _check(tag, ref, r, pats, frees, lb, br, rank_deficient=False):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # every route: root, random nodes at every depth, a batch of one node
 # ---------------------------------------------------------------------------------------------------------------------------------
-ROUTES = {   # id: (D, K, design, env, flags, random nodes)
-    "reg256-d15": (15, 4, ("offset", "overlap"), None, 0, 40),
-    "reg256-d16": (16, 5, ("empty",), None, 0, 40),
-    "reg256-d63": (63, 45, ("offset",), None, 0, 60),
-    "reg256-d159": (159, 12, ("dup",), None, 0, 30),
-    "reg512-d160": (160, 61, ("feasible",), None, 0, 40),
-    "reg512-d255": (255, 20, ("overlap", "eta"), None, 0, 30),
-    "reg512-d287": (287, 16, ("scaled", "offset"), None, 0, 24),
-    "regT19-d300": (300, 12, ("offset",), {"PARTLS_REG_MAXT": "20"}, 0, 16),
-    "regT20-d319": (319, 10, ("overlap", "eta"), {"PARTLS_REG_MAXT": "20"}, 0, 16),
-    "lazy-d288": (288, 12, ("offset",), None, 0, 16),
-    "lazy-d330": (330, 10, ("dup", "eta"), None, 0, 12),
-    "lazy-d520": (520, 8, ("scaled",), None, 0, 8),
-    "lazy-generic-d40": (40, 8, ("overlap", "offset"), None, GENERIC, 40),
-    "host-generic-d40": (40, 8, ("scaled",), {"PARTLS_EAGER_GENERIC": "1"}, GENERIC, 40),
-    "host-coop-d330": (330, 10, ("offset",), {"PARTLS_EAGER_GENERIC": "1"}, 0, 5),
+ROUTES = {   # id: (D, K, design, env, flags, random nodes, sweep_route(): (partls_route, tile count))
+    "reg256-d15": (15, 4, ("offset", "overlap"), None, 0, 40, (1, 1)),
+    "reg256-d16": (16, 5, ("empty",), None, 0, 40, (1, 2)),
+    "reg256-d63": (63, 45, ("offset",), None, 0, 60, (1, 4)),
+    "reg256-d159": (159, 12, ("dup",), None, 0, 30, (1, 10)),
+    "reg512-d160": (160, 61, ("feasible",), None, 0, 40, (2, 11)),
+    "reg512-d255": (255, 20, ("overlap", "eta"), None, 0, 30, (2, 16)),
+    "reg512-d287": (287, 16, ("scaled", "offset"), None, 0, 24, (2, 18)),
+    "regT19-d300": (300, 12, ("offset",), {"PARTLS_REG_MAXT": "20"}, 0, 16, (2, 19)),
+    "regT20-d319": (319, 10, ("overlap", "eta"), {"PARTLS_REG_MAXT": "20"}, 0, 16, (2, 20)),
+    "lazy-d288": (288, 12, ("offset",), None, 0, 16, (3, 0)),
+    "lazy-d330": (330, 10, ("dup", "eta"), None, 0, 12, (3, 0)),
+    "lazy-d520": (520, 8, ("scaled",), None, 0, 8, (3, 0)),
+    "lazy-generic-d40": (40, 8, ("overlap", "offset"), None, GENERIC, 40, (3, 0)),
+    "host-generic-d40": (40, 8, ("scaled",), {"PARTLS_EAGER_GENERIC": "1"}, GENERIC, 40, (4, 0)),
+    "host-coop-d330": (330, 10, ("offset",), {"PARTLS_EAGER_GENERIC": "1"}, 0, 5, (4, 0)),
 }
 
 
 @pytest.mark.parametrize("route", list(ROUTES))
 def test_node_bounds_and_branches(partls, monkeypatch, route):
-    D, K, design, env, flags, count = ROUTES[route]
+    D, K, design, env, flags, count, kernel = ROUTES[route]
     seed = 7100 + D + K
     X, y, P, eta = _problem(seed, max(3 * D, 400), D, K, design)
     Kp = K + 1
@@ -192,6 +192,7 @@ def test_node_bounds_and_branches(partls, monkeypatch, route):
         pats, frees = np.concatenate([pats, fp]), np.concatenate([frees, ff])
     ctx = _ctx(partls, monkeypatch, X, y, P, eta, flags, env)
     try:
+        assert ctx.sweep_route() == kernel, "%s runs on %s" % (route, ctx.sweep_route())
         if route.startswith("host-coop"):                    # one node per call: the cooperative kernel
             out = []
             for i in range(len(pats)):

@@ -360,6 +360,7 @@ def test_winner_from_the_512_thread_kernel_mid_sizes(partls, oracle, monkeypatch
         ctx = partls.Context(0)
         try:
             ctx.opt_prepare(X, y, P, eta, 0)
+            assert ctx.sweep_route() == (partls.lowlevel.ROUTE_REG_512, (D + 15) // 16)        # free intercept: n = D
             bo, bp, _, unconv = ctx.opt_sweep(0, -1)
             assert unconv == 0
             res[mode] = ctx.opt_finish(bp)

@@ -1,5 +1,6 @@
 """Randomised differential parity (GPU): the HIP path against the CPU oracle on many small random problems — random shapes
-(1..17 tile columns), unequal group sizes, eta values, noise levels, dependent / duplicate / null columns.  Every pattern's
+(D <= 93: 1..6 tile columns of the register kernel, measured by replaying the seeds; the other tile counts are
+tests/test_gpu_tile_counts.py's), unequal group sizes, eta values, noise levels, dependent / duplicate / null columns.  Every pattern's
 objective (faithful intercept: the reference's 2^(K+1) enumeration, Opt.jl:85-96) within 1e-8 relative (+2e-7 ||y|| absolute
 at zero objectives, where the Gram form has abs error ~ sqrt(eps * yy)), same winner up to ties, model within 1e-6.
 Seeds are fixed: failures reproduce (tools/fuzz_triage.py arbitrates a mismatch with KKT certificates; tools/tableau_emul.py
@@ -157,8 +158,8 @@ def test_fuzz_alt_same_start_vs_oracle(partls, oracle, block):
 
 @pytest.mark.parametrize("D", [273, 300, 305, 340])
 def test_fuzz_large_n_generic_path_vs_oracle(partls, oracle, D):
-    """the top of the register kernel's range (n = 274, 301, 306: T = 18, 19, 20 tile columns) and, beyond n = 320, the global-memory
-    tableau kernels (sweep_generic.hip chains, sweep_coop.hip single nodes)."""
+    """the top of the register kernel's range (n = 274: T = 18 tile columns) and, beyond n = 288, the deferred-update kernel
+    (sweep_lazy.hip: n = 301, 306, 341; the register kernel's T = 19 / 20 run behind PARTLS_REG_MAXT, next test)."""
     rng = np.random.default_rng(9900 + D)
     K = 3
     N = 2 * D + 11
@@ -169,6 +170,8 @@ def test_fuzz_large_n_generic_path_vs_oracle(partls, oracle, D):
     y = X @ (rng.random(D) * np.array([2.0, -1.0, 0.5])[grp]) + 0.7 + 0.1 * rng.standard_normal(N)
     ref = oracle.fit_opt(X, y, P, return_all=True)
     model, _, rep = partls.fit(partls.Opt, X, y, P, returnAllSolutions=True)
+    L = partls.lowlevel
+    assert partls.default_context().sweep_route() == ((L.ROUTE_REG_512, 18) if D == 273 else (L.ROUTE_DEFERRED, 0))
     got = np.array([rep.solutions._all[b] for b in range(len(ref["all_opt"]))])
     np.testing.assert_allclose(got, ref["all_opt"], rtol=1e-8, atol=1e-8)
     m2, _, r2 = partls.fit(partls.Opt, X, y, P)
@@ -197,6 +200,7 @@ def test_top_of_the_register_kernel_behind_its_knob(partls, oracle, D):
         finally:
             os.environ.pop("PARTLS_REG_MAXT", None)
         ctx.opt_prepare(X, y, P, 0.0, partls.lowlevel.OPT_FAITHFUL_INTERCEPT)
+        assert ctx.sweep_route() == ((partls.lowlevel.ROUTE_REG_512, (D + 16) // 16) if maxt == "20" else (partls.lowlevel.ROUTE_DEFERRED, 0))
         bo, bp, all_opt, unconv = ctx.opt_sweep(0, -1, want_all=True)
         assert unconv == 0
         got[maxt] = (all_opt.copy(), ctx.opt_finish(bp))

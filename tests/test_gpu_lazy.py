@@ -1,4 +1,4 @@
-"""GPU tests of the deferred-update sweep kernel (csrc/sweep_lazy.hip): fit(Opt) beyond n = 320 tableau variables, and the node batches
+"""GPU tests of the deferred-update sweep kernel (csrc/sweep_lazy.hip): fit(Opt) beyond n = 288 tableau variables, and the node batches
 of BnB / the bit-order calibration there (Opt.jl:87-90 per pattern; BnB.jl:69-92 per node).
 
 The kernel keeps the rank-1 terms of its pivots pending in LDS and brings the tableau in global memory up to date only every ~40 pivots,
@@ -41,6 +41,7 @@ def _sweep(partls, monkeypatch, X, y, P, eager, chain_len=None, flags=None):
     ctx = partls.Context(0)                                          # the knobs are read once, at partls_create
     try:
         ctx.opt_prepare(X, y, P, 0.0, partls.lowlevel.OPT_FAITHFUL_INTERCEPT if flags is None else flags)
+        assert ctx.sweep_route() == (partls.lowlevel.ROUTE_EAGER if eager else partls.lowlevel.ROUTE_DEFERRED, 0)
         bo, bp, allo, unconv = ctx.opt_sweep(0, -1, want_all=True)
         pivots, vetoes = ctx.pivots(), ctx.vetoes()                  # of the sweep (the finish's node solve has counters of its own)
         a, b, t, opt, bi = ctx.opt_finish(bp)

@@ -9,30 +9,11 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from models_reference import _cleanup, _close, _scatter
 
 pytestmark = pytest.mark.gpu
 
 FAITHFUL = 1
-
-
-def _close(a, ref, tol=1e-9):
-    a, ref = np.asarray(a), np.asarray(ref)
-    assert a.shape == ref.shape
-    err = np.abs(a - ref) / np.maximum(1.0, np.abs(ref))
-    assert np.all(err <= tol), f"max relative error {err.max():.3e}"
-
-
-def _scatter(r, npat):
-    """export rows (visiting order) -> arrays indexed by the reference pattern; every pattern exactly once"""
-    pat = r["pattern"]
-    assert np.array_equal(np.sort(pat), np.arange(npat))
-    out = {}
-    for k in ("opt", "alpha", "beta", "t", "raw_alpha"):
-        if k in r:
-            v = np.empty_like(r[k])
-            v[pat] = r[k]
-            out[k] = v
-    return out
 
 
 def _ctx(partls, X, y, P, eta=0.0, flags=FAITHFUL, monkeypatch=None, env=None):
@@ -45,19 +26,6 @@ def _ctx(partls, X, y, P, eta=0.0, flags=FAITHFUL, monkeypatch=None, env=None):
             monkeypatch.delenv(k)
     ctx.opt_prepare(X, y, P, eta, flags)
     return ctx
-
-
-def _cleanup(raw, P, b):
-    """cleanupResult (Opt.jl:34-44) from nonneg_lsq's alpha of pattern b (numpy; the reference formula)"""
-    M, K = P.shape
-    a = raw[:M]
-    s = np.array([1.0 if (b >> k) & 1 else -1.0 for k in range(K)])
-    sums = P.T @ a
-    beta = s * sums
-    A = np.where(sums == 0.0, 1.0, sums)
-    alpha = (P * (a[:, None] / A[None, :])).sum(axis=1)
-    f = 1.0 if (b >> K) & 1 else -1.0
-    return alpha, beta, f * raw[M]
 
 
 def test_toy_every_pattern_matches_the_golden_models(partls, monkeypatch):
