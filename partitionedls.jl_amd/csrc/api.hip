@@ -1,6 +1,7 @@
 // api.hip — the C ABI of include/partls.h: host orchestration of the HIP kernels.  No CPU fallback: every compute
 // entry needs a HIP device and fails with PARTLS_ERR_NO_DEVICE / PARTLS_ERR_HIP otherwise.
 #include "ctx.h"
+#include "sweep_rules.h"
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -316,8 +317,7 @@ void opt_codes(const partls_ctx *c, uint64_t pattern, std::vector<int8_t> &codes
     // multiplier of Opt.jl:28-29: f_m = sum_k P[m,k] s_k; only its sign matters for the constraint f_m w_m >= 0 (0: column is zero)
     codes.resize((size_t)c->n);
     for (int i = 0; i < c->n; ++i) {
-        const uint64_t m = c->mask_tab[(size_t)i];
-        const int f = 2 * __builtin_popcountll(m & pattern) - __builtin_popcountll(m);
+        const int f = sign_of_var(c->mask_tab[(size_t)i], pattern);
         codes[(size_t)i] = (int8_t)((f > 0) - (f < 0));
     }
 }
@@ -860,7 +860,7 @@ static void cleanup_opt(const partls_ctx *c, const std::vector<double> &w, uint6
     const int64_t M = c->M, K = c->K;
     std::vector<double> a((size_t)M, 0.0);
     for (int64_t m = 0; m < M; ++m) {
-        const int f = 2 * __builtin_popcountll(c->mask_aug[(size_t)m] & pattern) - __builtin_popcountll(c->mask_aug[(size_t)m]);
+        const int f = sign_of_var(c->mask_aug[(size_t)m], pattern);
         a[(size_t)m] = (f != 0) ? w[(size_t)m] / (double)f : 0.0;
         if (a[(size_t)m] < 0.0) a[(size_t)m] = 0.0;      // round-off guard: nonneg_lsq never returns negatives
     }
@@ -1415,7 +1415,7 @@ try {
     std::vector<int8_t> vcode((size_t)c->M + 1, 0);
     for (int64_t m = 0; m <= c->M; ++m) {
         if (m == c->M && !c->faithful) { vcode[(size_t)m] = 2; continue; }          // free intercept
-        const int f = 2 * __builtin_popcountll(c->mask_aug[(size_t)m] & full) - __builtin_popcountll(c->mask_aug[(size_t)m]);
+        const int f = sign_of_var(c->mask_aug[(size_t)m], full);
         vcode[(size_t)m] = (int8_t)((f > 0) - (f < 0));
     }
     int worst = -1;
@@ -1463,7 +1463,7 @@ try {
     if (optval) { st = data_objective(c, w, optval); if (st != PARTLS_OK) return st; }
     if (raw_alpha)
         for (int64_t m = 0; m <= c->M; ++m) {
-            const int f = 2 * __builtin_popcountll(c->mask_aug[(size_t)m] & (uint64_t)pattern) - __builtin_popcountll(c->mask_aug[(size_t)m]);
+            const int f = sign_of_var(c->mask_aug[(size_t)m], (uint64_t)pattern);
             const double a = (f != 0) ? w[(size_t)m] / (double)f : 0.0;
             raw_alpha[m] = a > 0.0 ? a : 0.0;
         }

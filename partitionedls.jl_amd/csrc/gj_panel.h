@@ -1,4 +1,5 @@
-// gj_panel.h — block principal pivots on a global-memory tableau (shared by sweep_generic.hip and sweep_coop.hip).
+// gj_panel.h — block principal pivots on a global-memory tableau (shared by sweep_generic.hip and sweep_coop.hip; sweep_lazy.hip takes
+// GJ_MB and the helpers of sweep_rules.h through it).  The decisions themselves are in sweep_rules.h.
 //
 // A block is a list ks[0..m) of pivot variables.  The panel P[j][i] = T[i][ks[j]] (all rows i; read as row ks[j] by symmetry)
 // is eliminated in LDS by m sequential Gauss–Jordan steps in the unified convention of the project
@@ -7,7 +8,7 @@
 // current basis, Lawson–Hanson).  The caller then applies  T_ic -= sum_s Z_s[i] Z_s[c] / d_s  to its rows in ONE pass and
 // overwrites the rows / columns of the pivoted variables from the final panel.  Block-local barriers only.
 #pragma once
-#include "common.h"
+#include "sweep_rules.h"
 #include <type_traits>
 
 namespace partls {
@@ -46,12 +47,19 @@ __device__ __forceinline__ void gj_panel_load(const double *T, int ld, const int
     __syncthreads();
 }
 
-__device__ __forceinline__ double gj_rcp(double d)       // v_rcp_f64 + two Newton steps (as sweep_blk.hip's fast_rcp): ~1 ulp
+// the violator list of a round, by thread 0 from the scan's mask words (ascending; the backup rule keeps only the last one); ends in a barrier
+__device__ __forceinline__ void violator_list(const unsigned long long *s_inf, int nwords, bool all, int *s_viol, int *s_nv)
 {
-    double y = __builtin_amdgcn_rcp(d);
-    y = fma(fma(-d, y, 1.0), y, y);
-    y = fma(fma(-d, y, 1.0), y, y);
-    return y;
+    if (threadIdx.x == 0) {
+        int nv = 0;
+        for (int w = 0; w < nwords; ++w) {
+            unsigned long long bits = s_inf[w];
+            while (bits) { s_viol[nv++] = (w << 6) + __builtin_ctzll(bits); bits &= bits - 1; }
+        }
+        if (!all) { s_viol[0] = s_viol[nv - 1]; nv = 1; }
+        *s_nv = nv;
+    }
+    __syncthreads();
 }
 
 // returns the number of accepted pivots (uniform).  Acceptance of an ENTERING variable k follows the leave-one-out rule of
@@ -100,7 +108,7 @@ __device__ __forceinline__ int gj_panel_eliminate(double *Pn, double *Zn, double
         const double flag = red[s & 1];
         const bool ok = bas || (__builtin_amdgcn_readfirstlane((int)(d > piv_eps && flag == 0.0)) != 0);
         if (tid == 0) red[(s + 1) & 1] = 0.0;                            // the other flag: last read before the previous closing barrier
-        const double inv = ok ? gj_rcp(d) : 0.0, ainv = fabs(inv);
+        const double inv = ok ? rcp_newton(d) : 0.0, ainv = fabs(inv);
         if (ok) {
             ++accepted;
             const double zi = pv[s];

@@ -1,5 +1,5 @@
 // misc.hip — the small kernels either side of the sweep: synthetic inputs, tableau preparation, residual from the data.
-#include "common.h"
+#include "sweep_rules.h"
 
 namespace partls {
 
@@ -205,8 +205,7 @@ __global__ void walk_codes_kernel(const uint64_t *__restrict__ mask, int n, int 
     uint64_t pat = walk_base(c, kbits);
     for (int j = 1; j <= i; ++j) pat ^= 1ULL << (((c % nseg) * seg_len + j - 1) % kbits);
     for (int v = threadIdx.x; v < n; v += blockDim.x) {
-        const uint64_t m = mask[v];
-        const int f = 2 * __popcll(m & pat) - __popcll(m);
+        const int f = sign_of_var(mask[v], pat);
         codes[(size_t)blockIdx.x * n + v] = (int8_t)((f > 0) - (f < 0));
     }
 }

@@ -10,7 +10,7 @@
 //     alpha_m = sum_{k ∋ m} a_m / A_k, t = w_I.
 // One wave per pattern; the sums run sequentially in index order (member terms only: the host's zero terms add nothing), so the
 // results are bitwise those of the host formulas applied to the same w.
-#include "common.h"
+#include "sweep_rules.h"
 
 namespace partls {
 
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(MD_THREADS) void models_cleanup_kernel(double *__re
         __syncthreads();
         for (int m = lane; m < n; m += MD_THREADS) {
             const uint64_t mk = msk[m];
-            const int f = 2 * __popcll(mk & b) - __popcll(mk);
+            const int f = sign_of_var(mk, b);
             const double r = (f != 0) ? w[m] / (double)f : 0.0;
             if (want_raw) row[m] = r > 0.0 ? r : 0.0;            // partls_opt_pattern's raw alpha, in place (row m of the output)
             if (m < M) a[m] = r < 0.0 ? 0.0 : r;

@@ -2,7 +2,7 @@
 //
 // Replaces the loop body of fit(Opt), Opt.jl:87-90 (indextobeta + bmatrix + nonneg_lsq + objective), for every pattern of a
 // Gray-code chain, and serves the node solves of Alt (Alt.jl:80-90) and BnB (BnB.jl:69-92); same mathematics and the same
-// per-pattern decisions as sweep_generic.hip.
+// per-pattern decisions as the other tableau kernels: the rules of sweep_rules.h.
 //
 // Data layout (one workgroup = 512 threads = 8 waves = 2 waves/SIMD on one CU, one tableau, one chain):
 //   * variables are padded to 16*T; the symmetric tableau is cut into 16x16 tiles (rho, gamma), rho <= gamma only;
@@ -33,7 +33,7 @@
 // The test needs no basis bookkeeping: for a NONBASIC row j the Schur complement is positive semidefinite, T_jk^2 <= T_jj T_kk
 // <= d_k, so d_k > piv_eps * T_jk^2 holds with a margin of 1e11 and every row can simply test its own entry; a leaving pivot
 // has 1/d < 0 and a rejected one 1/d = 0, which fail the test by sign.  Only the rhs row (no variable) must not report.
-#include "common.h"
+#include "sweep_rules.h"
 #include <atomic>
 #include <type_traits>
 
@@ -75,26 +75,11 @@ constexpr int colw(int T) { return 513; }                          // panel colu
 // interleave on the same SIMDs instead of one chain leaving them idle (BASELINE config 2: n = 128).
 static constexpr int MAXT_S = 10;
 static constexpr int CW_S = 257;                                   // one panel slot per thread of the 256-thread workgroup, odd
-__device__ __forceinline__ double fast_rcp(double d)
-{
-    double y = __builtin_amdgcn_rcp(d);
-    y = fma(fma(-d, y, 1.0), y, y);
-    y = fma(fma(-d, y, 1.0), y, y);
-    return y;
-}
 template <class PT> __device__ __forceinline__ PT *uniform_ptr(PT *p)     // a wave-uniform pointer the compiler cannot prove uniform -> SGPR pair
 {
     const unsigned long long v = (unsigned long long)p;
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32));
     return (PT *)(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ int sign_of_var(uint64_t m, uint64_t pat) { return 2 * __popcll(m & pat) - __popcll(m); }
-__device__ __forceinline__ double readlane_f64(double v, int lane)      // lane: wave-uniform
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_readlane(lo, lane);
-    hi = __builtin_amdgcn_readlane(hi, lane);
-    return __hiloint2double(hi, lo);
 }
 
 // Diagnostic build only (-DPARTLS_STAMPS): per-phase cycle shares of workgroup 0 / thread 0, written to p.scratch[0..23]
@@ -173,6 +158,21 @@ struct Half {
     __device__ static constexpr int idx(int rho, int gam) { return tri(gam) + rho - OFF; }
 };
 
+// ---- the thread's tile slots -> a tableau image in global memory (snapshots, node_tab) ----------------------------------
+// The address loop of the chain start in sweep_body (see the comment there), storing.  The load stays written out where it is
+// used: as a helper the same loop compiles to the same registers but reschedules the chain-mode kernels.
+template <class L>
+__device__ __forceinline__ void tiles_store(double *dst, const double (&S)[L::CNT], int t8)
+{
+    double *bp = uniform_ptr(dst) + (size_t)L::OFF * 256;
+#pragma unroll
+    for (int s = 0; s < L::CNT; ++s) {
+        if ((s & 1) == 0) asm volatile("" : "+s"(bp));
+        bp[(s & 1) * 256 + t8] = S[s];
+        if (s & 1) bp += 512;
+    }
+}
+
 // ---- tile-column gather ------------------------------------------------------------------------------------------------
 // Element (16 rho + a, 16 KAPPA + b) belongs to column b of the tile, row position a*RS + rho.  Only the pivot columns are
 // gathered, COMPACTED: the j-th pivot of the block (ascending local index) becomes panel column j = popc(pm below it).
@@ -249,7 +249,7 @@ __device__ __forceinline__ int panel_block(double *P, double *Z, double *U, doub
         U[(s & 1) * US + uslot] = pv[s];
         if (myj == s) {                                     // the one pivot-row thread (its wave only: the others branch over)
             const double d = pv[s];
-            Dinv[s] = (my_basic || d > piv_eps) ? fast_rcp(d) : 0.0;
+            Dinv[s] = (my_basic || d > piv_eps) ? rcp_newton(d) : 0.0;
         }
         __syncthreads();
         double inv = Dinv[s];
@@ -399,7 +399,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                 const int par = sc & 1;
                 ++sc;
                 bool bad = false;
-                if (has_var) {
+                if (has_var) {                                            // kkt_violates<NODE> (sweep_rules.h), written out: see the exchange rule below
                     const double fq = q * (double)(f > 1 ? 1 : (f < -1 ? -1 : f));     // sign(f) * q  (|f| = 2: feature of two groups)
                     if (NODE && isfree) bad = !basic && !blocked && (fabs(q) > p.tol);     // free: stationarity only
                     else if (basic) bad = (f == 0) || (fq < -p.tol);
@@ -425,6 +425,8 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                     tiles |= (sw >> 8) << (4 * w);
                 }
                 STAMP(0);
+                // ExchangeRule::next (sweep_rules.h), written out: through the helpers the same rules compile to the same VGPR count but
+                // move 2-4 spilled SGPRs, and this kernel is tuned to the register.  Keep both in step with sweep_rules.h by hand.
                 if (count == 0) break;
                 bool all;
                 if (count < ninf_best) { ninf_best = count; patience = 3; all = true; }
@@ -588,6 +590,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                     if (has_var) p.best_sol[(size_t)blockIdx.x * p.node_ld + tid] = basic ? q : 0.0;
                 }
             }
+            // the ranking of rank_pattern (sweep_rules.h) on objective^2 held in LDS, in this kernel's own form: it has no `best_pat >= 0` guard
             if (tid == THREADS - 1) {                                // lexicographic (objective, pattern) minimum: argmin's first-index rule
                 const double bo = s_best[0];
                 const long long bp = reinterpret_cast<long long *>(s_best)[1];
@@ -603,15 +606,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
             if (p.node_dst) {                                     // snapshot of the final state: what a child node starts from
                 double *snap = p.node_dst[chain];
                 if (snap && (H == 0 || T > 1)) {
-                    {
-                        double *bp = uniform_ptr(snap) + (size_t)L::OFF * 256;  // (addresses as at the chain start: see there)
-#pragma unroll
-                        for (int s = 0; s < L::CNT; ++s) {
-                            if ((s & 1) == 0) asm volatile("" : "+s"(bp));
-                            bp[(s & 1) * 256 + t8] = S[s];
-                            if (s & 1) bp += 512;
-                        }
-                    }
+                    tiles_store<L>(snap, S, t8);
                     if (tid < 16 * T) {
                         snap[(size_t)nslots(T) * 256 + tid] = q;
                         reinterpret_cast<int8_t *>(snap + (nslots(T) * 256 + 16 * T + 8))[tid] = basic ? 1 : 0;
@@ -621,15 +616,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
             }
             if (p.node_tab && (H == 0 || T > 1)) {                // final tableau + basis, same layout as T0 (half 1 of T = 1 owns nothing)
                 double *tab = p.node_tab + (size_t)chain * (nslots(T) * 256 + 16 * T + 8);
-                {
-                    double *bp = uniform_ptr(tab) + (size_t)L::OFF * 256;
-#pragma unroll
-                    for (int s = 0; s < L::CNT; ++s) {
-                        if ((s & 1) == 0) asm volatile("" : "+s"(bp));
-                        bp[(s & 1) * 256 + t8] = S[s];
-                        if (s & 1) bp += 512;
-                    }
-                }
+                tiles_store<L>(tab, S, t8);
                 if (tid < 16 * T) p.node_basic[(size_t)chain * 16 * T + tid] = basic ? 1 : 0;
             }
         }
@@ -688,39 +675,18 @@ __global__ __launch_bounds__(256, PARTLS_SMALL_OCC(T)) void sweep_small_kernel(S
     sweep_body<T, 0, NODE, 1, MODELS>(p);
 }
 
-// Tfull ((n+1)^2) -> tile-cyclic initial state: [slot = tri(gamma) + rho][256 = a + 16 b], then q0[16 T], then the corner
-__global__ void layout_reg_kernel(const double *__restrict__ Tfull, int n, int T, double *__restrict__ out)
-{
-    const int ld = n + 1;
-    const int ns = T * (T + 1) / 2;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int tot = ns * 256 + 16 * T + 1;
-    if (idx >= tot) return;
-    if (idx < ns * 256) {
-        const int s = idx >> 8, t8 = idx & 255, a = t8 & 15, b = t8 >> 4;
-        int gam = 0;
-        while ((gam + 1) * (gam + 2) / 2 <= s) ++gam;
-        const int rho = s - gam * (gam + 1) / 2;
-        const int i = 16 * rho + a, j = 16 * gam + b;
-        out[idx] = (i < n && j < n) ? Tfull[(size_t)i * ld + j] : ((i == j) ? 1.0 : 0.0);
-    } else if (idx < ns * 256 + 16 * T) {
-        const int v = idx - ns * 256;
-        out[idx] = (v < n) ? Tfull[(size_t)v * ld + n] : 0.0;
-    } else {
-        out[idx] = Tfull[(size_t)n * ld + n];
-    }
-}
-
-__global__ void layout_reg_batch_kernel(const double *__restrict__ Tfull, int n, int T, double *__restrict__ out)
+// Tfull ((n+1)^2) -> tile-cyclic initial state: [slot = tri(gamma) + rho][256 = a + 16 b], then q0[16 T], then the corner.
+// blockIdx.y selects one problem of a stacked batch; in_stride / out_stride: doubles from one problem to the next
+__global__ void layout_reg_kernel(const double *__restrict__ Tfull, int n, int T, double *__restrict__ out, int64_t in_stride, int64_t out_stride)
 {
     const int64_t q = blockIdx.y;
-    const int ns = T * (T + 1) / 2;
-    const int tot = ns * 256 + 16 * T + 1;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= tot) return;
     const int ld = n + 1;
-    const double *Tq = Tfull + q * (int64_t)ld * ld;
-    double *oq = out + q * (int64_t)(ns * 256 + 16 * T + 8);
+    const int ns = T * (T + 1) / 2;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int tot = ns * 256 + 16 * T + 1;
+    if (idx >= tot) return;
+    const double *Tq = Tfull + q * in_stride;
+    double *oq = out + q * out_stride;
     if (idx < ns * 256) {
         const int s = idx >> 8, t8 = idx & 255, a = t8 & 15, b = t8 >> 4;
         int gam = 0;
@@ -744,18 +710,34 @@ bool sweep_reg_exports(int T) { return PARTLS_EXPORT_BIG != 0 && T <= blk::EXPOR
 bool sweep_reg_small(int T) { return T <= blk::MAXT_S; }   // the 256-thread kernel (several chains per CU) runs this tile count
 size_t sweep_reg_t0_doubles(int T) { return (size_t)T * (T + 1) / 2 * 256 + 16 * (size_t)T + 8; }
 
-hipError_t launch_layout_reg(const double *Tfull, int n, int T, double *T0reg, hipStream_t s)
-{
-    const int tot = T * (T + 1) / 2 * 256 + 16 * T + 1;
-    hipLaunchKernelGGL(blk::layout_reg_kernel, dim3((tot + 255) / 256), dim3(256), 0, s, Tfull, n, T, T0reg);
-    return hipGetLastError();
-}
-
+// every problem of the batch writes tot = ns * 256 + 16 T + 1 doubles; the batch strides by sweep_reg_t0_doubles(T)
 hipError_t launch_layout_reg_batch(const double *Tfull, int n, int T, int batch, double *T0reg, hipStream_t s)
 {
     const int tot = T * (T + 1) / 2 * 256 + 16 * T + 1;
-    hipLaunchKernelGGL(blk::layout_reg_batch_kernel, dim3((tot + 255) / 256, batch), dim3(256), 0, s, Tfull, n, T, T0reg);
+    hipLaunchKernelGGL(blk::layout_reg_kernel, dim3((tot + 255) / 256, batch), dim3(256), 0, s, Tfull, n, T, T0reg,
+                       (int64_t)(n + 1) * (n + 1), (int64_t)sweep_reg_t0_doubles(T));
     return hipGetLastError();
+}
+
+hipError_t launch_layout_reg(const double *Tfull, int n, int T, double *T0reg, hipStream_t s)
+{
+    return launch_layout_reg_batch(Tfull, n, T, 1, T0reg, s);
+}
+
+// f(std::integral_constant<int, T>{}) for a compiled tile count T (PARTLS_ONLY_T: that one only), `none` for any other
+template <class R, class F>
+static R dispatch_T(int T, R none, F f)
+{
+    switch (T) {
+#ifdef PARTLS_ONLY_T
+        case PARTLS_ONLY_T: return f(std::integral_constant<int, PARTLS_ONLY_T>{});
+#else
+#define PARTLS_L(i) case i + 1: return f(std::integral_constant<int, i + 1>{});
+        PARTLS_CASES(PARTLS_L)
+#undef PARTLS_L
+#endif
+        default: return none;
+    }
 }
 
 template <int T>
@@ -769,16 +751,7 @@ static hipError_t launch_blk_batch_T(const SweepParams &p, int grid, int batch, 
 hipError_t launch_sweep_blk_batch(const SweepParams &p, int T, int grid, int batch, hipStream_t s)
 {
     if (p.node_code || batch < 1 || batch > 65535) return hipErrorInvalidValue;
-    switch (T) {
-#ifdef PARTLS_ONLY_T
-        case PARTLS_ONLY_T: return launch_blk_batch_T<PARTLS_ONLY_T>(p, grid, batch, s);
-#else
-#define PARTLS_L(i) case i + 1: return launch_blk_batch_T<i + 1>(p, grid, batch, s);
-        PARTLS_CASES(PARTLS_L)
-#undef PARTLS_L
-#endif
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_T(T, hipErrorInvalidValue, [&](auto t) { return launch_blk_batch_T<decltype(t)::value>(p, grid, batch, s); });
 }
 
 template <int T>
@@ -820,30 +793,12 @@ int sweep_reg_concurrency(int T)
 }
 int sweep_reg_concurrency_query(int T)
 {
-    switch (T) {
-#ifdef PARTLS_ONLY_T
-        case PARTLS_ONLY_T: return concurrency_T<PARTLS_ONLY_T>();
-#else
-#define PARTLS_L(i) case i + 1: return concurrency_T<i + 1>();
-        PARTLS_CASES(PARTLS_L)
-#undef PARTLS_L
-#endif
-        default: return 1;
-    }
+    return dispatch_T(T, 1, [](auto t) { return concurrency_T<decltype(t)::value>(); });
 }
 
 hipError_t launch_sweep_blk(const SweepParams &p, int T, int grid, hipStream_t s, bool models)
 {
-    switch (T) {
-#ifdef PARTLS_ONLY_T
-        case PARTLS_ONLY_T: return launch_blk_T<PARTLS_ONLY_T>(p, grid, s, models);
-#else
-#define PARTLS_L(i) case i + 1: return launch_blk_T<i + 1>(p, grid, s, models);
-        PARTLS_CASES(PARTLS_L)
-#undef PARTLS_L
-#endif
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_T(T, hipErrorInvalidValue, [&](auto t) { return launch_blk_T<decltype(t)::value>(p, grid, s, models); });
 }
 
 }  // namespace partls

@@ -2,7 +2,8 @@
 //
 // Used for single "node" solves whose tableau does not fit the register-resident kernel (n > 320): the α-step of
 // fit(Alt) at BASELINE config 4 (n = 513, Alt.jl:80-90) and the winner re-solve of fit(Opt) at such sizes.  Same
-// algorithm and decisions as sweep_generic.hip; the (n+1)^2 tableau lives in global memory (2.1 MB at n = 513,
+// algorithm as sweep_generic.hip, the decisions of sweep_rules.h (the KKT test and the exchange rule are hand-written
+// copies here: see that header); the (n+1)^2 tableau lives in global memory (2.1 MB at n = 513,
 // L2 resident) and every workgroup owns a slice of its ROWS.  All control state (basis flags, rejections, the violator
 // list) is replicated per workgroup and evolves identically everywhere because every workgroup reads the same data after
 // each grid barrier — no cross-workgroup messages besides the tableau itself.
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(COOP_THREADS) void sweep_coop_kernel(SweepParams p,
     for (;;) {
         if (progress) { for (int i = tid; i < n; i += COOP_THREADS) s_blocked[i] = 0; __syncthreads(); }
         progress = false;
-        // ---- KKT scan of the rhs row (every workgroup, identically) ------------------------------------------------------
+        // ---- KKT scan of the rhs row (every workgroup, identically); kkt_violates<true> (sweep_rules.h), written out -----------
         for (int base = 0; base < nwords * 64; base += COOP_THREADS) {
             const int v = base + tid;
             bool bad = false;
@@ -140,23 +141,13 @@ __global__ __launch_bounds__(COOP_THREADS) void sweep_coop_kernel(SweepParams p,
         __syncthreads();
         int count = 0;
         for (int w = 0; w < nwords; ++w) count += __popcll(s_inf[w]);
-        if (count == 0) break;
+        if (count == 0) break;                                    // ExchangeRule::next (sweep_rules.h), written out
         bool all;
         if (count < ninf_best) { ninf_best = count; patience = 3; all = true; }
         else if (patience > 0) { --patience; all = true; }
         else all = false;                                         // backup rule: only the largest violator
         if (++rounds > p.max_rounds) { ++nunconv; break; }
-        // the violator list of this round (ascending; the backup rule keeps only the last one)
-        if (tid == 0) {
-            int nv = 0;
-            for (int w = 0; w < nwords; ++w) {
-                unsigned long long bits = s_inf[w];
-                while (bits) { s_viol[nv++] = (w << 6) + __builtin_ctzll(bits); bits &= bits - 1; }
-            }
-            if (!all) { s_viol[0] = s_viol[nv - 1]; nv = 1; }
-            s_nv = nv;
-        }
-        __syncthreads();
+        violator_list(s_inf, nwords, all, s_viol, &s_nv);
         const int nv = s_nv;
 
         for (int b0 = 0; b0 < nv; b0 += mb) {

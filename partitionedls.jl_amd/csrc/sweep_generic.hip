@@ -18,19 +18,13 @@
 // tableaus of 2 MB (n = 513) the passes over the tableau are HBM-bound, so the violators of a scan are exchanged in BLOCKS of up
 // to 16 pivots (gj_panel.h: panel of the pivot columns eliminated in LDS, then ONE fused rank-m pass over the tableau) instead
 // of one full pass per pivot.  The register-resident production kernel is sweep_blk.hip; all share
-// SweepParams and agree in their decisions up to rounding.
+// SweepParams and the decisions of sweep_rules.h, and agree up to rounding.
 #include "gj_panel.h"
 
 namespace partls {
 
 static constexpr int GEN_THREADS = 1024;   // 16 waves per CU: the fused update is bound by memory latency, not by issue
 static constexpr int GEN_MAXWORDS = 16;     // n <= 1024
-
-__device__ __forceinline__ int sign_of_var(uint64_t m, uint64_t pat)
-{
-    // f = sum_k P[v,k] * s_k with s_k = +1 if bit k of pat else -1  ==  2*popc(m & pat) - popc(m)
-    return 2 * __popcll(m & pat) - __popcll(m);
-}
 
 // MODELS (chain mode, partls_opt_models): every finished pattern leaves its scaled solution in row g - g_begin of p.node_sol and its
 // objective in p.node_obj2 (NaN for a pattern that hit the pivot cap), as sweep_blk.hip's export instantiation does
@@ -77,7 +71,7 @@ __global__ __launch_bounds__(GEN_THREADS) void sweep_generic_kernel(SweepParams 
             if (code) pat = (uint64_t)chain;
             for (int i = tid; i < n; i += GEN_THREADS) s_blocked[i] = 0;
             __syncthreads();
-            int ninf_best = n + 1, patience = 3, rounds = 0;
+            ExchangeRule rule(n);
             bool progress = false;
             [[maybe_unused]] const unsigned long long nunconv0 = nunconv;   // MODELS: did this pattern hit the pivot cap?
             for (;;) {
@@ -92,12 +86,8 @@ __global__ __launch_bounds__(GEN_THREADS) void sweep_generic_kernel(SweepParams 
                     bool bad = false;
                     if (v < n) {
                         const double q = T[(size_t)v * ld + n];               // the rhs is COLUMN n of the stored upper triangle
-                        const int cd = code ? (int)code[v] : 0;
-                        const int f = code ? (cd == 2 ? 0 : cd) : sign_of_var(p.mask[v], pat);
-                        const double fq = (f > 0) ? q : ((f < 0) ? -q : 0.0);
-                        if (cd == 2) bad = !s_basic[v] && !s_blocked[v] && (fabs(q) > p.tol);     // free: stationarity only
-                        else if (s_basic[v]) bad = (f == 0) || (fq < -p.tol);
-                        else bad = (fq > p.tol) && !s_blocked[v];
+                        bad = code ? kkt_violates<true>(code[v], q, s_basic[v], s_blocked[v], p.tol)
+                                   : kkt_violates<false>(sign_of_var(p.mask[v], pat), q, s_basic[v], s_blocked[v], p.tol);
                     }
                     const unsigned long long b = __ballot(bad);
                     if (lane == 0 && (v >> 6) < nwords) s_inf[v >> 6] = b;
@@ -105,23 +95,10 @@ __global__ __launch_bounds__(GEN_THREADS) void sweep_generic_kernel(SweepParams 
                 __syncthreads();
                 int count = 0;
                 for (int w = 0; w < nwords; ++w) count += __popcll(s_inf[w]);
-                if (count == 0) break;
-                bool all;
-                if (count < ninf_best) { ninf_best = count; patience = 3; all = true; }
-                else if (patience > 0) { --patience; all = true; }
-                else all = false;                                  // backup rule: single pivot, largest index
-                if (++rounds > p.max_rounds) { ++nunconv; break; }
-                // the violator list of this round (ascending; the backup rule keeps only the last one), exchanged in blocks
-                if (tid == 0) {
-                    int nv = 0;
-                    for (int w = 0; w < nwords; ++w) {
-                        unsigned long long bits = s_inf[w];
-                        while (bits) { s_viol[nv++] = (w << 6) + __builtin_ctzll(bits); bits &= bits - 1; }
-                    }
-                    if (!all) { s_viol[0] = s_viol[nv - 1]; nv = 1; }
-                    s_nv = nv;
-                }
-                __syncthreads();
+                const ExchangeRule::Step step = rule.next(count, p.max_rounds);
+                if (step == ExchangeRule::CONVERGED) break;
+                if (step == ExchangeRule::CAPPED) { ++nunconv; break; }
+                violator_list(s_inf, nwords, step == ExchangeRule::ALL, s_viol, &s_nv);      // exchanged in blocks
                 const int nv = s_nv;
                 for (int b0 = 0; b0 < nv; b0 += mb) {
                     const int m = (nv - b0 < mb) ? nv - b0 : mb;
@@ -149,10 +126,7 @@ __global__ __launch_bounds__(GEN_THREADS) void sweep_generic_kernel(SweepParams 
                     p.node_sol[row * p.node_ld + i] = capped ? __builtin_nan("") : (s_basic[i] ? T[(size_t)i * ld + n] : 0.0);
                 if (tid == 0) p.node_obj2[row] = capped ? __builtin_nan("") : obj;
             }
-            if (obj < best_obj || (obj == best_obj && best_pat >= 0 && ref_index_less(pat, (unsigned long long)best_pat, p.rbit.gbit))) {
-                second_obj = best_obj; second_pat = best_pat;
-                best_obj = obj; best_pat = (long long)pat;
-            } else if (obj < second_obj) { second_obj = obj; second_pat = (long long)pat; }
+            rank_pattern(obj, pat, best_obj, best_pat, second_obj, second_pat, p.rbit.gbit);
             if (p.node_piv && code && tid == 0) {                  // [pivots, blocks, scans] so far; this kernel reports pivots only
                 unsigned *o = p.node_piv + 3 * ((size_t)chain * p.chain_len + (size_t)(g - g0));
                 o[0] = (unsigned)npiv; o[1] = 0; o[2] = 0;

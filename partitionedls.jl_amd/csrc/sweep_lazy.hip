@@ -1,9 +1,11 @@
 // sweep_lazy.hip — sign-pattern sweep beyond the register kernel (n > 320): the tableau in global memory, its updates DEFERRED.
 //
-// Same algorithm, same decisions and same SweepParams as sweep_generic.hip (block principal pivoting on the symmetric
-// principal-pivot tableau, Opt.jl:87-90 per pattern; node mode for BnB / Alt), one workgroup per Gray-code chain.  What differs is
-// where the bytes go.  sweep_generic.hip applies every block of <= 16 pivots to the whole (n+1)^2 / 2 triangle at once: 2 x 0.47 MB
-// through the memory system per block at n = 341 for ~0.7 MFLOP of work — it is bound by that traffic and its latency (1.06 M solves/s at D = 340).
+// Same algorithm and same SweepParams as sweep_generic.hip (block principal pivoting on the symmetric principal-pivot tableau,
+// Opt.jl:87-90 per pattern; node mode for BnB / Alt), one workgroup per Gray-code chain.  The decisions are those of
+// sweep_rules.h; the KKT test, the exchange rule and the ranking are hand-written copies here (marked "written out"; why: see that
+// header).  What differs from the eager kernel is where the bytes go.  sweep_generic.hip applies every block of <= 16 pivots to the
+// whole (n+1)^2 / 2 triangle at once: 2 x 0.47 MB through the memory system per block at n = 341 for ~0.7 MFLOP of work — it is
+// bound by that traffic and its latency (1.06 M solves/s at D = 340).
 // But a block only ever READS m columns of the tableau (its pivot columns) and the rhs column.  So here
 //   * the rhs column q (and the objective corner) lives in LDS and follows every block at once;
 //   * the rank-1 terms of a block (z_s = pivot column s as of its own step, 1/d_s) are appended to a PENDING list in LDS (R terms);
@@ -14,8 +16,9 @@
 //   * only when the pool is full is the base image brought up to date: ONE pass with a rank-R update (v_mfma_f64_16x16x4 on 16 x 16
 //     tiles of the upper triangle) — once per ~40 pivots instead of once per block.
 // Base-image bytes per pivot drop ~5x (measured: profiles/r03_d340_traffic.json), and the pass itself runs on the matrix pipe with
-// 16 x fewer LDS operand reads than the FMA form.  The panel of a block is eliminated in two phases with three barriers per block
-// (lz_panel_eliminate).  D = 340: 1.06 -> 4.0-4.5 M solves/s.  DESIGN.md §4 "Beyond n = 320".
+// 16 x fewer LDS operand reads than the FMA form.  The panel of a block is eliminated with one barrier per step on the 512-thread plan
+// (lz_panel_stepwise), in two phases with three barriers per block on the 1024-thread plan (lz_panel_eliminate).
+// D = 340: 1.06 -> 4.0-4.5 M solves/s.  DESIGN.md §4 "Beyond n = 320".
 #include "gj_panel.h"
 
 namespace partls {
@@ -24,12 +27,6 @@ static constexpr int LZ_MAXWORDS = 16;      // n <= 1024
 static constexpr int LZ_MAXR = 64;          // rows of the LDS pool at most
 #ifndef LZ_SPIN_SLEEP
 #define LZ_SPIN_SLEEP 1                     // s_sleep argument of the phase-2 waves' poll of the panel's progress word
-#endif
-#ifndef LZ_TWO_PHASE_MAX_NT
-#define LZ_TWO_PHASE_MAX_NT 1024           // workgroup sizes up to this run the two-phase panel (512: the 1024-thread plan keeps the step-by-step one)
-#endif
-#ifndef LZ_PANEL_STEPS
-#define LZ_PANEL_STEPS 1                    // 1: the 512-thread plan runs the block panel in the register kernel's one-barrier-per-step form (lz_panel_steps); 0: two-phase everywhere (round 3)
 #endif
 #ifndef LZ_MIN_SPLIT
 #define LZ_MIN_SPLIT 6                      // a block is cut short to fill the pool when at least this many pivots still fit
@@ -47,8 +44,6 @@ typedef double lz_double4 __attribute__((ext_vector_type(4)));
 #else
 #define LZ_STK nullptr
 #endif
-
-__device__ __forceinline__ int lz_sign_of_var(uint64_t m, uint64_t pat) { return 2 * __popcll(m & pat) - __popcll(m); }
 
 // entry (i, k) of the stored upper triangle
 __device__ __forceinline__ size_t lz_tri(int i, int k, int ld) { return i <= k ? (size_t)i * ld + k : (size_t)k * ld + i; }
@@ -141,12 +136,6 @@ __device__ __forceinline__ void lz_flush(double *T, int ld_, int n_, const doubl
 #endif
 }
 
-__device__ __forceinline__ double lz_readlane(double v, int l)            // l: wave-uniform
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-
 __device__ __forceinline__ double lz_bperm(double v, int srclane)        // v of lane `srclane` (any lane -> any lane; no LDS memory)
 {
     const int lo = __builtin_amdgcn_ds_bpermute(srclane << 2, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(srclane << 2, __double2hiint(v));
@@ -171,12 +160,14 @@ __device__ __forceinline__ void lz_fmac_bcast(double &acc, double y, double x, i
 //   phase 1: ONE wave runs those m rows (lane j = pivot row k_j; the u_s[j] of a step are DPP row broadcasts of the lanes' own entries)
 //            and leaves the table (u_s[j], d_s, 1/d_s) in LDS — m dependent steps, no barrier, no LDS round trip;
 //   phase 2: every other row runs its m steps against the table — no communication at all.
-// MT (8 or 16) is the compiled panel width: columns / lanes m..MT-1 are zero and stay zero, so no step carries per-column guards.
+// LZ_MT is the compiled panel width (the 1024-thread plan, the only user, has 128 VGPRs per thread: blocks of at most 8 pivots,
+// lazy_plan): columns / lanes m..LZ_MT-1 are zero and stay zero, so no step carries per-column guards.
 // The leave-one-out veto (an entering pivot is refused when ANY basic row j has T_jk^2 eps >= d_k) is only known after phase 2: the
 // steps are taken optimistically, every row raises the flag of a step it would have vetoed, and in the rare case that one is raised
 // the block is redone from its (still untouched) panel image with that step marked "refused" — exactly what the step-by-step form does.
 // tab: [GJ_MB][GJ_MB] u, [GJ_MB][GJ_MB] final pivot rows, [GJ_MB] d, [GJ_MB] 1/d;  red: [GJ_MB] veto flags.
-template <int NT, int MT>
+static constexpr int LZ_MT = 8;
+template <int NT>
 __device__ __forceinline__ int lz_panel_eliminate(double *__restrict__ Pn, double *__restrict__ Zn, double *__restrict__ dinv,
                                                   double *__restrict__ tab, double *__restrict__ red, const int *__restrict__ ks, int m_,
                                                   int ld_, uint8_t *__restrict__ s_basic, int myj, unsigned basm_, double piv_eps, int tid,
@@ -199,7 +190,7 @@ __device__ __forceinline__ int lz_panel_eliminate(double *__restrict__ Pn, doubl
     unsigned skip = 0;                                                   // steps refused by the veto (found in earlier trips)
     unsigned accm = 0;
     LZ_PSTAMP(8);
-    double pv[MT];                                                       // phase 2: this thread's own row
+    double pv[LZ_MT];                                                       // phase 2: this thread's own row
     // phase 1 runs on the LAST wave (at n <= 447 it owns no tableau row, so nobody waits for its phase 2), the other waves follow it step
     // by step: `prog` (LDS) = steps whose table row is complete; a row's step s starts as soon as prog > s.  The last wave takes its own
     // rows (if any) when it is through.  Every wait is on the last wave only, which never waits: no cycle.
@@ -228,11 +219,11 @@ __device__ __forceinline__ int lz_panel_eliminate(double *__restrict__ Pn, doubl
                 const double zi = lz_bperm(pp[cs], 16 * gs + jl);        // column s at pivot row j
                 const double zr = lz_bperm(pp[cs], 16 * gs + ((jl + 4 * g) & 15));   // ... at pivot row j + 4 g: lane c of row g = u_{4g+c}
                 if (lane < GJ_MB) tabU[s * GJ_MB + lane] = zi;           // phase 2 reads it as broadcasts
-                const double d = lz_readlane(zi, s);
+                const double d = readlane_f64(zi, s);
                 const bool bas = (basm >> s) & 1u, skp = (skip >> s) & 1u;
                 const bool pre = !skp && (bas || d > piv_eps);           // uniform
                 if (!bas && !skp && lane < m && lane != s && (zi * zi) * piv_eps >= d) red[s] = 1.0;
-                const double inv = pre ? gj_rcp(d) : 0.0, ainv = fabs(inv);    // refused: 1/d = 0 makes the step a no-op below
+                const double inv = pre ? rcp_newton(d) : 0.0, ainv = fabs(inv);    // refused: 1/d = 0 makes the step a no-op below
                 if (lane == 0) { tabD[s] = d; tabI[s] = inv; }
                 // the LDS executes one wave's operations in order: the progress word cannot become visible before the table row written
                 // above it — no s_waitcnt needed, only the compiler must keep the order
@@ -261,9 +252,9 @@ __device__ __forceinline__ int lz_panel_eliminate(double *__restrict__ Pn, doubl
         LZ_PSTAMP(9);
         if (has_row && myj < 0) {                                        // ---- phase 2: all other rows ---------------------------
 #pragma unroll
-            for (int j = 0; j < MT; ++j) pv[j] = (j < m) ? Pn[j * ld + tid] : 0.0;
+            for (int j = 0; j < LZ_MT; ++j) pv[j] = (j < m) ? Pn[j * ld + tid] : 0.0;
 #pragma unroll
-            for (int s = 0; s < MT; ++s) {
+            for (int s = 0; s < LZ_MT; ++s) {
                 if (s >= m) break;                                       // uniform
                 if (!p1wave) {                                           // (uniform) wait for the table row of step s
                     int spins = 0;
@@ -277,15 +268,15 @@ __device__ __forceinline__ int lz_panel_eliminate(double *__restrict__ Pn, doubl
                 // store that may alias it: read in program order behind them, every ds_read2 pays its own round trip — 5 per step)
                 const double inv = tabI[s];                              // 0: refused — the row does not move
                 const double ds_ = tabD[s];
-                double u[MT];
+                double u[LZ_MT];
 #pragma unroll
-                for (int j = 0; j < MT; ++j) u[j] = tabU[s * GJ_MB + j];
+                for (int j = 0; j < LZ_MT; ++j) u[j] = tabU[s * GJ_MB + j];
                 const double zi = pv[s];
                 if (!((basm >> s) & 1u) && var_row && (zi * zi) * piv_eps >= ds_) red[s] = 1.0;   // only counted when 1/d != 0
                 Zn[s * ld + tid] = zi;
                 const double mi = -zi * inv;
 #pragma unroll
-                for (int j = 0; j < MT; ++j) if (j != s) pv[j] = fma(mi, u[j], pv[j]);
+                for (int j = 0; j < LZ_MT; ++j) if (j != s) pv[j] = fma(mi, u[j], pv[j]);
                 pv[s] = (inv != 0.0) ? zi * fabs(inv) : zi;
             }
         }
@@ -299,11 +290,11 @@ __device__ __forceinline__ int lz_panel_eliminate(double *__restrict__ Pn, doubl
             // the final panel: rows / columns of the pivoted variables
             if (has_row && myj < 0) {
 #pragma unroll
-                for (int j = 0; j < MT; ++j) if (j < m) Pn[j * ld + tid] = pv[j];
+                for (int j = 0; j < LZ_MT; ++j) if (j < m) Pn[j * ld + tid] = pv[j];
             }
             if (p1wave && lane < m) {
 #pragma unroll
-                for (int j = 0; j < MT; ++j) if (j < m) Pn[j * ld + krow] = tabF[lane * GJ_MB + j];
+                for (int j = 0; j < LZ_MT; ++j) if (j < m) Pn[j * ld + krow] = tabF[lane * GJ_MB + j];
                 if (live) s_basic[krow] ^= 1;                            // accepted pivots change sides
                 dinv[lane] = tabI[lane];
             }
@@ -321,7 +312,7 @@ __device__ __forceinline__ int lz_panel_eliminate(double *__restrict__ Pn, doubl
 
 // NODE: node mode (BnB bounds, Alt alpha-steps, calibration walks) is its own instantiation: only there can the base image live in a
 // snapshot slot, so only there is T a per-chain variable (as a run-time choice it cost the chain-mode sweep 4 %: D = 340 56.7 -> 59.0 ms)
-// ---- the panel in the register kernel's form (round 4; LZ_PANEL_STEPS) ------------------------------------------------------------------
+// ---- the panel in the register kernel's form (round 4; the 512-thread plan) ------------------------------------------------------------------
 // sweep_blk.hip's panel_block: thread t owns ROW t of the block's M (compile-time) pivot columns in registers; M Gauss–Jordan steps, ONE
 // barrier each: the pivot-row threads publish their entry of the current pivot column (U, double buffered by step parity), the one
 // pivot-row thread of the step computes 1/d, everybody reads both back and updates its own row — straight-line code per M, no guards.
@@ -361,7 +352,7 @@ __device__ __forceinline__ int lz_panel_steps(double *__restrict__ Pn, double *_
         U[(s & 1) * US + uslot] = pv[s];
         if (myj == s) {                                      // the one pivot-row thread (its wave only: the others branch over)
             const double d = pv[s];
-            dn[s] = (!((skip >> s) & 1u) && (my_basic || d > piv_eps)) ? gj_rcp(d) : 0.0;
+            dn[s] = (!((skip >> s) & 1u) && (my_basic || d > piv_eps)) ? rcp_newton(d) : 0.0;
         }
         __syncthreads();
         // ONE LDS read brings the pivot rows' entries of column s into every wave: lane l of every row of 16 lanes holds u_l, and the row
@@ -532,12 +523,13 @@ __global__ __launch_bounds__(NT) void sweep_lazy_kernel(SweepParams p, int mb, i
                 }
                 progress = false;
                 // ---- KKT scan of the rhs column (LDS); every violator finds its own place in the list ------------------
+                // (kkt_violates of sweep_rules.h, written out: see the file header)
                 bool bad = false;
                 if (tid < n) {
                     const int v = tid;
                     const double q = qs[v];
                     const int cd = code ? (int)code[v] : 0;
-                    const int f = code ? (cd == 2 ? 0 : cd) : lz_sign_of_var(mymask, pat);
+                    const int f = code ? (cd == 2 ? 0 : cd) : sign_of_var(mymask, pat);
                     const double fq = (f > 0) ? q : ((f < 0) ? -q : 0.0);
                     if (cd == 2) bad = !s_basic[v] && !s_blocked[v] && (fabs(q) > p.tol);     // free: stationarity only
                     else if (s_basic[v]) bad = (f == 0) || (fq < -p.tol);
@@ -552,7 +544,7 @@ __global__ __launch_bounds__(NT) void sweep_lazy_kernel(SweepParams p, int mb, i
                     if (w < (tid >> 6)) before += c;
                     count += c;
                 }
-                if (count == 0) break;
+                if (count == 0) break;                             // ExchangeRule::next (sweep_rules.h), written out
                 bool all;
                 if (count < ninf_best) { ninf_best = count; patience = 3; all = true; }
                 else if (patience > 0) { --patience; all = true; }
@@ -650,21 +642,15 @@ __global__ __launch_bounds__(NT) void sweep_lazy_kernel(SweepParams p, int mb, i
                     LZ_STAMP(3);                                              // gather + materialise
                     double *Zn = Zp + (size_t)Rcur * ld, *dn = dp + Rcur;
                     int acc_piv;
-                    if constexpr (LZ_PANEL_STEPS && NT <= 512) {
+                    if constexpr (NT <= 512) {
                         // one barrier per step, the register kernel's panel: 2-4 % ahead of the two-phase form on the 512-thread plan (D = 340:
                         // 4.64 -> 4.74 M solves/s, D = 500: 608 -> 634 k), and no polled progress word; on the 1024-thread plan a barrier
                         // meets 16 waves and the form is 2x slower (D = 600: 12.5 -> 26.9 ms per 4096 patterns): there the two-phase form stays
                         acc_piv = lz_panel_stepwise<NT>(Pn, Zn, dn, tab, reinterpret_cast<int *>(red), m, ld, s_basic, myj, p.piv_eps, tid, nveto, LZ_STK);
                         (void)lz_fault; (void)basm;
-                    } else if constexpr (NT <= 512) {
-                        acc_piv = m <= 8 ? lz_panel_eliminate<NT, 8>(Pn, Zn, dn, tab, red, ks, m, ld, s_basic, myj, basm, p.piv_eps, tid, nveto, LZ_STK, lz_fault)
-                                         : lz_panel_eliminate<NT, GJ_MB>(Pn, Zn, dn, tab, red, ks, m, ld, s_basic, myj, basm, p.piv_eps, tid, nveto, LZ_STK, lz_fault);
+                    } else {                                                  // 128 VGPRs per thread: blocks of at most 8 pivots (lazy_plan), the narrow panel
+                        acc_piv = lz_panel_eliminate<NT>(Pn, Zn, dn, tab, red, ks, m, ld, s_basic, myj, basm, p.piv_eps, tid, nveto, LZ_STK, lz_fault);
                         lz_fault = false;
-                    } else if constexpr (NT <= LZ_TWO_PHASE_MAX_NT) {         // 128 VGPRs per thread: blocks of at most 8 pivots (lazy_plan), the narrow panel only
-                        acc_piv = lz_panel_eliminate<NT, 8>(Pn, Zn, dn, tab, red, ks, m, ld, s_basic, myj, basm, p.piv_eps, tid, nveto, LZ_STK, lz_fault);
-                        lz_fault = false;
-                    } else {                                                  // 128 VGPRs per thread: the step-by-step form (two barriers per pivot, few registers)
-                        acc_piv = gj_panel_eliminate<NT>(Pn, Zn, dn, tab, red, ks, m, ld, s_basic, p.piv_eps, tid);
                     }
                     LZ_STAMP(4);                                              // panel
                     // ---- after the panel: rhs column, replaced rows / columns, bookkeeping -----------------------------
@@ -690,7 +676,7 @@ __global__ __launch_bounds__(NT) void sweep_lazy_kernel(SweepParams p, int mb, i
                             double a = qs[tid];
     #pragma unroll
                             for (int j = 0; j < GJ_MB; ++j) {
-                                const double dj = lz_readlane(dmy_, j);          // 0 beyond m and for refused pivots
+                                const double dj = readlane_f64(dmy_, j);          // 0 beyond m and for refused pivots
                                 if ((accm >> j) & 1u) a = fma(-zs[j] * dj, zn[j], a);
                             }
                             qs[tid] = myj >= 0 ? qn : a;
@@ -745,6 +731,7 @@ __global__ __launch_bounds__(NT) void sweep_lazy_kernel(SweepParams p, int mb, i
                 for (int i = tid; i < n; i += NT) p.node_sol[row * p.node_ld + i] = capped ? __builtin_nan("") : (s_basic[i] ? qs[i] : 0.0);
                 if (tid == 0) p.node_obj2[row] = capped ? __builtin_nan("") : obj;
             }
+            // rank_pattern (sweep_rules.h), written out
             if (obj < best_obj || (obj == best_obj && best_pat >= 0 && ref_index_less(pat, (unsigned long long)best_pat, p.rbit.gbit))) {
                 second_obj = best_obj; second_pat = best_pat;
                 best_obj = obj; best_pat = (long long)pat;
@@ -808,30 +795,28 @@ bool lazy_plan(int ld, int *mb_out, int *rows_out, size_t *shmem_out)
     if (rows > LZ_MAXR) rows = LZ_MAXR;
     int mb = rows / 3;
     if (mb > GJ_MB) mb = GJ_MB;
-    if (ld > 512 && LZ_TWO_PHASE_MAX_NT >= 1024 && mb > 8) mb = 8;          // the 1024-thread plan compiles the 8-column panel only
+    if (ld > 512 && mb > LZ_MT) mb = LZ_MT;                                  // the 1024-thread plan compiles the 8-column panel only
     if (mb < 2) mb = 2;
     *mb_out = mb; *rows_out = rows;
     *shmem_out = ((size_t)(rows + 4) * ld + ld + rows + GJ_MB + (size_t)(rows + 4) * GJ_MB + 2 * GJ_MB * GJ_MB + 2 * GJ_MB + 18) * 8 + 3 * (size_t)ld + 16;
     return true;
 }
 
+template <int NT, bool NODE, bool MODELS>
+static hipError_t launch_lazy_kernel(const SweepParams &p, int grid, int mb, int rows, size_t shmem, hipStream_t s)
+{
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&sweep_lazy_kernel<NT, NODE, MODELS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((sweep_lazy_kernel<NT, NODE, MODELS>), dim3(grid), dim3(NT), shmem, s, p, mb, rows);
+    return hipGetLastError();
+}
+
 template <int NT>
 static hipError_t launch_lazy_nt(const SweepParams &p, int grid, int mb, int rows, size_t shmem, hipStream_t s, bool models)
 {
-    if (models && !p.node_code) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&sweep_lazy_kernel<NT, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((sweep_lazy_kernel<NT, false, true>), dim3(grid), dim3(NT), shmem, s, p, mb, rows);
-    } else if (p.node_code) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&sweep_lazy_kernel<NT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((sweep_lazy_kernel<NT, true>), dim3(grid), dim3(NT), shmem, s, p, mb, rows);
-    } else {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&sweep_lazy_kernel<NT, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((sweep_lazy_kernel<NT, false>), dim3(grid), dim3(NT), shmem, s, p, mb, rows);
-    }
-    return hipGetLastError();
+    if (models && !p.node_code) return launch_lazy_kernel<NT, false, true>(p, grid, mb, rows, shmem, s);
+    if (p.node_code) return launch_lazy_kernel<NT, true, false>(p, grid, mb, rows, shmem, s);
+    return launch_lazy_kernel<NT, false, false>(p, grid, mb, rows, shmem, s);
 }
 
 // one thread per tableau row in the panel: 512 threads up to n = 511 (half the waves at every barrier of the m panel steps), 1024 beyond

@@ -76,7 +76,7 @@ def test_every_pattern_equals_the_eager_kernel_and_the_oracle(partls, oracle, mo
 
 @pytest.mark.parametrize("D,K", [(520, 4), (700, 3)])
 def test_beyond_511_variables(partls, oracle, monkeypatch, D, K):
-    """1024-thread plan (fewer pending rows fit the LDS: flushes every ~15 pivots; the panel in the step-by-step form)"""
+    """1024-thread plan (fewer pending rows fit the LDS: flushes every ~15 pivots; blocks of at most 8 pivots, the panel in the two-phase form)"""
     X, y, P = _problem(2000 + D, 2 * D + 30, D, K)
     lz = _sweep(partls, monkeypatch, X, y, P, eager=False)
     eg = _sweep(partls, monkeypatch, X, y, P, eager=True)
