@@ -144,6 +144,8 @@ partls_status partls_opt_prepare(partls_ctx *ctx, const double *X, int64_t N, in
 partls_status partls_opt_prepare_weighted(partls_ctx *ctx, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
                                           const double *w, int x_on_device, const int64_t *P, int64_t K, int64_t ldP, double eta,
                                           uint32_t flags);
+/* float32 design matrices: partls_opt_prepare_f32 is this prepare for an X stored as float, with or without weights (partls_f32.h,
+ * included at the end of this header). */
 partls_status partls_opt_sweep(partls_ctx *ctx, int64_t g_begin, int64_t g_end,
                                double *best_obj, int64_t *best_pattern, double *all_opt, int64_t *n_unconverged);
 partls_status partls_opt_finish(partls_ctx *ctx, int64_t pattern,
@@ -313,6 +315,8 @@ partls_status partls_predict_device(partls_ctx *ctx, const double *dX, int64_t N
                                     const int64_t *P, int64_t K, int64_t ldP, const double *alpha, const double *beta,
                                     double t, double *dyhat);
 
+/* partls_predict_f32 / partls_predict_device_f32: the two predicts for an X stored as float (partls_f32.h). */
+
 /* ---- synthetic inputs of BASELINE.md §4, generated in HBM (bit-identical to oracle_synth on the host) -----------------
  * dX: device N x D (ld = N), dy: device N; wstar: HOST D doubles (alpha*_j beta*_g(j), from partls_synth_truth). */
 partls_status partls_synth_truth(uint64_t seed, int64_t D, int64_t K, int64_t *P, double *wstar);
@@ -331,7 +335,8 @@ typedef enum {
 partls_status partls_get_timing(const partls_ctx *ctx, partls_timer which, double *ms);
 /* host -> device upload of X inside the last prepare / fit on this context: wall time (ms) and bytes (0 / 0 when the inputs were device
  * pointers).  A host X larger than 8 MB is staged through page-locked buffers by four copier threads (42-55 GB/s on a 57 GB/s link
- * whatever the array's history; a plain copy from pageable memory pays for the pinning first: 8-25 GB/s on a fresh array). */
+ * whatever the array's history; a plain copy from pageable memory pays for the pinning first: 8-25 GB/s on a fresh array).  The bytes
+ * are those moved: 8 N M for a double X, 4 N M after partls_opt_prepare_f32. */
 partls_status partls_get_upload(const partls_ctx *ctx, double *ms, double *bytes);
 /* principal pivots executed by the last partls_opt_sweep (fp64 flop accounting: each pivot updates the whole symmetric tableau) */
 partls_status partls_get_pivots(const partls_ctx *ctx, int64_t *pivots);
@@ -364,6 +369,10 @@ partls_status partls_get_near_ties(const partls_ctx *ctx, int64_t *evaluated);
 /* debugging / tests: copy the Gram products of the prepared problem to the host: G ((M+2) x (M+2), column-major,
  * variables ordered [features, intercept, y]), i.e. G, c = G[:, M+1], yy = G[M+1, M+1], after η has been applied. */
 partls_status partls_get_gram(const partls_ctx *ctx, double *G_aug);
+
+/* ---- float32 design matrices: one prepare and two predicts that take X as float (uploaded, kept and read as float; results equal the
+ * fp64 path on the widened matrix bit for bit).  Part of this ABI; kept in a header of their own. */
+#include "partls_f32.h"
 
 #ifdef __cplusplus
 }

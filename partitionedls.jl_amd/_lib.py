@@ -88,6 +88,15 @@ SYMBOLS = [
     ("partls_get_sweep_route", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 ]
 
+# ... and every symbol include/partls_f32.h declares (the float32 entry points; X is a float pointer, passed as an address)
+SYMBOLS_F32 = [
+    ("partls_opt_prepare_f32", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                         _i64, _i64, C.c_double, C.c_uint32]),
+    ("partls_predict_f32", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, _i64, _i64, _dp, _dp, C.c_double, _dp]),
+    ("partls_predict_device_f32", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, _i64, _i64, _dp, _dp, C.c_double,
+                                            C.c_void_p]),
+]
+
 _lib = None
 
 
@@ -134,7 +143,7 @@ def lib():
                               f"(make -C '{CSRC}'); partitionedls.jl_amd has no CPU fallback")
         _preload_torch_hip_runtime()
         l = C.CDLL(SO_PATH)
-        for name, res, args in SYMBOLS:
+        for name, res, args in SYMBOLS + SYMBOLS_F32:
             if os.environ.get("PARTLS_LIB") and not hasattr(l, name):
                 continue                   # diagnostic A/B builds of older sources may lack the newest entry points
             f = getattr(l, name)           # AttributeError here = header/library mismatch

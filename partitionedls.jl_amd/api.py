@@ -81,6 +81,25 @@ def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int64))
 
 
+def _is_f32(dtype):
+    """float32 is the one element type besides float64 that X may keep on its way to the device"""
+    return dtype is not None and np.dtype(dtype) == np.float32
+
+
+def _x_host(X):
+    """host X as the library takes it — the ONE place that decides: a float32 array stays float32, every other dtype becomes float64;
+    F-contiguous either way (a C-ordered or strided input is copied, never widened; an array already in that form is returned as it is)"""
+    return np.asfortranarray(X, dtype=np.float32 if _is_f32(getattr(X, "dtype", None)) else np.float64)
+
+
+def _x_dtype(dtype, who):
+    if dtype is None or np.dtype(dtype) == np.float64:
+        return np.float64
+    if np.dtype(dtype) == np.float32:
+        return np.float32
+    raise TypeError("%s: dtype must be float64 or float32, got %s" % (who, np.dtype(dtype)))
+
+
 class Context:
     """Thin owner of a partls_ctx (one per device)."""
 
@@ -114,15 +133,26 @@ class Context:
 
     # ---- staged Opt path -------------------------------------------------------------------------------------------
     def opt_prepare(self, X, y, P, eta=0.0, flags=0, weights=None):
-        """X, y: host arrays (float64, any layout; copied F-contiguous).  weights: optional per-row sample weights (host, length N):
-        partls_opt_prepare_weighted, after which every staged call on the problem is weighted."""
-        X = np.asfortranarray(X, dtype=np.float64)
+        """X, y: host arrays (any layout; copied F-contiguous).  weights: optional per-row sample weights (host, length N):
+        partls_opt_prepare_weighted, after which every staged call on the problem is weighted.
+        A float32 X stays float32 — uploaded and read as such through partls_opt_prepare_f32, with or without weights; the results are
+        those of X.astype(float64) bit for bit.  Every other dtype is converted to float64; y always is."""
+        X = _x_host(X)
+        f32 = X.dtype == np.float32
         y = np.ascontiguousarray(y, dtype=np.float64)
         P = np.asfortranarray(P, dtype=np.int64)
         N, M = X.shape
         self._shape = (N, M, P.shape[1])
         self.generation += 1
-        if weights is None:
+        if f32:
+            w = None
+            if weights is not None:
+                w = np.ascontiguousarray(weights, dtype=np.float64)
+                if w.shape != (N,):
+                    raise ValueError("weights: expected shape (%d,), got %s" % (N, w.shape))
+            _check(L.lib().partls_opt_prepare_f32(self._h, X.ctypes.data, N, M, N, y.ctypes.data, None if w is None else w.ctypes.data, 0,
+                                                  P.ctypes.data, P.shape[1], P.shape[0], float(eta), int(flags)))
+        elif weights is None:
             _check(L.lib().partls_opt_prepare(self._h, X.ctypes.data, N, M, N, y.ctypes.data, 0, P.ctypes.data, P.shape[1],
                                               P.shape[0], float(eta), int(flags)))
         else:
@@ -132,13 +162,19 @@ class Context:
             _check(L.lib().partls_opt_prepare_weighted(self._h, X.ctypes.data, N, M, N, y.ctypes.data, w.ctypes.data, 0, P.ctypes.data,
                                                        P.shape[1], P.shape[0], float(eta), int(flags)))
 
-    def opt_prepare_device(self, dX_ptr, dy_ptr, N, M, ldX, P, eta=0.0, flags=0, dw_ptr=None):
+    def opt_prepare_device(self, dX_ptr, dy_ptr, N, M, ldX, P, eta=0.0, flags=0, dw_ptr=None, dtype=np.float64):
         """dX_ptr, dy_ptr (and dw_ptr, optional per-row sample weights, N doubles): raw device addresses (e.g. torch tensor
-        .data_ptr()) that stay owned by the caller."""
+        .data_ptr()) that stay owned by the caller.  dtype: element type of X — float64, or float32 (a float32 tensor; ldX counts
+        elements; y and the weights stay float64): partls_opt_prepare_f32."""
         P = np.asfortranarray(P, dtype=np.int64)
+        f32 = _x_dtype(dtype, "opt_prepare_device") == np.float32
         self._shape = (N, M, P.shape[1])
         self.generation += 1
-        if dw_ptr is None:
+        if f32:
+            _check(L.lib().partls_opt_prepare_f32(self._h, C.c_void_p(dX_ptr), N, M, ldX, C.c_void_p(dy_ptr),
+                                                  None if dw_ptr is None else C.c_void_p(dw_ptr), 1, P.ctypes.data, P.shape[1], P.shape[0],
+                                                  float(eta), int(flags)))
+        elif dw_ptr is None:
             _check(L.lib().partls_opt_prepare(self._h, C.c_void_p(dX_ptr), N, M, ldX, C.c_void_p(dy_ptr), 1, P.ctypes.data,
                                               P.shape[1], P.shape[0], float(eta), int(flags)))
         else:
@@ -336,6 +372,30 @@ class Context:
         t = C.c_double(); o = C.c_double()
         self._ill(L.lib().partls_bnb_leaf(self._h, C.c_uint64(int(pat)), C.c_uint64(int(free)), _dp(a), _dp(b), C.byref(t), C.byref(o)))
         return a, b, t.value, o.value
+
+    def predict(self, X, P, alpha, beta, t):
+        """yhat = X (P .* alpha) beta .+ t for a host X of any layout (partls_predict).  A float32 X stays float32 — copied F-contiguous
+        when it is C-ordered or strided, never widened — and is uploaded and read as such (partls_predict_f32); every
+        other dtype is converted to float64."""
+        X = _x_host(X)
+        f32 = X.dtype == np.float32
+        P = np.asfortranarray(P, dtype=np.int64)
+        a = np.ascontiguousarray(alpha, dtype=np.float64)
+        b = np.ascontiguousarray(beta, dtype=np.float64)
+        N, M = X.shape
+        yh = np.zeros(N)
+        fn = L.lib().partls_predict_f32 if f32 else L.lib().partls_predict
+        _check(fn(self._h, X.ctypes.data, N, M, N, P.ctypes.data, P.shape[1], M, _dp(a), _dp(b), float(t), _dp(yh)))
+        return yh
+
+    def predict_device(self, dX_ptr, N, M, ldX, P, alpha, beta, t, dyhat_ptr, dtype=np.float64):
+        """the same with X (N x M, ldX, elements of `dtype`: float64 or float32) and yhat (N doubles) in HBM: raw device addresses"""
+        P = np.asfortranarray(P, dtype=np.int64)
+        a = np.ascontiguousarray(alpha, dtype=np.float64)
+        b = np.ascontiguousarray(beta, dtype=np.float64)
+        fn = L.lib().partls_predict_device_f32 if _x_dtype(dtype, "predict_device") == np.float32 else L.lib().partls_predict_device
+        _check(fn(self._h, C.c_void_p(dX_ptr), int(N), int(M), int(ldX), P.ctypes.data, P.shape[1], int(M), _dp(a), _dp(b), float(t),
+                  C.c_void_p(dyhat_ptr)))
 
     def timing(self, which):
         ms = C.c_double()
@@ -602,7 +662,9 @@ def regularizeProblem(X, y, P, η):
 # ---------------------------------------------------------------------------------------------------------------------
 # fit / predict
 # ---------------------------------------------------------------------------------------------------------------------
-def _marshal(X, y, P):
+def _marshal(X, y, P, keep_f32=False):
+    """keep_f32: a float32 X stays float32 (F-contiguous: a C-ordered or strided input is copied, never widened) for the entry points
+    that read it as such; every other floating dtype, and every caller without keep_f32, gets float64."""
     X = np.asarray(X)
     y = np.asarray(y)
     P = np.asarray(P)
@@ -614,8 +676,10 @@ def _marshal(X, y, P):
         raise TypeError("fit: P must be an integer matrix (P::Array{Int,2})")
     if X.shape[0] != y.shape[0] or P.shape[0] != X.shape[1]:
         raise ValueError("DimensionMismatch: X is %s, y is %s, P is %s" % (X.shape, y.shape, P.shape))
-    # Float32 inputs (test/runtests.jl:123-146) are widened; result fields are abstract floats in the reference
-    return (np.asfortranarray(X, dtype=np.float64), np.ascontiguousarray(y, dtype=np.float64),
+    # Float32 inputs (test/runtests.jl:123-146): y is widened (N numbers), X only where the device path has no float32 form; result
+    # fields are abstract floats in the reference
+    xt = np.float32 if (keep_f32 and X.dtype == np.float32) else np.float64
+    return (np.asfortranarray(X, dtype=xt), np.ascontiguousarray(y, dtype=np.float64),
             np.asfortranarray(P, dtype=np.int64))
 
 
@@ -730,6 +794,8 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
     weights: optional per-row sample weights w[N] (floating, finite, >= 0, sum > 0): the data term becomes sum_i w_i r_i^2 (the η rows
     stay unweighted) and report.opt its square root with the η rows; a row of weight 0 acts as an absent row.  Single device only
     (NotImplementedError with devices=).  DESIGN.md §4.7.
+    A float32 X is uploaded and read as float32 (half the transfer and half the device memory of float64); all arithmetic stays fp64
+    and every result equals the fit of X.astype(float64) bit for bit.  With devices= it is widened on the host.  DESIGN.md §4.8.
     """
     if alg not in (Opt, Alt, BnB):
         raise TypeError("fit: first argument must be Opt, Alt or BnB")
@@ -739,10 +805,11 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
         raise ValueError("nnlsalg must be one of :nnls, :pivot, :fnnls")
     if on_ill_conditioned not in ("warn", "raise"):
         raise ValueError('on_ill_conditioned must be "warn" or "raise"')
-    Xf, yf, Pf = _marshal(X, y, P)
+    Xf, yf, Pf = _marshal(X, y, P, keep_f32=devices is None)
     N, M = Xf.shape
     K = Pf.shape[1]
     wf = _weights(weights, N, "fit")
+    staged = wf is not None or Xf.dtype == np.float32     # fits that exist as prepare + a staged call only
     if wf is not None and devices is not None:
         raise NotImplementedError("fit: sample weights are not supported on several devices (devices=)")
     ctx = default_context(device)
@@ -797,7 +864,7 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
         b0 = np.ascontiguousarray(beta0, dtype=np.float64)
         if a0.shape != (M + 1,) or b0.shape != (K + 1,):
             raise ValueError("alpha0 must have M+1 and beta0 K+1 entries")
-        if wf is not None:                                # partls_fit_alt = prepare (faithful) + partls_alt_prepared
+        if staged:                                        # partls_fit_alt = prepare (faithful) + partls_alt_prepared
             ctx.opt_prepare(Xf, yf, Pf, eta_v, L.OPT_FAITHFUL_INTERCEPT, weights=wf)
             a, b, t, o, it = ctx.alt_prepared(a0, b0, eps_v, int(T))
             return PartLSFitResult(a, b, t, Pout), None, report(ctx, opt=o, iters=it)
@@ -813,7 +880,7 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
             mc.tolerate_ill = ctx.tolerate_ill
             a, b, t, opt, nopen = mc.fit_bnb(Xf, yf, Pf, eta_v)
             return PartLSFitResult(a, b, t, Pout), None, report(mc, opt=opt, nopen=nopen)
-        if wf is not None:                                # partls_fit_bnb = prepare (faithful) + partls_bnb_prepared
+        if staged:                                        # partls_fit_bnb = prepare (faithful) + partls_bnb_prepared
             ctx.opt_prepare(Xf, yf, Pf, eta_v, L.OPT_FAITHFUL_INTERCEPT, weights=wf)
             a, b, t, o, no = ctx.bnb_prepared()
             return PartLSFitResult(a, b, t, Pout), None, report(ctx, opt=o, nopen=no)
@@ -959,27 +1026,19 @@ def predict(*args, device=0):
     X = np.asarray(X)
     if not np.issubdtype(X.dtype, np.floating) or X.ndim != 2:
         raise TypeError("predict: X must be a floating-point matrix")
-    Xf = np.asfortranarray(X, dtype=np.float64)
     Pf = np.asfortranarray(P, dtype=np.int64)
     a = np.ascontiguousarray(α, dtype=np.float64)
     b = np.ascontiguousarray(β, dtype=np.float64)
-    N, M = Xf.shape
+    Xf = _x_host(X)                                     # what the context is handed is what goes up (Context.predict takes it as it is)
+    M = Xf.shape[1]
     if Pf.shape[0] != M or a.shape != (M,) or b.shape != (Pf.shape[1],):
         raise ValueError("DimensionMismatch in predict")
-    yh = np.zeros(N)
-    ctx = default_context(device)
-    _check(L.lib().partls_predict(ctx._h, Xf.ctypes.data, N, M, N, Pf.ctypes.data, Pf.shape[1], M, _dp(a), _dp(b),
-                                  float(t), _dp(yh)))
-    return yh
+    return default_context(device).predict(Xf, Pf, a, b, t)
 
 
-def predict_device(model, dX_ptr, N, ldX, dyhat_ptr, device=0):
+def predict_device(model, dX_ptr, N, ldX, dyhat_ptr, device=0, dtype=np.float64):
     """predict with X (N x M, column-major, leading dimension ldX) and yhat (N) resident in HBM: raw device addresses (e.g.
-    torch tensor .data_ptr()) that stay owned by the caller.  PartitionedLS.jl:132-134 without the PCIe copy of X."""
+    torch tensor .data_ptr()) that stay owned by the caller.  PartitionedLS.jl:132-134 without the PCIe copy of X.
+    dtype: element type of X, float64 or float32 (ldX counts elements); yhat is float64 either way."""
     Pf = np.asfortranarray(model.P, dtype=np.int64)
-    a = np.ascontiguousarray(model.α, dtype=np.float64)
-    b = np.ascontiguousarray(model.β, dtype=np.float64)
-    M, K = Pf.shape
-    ctx = default_context(device)
-    _check(L.lib().partls_predict_device(ctx._h, C.c_void_p(dX_ptr), int(N), M, int(ldX), Pf.ctypes.data, K, M, _dp(a), _dp(b),
-                                         float(model.t), C.c_void_p(dyhat_ptr)))
+    default_context(device).predict_device(dX_ptr, N, Pf.shape[0], ldX, Pf, model.α, model.β, model.t, dyhat_ptr, dtype=dtype)

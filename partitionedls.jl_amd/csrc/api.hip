@@ -84,11 +84,13 @@ namespace {
 constexpr int UP_T = 4;
 constexpr size_t UP_BUF = (size_t)8 << 20;
 }
-partls_status upload_matrix(partls_ctx *c, double *dst, const double *X, int64_t N, int64_t M, int64_t ldX)
+partls_status upload_matrix(partls_ctx *c, void *dst_, const void *X_, int64_t N, int64_t M, int64_t ldX, size_t esz)
 {
-    const size_t bytes = (size_t)N * M * sizeof(double);
+    char *dst = static_cast<char *>(dst_);                 // everything below goes by bytes: esz = 8 (double) or 4 (float)
+    const char *X = static_cast<const char *>(X_);
+    const size_t bytes = (size_t)N * M * esz;
     if (bytes < ((size_t)8 << 20) || c->knobs.no_staged_upload) {
-        PARTLS_HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)N * sizeof(double), X, (size_t)ldX * sizeof(double), (size_t)N * sizeof(double), (size_t)M,
+        PARTLS_HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)N * esz, X, (size_t)ldX * esz, (size_t)N * esz, (size_t)M,
                                           hipMemcpyHostToDevice, c->stream));
         return PARTLS_OK;
     }
@@ -98,7 +100,7 @@ partls_status upload_matrix(partls_ctx *c, double *dst, const double *X, int64_t
         for (int i = 0; i < 2 * UP_T; ++i) PARTLS_HIP_CHECK(hipEventCreateWithFlags(&c->upEvent[i], hipEventDisableTiming));
     }
     // rows per piece of a column (a column longer than a staging buffer goes in pieces), columns per batch otherwise
-    const size_t col_bytes = (size_t)N * sizeof(double);
+    const size_t col_bytes = (size_t)N * esz, ld_bytes = (size_t)ldX * esz;
     hipError_t err[UP_T];
     for (int t = 0; t < UP_T; ++t) err[t] = hipSuccess;
     const int device = c->device;
@@ -119,16 +121,16 @@ partls_status upload_matrix(partls_ctx *c, double *dst, const double *X, int64_t
             const int64_t per = (int64_t)(UP_BUF / col_bytes);
             for (int64_t j0 = c0; j0 < c1 && e == hipSuccess; j0 += per) {
                 const int64_t j1 = j0 + per < c1 ? j0 + per : c1;
-                for (int64_t j = j0; j < j1; ++j) std::memcpy(pin[b] + (size_t)(j - j0) * col_bytes, X + j * ldX, col_bytes);
-                flush(reinterpret_cast<char *>(dst + j0 * N), (size_t)(j1 - j0) * col_bytes);
+                for (int64_t j = j0; j < j1; ++j) std::memcpy(pin[b] + (size_t)(j - j0) * col_bytes, X + (size_t)j * ld_bytes, col_bytes);
+                flush(dst + (size_t)j0 * col_bytes, (size_t)(j1 - j0) * col_bytes);
             }
         } else {
-            const int64_t rows = (int64_t)(UP_BUF / sizeof(double));
+            const int64_t rows = (int64_t)(UP_BUF / esz);
             for (int64_t j = c0; j < c1 && e == hipSuccess; ++j)
                 for (int64_t r0 = 0; r0 < N && e == hipSuccess; r0 += rows) {
                     const int64_t r1 = r0 + rows < N ? r0 + rows : N;
-                    std::memcpy(pin[b], X + j * ldX + r0, (size_t)(r1 - r0) * sizeof(double));
-                    flush(reinterpret_cast<char *>(dst + j * N + r0), (size_t)(r1 - r0) * sizeof(double));
+                    std::memcpy(pin[b], X + (size_t)j * ld_bytes + (size_t)r0 * esz, (size_t)(r1 - r0) * esz);
+                    flush(dst + (size_t)j * col_bytes + (size_t)r0 * esz, (size_t)(r1 - r0) * esz);
                 }
         }
         if (e == hipSuccess) e = hipStreamSynchronize(c->upStream[t]);
@@ -180,8 +182,8 @@ partls_status prepare_weights(partls_ctx *c, const double *w, int64_t N, int on_
     return PARTLS_OK;
 }
 
-partls_status ctx_prepare(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
-                          const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags, const double *w)
+partls_status ctx_prepare(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
+                          const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags, const double *w, bool x_f32)
 {
     partls_status st = check_common(c, X, N, M, ldX, P, K, ldP);
     if (st != PARTLS_OK) return st;
@@ -195,6 +197,8 @@ partls_status ctx_prepare(partls_ctx *c, const double *X, int64_t N, int64_t M, 
     c->coop_state_valid = false;
     c->order_ready = false; c->order_identity = true; c->flip_cost.clear(); c->ms[PARTLS_T_CALIB] = 0.0;
     c->dw = nullptr; c->ds = nullptr;
+    c->x_f32 = false;
+    if (x_f32 && c->multi_rank) { set_error("float X: a context of a partls_multi is not supported (row-sharded multi-GPU fits are fp64)"); return PARTLS_ERR_UNSUPPORTED; }
     PARTLS_HIP_CHECK(hipSetDevice(c->device));
     if (w) {
         if (c->multi_rank) { set_error("sample weights: a context of a partls_multi is not supported (multi-GPU fits are unweighted)"); return PARTLS_ERR_UNSUPPORTED; }
@@ -208,16 +212,18 @@ partls_status ctx_prepare(partls_ctx *c, const double *X, int64_t N, int64_t M, 
     if (x_on_device) {
         c->dX = X; c->dy = y; c->ldX = ldX;
     } else {
-        PARTLS_HIP_CHECK(c->ownX.ensure((size_t)N * M * sizeof(double)));
+        const size_t esz = x_f32 ? sizeof(float) : sizeof(double);
+        PARTLS_HIP_CHECK(c->ownX.ensure((size_t)N * M * esz));
         PARTLS_HIP_CHECK(c->ownY.ensure((size_t)N * sizeof(double)));
         PARTLS_HIP_CHECK(hipMemcpyAsync(c->ownY.p, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
         const auto u0 = std::chrono::steady_clock::now();
-        st = upload_matrix(c, c->ownX.as<double>(), X, N, M, ldX);
+        st = upload_matrix(c, c->ownX.p, X, N, M, ldX, esz);
         if (st != PARTLS_OK) return st;
         c->last_upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
-        c->last_upload_bytes = (double)N * (double)M * sizeof(double);
-        c->dX = c->ownX.as<double>(); c->dy = c->ownY.as<double>(); c->ldX = N;
+        c->last_upload_bytes = (double)N * (double)M * (double)esz;
+        c->dX = c->ownX.p; c->dy = c->ownY.as<double>(); c->ldX = N;
     }
+    c->x_f32 = x_f32;
 
     // Gram products (fp64 MFMA)
     const size_t slabd = gram_slab_doubles(N, M, c->knobs.gram_S, c->knobs.gram_cr, &c->chunks, &c->ldg);
@@ -225,7 +231,7 @@ partls_status ctx_prepare(partls_ctx *c, const double *X, int64_t N, int64_t M, 
     PARTLS_HIP_CHECK(c->G.ensure((size_t)c->ldg * c->ldg * sizeof(double)));
     t_begin(c, PARTLS_T_GRAM);
     PARTLS_HIP_CHECK(launch_gram(c->dX, N, M, c->ldX, c->dy, c->slab.as<double>(), c->chunks, c->ldg, c->knobs.gram_S, c->knobs.gram_cr,
-                                 c->G.as<double>(), c->stream, c->ds));
+                                 c->G.as<double>(), c->stream, c->ds, c->x_f32));
     t_end(c, PARTLS_T_GRAM);
     // rows of X sharded over several devices: the Gram products of the blocks are summed here (partls_fit_opt_multi, multi.hip)
     if (c->gram_hook) { st = c->gram_hook(c); if (st != PARTLS_OK) return st; }
@@ -483,9 +489,9 @@ partls_status data_pass(partls_ctx *c, const std::vector<double> &w, bool want_o
             PARTLS_HIP_CHECK(q->hGpart.resize((size_t)xr * (M + 1)));
         }
         PARTLS_HIP_CHECK(launch_residual(q->dX, N, M, q->ldX, want_obj ? q->dy : nullptr, q->wdev.as<double>(), w[(size_t)M],
-                                         want_obj ? q->partial.as<double>() : nullptr, nb, yhat, q->stream, q->dw));
+                                         want_obj ? q->partial.as<double>() : nullptr, nb, yhat, q->stream, q->dw, q->x_f32));
         if (want_grad) {
-            PARTLS_HIP_CHECK(launch_xtr(q->dX, N, M, q->ldX, q->dy, yhat, q->gD.as<double>(), q->stream, q->dw));
+            PARTLS_HIP_CHECK(launch_xtr(q->dX, N, M, q->ldX, q->dy, yhat, q->gD.as<double>(), q->stream, q->dw, q->x_f32));
             PARTLS_HIP_CHECK(hipMemcpyAsync(q->hGpart.data(), q->gD.p, q->hGpart.size() * sizeof(double), hipMemcpyDeviceToHost, q->stream));
         }
         if (want_obj) PARTLS_HIP_CHECK(hipMemcpyAsync(q->hPart.data(), q->partial.p, nb * sizeof(double), hipMemcpyDeviceToHost, q->stream));
@@ -886,7 +892,7 @@ using namespace partls;
 
 extern "C" {
 
-int partls_version(void) { return 101; }
+int partls_version(void) { return 102; }
 const char *partls_last_error(void) { return g_err; }
 
 int partls_device_count(void)
@@ -1007,6 +1013,14 @@ partls_status partls_opt_prepare_weighted(partls_ctx *c, const double *X, int64_
                                           uint32_t flags)
 try {
     return ctx_prepare(c, X, N, M, ldX, y, x_on_device, P, K, ldP, eta, (flags & PARTLS_OPT_FAITHFUL_INTERCEPT) != 0, flags, w);
+}
+catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
+catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+
+partls_status partls_opt_prepare_f32(partls_ctx *c, const float *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w,
+                                     int x_on_device, const int64_t *P, int64_t K, int64_t ldP, double eta, uint32_t flags)
+try {
+    return ctx_prepare(c, X, N, M, ldX, y, x_on_device, P, K, ldP, eta, (flags & PARTLS_OPT_FAITHFUL_INTERCEPT) != 0, flags, w, /*x_f32=*/true);
 }
 catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
 catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
@@ -1615,9 +1629,9 @@ catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return
 catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
 
 // predict: w_m = sum_k P[m,k] alpha_m beta_k on the host (M*K flops), yhat = X w + t on the device (one pass over X)
-static partls_status predict_common(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, int x_on_device,
+static partls_status predict_common(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, int x_on_device,
                                     const int64_t *P, int64_t K, int64_t ldP, const double *alpha, const double *beta, double t,
-                                    double *yhat)
+                                    double *yhat, bool x_f32 = false)
 {
     partls_status st = check_common(c, X, N, M, ldX, P, K, ldP);
     if (st != PARTLS_OK) return st;
@@ -1635,17 +1649,18 @@ static partls_status predict_common(partls_ctx *c, const double *X, int64_t N, i
     }
     PARTLS_HIP_CHECK(c->wdev.ensure((size_t)(M + 1) * sizeof(double)));
     PARTLS_HIP_CHECK(hipMemcpyAsync(c->wdev.p, w.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const double *dX = X;
+    const void *dX = X;
     int64_t ld = ldX;
     double *dyh = yhat;
     if (!x_on_device) {
-        PARTLS_HIP_CHECK(c->predX.ensure((size_t)N * M * sizeof(double)));
+        const size_t esz = x_f32 ? sizeof(float) : sizeof(double);
+        PARTLS_HIP_CHECK(c->predX.ensure((size_t)N * M * esz));
         PARTLS_HIP_CHECK(c->predY.ensure((size_t)N * sizeof(double)));
-        const partls_status us = upload_matrix(c, c->predX.as<double>(), X, N, M, ldX);
+        const partls_status us = upload_matrix(c, c->predX.p, X, N, M, ldX, esz);
         if (us != PARTLS_OK) return us;
-        dX = c->predX.as<double>(); ld = N; dyh = c->predY.as<double>();
+        dX = c->predX.p; ld = N; dyh = c->predY.as<double>();
     }
-    PARTLS_HIP_CHECK(launch_residual(dX, N, M, ld, nullptr, c->wdev.as<double>(), t, nullptr, 1024, dyh, c->stream));
+    PARTLS_HIP_CHECK(launch_residual(dX, N, M, ld, nullptr, c->wdev.as<double>(), t, nullptr, 1024, dyh, c->stream, nullptr, x_f32));
     if (!x_on_device)
         PARTLS_HIP_CHECK(hipMemcpyAsync(yhat, c->predY.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -1665,6 +1680,22 @@ partls_status partls_predict_device(partls_ctx *c, const double *dX, int64_t N, 
                                     int64_t K, int64_t ldP, const double *alpha, const double *beta, double t, double *dyhat)
 try {
     return predict_common(c, dX, N, M, ldX, 1, P, K, ldP, alpha, beta, t, dyhat);
+}
+catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
+catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+
+partls_status partls_predict_f32(partls_ctx *c, const float *X, int64_t N, int64_t M, int64_t ldX, const int64_t *P, int64_t K,
+                                 int64_t ldP, const double *alpha, const double *beta, double t, double *yhat)
+try {
+    return predict_common(c, X, N, M, ldX, 0, P, K, ldP, alpha, beta, t, yhat, /*x_f32=*/true);
+}
+catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
+catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+
+partls_status partls_predict_device_f32(partls_ctx *c, const float *dX, int64_t N, int64_t M, int64_t ldX, const int64_t *P,
+                                        int64_t K, int64_t ldP, const double *alpha, const double *beta, double t, double *dyhat)
+try {
+    return predict_common(c, dX, N, M, ldX, 1, P, K, ldP, alpha, beta, t, dyhat, /*x_f32=*/true);
 }
 catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
 catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }

@@ -132,8 +132,10 @@ hipError_t launch_layout_reg(const double *Tfull, int n, int T, double *T0reg, h
 // (gram_S / gram_cr: tuning overrides read once at partls_create, 0 = automatic)
 // sw (optional, device, N): s = sqrt(w) of the sample weights -> G_aug = Z~'Z~ with Z~ = diag(s) [X 1 y]
 size_t     gram_slab_doubles(int64_t N, int64_t M, int gram_S, int gram_cr, int *chunks_out, int *ldg_out);
-hipError_t launch_gram(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, double *slab, int chunks,
-                       int ldg, int gram_S, int gram_cr, double *G, hipStream_t s, const double *sw = nullptr);
+// x_f32 (here and in launch_residual / launch_xtr): X holds float elements (ldX counts elements); each is widened to double as it is
+// loaded, so the results are those of the widened matrix bit for bit
+hipError_t launch_gram(const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, double *slab, int chunks,
+                       int ldg, int gram_S, int gram_cr, double *G, hipStream_t s, const double *sw = nullptr, bool x_f32 = false);
 // sample weights (misc.hip): s[i] = sqrt(w[i]) and, per block b of weight_prep_blocks(N), part[3 b ..] = (any w < 0, any non-finite w,
 // sum of w) — the host adds the blocks in index order
 int        weight_prep_blocks(int64_t N);
@@ -173,13 +175,13 @@ hipError_t launch_gersh(const double *Tfull, int n, double *out, hipStream_t s);
 hipError_t launch_alt_beta_system(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, const double *a, int Kp,
                                   double *GA, double *Hg, hipStream_t s);
 // wt (optional, device, N): sample weights -> sum_i wt[i] (...)^2
-hipError_t launch_residual(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w, double t,
-                           double *partial, int nblocks, double *yhat, hipStream_t s, const double *wt = nullptr);
+hipError_t launch_residual(const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w, double t,
+                           double *partial, int nblocks, double *yhat, hipStream_t s, const double *wt = nullptr, bool x_f32 = false);
 // g[0..M] = Xo' (y - yhat): the gradient pass of the data-space refinement (wt: Xo' W (y - yhat))
 // gpart: xtr_slices(N) x (M + 1) partial sums; g[m] = sum over the slices in order
 int        xtr_slices(int64_t N);
-hipError_t launch_xtr(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *yhat, double *gpart,
-                      hipStream_t s, const double *wt = nullptr);
+hipError_t launch_xtr(const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *yhat, double *gpart,
+                      hipStream_t s, const double *wt = nullptr, bool x_f32 = false);
 hipError_t launch_synth(uint64_t seed, int64_t N, int64_t D, const double *wstar_dev, double *X, double *y, hipStream_t s);
 
 // host-side mirror of the device generator (synth.hip); also used by partls_synth_truth

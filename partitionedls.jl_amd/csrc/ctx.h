@@ -99,7 +99,9 @@ struct partls_ctx {
     double eta = 0.0;
     uint32_t flags = 0;
     bool faithful = false;                         // intercept is a sign-constrained tableau variable (2^(K+1) patterns)
-    const double *dX = nullptr, *dy = nullptr;     // device views (owned copies below, or the caller's)
+    const void *dX = nullptr;                      // device views (owned copies below, or the caller's): X, elements of type ...
+    bool x_f32 = false;                            // ... float (partls_opt_prepare_f32) or double; set by every prepare
+    const double *dy = nullptr;
     partls::DevBuf ownX, ownY;
     // sample weights of the prepared problem (partls_opt_prepare_weighted / partls_cv_opt_weighted; nullptr: unweighted): dw = w (the
     // caller's device array, or ownW, the upload of a host one), ds = sqrt(w) (ownS, written by weight_prep_kernel).  Every Gram build
@@ -192,8 +194,10 @@ void t_collect(partls_ctx *c);
 
 // Upload (or adopt) X, y; build the Gram products; lay the tableau out.  faithful = intercept is a regular variable.
 // w (optional): sample weights, a device pointer when x_on_device (see prepare_weights)
-partls_status ctx_prepare(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
-                          const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags, const double *w = nullptr);
+// x_f32: X holds float elements (host or device; ldX in elements) and is kept, uploaded and read as such
+partls_status ctx_prepare(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
+                          const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags, const double *w = nullptr,
+                          bool x_f32 = false);
 // Sample weights w[N] (host, or device when on_device) -> c->dw, c->ds after one weight_prep_kernel pass, or the status of the first
 // failed check: NaN / Inf -> PARTLS_ERR_NONFINITE; a negative weight or a sum that is not > 0 -> PARTLS_ERR_BAD_ARG.
 partls_status prepare_weights(partls_ctx *c, const double *w, int64_t N, int on_device);
@@ -201,8 +205,8 @@ partls_status prepare_weights(partls_ctx *c, const double *w, int64_t N, int on_
 // tableau, the host copies and the tolerance.  partls_cv_opt calls it on a context whose G it filled itself.
 partls_status ctx_prepare_tableau(partls_ctx *c);
 partls_status load_partition(partls_ctx *c, const int64_t *P, int64_t M, int64_t K, int64_t ldP);
-// host X (N x M, ldX) -> packed device image (ld N) on c->stream, staged through page-locked buffers when large
-partls_status upload_matrix(partls_ctx *c, double *dst, const double *X, int64_t N, int64_t M, int64_t ldX);
+// host X (N x M, ldX, elements of `esz` bytes) -> packed device image (ld N) on c->stream, staged through page-locked buffers when large
+partls_status upload_matrix(partls_ctx *c, void *dst, const void *X, int64_t N, int64_t M, int64_t ldX, size_t esz = sizeof(double));
 // the Opt sweep's pieces that partls_cv_opt shares (api.hip)
 partls_status calibrate_bit_order(partls_ctx *c);
 bool sweep_plan(partls_ctx *c, int64_t total, int64_t *chain_len_out, int *grid_out, const char *who);

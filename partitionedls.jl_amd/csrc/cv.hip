@@ -53,7 +53,7 @@ static void point_rows(partls_ctx *c, partls_ctx *W, const int64_t *fold_ptr, in
     for (int64_t g = 0; g < F; ++g) {
         if (g == f) continue;
         if (first) {
-            W->dX = c->dX + fold_ptr[g]; W->dy = c->dy + fold_ptr[g]; W->N = fold_ptr[g + 1] - fold_ptr[g];
+            W->dX = static_cast<const double *>(c->dX) + fold_ptr[g]; W->dy = c->dy + fold_ptr[g]; W->N = fold_ptr[g + 1] - fold_ptr[g];
             W->dw = c->dw ? c->dw + fold_ptr[g] : nullptr; W->ds = c->ds ? c->ds + fold_ptr[g] : nullptr;
             first = false;
         } else {
@@ -125,6 +125,7 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
     c->last_upload_ms = 0.0; c->last_upload_bytes = 0.0;
     c->N = N; c->M = M; c->K = K; c->flags = flags; c->faithful = faithful;
     c->dw = nullptr; c->ds = nullptr;
+    c->x_f32 = false;                              // cross-validation reads X as double (no float form)
     // ---- sample weights (partls_cv_opt_weighted): checked and square-rooted before anything else; every fold Gram and every data pass
     // (finish, held-out SSE) then reads its rows' slice of them
     if (w) {
@@ -146,6 +147,7 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
         c->last_upload_bytes = (double)N * (double)M * sizeof(double);
         c->dX = c->ownX.as<double>(); c->dy = c->ownY.as<double>(); c->ldX = N;
     }
+    const double *Xd = static_cast<const double *>(c->dX);
 
     // ---- internal contexts: the working context and one row view per fold
     partls_status st = make_internal(c, &c->cv_work);
@@ -157,7 +159,7 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
         st = make_internal(c, &c->cv_view[(size_t)g]);
         if (st != PARTLS_OK) return st;
         partls_ctx *v = c->cv_view[(size_t)g];
-        v->dX = c->dX + fold_ptr[g]; v->dy = c->dy + fold_ptr[g]; v->ldX = c->ldX;
+        v->dX = Xd + fold_ptr[g]; v->dy = c->dy + fold_ptr[g]; v->ldX = c->ldX;
         v->dw = c->dw ? c->dw + fold_ptr[g] : nullptr; v->ds = c->ds ? c->ds + fold_ptr[g] : nullptr;
         v->N = fold_ptr[g + 1] - fold_ptr[g]; v->M = M; v->K = K;
         v->peers.clear();
@@ -180,7 +182,7 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
         const int64_t r0 = F > 0 ? fold_ptr[g] : 0, n_g = F > 0 ? fold_ptr[g + 1] - fold_ptr[g] : N;
         int ch = 0, ld2 = 0;
         (void)gram_slab_doubles(n_g, M, c->knobs.gram_S, c->knobs.gram_cr, &ch, &ld2);
-        PARTLS_HIP_CHECK(launch_gram(c->dX + r0, n_g, M, c->ldX, c->dy + r0, c->slab.as<double>(), ch, ldg, c->knobs.gram_S, c->knobs.gram_cr,
+        PARTLS_HIP_CHECK(launch_gram(Xd + r0, n_g, M, c->ldX, c->dy + r0, c->slab.as<double>(), ch, ldg, c->knobs.gram_S, c->knobs.gram_cr,
                                      Gf + (size_t)g * gs, c->stream, c->ds ? c->ds + r0 : nullptr));
     }
     PARTLS_HIP_CHECK(launch_fold_gram_combine(Gf, nf, (int)F, gs, Gc, c->stream));

@@ -52,8 +52,12 @@ static constexpr int NL = GT / (NWV * CPW);    // loads per thread, panel and ma
 //   z_value : zero for the padding columns of the last tile (EDGE) and for the row tail, applied at the LDS store.
 // Addresses: wave-uniform 64-bit base (tile column block, panel row: SGPRs) + ONE per-lane 32-bit element offset shared by all the
 // loads of a panel (csub * ldX + row in panel), so the 2 x NL loads in flight cost no address registers (element offsets, not bytes: 3 * ldX + 15 must fit 32 bits; the host refuses ldX >= 2^30).
-template <bool EDGE>
-__device__ __forceinline__ double z_load(const double *__restrict__ Xrow, int64_t ldX, int M, int colu, int csub, unsigned lane_off, unsigned rowoff)
+// XT (element type of X): double, or float — loaded as stored and widened where z_value touches it, at the LDS store.
+// float -> double is exact (subnormals included: the build keeps fp32 denormals), so everything from the LDS image on sees the values
+// of the widened matrix.  A lane loads ONE element, so a column that is only 4-byte aligned (odd ldX, odd row start) needs nothing
+// special; the 16 lanes of a column read one 64-byte segment instead of 128 bytes.
+template <bool EDGE, class XT>
+__device__ __forceinline__ XT z_load(const XT *__restrict__ Xrow, int64_t ldX, int M, int colu, int csub, unsigned lane_off, unsigned rowoff)
 {
     if constexpr (!EDGE) {
         return (Xrow + (int64_t)colu * ldX)[lane_off];
@@ -165,8 +169,8 @@ __host__ __device__ constexpr size_t slice_doubles(int np, int nt) { return (siz
 // the B fragment of block c are the same LDS words (diag_panel).  The ones column stages s_i, y stages s_i y_i, and the corner sums of
 // tile (0, 0) are formed from those same scaled values.  s of panel p + 1 is one more per-lane register, loaded behind the last store
 // that reads it (the last slot of the phase).  WT = false compiles to the unweighted kernel unchanged.
-template <bool WT, bool EA, bool EB, bool DIAG>
-__device__ __forceinline__ void gram_body(const double *__restrict__ X, int64_t N, int M, int64_t ldX,
+template <class XT, bool WT, bool EA, bool EB, bool DIAG>
+__device__ __forceinline__ void gram_body(const XT *__restrict__ X, int64_t N, int M, int64_t ldX,
                                           const double *__restrict__ y, double *__restrict__ slab, int np, int nt, int pair,
                                           int chunk_rows, int S, int I, int J, int xg, int sl, double *sA, double *sB, double *sV,
                                           const double *__restrict__ sw)
@@ -191,10 +195,11 @@ __device__ __forceinline__ void gram_body(const double *__restrict__ X, int64_t 
     // phase p - 1) are stored to the other buffer and immediately refilled by the loads of panel p + 2.  One barrier per phase
     // separates the reads of a buffer from its refill and the stores from their reads.  Everything inside a phase is branch-free: a
     // panel that does not exist is "loaded" from a clamped valid address with its row predicate false (zeros reach the LDS).
-    double va[NL], vb[DIAG ? 1 : NL], vy = 0.0;        // raw values of panel p + 1 (+ y for the diagonal tiles)
+    XT va[NL], vb[DIAG ? 1 : NL];                      // raw values of panel p + 1, as stored (XT)
+    double vy = 0.0;                                   // ... + y for the diagonal tiles
     double vs = 1.0;                                   // WT: s of this lane's sample of panel p + 1
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    struct Panel { const double *Xrow; const double *yrow; unsigned lane_off, rowoff; bool rv; };
+    struct Panel { const XT *Xrow; const double *yrow; unsigned lane_off, rowoff; bool rv; };
     int64_t chunk = xg + (int64_t)8 * sl;
     int kb = 0;
     bool live = chunk < nchunks;                        // does the panel (chunk, kb) exist?
@@ -225,11 +230,11 @@ __device__ __forceinline__ void gram_body(const double *__restrict__ X, int64_t 
         const int i = g & (NL - 1);
         const int c = i * (NWV * CPW) + wave * CPW + csub;
         if constexpr (WT) {
-            if (g < NL) (sA + buf * (GT * GLD))[c * GLD + smp] = z_value<EA>(va[i], rv, M, I * GT + c) * vs;
-            else if constexpr (!DIAG) (sB + buf * (GT * GLD))[c * GLD + smp] = z_value<EB>(vb[i], rv, M, J * GT + c) * vs;
+            if (g < NL) (sA + buf * (GT * GLD))[c * GLD + smp] = z_value<EA>((double)va[i], rv, M, I * GT + c) * vs;
+            else if constexpr (!DIAG) (sB + buf * (GT * GLD))[c * GLD + smp] = z_value<EB>((double)vb[i], rv, M, J * GT + c) * vs;
         } else {
-            if (g < NL) (sA + buf * (GT * GLD))[c * GLD + smp] = z_value<EA>(va[i], rv, M, I * GT + c);
-            else if constexpr (!DIAG) (sB + buf * (GT * GLD))[c * GLD + smp] = z_value<EB>(vb[i], rv, M, J * GT + c);
+            if (g < NL) (sA + buf * (GT * GLD))[c * GLD + smp] = z_value<EA>((double)va[i], rv, M, I * GT + c);
+            else if constexpr (!DIAG) (sB + buf * (GT * GLD))[c * GLD + smp] = z_value<EB>((double)vb[i], rv, M, J * GT + c);
         }
     };
     auto store_virtual = [&](int buf, bool rv) {        // diagonal tiles: [valid, y] of the panel, and the corner sums of tile (0, 0)
@@ -340,9 +345,9 @@ __device__ __forceinline__ void gram_body(const double *__restrict__ X, int64_t 
     }
 }
 
-template <bool WT>
+template <class XT, bool WT>
 __global__ __launch_bounds__(64 * NWV, 4) void gram_kernel(      // 4 waves per SIMD (HIP: the second argument counts waves per EU): <= 128 VGPRs
-const double *__restrict__ X, int64_t N, int M, int64_t ldX,
+const XT *__restrict__ X, int64_t N, int M, int64_t ldX,
                                                    const double *__restrict__ y, double *__restrict__ slab,
                                                    int chunk_rows, int S, int np, const double *__restrict__ sw)
 {
@@ -359,11 +364,11 @@ const double *__restrict__ X, int64_t N, int M, int64_t ldX,
     const bool ragged = (M % GT) != 0;
     const bool ea = ragged && I == nt - 1, eb = ragged && J == nt - 1;
     if (I == J) {
-        if (ea) gram_body<WT, true, true, true>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV, sw);
-        else gram_body<WT, false, false, true>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV, sw);
+        if (ea) gram_body<XT, WT, true, true, true>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV, sw);
+        else gram_body<XT, WT, false, false, true>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV, sw);
     } else {
-        if (eb) gram_body<WT, false, true, false>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV, sw);
-        else gram_body<WT, false, false, false>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV, sw);
+        if (eb) gram_body<XT, WT, false, true, false>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV, sw);
+        else gram_body<XT, WT, false, false, false>(X, N, M, ldX, y, slab, np, nt, pair, chunk_rows, S, I, J, xg, sl, sA, sB, sV, sw);
     }
 }
 
@@ -462,14 +467,22 @@ size_t gram_slab_doubles(int64_t N, int64_t M, int gram_S, int gram_cr, int *chu
     return (size_t)8 * S * slice_doubles(np, nt);
 }
 
-hipError_t launch_gram(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, double *slab, int chunks,
-                       int ldg, int gram_S, int gram_cr, double *G, hipStream_t s, const double *sw)
+template <class XT>
+static void launch_gram_kernel(const XT *X, int64_t N, int M, int64_t ldX, const double *y, double *slab, int cr, int S, int np,
+                               const double *sw, hipStream_t s)
+{
+    if (sw) hipLaunchKernelGGL((gram_kernel<XT, true>), dim3(8 * S * np), dim3(64 * NWV), 0, s, X, N, M, ldX, y, slab, cr, S, np, sw);
+    else hipLaunchKernelGGL((gram_kernel<XT, false>), dim3(8 * S * np), dim3(64 * NWV), 0, s, X, N, M, ldX, y, slab, cr, S, np, sw);
+}
+
+hipError_t launch_gram(const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, double *slab, int chunks,
+                       int ldg, int gram_S, int gram_cr, double *G, hipStream_t s, const double *sw, bool x_f32)
 {
     int ldg2, S, cr, np, nt;
     gram_plan(N, M, gram_S, gram_cr, &ldg2, &S, &cr, &np, &nt);
     if (ldX >= ((int64_t)1 << 30)) return hipErrorInvalidValue;          // 32-bit per-lane element offsets (see z_load)
-    if (sw) hipLaunchKernelGGL(gram_kernel<true>, dim3(8 * S * np), dim3(64 * NWV), 0, s, X, N, (int)M, ldX, y, slab, cr, S, np, sw);
-    else hipLaunchKernelGGL(gram_kernel<false>, dim3(8 * S * np), dim3(64 * NWV), 0, s, X, N, (int)M, ldX, y, slab, cr, S, np, sw);
+    if (x_f32) launch_gram_kernel(static_cast<const float *>(X), N, (int)M, ldX, y, slab, cr, S, np, sw, s);
+    else launch_gram_kernel(static_cast<const double *>(X), N, (int)M, ldX, y, slab, cr, S, np, sw, s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int tot = ldg * ldg;

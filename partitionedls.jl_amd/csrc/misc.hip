@@ -418,8 +418,8 @@ hipError_t launch_alt_beta_system(const double *G, int ldg, int M, double eta, c
 // with one exact factor when wt_i = 1.
 // Blocks are summed on the host in index order (reproducible).
 // ---------------------------------------------------------------------------------------------------------------------
-template <bool WT>
-__global__ __launch_bounds__(256) void residual_kernel(const double *__restrict__ X, int64_t N, int64_t M, int64_t ldX,
+template <class XT, bool WT>
+__global__ __launch_bounds__(256) void residual_kernel(const XT *__restrict__ X, int64_t N, int64_t M, int64_t ldX,
                                                        const double *__restrict__ y, const double *__restrict__ w, double t,
                                                        double *__restrict__ partial, double *__restrict__ yhat,
                                                        const double *__restrict__ wt)
@@ -432,12 +432,12 @@ __global__ __launch_bounds__(256) void residual_kernel(const double *__restrict_
         double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
         int64_t m = 0;
         for (; m + 3 < M; m += 4) {
-            a0 = fma(X[i + m * ldX], sw[m], a0);
-            a1 = fma(X[i + (m + 1) * ldX], sw[m + 1], a1);
-            a2 = fma(X[i + (m + 2) * ldX], sw[m + 2], a2);
-            a3 = fma(X[i + (m + 3) * ldX], sw[m + 3], a3);
+            a0 = fma((double)X[i + m * ldX], sw[m], a0);
+            a1 = fma((double)X[i + (m + 1) * ldX], sw[m + 1], a1);
+            a2 = fma((double)X[i + (m + 2) * ldX], sw[m + 2], a2);
+            a3 = fma((double)X[i + (m + 3) * ldX], sw[m + 3], a3);
         }
-        for (; m < M; ++m) a0 = fma(X[i + m * ldX], sw[m], a0);
+        for (; m < M; ++m) a0 = fma((double)X[i + m * ldX], sw[m], a0);
         const double p = ((a0 + a1) + (a2 + a3)) + t;
         if (yhat) yhat[i] = p;
         if (y) {
@@ -456,15 +456,23 @@ __global__ __launch_bounds__(256) void residual_kernel(const double *__restrict_
     if (threadIdx.x == 0 && partial) partial[blockIdx.x] = red[0];
 }
 
-hipError_t launch_residual(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w, double t,
-                           double *partial, int nblocks, double *yhat, hipStream_t s, const double *wt)
+template <class XT>
+static void launch_residual_kernel(const XT *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w, double t,
+                                   double *partial, int nblocks, double *yhat, hipStream_t s, const double *wt)
 {
     if (wt && y)
-        hipLaunchKernelGGL(residual_kernel<true>, dim3(nblocks), dim3(256), (size_t)M * sizeof(double), s, X, N, M, ldX, y, w, t,
+        hipLaunchKernelGGL((residual_kernel<XT, true>), dim3(nblocks), dim3(256), (size_t)M * sizeof(double), s, X, N, M, ldX, y, w, t,
                            partial, yhat, wt);
     else
-        hipLaunchKernelGGL(residual_kernel<false>, dim3(nblocks), dim3(256), (size_t)M * sizeof(double), s, X, N, M, ldX, y, w, t,
+        hipLaunchKernelGGL((residual_kernel<XT, false>), dim3(nblocks), dim3(256), (size_t)M * sizeof(double), s, X, N, M, ldX, y, w, t,
                            partial, yhat, nullptr);
+}
+
+hipError_t launch_residual(const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w, double t,
+                           double *partial, int nblocks, double *yhat, hipStream_t s, const double *wt, bool x_f32)
+{
+    if (x_f32) launch_residual_kernel(static_cast<const float *>(X), N, M, ldX, y, w, t, partial, nblocks, yhat, s, wt);
+    else launch_residual_kernel(static_cast<const double *>(X), N, M, ldX, y, w, t, partial, nblocks, yhat, s, wt);
     return hipGetLastError();
 }
 
@@ -476,20 +484,21 @@ hipError_t launch_residual(const double *X, int64_t N, int64_t M, int64_t ldX, c
 // in flight: 100 us for 205 MB at C3.
 // WT (sample weights): the residual of row i enters as wt[i] (y_i - yhat_i), i.e. g = Xo' W (y - yhat).
 // ---------------------------------------------------------------------------------------------------------------------
-template <bool WT>
-__global__ __launch_bounds__(256) void xtr_kernel(const double *__restrict__ X, int64_t N, int64_t M, int64_t ldX,
+template <class XT, bool WT>
+__global__ __launch_bounds__(256) void xtr_kernel(const XT *__restrict__ X, int64_t N, int64_t M, int64_t ldX,
                                                   const double *__restrict__ y, const double *__restrict__ yhat,
                                                   double *__restrict__ gpart, int R, const double *__restrict__ wt)
 {
     const int64_t m = blockIdx.x;
     const int r = blockIdx.y;
     const int64_t rows = (N + R - 1) / R, r0 = (int64_t)r * rows, r1 = (r0 + rows < N) ? r0 + rows : N;
-    const double *col = X + m * ldX;
+    const XT *col = X + m * ldX;
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     int64_t i = r0 + threadIdx.x;
     if (m < M) {
         for (; i + 768 < r1; i += 1024) {
-            double x[4], d[4];
+            XT x[4];
+            double d[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 x[u] = col[i + 256 * u];
@@ -497,10 +506,10 @@ __global__ __launch_bounds__(256) void xtr_kernel(const double *__restrict__ X, 
                 else d[u] = y[i + 256 * u] - yhat[i + 256 * u];
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) acc[u] = fma(x[u], d[u], acc[u]);
+            for (int u = 0; u < 4; ++u) acc[u] = fma((double)x[u], d[u], acc[u]);
         }
-        if constexpr (WT) for (; i < r1; i += 256) acc[0] = fma(col[i], wt[i] * (y[i] - yhat[i]), acc[0]);
-        else for (; i < r1; i += 256) acc[0] = fma(col[i], y[i] - yhat[i], acc[0]);
+        if constexpr (WT) for (; i < r1; i += 256) acc[0] = fma((double)col[i], wt[i] * (y[i] - yhat[i]), acc[0]);
+        else for (; i < r1; i += 256) acc[0] = fma((double)col[i], y[i] - yhat[i], acc[0]);
     } else {
         if constexpr (WT) for (; i < r1; i += 256) acc[0] += wt[i] * (y[i] - yhat[i]);
         else for (; i < r1; i += 256) acc[0] += y[i] - yhat[i];
@@ -523,12 +532,20 @@ int xtr_slices(int64_t N)
     return R;
 }
 
-hipError_t launch_xtr(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *yhat, double *gpart,
-                      hipStream_t s, const double *wt)
+template <class XT>
+static void launch_xtr_kernel(const XT *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *yhat, double *gpart,
+                              hipStream_t s, const double *wt)
 {
     const int R = xtr_slices(N);
-    if (wt) hipLaunchKernelGGL(xtr_kernel<true>, dim3((unsigned)(M + 1), (unsigned)R), dim3(256), 0, s, X, N, M, ldX, y, yhat, gpart, R, wt);
-    else hipLaunchKernelGGL(xtr_kernel<false>, dim3((unsigned)(M + 1), (unsigned)R), dim3(256), 0, s, X, N, M, ldX, y, yhat, gpart, R, wt);
+    if (wt) hipLaunchKernelGGL((xtr_kernel<XT, true>), dim3((unsigned)(M + 1), (unsigned)R), dim3(256), 0, s, X, N, M, ldX, y, yhat, gpart, R, wt);
+    else hipLaunchKernelGGL((xtr_kernel<XT, false>), dim3((unsigned)(M + 1), (unsigned)R), dim3(256), 0, s, X, N, M, ldX, y, yhat, gpart, R, wt);
+}
+
+hipError_t launch_xtr(const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *yhat, double *gpart,
+                      hipStream_t s, const double *wt, bool x_f32)
+{
+    if (x_f32) launch_xtr_kernel(static_cast<const float *>(X), N, M, ldX, y, yhat, gpart, s, wt);
+    else launch_xtr_kernel(static_cast<const double *>(X), N, M, ldX, y, yhat, gpart, s, wt);
     return hipGetLastError();
 }
 

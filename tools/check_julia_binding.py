@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""check_julia_binding.py — static check of the Julia patch in INTEGRATION.md against include/partls.h.
+"""check_julia_binding.py — static check of the Julia patch in INTEGRATION.md against include/partls.h and the include/partls_f32.h it
+includes.
 
 No Julia toolchain exists in this image, so the `ccall`s of the patch cannot be executed here.  What CAN be checked without
 one: every `ccall((:sym, _PARTLS_LIB), Ret, (ArgTypes...), args...)` in the fenced ```julia blocks names a symbol the header
@@ -23,6 +24,7 @@ JULIA_FOR_C = {
     "partls_frontier*": {"Ptr{Cvoid}"},
     "partls_frontier**": {"Ref{Ptr{Cvoid}}", "Ptr{Ptr{Cvoid}}"},
     "double*": {"Ptr{Float64}", "Ref{Float64}"},
+    "float*": {"Ptr{Float32}", "Ptr{Cfloat}"},
     "int64_t*": {"Ptr{Int64}", "Ref{Int64}"},
     "uint64_t*": {"Ptr{UInt64}", "Ref{UInt64}"},
     "int32_t*": {"Ptr{Int32}", "Ref{Int32}"},
@@ -69,6 +71,7 @@ def parse_header(path=None):
     text = open(path or os.path.join(ROOT, "include", "partls.h")).read()
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)        # preprocessor lines (include guards, #include, #define)
     text = re.sub(r"typedef\s+enum\s*\{.*?\}\s*\w+\s*;", " ", text, flags=re.S)
     protos = {}
     for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(partls_\w+)\s*\(([^;{}]*?)\)\s*;", text):
@@ -84,6 +87,16 @@ def parse_header(path=None):
                     raise ValueError(f"{name}: cannot parse parameter '{p}'")
                 ptypes.append((mm.group(1).strip() + mm.group(2)).strip())
         protos[name] = (ret, ptypes)
+    return protos
+
+
+F32_HEADER = os.path.join(ROOT, "include", "partls_f32.h")
+
+
+def parse_headers():
+    """the whole ABI: include/partls.h and the float32 entry points of include/partls_f32.h, which it includes"""
+    protos = parse_header()
+    protos.update(parse_header(F32_HEADER))
     return protos
 
 
@@ -117,7 +130,7 @@ def parse_ccalls(path=None):
 
 def check(header=None, integration=None, verbose=False):
     """Raises AssertionError on the first mismatch; returns the list of checked (symbol, line) pairs."""
-    protos, calls = parse_header(header), parse_ccalls(integration)
+    protos, calls = (parse_header(header) if header else parse_headers()), parse_ccalls(integration)
     assert calls, "no ccall found in INTEGRATION.md"
     done = []
     for sym, ret, types, nactual, line in calls:
