@@ -251,6 +251,27 @@ partls_status partls_alt_prepared(partls_ctx *ctx, double eps, int64_t T, const 
                                   double *alpha, double *beta, double *t, double *opt, int64_t *iters);
 partls_status partls_bnb_prepared(partls_ctx *ctx, double *alpha, double *beta, double *t, double *opt, int64_t *nopen);
 
+/* ---- fit(Alt) from R starting points in one batched call ----------------------------------------------
+ * On a context prepared like partls_alt_prepared's (any prepare: plain, weighted, float32, device-resident; else PARTLS_ERR_STATE).
+ * alpha0: (M+1) x R, column r = start r (leading dimension ld_alpha0 >= M+1); beta0: (K+1) x R (ld_beta0 >= K+1).  Start r runs
+ * exactly the iteration of partls_alt_prepared(ctx, eps, T, alpha0[:, r], beta0[:, r]) — up to the rounding of the alpha-step solver,
+ * which solves every alpha-step from the fresh tableau here — and stops on its own; all active starts advance together on the
+ * device.  A start's result does not depend on R, on its position or on the chunking (PARTLS_ALT_MS_CHUNK), bit for bit.
+ * Per start (each array optional, NULL to skip): alpha_all (M x R, ld_alpha_all >= M), beta_all (K x R, ld_beta_all >= K), t_all[R]
+ * (Alt.jl:119), opt_all[R] = the Gram-form loss of its last iteration, iters_all[R] = completed iterations, status_all[R]:
+ *   PARTLS_OK;  PARTLS_ERR_NONFINITE: NaN / Inf in its alpha0 / beta0 (checked on the host; the start takes no part);
+ *   PARTLS_ERR_NOT_CONVERGED: an alpha-step hit the pivot cap or its beta-step system is singular.  Rows of a failed start are NaN.
+ * The winner — the PARTLS_OK start with the smallest final loss, lowest index on an exact tie, *best_start — goes through the ending
+ * of partls_alt_prepared: alpha[M], beta[K], *t, *opt (from the data where that function takes it from the data), *iters, the
+ * data-space KKT check (partls_get_kkt_violation) and PARTLS_ERR_ILL_CONDITIONED with the outputs filled.  Without a PARTLS_OK start:
+ * PARTLS_ERR_NOT_CONVERGED, the per-start arrays filled, the winner's outputs NaN and *best_start = -1.
+ * PARTLS_ERR_BAD_ARG: eps <= 0, T < 1, R < 1, a NULL start or winner output, a leading dimension below its row count. */
+partls_status partls_alt_multistart(partls_ctx *ctx, double eps, int64_t T, int64_t R,
+                                    const double *alpha0, int64_t ld_alpha0, const double *beta0, int64_t ld_beta0,
+                                    double *alpha, double *beta, double *t, double *opt, int64_t *iters, int64_t *best_start,
+                                    double *alpha_all, int64_t ld_alpha_all, double *beta_all, int64_t ld_beta_all,
+                                    double *t_all, double *opt_all, int64_t *iters_all, int32_t *status_all);
+
 /* ---- fit(BnB, X, y, P; η)  — replaces BnB.jl:30-132 -------------------------------------------------------------------
  * Outputs as BnB.jl:36-40; *nopen = nodes bounded (search order differs from the reference's DFS, so it is not a
  * parity quantity). */

@@ -59,6 +59,8 @@ SYMBOLS = [
                                  _dp, _dp, _dp, _dp, _ip]),
     ("partls_alt_prepared", C.c_int, [C.c_void_p, C.c_double, _i64, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     ("partls_bnb_prepared", C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _ip]),
+    ("partls_alt_multistart", C.c_int, [C.c_void_p, C.c_double, _i64, _i64, _dp, _i64, _dp, _i64, _dp, _dp, _dp, _dp, _ip, _ip,
+                                        _dp, _i64, _dp, _i64, _dp, _dp, _ip, C.POINTER(C.c_int32)]),
     ("partls_bnb_bound", C.c_int, [C.c_void_p, _i64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _dp, C.POINTER(C.c_int32)]),
     ("partls_bnb_snap_begin", C.c_int, [C.c_void_p]),
     ("partls_bnb_bound_snap", C.c_int, [C.c_void_p, _i64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),

@@ -318,6 +318,32 @@ class Context:
                                               C.byref(o), C.byref(it)))
         return a, b, t.value, o.value, it.value
 
+    def alt_multistart(self, alpha0s, beta0s, eps=1e-6, T=100, raise_if_none=True):
+        """Alt from R starting points in one batched device call (partls_alt_multistart) on a context prepared with
+        OPT_FAITHFUL_INTERCEPT.  alpha0s: (R, M+1), beta0s: (R, K+1), row r = start r.  Returns (alpha, beta, t, opt, iters, best_start,
+        starts): the winner as alt_prepared returns a fit, and starts = dict of per-start arrays in start order — opt[R] (Gram-form loss
+        of the last iteration), iters[R], status[R] (OK, ERR_NONFINITE for a non-finite starting point, ERR_NOT_CONVERGED), alpha[R, M],
+        beta[R, K], t[R]; rows of a failed start are NaN.  When no start finished: PartlsError(ERR_NOT_CONVERGED), or with
+        raise_if_none=False the same tuple with NaN for the winner and best_start = -1."""
+        N, M, K = self._shape
+        a0 = np.ascontiguousarray(alpha0s, dtype=np.float64); b0 = np.ascontiguousarray(beta0s, dtype=np.float64)
+        if a0.ndim != 2 or b0.ndim != 2 or a0.shape[1] != M + 1 or b0.shape[1] != K + 1 or a0.shape[0] != b0.shape[0] or a0.shape[0] < 1:
+            raise ValueError("alt_multistart: alpha0s must be (R, %d) and beta0s (R, %d) with R >= 1, got %s and %s"
+                             % (M + 1, K + 1, a0.shape, b0.shape))
+        R = a0.shape[0]
+        a = np.zeros(M); b = np.zeros(K)
+        t = C.c_double(); o = C.c_double(); it = C.c_int64(); best = C.c_int64()
+        aa = np.zeros((R, M)); ba = np.zeros((R, K)); ta = np.zeros(R); oa = np.zeros(R)
+        ia = np.zeros(R, dtype=np.int64); sa = np.zeros(R, dtype=np.int32)
+        st = L.lib().partls_alt_multistart(self._h, float(eps), int(T), R, _dp(a0), M + 1, _dp(b0), K + 1, _dp(a), _dp(b), C.byref(t),
+                                           C.byref(o), C.byref(it), C.byref(best), _dp(aa), M, _dp(ba), K, _dp(ta), _dp(oa), _ip(ia),
+                                           sa.ctypes.data_as(C.POINTER(C.c_int32)))
+        if st == L.ERR_NOT_CONVERGED and not raise_if_none:
+            self.last_ill = False
+        else:
+            self._ill(st)
+        return a, b, t.value, o.value, it.value, best.value, dict(opt=oa, iters=ia, status=sa, alpha=aa, beta=ba, t=ta)
+
     def bnb_prepared(self):
         N, M, K = self._shape
         a = np.zeros(M); b = np.zeros(K)
@@ -703,6 +729,49 @@ def _weights(weights, N, who):
     return w
 
 
+def _alt_starts(alg, M, K, restarts, alpha0, beta0, rng):
+    """The starting points of a multistart fit(Alt) — (alpha0s[R, M+1], beta0s[R, K+1]) — or None for a single fit; every misuse is a
+    ValueError here, before any device work.  Drawn starts are R successive single draws (Alt.jl:65-66), so start 0 is the start of the
+    single fit with the same rng."""
+    nd = [np.ndim(v) for v in (alpha0, beta0) if v is not None]
+    if restarts is None and 2 not in nd:
+        return None
+    if alg is not Alt:
+        if restarts is not None:
+            raise ValueError("fit: restarts is an option of Alt")
+        return None                                           # Opt / BnB ignore alpha0 / beta0, as before
+    if restarts is not None:
+        if isinstance(restarts, bool) or not isinstance(restarts, (int, np.integer)) or int(restarts) < 1:
+            raise ValueError("fit: restarts must be an integer >= 1, got %r" % (restarts,))
+        if 1 in nd:
+            raise ValueError("fit: restarts with a single starting point (1-D alpha0 / beta0); pass (R, M+1) and (R, K+1) arrays")
+    if nd:
+        if alpha0 is None or beta0 is None or nd != [2, 2]:
+            raise ValueError("fit: explicit starts need alpha0 of shape (R, M+1) and beta0 of shape (R, K+1)")
+        a0 = np.ascontiguousarray(alpha0, dtype=np.float64)
+        b0 = np.ascontiguousarray(beta0, dtype=np.float64)
+        if a0.shape[0] < 1 or a0.shape != (a0.shape[0], M + 1) or b0.shape != (a0.shape[0], K + 1):
+            raise ValueError("fit: alpha0 must be (R, %d) and beta0 (R, %d), got %s and %s" % (M + 1, K + 1, a0.shape, b0.shape))
+        if restarts is not None and int(restarts) != a0.shape[0]:
+            raise ValueError("fit: restarts = %d but %d explicit starts" % (int(restarts), a0.shape[0]))
+        if not (np.all(np.isfinite(a0)) and np.all(np.isfinite(b0))):
+            raise ValueError("fit: the starting points must be finite")
+        return a0, b0
+    if rng is None:
+        gen = np.random.default_rng()
+    elif isinstance(rng, (int, np.integer)):
+        gen = np.random.default_rng(int(rng))
+    else:
+        gen = rng
+    R = int(restarts)
+    a0 = np.empty((R, M + 1))
+    b0 = np.empty((R, K + 1))
+    for r in range(R):
+        a0[r] = gen.random(M + 1)                             # Alt.jl:65
+        b0[r] = (gen.random(K + 1) - 0.5) * 10                # Alt.jl:66
+    return a0, b0
+
+
 class _Solutions:
     """returnAllSolutions (Opt.jl:99-101): element b is (opt_b, PartLSFitResult_b); models are rebuilt on demand from the context
     that holds the fitted problem.  They stay valid whatever is fitted afterwards, as in the reference: when a later fit has taken
@@ -778,7 +847,7 @@ class _Solutions:
 
 def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="nnls", returnAllSolutions=False, rng=None,
         alpha0=None, beta0=None, device=0, devices=None, faithful_intercept=False, generic_kernel=False, on_ill_conditioned="warn",
-        weights=None):
+        weights=None, restarts=None):
     """fit(::Type{Opt|Alt|BnB}, X, y, P; η, ...) -> (PartLSFitResult, None, Report)   [Opt.jl:73, Alt.jl:50, BnB.jl:30]
 
     η/eta: regularisation (default 0.0);  Alt: ϵ/eps (1e-6), T (100), rng (None | int seed | numpy Generator) or an
@@ -796,6 +865,13 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
     (NotImplementedError with devices=).  DESIGN.md §4.7.
     A float32 X is uploaded and read as float32 (half the transfer and half the device memory of float64); all arithmetic stays fp64
     and every result equals the fit of X.astype(float64) bit for bit.  With devices= it is widened on the host.  DESIGN.md §4.8.
+    Alt, restarts=R (int >= 1): Alt is a local method — R starting points run in one batched device call on one Gram matrix
+    (partls_alt_multistart) and the best one is returned.  The starts are R successive single draws from rng (start 0
+    is the start of fit(Alt, rng=seed)), or explicit: alpha0 of shape (R, M+1) with beta0 of shape (R, K+1) (restarts then None or R).
+    report.opt / .iters are the winner's, report.best_start its index, report.starts = Report(opt, iters, status, alpha, beta, t) with
+    one row per start (opt: the Gram-form loss of its last iteration; NaN rows where status != 0).  ValueError: 1-D starts together
+    with restarts, mismatched shapes, non-finite starts, restarts < 1, restarts with Opt / BnB.  PartlsError(ERR_NOT_CONVERGED) when
+    every start failed.
     """
     if alg not in (Opt, Alt, BnB):
         raise TypeError("fit: first argument must be Opt, Alt or BnB")
@@ -810,6 +886,7 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
     K = Pf.shape[1]
     wf = _weights(weights, N, "fit")
     staged = wf is not None or Xf.dtype == np.float32     # fits that exist as prepare + a staged call only
+    starts = _alt_starts(alg, M, K, restarts, alpha0, beta0, rng)     # None: a single fit, today's path
     if wf is not None and devices is not None:
         raise NotImplementedError("fit: sample weights are not supported on several devices (devices=)")
     ctx = default_context(device)
@@ -850,6 +927,10 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
         if returnAllSolutions:
             return model, None, report(ctx, solutions=_Solutions(ctx, allopt, Pout, (Xf, yf, Pf, eta_v, flags, device, wf)))
         return model, None, report(ctx, opt=opt, best_index=bi)
+    if alg is Alt and starts is not None:
+        ctx.opt_prepare(Xf, yf, Pf, eta_v, L.OPT_FAITHFUL_INTERCEPT, weights=wf)
+        a, b, t, o, it, best, per = ctx.alt_multistart(starts[0], starts[1], eps_v, int(T))
+        return PartLSFitResult(a, b, t, Pout), None, report(ctx, opt=o, iters=it, best_start=best, starts=Report(**per))
     if alg is Alt:
         if alpha0 is None or beta0 is None:
             if rng is None:

@@ -449,6 +449,31 @@ partls_status solve_nodes(partls_ctx *c, const std::vector<int8_t> &codes, size_
     return PARTLS_OK;
 }
 
+partls_status solve_nodes_device(partls_ctx *c, size_t cnt, const int8_t *code, double *obj2, double *sol,
+                                 unsigned long long *counters, int max_rounds)
+{
+    c->tab_valid = false;
+    c->coop_state_valid = false;
+    if (cnt == 0) return PARTLS_OK;
+    const int n = c->n, ld = n + 1;
+    const int grid = (int)std::min<size_t>(cnt, c->use_reg ? 2048 : 512);
+    PARTLS_HIP_CHECK(c->bestObj.ensure(sizeof(double) * 4096));
+    PARTLS_HIP_CHECK(c->bestPat.ensure(sizeof(int64_t) * 4096));
+    if (!c->use_reg) PARTLS_HIP_CHECK(c->scratch.ensure((size_t)grid * ld * ld * sizeof(double)));
+    else PARTLS_HIP_CHECK(c->scratch.ensure(64 * sizeof(double)));
+    SweepParams p{};
+    p.n = n; p.kbits = c->kbits;
+    p.mask = c->maskTabP;
+    p.scratch = c->scratch.as<double>();
+    p.g_begin = 0; p.g_end = (int64_t)cnt; p.chain_len = 1;
+    p.tol = c->tol; p.piv_eps = 1e-11; p.max_rounds = max_rounds;
+    p.best_obj = c->bestObj.as<double>(); p.best_pat = c->bestPat.as<int64_t>();
+    p.n_unconverged = counters; p.n_pivots = counters + 1; p.n_vetoes = counters + 2;
+    p.node_code = code; p.node_obj2 = obj2; p.node_sol = sol; p.node_ld = n;
+    PARTLS_HIP_CHECK(launch_any_sweep(c, p, grid));
+    return PARTLS_OK;
+}
+
 void unscale_solution(const partls_ctx *c, const double *sol, std::vector<double> &w)
 {
     const int M = (int)c->M;
@@ -892,7 +917,7 @@ using namespace partls;
 
 extern "C" {
 
-int partls_version(void) { return 102; }
+int partls_version(void) { return 103; }
 const char *partls_last_error(void) { return g_err; }
 
 int partls_device_count(void)
@@ -923,6 +948,8 @@ try {
     if (const char *e = getenv("PARTLS_GRAM_CR")) c->knobs.gram_cr = atoi(e);
     if (const char *e = getenv("PARTLS_COOP_ROWS")) c->knobs.coop_rows = atoi(e);
     if (const char *e = getenv("PARTLS_BIT_ORDER")) c->knobs.bit_order = !strcmp(e, "identity") ? 1 : (!strcmp(e, "calibrate") ? 2 : 0);
+    if (const char *e = getenv("PARTLS_ALT_MS_MAX_ROUNDS")) c->knobs.alt_ms_max_rounds = atoi(e);
+    if (const char *e = getenv("PARTLS_ALT_MS_CHUNK")) c->knobs.alt_ms_chunk = atoll(e);
     if (const char *e = getenv("PARTLS_KKT_TOL")) c->knobs.kkt_tol = atof(e);
     if (const char *e = getenv("PARTLS_NEAR_TIE_REL")) c->knobs.near_tie_rel = atof(e);
     if (const char *e = getenv("PARTLS_CAL_WB")) c->knobs.cal_wb = atof(e);
@@ -978,13 +1005,13 @@ void partls_destroy(partls_ctx *c)
                           &c->T0reg, &c->scratch, &c->bestObj, &c->bestPat, &c->counters, &c->allOpt, &c->wdev, &c->partial,
                           &c->yhatD, &c->gD, &c->nodeCode, &c->nodeSol, &c->nodeObj, &c->gridCtr,
                           &c->predX, &c->predY, &c->nodeTab, &c->nodeBasic, &c->altA, &c->altGA, &c->altHg,
-                          &c->nodePiv, &c->maskInt, &c->allOptRef, &c->bnbIn, &c->bnbOut, &c->altGersh, &c->mdlRows, &c->mdlOut, &c->mdlCtr,
+                          &c->nodePiv, &c->maskInt, &c->allOptRef, &c->bnbIn, &c->bnbOut, &c->altGersh, &c->amsState, &c->amsWork, &c->mdlRows, &c->mdlOut, &c->mdlCtr,
                           &c->cvG, &c->cvBatch, &c->cvEta, &c->ownW, &c->ownS, &c->wPart};
         for (DevBuf *b : bufs) b->release();
         for (void *q : c->bnbChunks) (void)hipFree(q);
         c->bnbChunks.clear();
         c->hG.release();
-        c->bnbHostIn.release(); c->bnbHostOut.release();
+        c->bnbHostIn.release(); c->bnbHostOut.release(); c->amsHostIn.release(); c->amsHostOut.release();
         c->hScale.release(); c->hPart.release(); c->hGpart.release(); c->sweepOut.release(); c->nodeOut.release(); c->exportSol.release(); c->mdlStage.release();
         c->cvHost.release(); c->cvHostG.release();
         for (int i = 0; i < 8; ++i) { if (c->upPin[i]) (void)hipHostFree(c->upPin[i]); if (c->upEvent[i]) (void)hipEventDestroy(c->upEvent[i]); }

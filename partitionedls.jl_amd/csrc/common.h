@@ -174,6 +174,9 @@ hipError_t launch_gersh(const double *Tfull, int n, double *out, hipStream_t s);
 // beta-step system of fit(Alt): Hg[k * (Kp + 1) + k2] = H[k][k2] (k2 < Kp), g[k] (k2 = Kp); GA is (M + 1) x Kp scratch
 hipError_t launch_alt_beta_system(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, const double *a, int Kp,
                                   double *GA, double *Hg, hipStream_t s);
+// ... of `cnt` starts at once: start j reads a + slot[j] (M + 1), writes GA + j (M + 1) Kp and Hg + j Kp (Kp + 1)   (misc.hip)
+hipError_t launch_alt_beta_system_batch(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, const double *a, int Kp,
+                                        const int *slot, int cnt, double *GA, double *Hg, hipStream_t s);
 // wt (optional, device, N): sample weights -> sum_i wt[i] (...)^2
 hipError_t launch_residual(const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w, double t,
                            double *partial, int nblocks, double *yhat, hipStream_t s, const double *wt = nullptr, bool x_f32 = false);

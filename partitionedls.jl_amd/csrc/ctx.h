@@ -76,6 +76,8 @@ struct partls_knobs {
     bool alt_trace = false;      // PARTLS_ALT_TRACE
     bool alt_always_check = false; // PARTLS_ALT_ALWAYS_CHECK: fit(Alt) verifies its last iteration against the data even when Gershgorin certifies the Gram form (tests)
     bool print_stamps = false;   // PARTLS_PRINT_STAMPS (diagnostic build only)
+    int alt_ms_max_rounds = 0;   // PARTLS_ALT_MS_MAX_ROUNDS: pivot cap of the alpha-steps of partls_alt_multistart only (0: 20 (n + 1), as everywhere); tests
+    long long alt_ms_chunk = 0;  // PARTLS_ALT_MS_CHUNK: starts per chunk of partls_alt_multistart (0: what fits 256 MB of per-start scratch)
     double kkt_tol = 1e-12;      // PARTLS_KKT_TOL: data-space KKT violation of the winner (units of ||x_m|| ||y||) above which fit(Opt) / fit(BnB) report
                                  // PARTLS_ERR_ILL_CONDITIONED instead of PARTLS_OK (see kkt_says_ill_conditioned, api.hip)
     double near_tie_rel = 1e-13; // PARTLS_NEAR_TIE_REL (tests): width of the near-tie window of the sweep, in units of y'y on the objective^2
@@ -118,7 +120,7 @@ struct partls_ctx {
     int ldg = 0, chunks = 0;
     partls::DevBuf slab, G, maskAugD /* + maskTabP, permP: one upload */, scale, Tfull, T0reg, scratch, bestObj, bestSol /* [workgroups][n]: solution of every workgroup's best pattern (register kernels) */, bestPat, counters, allOpt,
         wdev, partial, yhatD, gD, nodeCode, nodeSol, nodeObj, predX, predY, gridCtr, nodeTab, nodeBasic, altA, altGA, altHg,
-        nodePiv, maskInt, allOptRef, bnbIn, bnbOut, altGersh;
+        nodePiv, maskInt, allOptRef, bnbIn, bnbOut, altGersh, amsState, amsWork;   // ams*: partls_alt_multistart (alt_multi.hip)
     // BnB: tableau snapshots of open nodes (solvers.hip: SnapshotPool), kept across fits; host staging of a node batch
     std::vector<void *> bnbChunks;
     size_t bnbSlotBytes = 0, bnbMaxSlots = 0;
@@ -135,6 +137,7 @@ struct partls_ctx {
     partls::PinnedDoubles mdlStage;
     // called between the Gram build and the tableau preparation (partls_fit_opt_multi: the Gram products of the row blocks are summed)
     std::function<partls_status(partls_ctx *)> gram_hook;
+    partls::PinnedDoubles amsHostIn, amsHostOut;   // ... of an iteration of partls_alt_multistart: the active list up, the records back
     partls::PinnedDoubles bnbHostIn, bnbHostOut;   // page-locked staging of a node batch (8-byte words): the two copies of a round cost ~10 us each instead of ~25 pageable
     // staged upload of a host X (api.hip: upload_matrix): 4 copier threads x 2 page-locked buffers, one stream each; wall time and bytes of
     // the last one (0 when the inputs were device-resident)
@@ -218,6 +221,16 @@ void install_sweep_result(partls_ctx *c, const double *sweep_out, int grid, bool
 // scaled solutions in tableau order (0 for nonbasic); obj2: objective^2 from the tableau corner.
 partls_status solve_nodes(partls_ctx *c, const std::vector<int8_t> &codes, size_t cnt, std::vector<double> &sols,
                           std::vector<double> &obj2, unsigned long long *unconv, bool resume = false, bool want_tab = false);
+// The same for codes that are already on the device, with everything left there (partls_alt_multistart): enqueues the node-mode
+// sweep of `cnt` nodes on c->stream and returns.  code: cnt x n; obj2: cnt; sol: cnt x n; counters: 4 words (unconverged, pivots,
+// vetoes, -), zeroed by the caller.  Grid and scratch as solve_nodes; never the cooperative kernel; always from the fresh tableau.
+partls_status solve_nodes_device(partls_ctx *c, size_t cnt, const int8_t *code, double *obj2, double *sol,
+                                 unsigned long long *counters, int max_rounds);
+// the ending of fit(Alt) (solvers.hip)
+partls_status alt_finish(partls_ctx *c, const std::vector<double> &a, const std::vector<double> &b, const std::vector<double> &wv,
+                         const std::vector<int8_t> &vcode_last, const std::vector<double> &hdiag, const std::vector<double> &gersh,
+                         double optval, int64_t iters_done, unsigned long long unconv_total,
+                         double *alpha, double *beta, double *t, double *opt, int64_t *iters);
 // node codes of one Opt sign pattern (Opt.jl:28-29): sign of the multiplier sum_k P[m,k] s_k of every tableau variable
 void opt_codes(const partls_ctx *c, uint64_t pattern, std::vector<int8_t> &codes);
 

@@ -337,10 +337,11 @@ static constexpr int ALT_WAVES = 16;
 
 __global__ __launch_bounds__(64 * ALT_WAVES) void alt_ga_kernel(const double *__restrict__ G, int ldg, int M, double eta,
                                                                const uint64_t *__restrict__ mask_aug, const double *__restrict__ a, int Kp,
-                                                               double *__restrict__ GA)
+                                                               double *__restrict__ GA, const int *__restrict__ slot)
 {
     __shared__ double part[ALT_WAVES][64];
     const int m = blockIdx.x, k2 = threadIdx.x & 63, wave = threadIdx.x >> 6, Mp = M + 1;
+    if (slot) { a += (size_t)slot[blockIdx.y] * Mp; GA += (size_t)blockIdx.y * Mp * Kp; }      // start blockIdx.y of a batch (see below)
     // branch-free and unrolled: the loads of a step are wave-uniform (row m of G, alpha and the mask of variable m2), eight steps
     // are in flight together; a lane adds the product when variable m2 belongs to ITS group
     const int wu = __builtin_amdgcn_readfirstlane(wave);
@@ -371,9 +372,11 @@ __global__ __launch_bounds__(64 * ALT_WAVES) void alt_ga_kernel(const double *__
 
 __global__ __launch_bounds__(64 * ALT_WAVES) void alt_h_kernel(const double *__restrict__ G, int ldg, int M, double eta,
                                                               const uint64_t *__restrict__ mask_aug, const double *__restrict__ a, int Kp,
-                                                              const double *__restrict__ GA, double *__restrict__ Hg)
+                                                              const double *__restrict__ GA, double *__restrict__ Hg,
+                                                              const int *__restrict__ slot)
 {
     __shared__ double part[ALT_WAVES][65];
+    if (slot) { a += (size_t)slot[blockIdx.y] * (M + 1); GA += (size_t)blockIdx.y * (M + 1) * Kp; Hg += (size_t)blockIdx.y * Kp * (Kp + 1); }
     const int k = blockIdx.x, k2 = threadIdx.x & 63, wave = threadIdx.x >> 6, Mp = M + 1;     // column Kp of row k holds g[k] (Kp <= 64: lane Kp <= 64 ... handled by lane 63 when Kp == 64)
     // lanes 0..Kp-1: H[k][k2]; the g column is computed by lane Kp when Kp < 64, else by a second pass of lane 0
     auto term = [&](int m, int col) { return col < Kp ? GA[(size_t)m * Kp + col] : reg_entry(G, ldg, M, eta, mask_aug, m, M + 1); };
@@ -404,11 +407,29 @@ __global__ __launch_bounds__(64 * ALT_WAVES) void alt_h_kernel(const double *__r
 hipError_t launch_alt_beta_system(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, const double *a, int Kp,
                                   double *GA, double *Hg, hipStream_t s)
 {
-    hipLaunchKernelGGL(alt_ga_kernel, dim3(M + 1), dim3(64 * ALT_WAVES), 0, s, G, ldg, M, eta, mask_aug, a, Kp, GA);
+    hipLaunchKernelGGL(alt_ga_kernel, dim3(M + 1), dim3(64 * ALT_WAVES), 0, s, G, ldg, M, eta, mask_aug, a, Kp, GA, (const int *)nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(alt_h_kernel, dim3(Kp), dim3(64 * ALT_WAVES), 0, s, G, ldg, M, eta, mask_aug, a, Kp, GA, Hg);
+    hipLaunchKernelGGL(alt_h_kernel, dim3(Kp), dim3(64 * ALT_WAVES), 0, s, G, ldg, M, eta, mask_aug, a, Kp, GA, Hg, (const int *)nullptr);
     return hipGetLastError();
+}
+
+// The same for `cnt` starts at once (partls_alt_multistart): start j of the batch = blockIdx.y reads alpha from a + slot[j] (M + 1) and
+// writes GA + j (M + 1) Kp and Hg + j Kp (Kp + 1).  Every start is summed exactly as a single one is: same workgroup shape, same orders.
+hipError_t launch_alt_beta_system_batch(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, const double *a, int Kp,
+                                        const int *slot, int cnt, double *GA, double *Hg, hipStream_t s)
+{
+    for (int j0 = 0; j0 < cnt; j0 += 65535) {                     // gridDim.y <= 65535
+        const int nb = cnt - j0 < 65535 ? cnt - j0 : 65535;
+        double *ga = GA + (size_t)j0 * (M + 1) * Kp, *hg = Hg + (size_t)j0 * Kp * (Kp + 1);
+        hipLaunchKernelGGL(alt_ga_kernel, dim3(M + 1, nb), dim3(64 * ALT_WAVES), 0, s, G, ldg, M, eta, mask_aug, a, Kp, ga, slot + j0);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(alt_h_kernel, dim3(Kp, nb), dim3(64 * ALT_WAVES), 0, s, G, ldg, M, eta, mask_aug, a, Kp, ga, hg, slot + j0);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -198,6 +198,90 @@ partls_status bnb_bound_batch(partls_ctx *c, size_t cnt, const uint64_t *pat, co
 
 }  // namespace
 
+// The ending of fit(Alt), shared by partls_alt_prepared and partls_alt_multistart (alt_multi.hip): the iterate (a, b) after `iters_done`
+// completed iterations with Gram-form loss `optval`; wv / vcode_last / hdiag describe the LAST iteration (the alpha-step's raw solution
+// over [features, intercept], its constraint codes, the diagonal of the beta-step system); gersh = launch_gersh's radii.
+partls_status partls::alt_finish(partls_ctx *c, const std::vector<double> &a, const std::vector<double> &b, const std::vector<double> &wv,
+                                 const std::vector<int8_t> &vcode_last, const std::vector<double> &hdiag, const std::vector<double> &gersh,
+                                 double optval, int64_t iters_done, unsigned long long unconv_total,
+                                 double *alpha, double *beta, double *t, double *opt, int64_t *iters)
+{
+    partls_status st = PARTLS_OK;
+    const int64_t M = c->M, K = c->K, i = iters_done + 1;
+    const int Mp = (int)M + 1, Kp = (int)K + 1, Y = (int)M + 1;
+    std::vector<double> w((size_t)Mp, 0.0);
+    for (int m = 0; m < Mp; ++m) {                          // w = alpha o f,  f_m = sum_k Po[m,k] beta_k   (Alt.jl:80)
+        double v = 0.0;
+        for (int k = 0; k < Kp; ++k) if ((c->mask_aug[(size_t)m] >> k) & 1ULL) v += b[(size_t)k];
+        w[(size_t)m] = a[(size_t)m] * v;
+    }
+    // Final objective and the data-space check of the last iteration (round 4).  Both solves of an iteration work on the Gram form — the
+    // alpha-step on the tableau, the beta-step on the K' x K' normal equations A'GA beta = A'c, whose condition is the SQUARE of that of the
+    // reference's QR solve (Alt.jl:110) — so the model is verified against the DATA before it is returned, as fit(Opt) / fit(BnB) verify
+    // theirs: one pass over X gives the loss (Alt.jl:112-113: no Gram cancellation) and g = Xo'(yo - Xo w) at the final w, and
+    //   * the beta-step is stationary iff A'g = 0: |sum_m A_mk g_m| in units of ||Xo A_k|| ||y|| per group;
+    //   * the alpha-step's KKT conditions (sign-constrained LS with the multipliers of the previous beta, Alt.jl:80-90) hold at ITS
+    //     solution w_alpha, which differs from the final w by the beta-step only: g_alpha = g + B (w - w_alpha) is carried over with the
+    //     host Gram copy (error ~eps |B| |w - w_alpha|: exact at convergence, ~1e-13 when the beta-step still moves w by O(1)) instead
+    //     of a second pass over X.
+    // Above PARTLS_KKT_TOL the call returns PARTLS_ERR_ILL_CONDITIONED with the model in the outputs (INTEGRATION.md reroutes that
+    // status to the stock Julia body).
+    // WHEN the pass is needed.  It costs two reads of X (2.2 ms of a 6.9 ms fit at C4), and on well-conditioned data it can only confirm
+    // what perturbation theory already guarantees: the solves work on G~ (unit diagonal), and normal-equation solutions carry a relative
+    // error of at most ~n eps cond(G~).  Gershgorin gives a RIGOROUS bound from the matrix itself: with r = max_i sum_{j != i} |G~_ij|,
+    // lambda_min >= 1 - r and lambda_max <= 1 + r.  For r <= 0.75 (cond <= 7: n eps cond < 1e-12 up to n = 1023, the threshold of the check
+    // itself) the fit is certified without touching X again — Gaussian-like designs (C4: r = 0.41).  Anything else — correlated features,
+    // uncentred columns against the intercept, eta-coupled groups — takes the pass.  PARTLS_ALT_ALWAYS_CHECK forces it (tests).
+    double radius = 0.0;
+    for (int v = 0; v < c->n; ++v) radius = std::max(radius, gersh[(size_t)v]);
+    const bool certified = i > 1 && radius <= 0.75 && std::isfinite(radius) && !c->knobs.alt_always_check;
+    double dopt = optval;
+    std::vector<double> g;
+    c->last_kkt = 0.0;
+    c->last_min_loo = 0.0;
+    int worst = -1;
+    const char *which = "";
+    if (certified) {
+        // the loss of the last iteration, beta'H beta - 2 g'beta + y'y from the K' x K' system, carries an absolute error of ~eps * y'y
+        // (cancellation against y'y): only a near-interpolating fit (the reference's toy: opt = 0) needs the objective from the data
+        if (!(optval * optval > 1e-6 * h_reg(c, Y, Y))) { st = data_objective(c, w, &dopt); if (st != PARTLS_OK) return st; }
+    } else {
+        st = data_objective(c, w, &dopt, &g);
+        if (st != PARTLS_OK) return st;
+    }
+    if (!certified && i > 1 && unconv_total == 0) {          // at least one iteration ran
+        const double yy = h_reg(c, Y, Y), ynorm = std::sqrt(yy > 0.0 ? yy : 0.0);
+        for (int k = 0; k < Kp; ++k) {
+            double s = 0.0;
+            for (int m = 0; m < Mp; ++m) if ((c->mask_aug[(size_t)m] >> k) & 1ULL) s += a[(size_t)m] * g[(size_t)m];
+            const double nrm = std::sqrt(hdiag[(size_t)k] > 0.0 ? hdiag[(size_t)k] : 0.0) * (ynorm > 0.0 ? ynorm : 1.0);
+            const double v = nrm > 0.0 ? std::fabs(s) / nrm : 0.0;
+            if (v > c->last_kkt) { c->last_kkt = v; worst = k; which = "beta-step, group"; }
+        }
+        std::vector<double> ga(g);
+        for (int j = 0; j < Mp; ++j) {
+            const double dj = w[(size_t)j] - wv[(size_t)j];
+            if (dj == 0.0) continue;
+            for (int m = 0; m < Mp; ++m) ga[(size_t)m] += h_reg(c, m, j) * dj;
+        }
+        int wa = -1;
+        const double va = kkt_violation_data(c, wv, ga, vcode_last, &wa);
+        if (va > c->last_kkt) { c->last_kkt = va; worst = wa; which = "alpha-step, variable"; }
+    }
+    for (int64_t m = 0; m < M; ++m) alpha[m] = a[(size_t)m];
+    for (int64_t k = 0; k < K; ++k) beta[k] = b[(size_t)k];
+    *t = b[(size_t)K] * a[(size_t)M];                    // Alt.jl:119
+    *opt = dopt;
+    if (iters) *iters = i - 1;
+    if (unconv_total) { set_error("partls_fit_alt: an alpha-step hit the pivot cap"); return PARTLS_ERR_NOT_CONVERGED; }
+    if (kkt_says_ill_conditioned(c)) {
+        set_error("partls_fit_alt: the last iteration's solves do not hold in data space (violation %.2e of ||x|| ||y|| at %s %d, tolerance %.1e): "
+                  "X is too ill-conditioned for the fp64 Gram form; the outputs hold the Gram-form iterate", c->last_kkt, which, worst, c->knobs.kkt_tol);
+        return PARTLS_ERR_ILL_CONDITIONED;
+    }
+    return PARTLS_OK;
+}
+
 extern "C" {
 
 partls_status partls_fit_alt(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
@@ -222,7 +306,7 @@ try {
     partls_status st = PARTLS_OK;
     const int64_t M = c->M, K = c->K;
     const int Mp = (int)M + 1, Kp = (int)K + 1, Y = (int)M + 1;
-    std::vector<double> a(alpha0, alpha0 + Mp), b(beta0, beta0 + Kp), w((size_t)Mp, 0.0), f((size_t)Mp, 0.0), sols, obj2;
+    std::vector<double> a(alpha0, alpha0 + Mp), b(beta0, beta0 + Kp), f((size_t)Mp, 0.0), sols, obj2;
     // Po as lists: groups of every variable (features, then the intercept in its own group K; PartitionedLS.jl:76-81)
     std::vector<std::vector<int>> groups_of((size_t)Mp);
     for (int m = 0; m < Mp; ++m)
@@ -230,7 +314,6 @@ try {
     auto feature_mul = [&]() {                            // f_m = sum_k Po[m,k] β_k   (Alt.jl:80)
         for (int m = 0; m < Mp; ++m) { double v = 0.0; for (int k : groups_of[(size_t)m]) v += b[(size_t)k]; f[(size_t)m] = v; }
     };
-    auto w_from = [&]() { feature_mul(); for (int m = 0; m < Mp; ++m) w[(size_t)m] = a[(size_t)m] * f[(size_t)m]; };
     std::vector<int8_t> codes((size_t)c->n);
     // Gershgorin radii of the scaled Gram block (one tiny kernel now, read back with the first alpha-step's results): decides after the
     // loop whether the last iteration must be verified against the data (see there)
@@ -309,72 +392,7 @@ try {
         if (c->knobs.alt_trace) fprintf(stderr, "[alt] iter %d: alpha-step %.3f ms (%llu pivots, %llu blocks), rest %.3f ms\n", (int)i, std::chrono::duration<double, std::milli>(tt1 - tt0).count(), apiv, ablk, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tt1).count());
         ++i;
     }
-    w_from();
-    // Final objective and the data-space check of the last iteration (round 4).  Both solves of an iteration work on the Gram form — the
-    // alpha-step on the tableau, the beta-step on the K' x K' normal equations A'GA beta = A'c, whose condition is the SQUARE of that of the
-    // reference's QR solve (Alt.jl:110) — so the model is verified against the DATA before it is returned, as fit(Opt) / fit(BnB) verify
-    // theirs: one pass over X gives the loss (Alt.jl:112-113: no Gram cancellation) and g = Xo'(yo - Xo w) at the final w, and
-    //   * the beta-step is stationary iff A'g = 0: |sum_m A_mk g_m| in units of ||Xo A_k|| ||y|| per group;
-    //   * the alpha-step's KKT conditions (sign-constrained LS with the multipliers of the previous beta, Alt.jl:80-90) hold at ITS
-    //     solution w_alpha, which differs from the final w by the beta-step only: g_alpha = g + B (w - w_alpha) is carried over with the
-    //     host Gram copy (error ~eps |B| |w - w_alpha|: exact at convergence, ~1e-13 when the beta-step still moves w by O(1)) instead
-    //     of a second pass over X.
-    // Above PARTLS_KKT_TOL the call returns PARTLS_ERR_ILL_CONDITIONED with the model in the outputs (INTEGRATION.md reroutes that
-    // status to the stock Julia body).
-    // WHEN the pass is needed.  It costs two reads of X (2.2 ms of a 6.9 ms fit at C4), and on well-conditioned data it can only confirm
-    // what perturbation theory already guarantees: the solves work on G~ (unit diagonal), and normal-equation solutions carry a relative
-    // error of at most ~n eps cond(G~).  Gershgorin gives a RIGOROUS bound from the matrix itself: with r = max_i sum_{j != i} |G~_ij|,
-    // lambda_min >= 1 - r and lambda_max <= 1 + r.  For r <= 0.75 (cond <= 7: n eps cond < 1e-12 up to n = 1023, the threshold of the check
-    // itself) the fit is certified without touching X again — Gaussian-like designs (C4: r = 0.41).  Anything else — correlated features,
-    // uncentred columns against the intercept, eta-coupled groups — takes the pass.  PARTLS_ALT_ALWAYS_CHECK forces it (tests).
-    double radius = 0.0;
-    for (int v = 0; v < c->n; ++v) radius = std::max(radius, gersh[(size_t)v]);
-    const bool certified = i > 1 && radius <= 0.75 && std::isfinite(radius) && !c->knobs.alt_always_check;
-    double dopt = optval;
-    std::vector<double> g;
-    c->last_kkt = 0.0;
-    c->last_min_loo = 0.0;
-    int worst = -1;
-    const char *which = "";
-    if (certified) {
-        // the loss of the last iteration, beta'H beta - 2 g'beta + y'y from the K' x K' system, carries an absolute error of ~eps * y'y
-        // (cancellation against y'y): only a near-interpolating fit (the reference's toy: opt = 0) needs the objective from the data
-        if (!(optval * optval > 1e-6 * h_reg(c, Y, Y))) { st = data_objective(c, w, &dopt); if (st != PARTLS_OK) return st; }
-    } else {
-        st = data_objective(c, w, &dopt, &g);
-        if (st != PARTLS_OK) return st;
-    }
-    if (!certified && i > 1 && unconv_total == 0) {          // at least one iteration ran
-        const double yy = h_reg(c, Y, Y), ynorm = std::sqrt(yy > 0.0 ? yy : 0.0);
-        for (int k = 0; k < Kp; ++k) {
-            double s = 0.0;
-            for (int m = 0; m < Mp; ++m) if ((c->mask_aug[(size_t)m] >> k) & 1ULL) s += a[(size_t)m] * g[(size_t)m];
-            const double nrm = std::sqrt(hdiag[(size_t)k] > 0.0 ? hdiag[(size_t)k] : 0.0) * (ynorm > 0.0 ? ynorm : 1.0);
-            const double v = nrm > 0.0 ? std::fabs(s) / nrm : 0.0;
-            if (v > c->last_kkt) { c->last_kkt = v; worst = k; which = "beta-step, group"; }
-        }
-        std::vector<double> ga(g);
-        for (int j = 0; j < Mp; ++j) {
-            const double dj = w[(size_t)j] - wv[(size_t)j];
-            if (dj == 0.0) continue;
-            for (int m = 0; m < Mp; ++m) ga[(size_t)m] += h_reg(c, m, j) * dj;
-        }
-        int wa = -1;
-        const double va = kkt_violation_data(c, wv, ga, vcode_last, &wa);
-        if (va > c->last_kkt) { c->last_kkt = va; worst = wa; which = "alpha-step, variable"; }
-    }
-    for (int64_t m = 0; m < M; ++m) alpha[m] = a[(size_t)m];
-    for (int64_t k = 0; k < K; ++k) beta[k] = b[(size_t)k];
-    *t = b[(size_t)K] * a[(size_t)M];                    // Alt.jl:119
-    *opt = dopt;
-    if (iters) *iters = i - 1;
-    if (unconv_total) { set_error("partls_fit_alt: an alpha-step hit the pivot cap"); return PARTLS_ERR_NOT_CONVERGED; }
-    if (kkt_says_ill_conditioned(c)) {
-        set_error("partls_fit_alt: the last iteration's solves do not hold in data space (violation %.2e of ||x|| ||y|| at %s %d, tolerance %.1e): "
-                  "X is too ill-conditioned for the fp64 Gram form; the outputs hold the Gram-form iterate", c->last_kkt, which, worst, c->knobs.kkt_tol);
-        return PARTLS_ERR_ILL_CONDITIONED;
-    }
-    return PARTLS_OK;
+    return alt_finish(c, a, b, wv, vcode_last, hdiag, gersh, optval, i - 1, unconv_total, alpha, beta, t, opt, iters);
 }
 catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
 catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
