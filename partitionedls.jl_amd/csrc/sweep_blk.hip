@@ -49,6 +49,12 @@ static constexpr int MB = 8;                    // pivots per block (a tile colu
 #ifndef PARTLS_EXPORT_BIG
 #define PARTLS_EXPORT_BIG 1      // the 512-thread kernel leaves the solution of every workgroup's best pattern behind (round 4: C3 finish 0.54 -> 0.16 ms, sweep 49.1 -> 48.6)
 #endif
+#ifndef PARTLS_MERGED_SCAN
+#define PARTLS_MERGED_SCAN 1     // 0: every pattern starts with a KKT scan of its own (A/B of the two round-5 pieces apart: profiles/r05_ab_c3.txt)
+#endif
+#ifndef PARTLS_LANE_MASKS
+#define PARTLS_LANE_MASKS 1      // 0: a tile column's masks come from LDS
+#endif
 #ifndef PARTLS_MB_BIG
 #define PARTLS_MB_BIG 8
 #endif
@@ -108,9 +114,9 @@ struct LdsImageT {
     double Z[MB * CWX];
     double U[2 * (MB + 64)];
     double Dinv[MB + 64];
-    unsigned long long s_inf[16];
+    unsigned long long s_inf[32];
     unsigned long long s_bas[16];
-    unsigned s_sum[16];
+    unsigned long long s_sum[16];
     int s_veto[2];
     double s_best[4];
     unsigned char s_rbit[64];
@@ -124,9 +130,9 @@ struct LdsImage {
     double Z[MBB * CWMAX];                     // [MB][CW] pivot column s as of its own step
     double U[2 * (MBB + 64)];                  // [2][MB+64] pivot-row entries of the current column (+ per-lane dummies)
     double Dinv[MBB + 64];                     // 1/d_s
-    unsigned long long s_inf[16];              // [2][8] violator mask of the scan
+    unsigned long long s_inf[32];              // [2][2][8] violator masks of the scan: [0] of the pattern being solved, [1] ("s_inf2") of the NEXT pattern of the chain on the same rhs column
     unsigned long long s_bas[16];              // [2][8] basis mask of the scan
-    unsigned s_sum[16];                        // [2][8] per-wave summary of s_inf: count | tile bits << 8
+    unsigned long long s_sum[16];              // [2][8] per-wave summaries, count | tile bits << 8: of s_inf in the low word, of s_inf2 in the high word (one read)
     int s_veto[2];                             // first vetoed step of a block (by block parity)
     // per-thread state that is touched once per pattern lives in LDS, not in VGPRs (the register file holds the tableau):
     double s_best[4];                          // running minimum: obj^2, pattern (as bits); runner-up: obj^2, pattern
@@ -288,13 +294,20 @@ __device__ __forceinline__ int panel_block(double *P, double *Z, double *U, doub
 // row g - g_begin of p.node_sol (leading dimension p.node_ld) and sqrt(obj2) in p.node_obj2[g - g_begin]; a pattern that hit the pivot
 // cap leaves NaN in both.  The row follows from the chain and pattern counters alone (no live register beyond the default build's); the
 // export instantiation writes no best_sol.  A separate instantiation: the default ones keep their code.
-template <int T, int H, bool NODE, int W = 2, bool MODELS = false>
+template <int T, int H, bool NODE, int W = 2, bool MODELS = false, bool BATCH = false>
 __device__ __forceinline__ void sweep_body(const SweepParams &p)
 {
     using L = Half<T, H, W>;
     constexpr int RS = L::RS, CW = L::CW, RHSPOS = 16 * RS, NW = (T + 3) / 4;      // NW: 64-bit mask words that can be non-empty
     constexpr int THREADS = L::NT;                                                  // shadows the namespace constant
     constexpr int MB = W == 1 ? blk::MB : MBB;                                      // pivots per block of this kernel (shadows the namespace constant)
+    // MERGED: the merged KKT scan (below); LANE_MASKS: the round's tile-column masks live in a VGPR (see the exchange).  Both only where the
+    // allocation takes them without new spills (profiles/r05_sweep_resource_usage.txt): with the merged scan the chain kernel of T = 18 spills
+    // 25 VGPRs instead of 22 and the batch instantiations spill at T = 7, 8 and from 17 on, with the masks the chain kernel of T = 17 spills 2
+    // — those keep the one-scan-per-decision loop and the LDS reads, and with them their former allocation.
+    static_assert(!(NODE && MODELS), "node mode exports no per-pattern models (finish_pattern's capped flag is chain mode's)");
+    constexpr bool MERGED = PARTLS_MERGED_SCAN && !NODE && !BATCH && T <= 17;
+    constexpr bool LANE_MASKS = PARTLS_LANE_MASKS && !BATCH && T <= 16;
     static_assert(W == 2 || RHSPOS < 256, "the 256-thread kernel needs every panel row position (and the rhs row) below 256");
     auto &lds_image = *image_of<W>();
     const int tid = threadIdx.x, t8 = tid & 255, a = t8 & 15, b = t8 >> 4, lane = tid & 63, wave = tid >> 6;
@@ -304,14 +317,15 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
     // link-time constant addresses into the LDS image
     double *const Pbase = lds_image.Pbase, *const Z = lds_image.Z, *const U = lds_image.U, *const Dinv = lds_image.Dinv;
     unsigned long long *const s_inf = lds_image.s_inf, *const s_bas = lds_image.s_bas, *const s_vmask = lds_image.s_vmask;
-    unsigned *const s_sum = lds_image.s_sum;
+    unsigned long long *const s_sum = lds_image.s_sum;
     int *const s_veto = lds_image.s_veto;
     double *const s_best = lds_image.s_best;
     for (int i = tid; i < 2 * MB * CW; i += THREADS) Pbase[i] = 0.0;                   // padding rows are never gathered
     for (int i = tid; i < MB * CW; i += THREADS) Z[i] = 0.0;
     if (tid < 2 * (MB + 64)) U[tid] = 0.0;
     if (tid < MB + 64) Dinv[tid] = 0.0;
-    if (tid < 16) { s_inf[tid] = 0; s_bas[tid] = 0; s_sum[tid] = 0; }
+    if (tid < 32) s_inf[tid] = 0;                                                      // both sets
+    if (tid < 16) { s_bas[tid] = 0; s_sum[tid] = 0; }
     if (tid < 2) s_veto[tid] = NO_VETO;
     if (tid == 0) {
         s_best[0] = __builtin_inf(); reinterpret_cast<long long *>(s_best)[1] = -1;
@@ -372,24 +386,77 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
         }
         STAMP(6);
 
-        for (int gi = 0; gi < glen; ++gi) {
+        // ONE loop over the exchange rounds of the whole chain.  In chain mode every KKT scan evaluates two predicates on the same rhs column
+        // and basis: `bad` under the signs f of the pattern being solved and `nxt` under the signs fn of its successor in the chain, with no
+        // column rejected — what the successor's first scan would see, since nothing touches the tableau between the scan that finds a
+        // pattern solved and the first scan of the next one.  The confirming scan of pattern g therefore IS the first scan of g + 1: its
+        // second summary and mask words (s_inf set 1) start the exchange of g + 1 directly, one scan (two ballots' worth of LDS words, a
+        // barrier and a reduction) less per pattern, the same violators round for round.  Node mode takes its codes per node from global
+        // memory and keeps one scan per decision (!MERGED, as do the instantiations listed at MERGED above): there the second predicate is
+        // not compiled and every pattern starts with a scan — the round loop ends with the pattern and the loop around it starts the next one
+        // (with MERGED that outer loop runs once; with a node's bookkeeping and the next node's codes inside the round loop the node-mode
+        // kernel spills 421 VGPRs at T = 16).
+        // bookkeeping of a finished pattern (converged, or capped: it hit the pivot cap); touches no tile slot
+        auto finish_pattern = [&](int gi, [[maybe_unused]] bool capped) {
             const uint64_t g = (uint64_t)g0 + (unsigned)gi;
-            uint64_t pat = g ^ (g >> 1);
-            const uint64_t vmask = s_vmask[tid < 16 * T ? tid : 0] & (has_var ? ~0ULL : 0ULL);
+            const uint64_t pat = NODE ? (uint64_t)chain : g ^ (g >> 1);
+            // patterns are ranked on objective^2 (the tableau corner; sqrt is monotone): one sqrt per workgroup instead of one per
+            // pattern, unless every pattern's objective is wanted
+            const double obj2 = corner > 0.0 ? corner : 0.0;
+            // bookkeeping of the finished pattern: by the last thread — its wave owns no panel row and has slack, wave 0 has none
+            if constexpr (NODE) {                                     // chain of nodes (bit-order calibration): pivots, blocks, scans so far
+                if (p.node_piv && tid == 0) {
+                    unsigned *o = p.node_piv + 3 * ((size_t)chain * clen + gi);
+                    o[0] = npiv; o[1] = bc; o[2] = sc;
+                }
+            }
+            if (p.all_opt && tid == THREADS - 1) p.all_opt[pat] = sqrt(obj2);
+            if constexpr (MODELS) {
+                const size_t row = (size_t)chain * (size_t)clen + (size_t)gi;
+                if (has_var) p.node_sol[row * p.node_ld + tid] = capped ? __builtin_nan("") : (basic ? q : 0.0);
+                if (tid == THREADS - 1) p.node_obj2[row] = capped ? __builtin_nan("") : sqrt(obj2);
+            }
+            if constexpr (!NODE && !MODELS && (W == 1 || (PARTLS_EXPORT_BIG && T <= EXPORT_MAXT))) {
+                // (round 3: 256-thread kernel only — in the 512-thread kernel the two extra live registers moved 8 spills and cost 1.8 % of the
+                // C3 sweep.  Round 4: the spills turned out to be hoisted address offsets and are gone; -DPARTLS_EXPORT_BIG=1 measures it again)
+                // the workgroup's best pattern so far leaves its solution behind (rhs column of the basic variables, as node mode's
+                // node_sol): the host takes the winner's from here instead of solving that pattern again from the empty basis.  Every
+                // thread decides for itself on the replicated corner; on exact objective ties the FIRST pattern's solution stays (the
+                // host checks the solution against the winning pattern's signs and re-solves if they disagree).
+                if (p.best_sol && obj2 < mybest) {
+                    mybest = obj2;
+                    if (has_var) p.best_sol[(size_t)blockIdx.x * p.node_ld + tid] = basic ? q : 0.0;
+                }
+            }
+            // the ranking of rank_pattern (sweep_rules.h) on objective^2 held in LDS, in this kernel's own form: it has no `best_pat >= 0` guard
+            if (tid == THREADS - 1) {                                // lexicographic (objective, pattern) minimum: argmin's first-index rule
+                const double bo = s_best[0];
+                const long long bp = reinterpret_cast<long long *>(s_best)[1];
+                if (obj2 < bo || (obj2 == bo && ref_index_less(pat, (unsigned long long)bp, lds_image.s_rbit))) {
+                    s_best[2] = bo; reinterpret_cast<long long *>(s_best)[3] = bp;             // the old minimum becomes the runner-up
+                    s_best[0] = obj2; reinterpret_cast<long long *>(s_best)[1] = (long long)pat;
+                } else if (obj2 < s_best[2]) { s_best[2] = obj2; reinterpret_cast<long long *>(s_best)[3] = (long long)pat; }
+            }
+        };
+        int gi = 0;
+        for (;;) {                                                    // !MERGED: one turn per pattern; MERGED: one turn
+            [[maybe_unused]] const unsigned nunconv0 = nunconv;           // !MERGED: did this pattern hit the pivot cap?
             bool isfree = false;
-            int f;
-            if constexpr (NODE) {                                   // node mode: chain index = node index, per-variable codes
-                pat = (uint64_t)chain;
+            int f = 0;
+            [[maybe_unused]] int fn = 0;                                  // chain mode: the sign of this variable under pattern gi + 1 (the last pattern of a chain: f)
+            if constexpr (NODE) {                                         // node mode: chain index = node index, per-variable codes
                 const int code = has_var ? (int)p.node_code[((size_t)chain * clen + gi) * p.node_ld + tid] : 0;   // a chain of nodes: warm start
                 isfree = code == 2;
                 f = isfree ? 0 : code;
             } else {
-                f = sign_of_var(vmask, pat);
+                const uint64_t vmask = s_vmask[tid < 16 * T ? tid : 0] & (has_var ? ~0ULL : 0ULL);
+                const uint64_t g = (uint64_t)g0 + (unsigned)gi, gn = g + 1;                 // MERGED: gi = 0 here
+                f = sign_of_var(vmask, g ^ (g >> 1));
+                if constexpr (MERGED) fn = glen > 1 ? sign_of_var(vmask, gn ^ (gn >> 1)) : f;
             }
             blocked = false;
             int ninf_best = n + 1, patience = 3, rounds = 0;
-            bool progress = false;                                    // did the previous round change the basis?
-            [[maybe_unused]] const unsigned nunconv0 = nunconv;      // MODELS: did this pattern hit the pivot cap?
+            bool progress = false;                                        // did the previous round change the basis?
             for (;;) {
                 // ---- KKT scan of the rhs column (registers) ------------------------------------------------------------
                 // a column rejected as dependent is only dependent on the basis it was tested against (Lawson–Hanson
@@ -399,11 +466,16 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                 const int par = sc & 1;
                 ++sc;
                 bool bad = false;
+                [[maybe_unused]] bool nxt = false;
                 if (has_var) {                                            // kkt_violates<NODE> (sweep_rules.h), written out: see the exchange rule below
                     const double fq = q * (double)(f > 1 ? 1 : (f < -1 ? -1 : f));     // sign(f) * q  (|f| = 2: feature of two groups)
                     if (NODE && isfree) bad = !basic && !blocked && (fabs(q) > p.tol);     // free: stationarity only
                     else if (basic) bad = (f == 0) || (fq < -p.tol);
                     else bad = (fq > p.tol) && !blocked;
+                    if constexpr (MERGED) {                               // the same test under the next pattern's signs; a pattern starts with no rejections
+                        const double fqn = q * (double)(fn > 1 ? 1 : (fn < -1 ? -1 : fn));
+                        nxt = basic ? ((fn == 0) || (fqn < -p.tol)) : (fqn > p.tol);
+                    }
                 }
                 const unsigned long long bb = __ballot(bad), bs = __ballot(basic);
                 // every wave condenses ITS mask word before the barrier (count in bits 0..7, one bit per 16-variable tile column in
@@ -412,29 +484,75 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
 #pragma unroll
                 for (int sub = 0; sub < 4; ++sub)
                     if ((bb >> (16 * sub)) & 0xFFFFull) summ |= 0x100u << sub;
-                if (lane == 0 && wave < nwords) { s_inf[par * 8 + wave] = bb; s_bas[par * 8 + wave] = bs; s_sum[par * 8 + wave] = summ; }
+                if constexpr (!MERGED) {
+                    if (lane == 0 && wave < nwords) { s_inf[par * 8 + wave] = bb; s_bas[par * 8 + wave] = bs; s_sum[par * 8 + wave] = summ; }
+                } else {
+                    const unsigned long long bn = __ballot(nxt);
+                    unsigned summ2 = (unsigned)__popcll(bn);
+#pragma unroll
+                    for (int sub = 0; sub < 4; ++sub)
+                        if ((bn >> (16 * sub)) & 0xFFFFull) summ2 |= 0x100u << sub;
+                    if (lane == 0 && wave < nwords) {
+                        s_inf[par * 8 + wave] = bb; s_inf[16 + par * 8 + wave] = bn; s_bas[par * 8 + wave] = bs;
+                        s_sum[par * 8 + wave] = ((unsigned long long)summ2 << 32) | summ;
+                    }
+                }
                 STAMP(9);
                 __syncthreads();
                 STAMP(10);
                 int count = 0;
                 unsigned tiles = 0;
+                [[maybe_unused]] int count2 = 0;
+                [[maybe_unused]] unsigned tiles2 = 0;
 #pragma unroll
                 for (int w = 0; w < NW; ++w) {
-                    const unsigned sw = (unsigned)__builtin_amdgcn_readfirstlane((int)s_sum[par * 8 + w]);    // 0 for w >= nwords
+                    const unsigned long long sw2 = s_sum[par * 8 + w];                                       // 0 for w >= nwords
+                    const unsigned sw = (unsigned)__builtin_amdgcn_readfirstlane((int)sw2);
                     count += (int)(sw & 0xFFu);
                     tiles |= (sw >> 8) << (4 * w);
+                    if constexpr (MERGED) {
+                        const unsigned sn = (unsigned)__builtin_amdgcn_readfirstlane((int)(sw2 >> 32));
+                        count2 += (int)(sn & 0xFFu);
+                        tiles2 |= (sn >> 8) << (4 * w);
+                    }
                 }
                 STAMP(0);
                 // ExchangeRule::next (sweep_rules.h), written out: through the helpers the same rules compile to the same VGPR count but
                 // move 2-4 spilled SGPRs, and this kernel is tuned to the register.  Keep both in step with sweep_rules.h by hand.
-                if (count == 0) break;
-                bool all;
-                if (count < ninf_best) { ninf_best = count; patience = 3; all = true; }
-                else if (patience > 0) { --patience; all = true; }
-                else all = false;                                     // backup rule: only the largest violator
-                if (++rounds > p.max_rounds) { ++nunconv; break; }
+                // Everything below up to the exchange is decided from count / count2 / rounds / gi: LDS words and kernel arguments that are the
+                // same for all threads of both halves (the barrier invariant above batch_select).
+                int soff = par * 8;                                       // the mask words this round exchanges: s_inf set 0 (+ 16: set 1)
+                bool all = true;
+                bool done = count == 0;
+                if (!done) {
+                    if (count < ninf_best) { ninf_best = count; patience = 3; }
+                    else if (patience > 0) --patience;
+                    else all = false;                                     // backup rule: only the largest violator
+                    if (++rounds > p.max_rounds) { ++nunconv; done = true; }
+                }
+                if (done) {
+                    // ---- pattern gi is finished (converged, or the pivot cap: count != 0) ---------------------------------------
+                    if constexpr (!MERGED) break;                         // the turn of the outer loop ends
+                    finish_pattern(gi, count != 0);
+                    // ---- ... and the next one starts: from this very scan where it can ---------------------------------------------
+                    if (++gi >= glen) break;
+                    blocked = false;
+                    ninf_best = n + 1; patience = 3; rounds = 0;
+                    if constexpr (MERGED) {
+                        const uint64_t vmask = s_vmask[tid < 16 * T ? tid : 0] & (has_var ? ~0ULL : 0ULL);
+                        const uint64_t gn = (uint64_t)g0 + (unsigned)gi + 1;
+                        f = fn;
+                        fn = gi + 1 < glen ? sign_of_var(vmask, gn ^ (gn >> 1)) : f;
+                        // count2 == 0: the new pattern is optimal as it stands — the next scan records it (and looks one pattern further)
+                        if (count2 == 0 || p.max_rounds < 1) continue;
+                        ninf_best = count2; rounds = 1;                   // ExchangeRule::next of a first round: count2 < n + 1, 1 <= max_rounds
+                        all = true;
+                        tiles = tiles2;
+                        soff += 16;
+                    }
+                }
                 int single_k = -1;
-                if (!all) {                                           // rare: the largest violator, from the mask words themselves
+                if (!all) {                                               // rare: the largest violator, from the mask words themselves
 #pragma unroll
                     for (int w = 0; w < NW; ++w) {
                         unsigned long long ww = s_inf[par * 8 + w];
@@ -445,14 +563,30 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                     tiles = 1u << (single_k >> 4);
                 }
                 tiles = (unsigned)__builtin_amdgcn_readfirstlane((int)tiles);
+                // lane t of every wave keeps the violator and basis masks of tile column t (16 + 16 bits) for the round: one v_readlane per
+                // tile column instead of two LDS reads, a wait and 64-bit shifts (LANE_MASKS: up to T = 16 — with the extra live register the
+                // chain-mode kernel of T = 17 would spill 2 VGPRs, so from there on the masks come from LDS per tile column)
+                [[maybe_unused]] unsigned tmask = 0;
+                if constexpr (LANE_MASKS) {
+                    const int tl = lane < T ? lane : 0, wl = tl >> 2, shl = 16 * (tl & 3);
+                    tmask = (unsigned)((s_inf[soff + wl] >> shl) & 0xFFFFull) | ((unsigned)((s_bas[par * 8 + wl] >> shl) & 0xFFFFull) << 16);
+                }
 
                 while (tiles) {
                     const int kappa = __builtin_ctz(tiles);
-                    const int wsel = kappa >> 2, sh = 16 * (kappa & 3);
-                    unsigned pmall = (unsigned)((s_inf[par * 8 + wsel] >> sh) & 0xFFFFull);
-                    if (!all) pmall = 1u << (single_k & 15);
-                    const unsigned basm = (unsigned)__builtin_amdgcn_readfirstlane((int)((s_bas[par * 8 + wsel] >> sh) & 0xFFFFull));
-                    pmall = (unsigned)__builtin_amdgcn_readfirstlane((int)pmall);
+                    unsigned pmall, basm;
+                    if constexpr (LANE_MASKS) {
+                        const unsigned tm = (unsigned)__builtin_amdgcn_readlane((int)tmask, kappa);
+                        pmall = tm & 0xFFFFu;
+                        if (!all) pmall = 1u << (single_k & 15);
+                        basm = tm >> 16;
+                    } else {
+                        const int wsel = kappa >> 2, sh = 16 * (kappa & 3);
+                        pmall = (unsigned)((s_inf[soff + wsel] >> sh) & 0xFFFFull);
+                        if (!all) pmall = 1u << (single_k & 15);
+                        basm = (unsigned)__builtin_amdgcn_readfirstlane((int)((s_bas[par * 8 + wsel] >> sh) & 0xFFFFull));
+                        pmall = (unsigned)__builtin_amdgcn_readfirstlane((int)pmall);
+                    }
                     while (pmall) {
                         // ---- block: the lowest <= MB violators of tile column kappa -------------------------------------
                         unsigned rest = 0;
@@ -561,44 +695,10 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                     tiles &= tiles - 1;
                 }
             }
-            // patterns are ranked on objective^2 (the tableau corner; sqrt is monotone): one sqrt per workgroup instead of one per
-            // pattern, unless every pattern's objective is wanted
-            const double obj2 = corner > 0.0 ? corner : 0.0;
-            // bookkeeping of the finished pattern: by the last thread — its wave owns no panel row and has slack, wave 0 has none
-            if constexpr (NODE) {                                     // chain of nodes (bit-order calibration): pivots, blocks, scans so far
-                if (p.node_piv && tid == 0) {
-                    unsigned *o = p.node_piv + 3 * ((size_t)chain * clen + gi);
-                    o[0] = npiv; o[1] = bc; o[2] = sc;
-                }
-            }
-            if (p.all_opt && tid == THREADS - 1) p.all_opt[pat] = sqrt(obj2);
-            if constexpr (MODELS) {
-                const size_t row = (size_t)chain * (size_t)clen + (size_t)gi;
-                const bool capped = nunconv != nunconv0;
-                if (has_var) p.node_sol[row * p.node_ld + tid] = capped ? __builtin_nan("") : (basic ? q : 0.0);
-                if (tid == THREADS - 1) p.node_obj2[row] = capped ? __builtin_nan("") : sqrt(obj2);
-            }
-            if constexpr (!NODE && !MODELS && (W == 1 || (PARTLS_EXPORT_BIG && T <= EXPORT_MAXT))) {
-                // (round 3: 256-thread kernel only — in the 512-thread kernel the two extra live registers moved 8 spills and cost 1.8 % of the
-                // C3 sweep.  Round 4: the spills turned out to be hoisted address offsets and are gone; -DPARTLS_EXPORT_BIG=1 measures it again)
-                // the workgroup's best pattern so far leaves its solution behind (rhs column of the basic variables, as node mode's
-                // node_sol): the host takes the winner's from here instead of solving that pattern again from the empty basis.  Every
-                // thread decides for itself on the replicated corner; on exact objective ties the FIRST pattern's solution stays (the
-                // host checks the solution against the winning pattern's signs and re-solves if they disagree).
-                if (p.best_sol && obj2 < mybest) {
-                    mybest = obj2;
-                    if (has_var) p.best_sol[(size_t)blockIdx.x * p.node_ld + tid] = basic ? q : 0.0;
-                }
-            }
-            // the ranking of rank_pattern (sweep_rules.h) on objective^2 held in LDS, in this kernel's own form: it has no `best_pat >= 0` guard
-            if (tid == THREADS - 1) {                                // lexicographic (objective, pattern) minimum: argmin's first-index rule
-                const double bo = s_best[0];
-                const long long bp = reinterpret_cast<long long *>(s_best)[1];
-                if (obj2 < bo || (obj2 == bo && ref_index_less(pat, (unsigned long long)bp, lds_image.s_rbit))) {
-                    s_best[2] = bo; reinterpret_cast<long long *>(s_best)[3] = bp;             // the old minimum becomes the runner-up
-                    s_best[0] = obj2; reinterpret_cast<long long *>(s_best)[1] = (long long)pat;
-                } else if (obj2 < s_best[2]) { s_best[2] = obj2; reinterpret_cast<long long *>(s_best)[3] = (long long)pat; }
-            }
+            if constexpr (!MERGED) {
+                finish_pattern(gi, nunconv != nunconv0);
+                if (++gi >= glen) break;
+            } else break;
         }
         if constexpr (NODE) {
             if (has_var) p.node_sol[(size_t)chain * p.node_ld + tid] = basic ? q : 0.0;
@@ -661,8 +761,8 @@ __global__ __launch_bounds__(THREADS, 2) void sweep_blk_kernel(SweepParams p)
 {
     if constexpr (BATCH) batch_select(p);
     const int half = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
-    if (half == 0) sweep_body<T, 0, NODE, 2, MODELS>(p);
-    else sweep_body<T, 1, NODE, 2, MODELS>(p);
+    if (half == 0) sweep_body<T, 0, NODE, 2, MODELS, BATCH>(p);
+    else sweep_body<T, 1, NODE, 2, MODELS, BATCH>(p);
 }
 
 #ifndef PARTLS_SMALL_OCC
@@ -672,7 +772,7 @@ template <int T, bool NODE, bool MODELS = false, bool BATCH = false>
 __global__ __launch_bounds__(256, PARTLS_SMALL_OCC(T)) void sweep_small_kernel(SweepParams p)
 {
     if constexpr (BATCH) batch_select(p);
-    sweep_body<T, 0, NODE, 1, MODELS>(p);
+    sweep_body<T, 0, NODE, 1, MODELS, BATCH>(p);
 }
 
 // Tfull ((n+1)^2) -> tile-cyclic initial state: [slot = tri(gamma) + rho][256 = a + 16 b], then q0[16 T], then the corner.

@@ -10,11 +10,13 @@
 // Only sweep_generic.hip, the tests' reference, is built from all of these definitions.  The three production kernels take sign_of_var,
 // rcp_newton, readlane_f64 (and coop: gj_panel.h's violator_list) from here but keep HAND-WRITTEN COPIES of the decision rules, because
 // through the helpers their device code moves (profiles/sweep_rules_resource_usage.txt), each marked "(sweep_rules.h), written out":
-//   sweep_blk.hip   sweep_body: the KKT scan, the round's exchange, and the ranking at the end of a pattern (on objective^2 in LDS,
-//                   its own form);
+//   sweep_blk.hip   sweep_body: the KKT scan — where the merged scan is compiled (MERGED) written out TWICE in the same scan, once under the pattern's signs and once
+//                   under its successor's with no column rejected (the merged scan: `bad` and `nxt`) —, the round's exchange, with the
+//                   first round of a pattern that starts from its predecessor's confirming scan set up next to it (ninf_best = count2,
+//                   rounds = 1), and the ranking at the end of a pattern (finish_pattern, on objective^2 in LDS, its own form);
 //   sweep_lazy.hip  sweep_lazy_kernel: the KKT scan, the exchange and the ranking;
 //   sweep_coop.hip  sweep_coop_kernel: the KKT scan and the exchange (a single solve ranks nothing).
-// A change to kkt_violates, ExchangeRule or rank_pattern is made here AND in those eight places.
+// A change to kkt_violates, ExchangeRule or rank_pattern is made here AND in those places (ten with the merged scan's two).
 #pragma once
 #include "common.h"
 
