@@ -187,7 +187,7 @@ class Context:
     def bit_order(self):
         """(gbit, flip_cost): gbit[k] = Gray-index bit that carries group k in this context's sweeps; flip_cost[k] = measured
         pivots per flip of group k (-1 where the calibration did not run).  Runs the calibration if no sweep has yet."""
-        kb = self.num_patterns().bit_length() - 1
+        kb = max(self.num_patterns().bit_length() - 1, 0)   # beyond 40 sign bits num_patterns() is 0: the library raises ERR_UNSUPPORTED
         g = np.zeros(kb, dtype=np.int64)
         fc = np.zeros(kb)
         _check(L.lib().partls_opt_bit_order(self._h, _ip(g), _dp(fc)))

@@ -210,11 +210,20 @@ __device__ __forceinline__ void gj_apply(double *T, int ld_, int row0_, int row1
         }
     }
     __syncthreads();                                                       // all generic updates of this workgroup are issued
+    // Rows first, then a barrier, then columns.  An entry (k_a, k_b) with both indices pivots of the block belongs to row k_a AND to
+    // column k_b, and the panel holds two values for it that agree only to round-off (fl(z_a / d) z_b against fl(z_b / d) z_a in
+    // gj_panel_eliminate).  Written in one loop by different threads without a barrier between them, either could land last, so two
+    // launches on the same data could differ in the last bit (found by partls_opt_models against partls_opt_sweep on the eager
+    // kernel: tests/test_gpu_wide_patterns.py).  Now the column's value stays, always.
+    for (int j = 0; j < m; ++j) {
+        const int k = __builtin_amdgcn_readfirstlane(ks[j]);
+        if (k >= row0 && k < row1)
+            for (int c = (TRI ? k : 0) + tid; c < ld; c += NT) T[(size_t)k * ld + c] = Pn[j * ld + c];     // row k (TRI: columns >= k)
+    }
+    __syncthreads();
     for (int j = 0; j < m; ++j) {
         const int k = __builtin_amdgcn_readfirstlane(ks[j]);
         for (int i = row0 + tid; i < (TRI ? (k + 1 < row1 ? k + 1 : row1) : row1); i += NT) T[(size_t)i * ld + k] = Pn[j * ld + i];   // column k (TRI: rows <= k)
-        if (k >= row0 && k < row1)
-            for (int c = (TRI ? k : 0) + tid; c < ld; c += NT) T[(size_t)k * ld + c] = Pn[j * ld + c];     // row k (TRI: columns >= k)
     }
     __syncthreads();
 }
