@@ -3,7 +3,7 @@
 // Every start runs the iteration of partls_alt_prepared (solvers.hip) — alpha-step, checkalpha, renormalisation, beta-step, loss,
 // stop rule — but all active starts of a chunk advance together and their state stays in HBM:
 //   codes    f = Po beta, sign(f) in tableau order straight into the node-code buffer               (alt_multi_codes_kernel)
-//   alpha    the sweep kernels in node mode, one node per start, from the fresh tableau            (solve_nodes_device, api.hip)
+//   alpha    the sweep kernels in node mode, one node per start, from the fresh tableau            (solve_nodes_device, sweep_setup.hip)
 //   alpha    unscale, alpha = max(w / f, 0), checkalpha, renormalise, beta o= sum alpha            (alt_multi_alpha_kernel)
 //   beta     H = A'G_reg A, g = A'c per start                                                      (launch_alt_beta_system_batch, misc.hip)
 //   beta     Gaussian elimination in LDS, loss, stop rule, one record per start                    (alt_multi_beta_kernel)
@@ -416,7 +416,6 @@ try {
     *best_start = best;
     return alt_finish(c, wa, wb, wwv, wvc, whd, gersh, best_opt, best_iters, 0, alpha, beta, t, opt, iters);
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <new>
 #include <vector>
 #include <string>
 #include "../../include/partls.h"
@@ -20,6 +21,10 @@ void set_error(const char *fmt, ...);
             return PARTLS_ERR_HIP;                                                                  \
         }                                                                                           \
     } while (0)
+// the ending of every C-ABI entry (a function-try-block): `try { ... } PARTLS_ABI_GUARD`
+#define PARTLS_ABI_GUARD                                                                                                          \
+    catch (const std::bad_alloc &) { ::partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }                      \
+    catch (...) { ::partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // sweep parameters (shared by the register-resident and the global-memory tableau kernels)

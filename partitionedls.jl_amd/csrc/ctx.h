@@ -1,4 +1,6 @@
-// ctx.h — the context behind the opaque partls_ctx handle and the host helpers shared by api.hip and solvers.hip.
+// ctx.h — the context behind the opaque partls_ctx handle, the owning buffer types it is made of, and the host helpers the host
+// translation units share: api.hip (create / destroy / predict / getters), prepare.hip, sweep_setup.hip, opt.hip, refine.hip,
+// solvers.hip, multi.hip and the host halves of cv.hip and alt_multi.hip.
 #pragma once
 #include "common.h"
 #include <functional>
@@ -6,9 +8,20 @@
 
 namespace partls {
 
-struct DevBuf {
+// Every device / page-locked allocation of a context lives in one of the owning types below: non-copyable, released by the
+// destructor, so `delete c` frees whatever partls_ctx declares and no list has to be kept in step with it.  runtime_gone() (api.hip)
+// is true while partls_destroy drops a context whose HIP runtime no longer answers: release() then only forgets the handle.
+bool runtime_gone();
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy &) = delete;
+    NoCopy &operator=(const NoCopy &) = delete;
+};
+
+struct DevBuf : NoCopy {
     void *p = nullptr;
     size_t bytes = 0;
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t b)
     {
         if (b <= bytes && p) return hipSuccess;
@@ -17,14 +30,25 @@ struct DevBuf {
         if (e == hipSuccess) bytes = b;
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    void release() { if (p && !runtime_gone()) (void)hipFree(p); p = nullptr; bytes = 0; }
     template <class T> T *as() const { return static_cast<T *>(p); }
 };
 
+// device chunks allocated one by one and freed together (the snapshot pool of the BnB search, solvers.hip)
+struct DevChunks : NoCopy {
+    std::vector<void *> v;
+    ~DevChunks() { release(); }
+    void release() { if (!runtime_gone()) for (void *q : v) (void)hipFree(q); v.clear(); }
+    size_t size() const { return v.size(); }
+    void push_back(void *q) { v.push_back(q); }
+    void *operator[](size_t i) const { return v[i]; }
+};
+
 // page-locked host array of doubles (device -> host copies at full PCIe rate instead of through a staging buffer)
-struct PinnedDoubles {
+struct PinnedDoubles : NoCopy {
     double *p = nullptr;
     size_t cap = 0, n = 0, cap_prev = 0;
+    ~PinnedDoubles() { release(); }
     hipError_t resize(size_t count)
     {
         if (count > cap) {
@@ -40,10 +64,38 @@ struct PinnedDoubles {
         n = count;
         return hipSuccess;
     }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = n = 0; }
+    void release() { if (p && !runtime_gone()) (void)hipHostFree(p); p = nullptr; cap = n = 0; }
     double *data() const { return p; }
     size_t size() const { return n; }
     double &operator[](size_t i) const { return p[i]; }
+};
+
+// page-locked host array of exactly `count` elements; reads like the plain pointer it owns
+template <class T> struct PinnedArray : NoCopy {
+    T *p = nullptr;
+    ~PinnedArray() { release(); }
+    hipError_t alloc(size_t count)
+    {
+        release();
+        const hipError_t e = hipHostMalloc((void **)&p, count * sizeof(T), hipHostMallocDefault);
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    void release() { if (p && !runtime_gone()) (void)hipHostFree(p); p = nullptr; }
+    operator T *() const { return p; }
+};
+
+// staged upload of a host X (prepare.hip: upload_matrix): 4 copier threads x 2 page-locked buffers, one stream each
+struct UploadStaging : NoCopy {
+    char *pin[8] = {};
+    hipStream_t stream[4] = {};
+    hipEvent_t event[8] = {};
+    ~UploadStaging()
+    {
+        if (runtime_gone()) return;
+        for (int i = 0; i < 8; ++i) { if (pin[i]) (void)hipHostFree(pin[i]); if (event[i]) (void)hipEventDestroy(event[i]); }
+        for (int t = 0; t < 4; ++t) if (stream[t]) (void)hipStreamDestroy(stream[t]);
+    }
 };
 
 }  // namespace partls
@@ -79,7 +131,7 @@ struct partls_knobs {
     int alt_ms_max_rounds = 0;   // PARTLS_ALT_MS_MAX_ROUNDS: pivot cap of the alpha-steps of partls_alt_multistart only (0: 20 (n + 1), as everywhere); tests
     long long alt_ms_chunk = 0;  // PARTLS_ALT_MS_CHUNK: starts per chunk of partls_alt_multistart (0: what fits 256 MB of per-start scratch)
     double kkt_tol = 1e-12;      // PARTLS_KKT_TOL: data-space KKT violation of the winner (units of ||x_m|| ||y||) above which fit(Opt) / fit(BnB) report
-                                 // PARTLS_ERR_ILL_CONDITIONED instead of PARTLS_OK (see kkt_says_ill_conditioned, api.hip)
+                                 // PARTLS_ERR_ILL_CONDITIONED instead of PARTLS_OK (see kkt_says_ill_conditioned, refine.hip)
     double near_tie_rel = 1e-13; // PARTLS_NEAR_TIE_REL (tests): width of the near-tie window of the sweep, in units of y'y on the objective^2
     double cal_wb = 1.0, cal_ws = 1.0;  // PARTLS_CAL_WB / PARTLS_CAL_WS: multipliers of the block / scan weights of the bit-order cost model (experiments)
     bool cv_serial = false;      // PARTLS_CV_SERIAL: partls_cv_opt sweeps its problems one after another through partls_opt_sweep (A/B tests, timing)
@@ -89,6 +141,7 @@ struct partls_knobs {
 
 struct partls_ctx {
     int device = 0;
+    int ncu = 256;                                 // compute units of the device (256 when the attribute cannot be read); set by partls_create
     partls_knobs knobs;
     hipStream_t stream = nullptr;
     hipEvent_t ev0[PARTLS_T_COUNT] = {}, ev1[PARTLS_T_COUNT] = {};
@@ -122,12 +175,12 @@ struct partls_ctx {
         wdev, partial, yhatD, gD, nodeCode, nodeSol, nodeObj, predX, predY, gridCtr, nodeTab, nodeBasic, altA, altGA, altHg,
         nodePiv, maskInt, allOptRef, bnbIn, bnbOut, altGersh, amsState, amsWork;   // ams*: partls_alt_multistart (alt_multi.hip)
     // BnB: tableau snapshots of open nodes (solvers.hip: SnapshotPool), kept across fits; host staging of a node batch
-    std::vector<void *> bnbChunks;
+    partls::DevChunks bnbChunks;
     size_t bnbSlotBytes = 0, bnbMaxSlots = 0;
     int bnbChunkSlots = 512;
     std::vector<int> bnbFree, bnbRefs;             // free slots; reference counts of the in-library search (the ABI's host keeps its own)
     // rows of X sharded over several devices (partls_fit_opt_multi): the contexts that hold the OTHER row blocks of the problem this
-    // context is prepared for; every pass over the data (data_pass, api.hip) then covers them too.  Cleared by every prepare.
+    // context is prepared for; every pass over the data (data_pass, refine.hip) then covers them too.  Cleared by every prepare.
     std::vector<partls_ctx *> peers;
     partls::PinnedDoubles hPart, hGpart;           // host staging of a data pass (page-locked like every device -> host destination of a fit: a pageable
                                                    // one costs 17-30 us of runtime staging per copy and blocks the caller — a third of a C2-sized fit's host time)
@@ -139,11 +192,8 @@ struct partls_ctx {
     std::function<partls_status(partls_ctx *)> gram_hook;
     partls::PinnedDoubles amsHostIn, amsHostOut;   // ... of an iteration of partls_alt_multistart: the active list up, the records back
     partls::PinnedDoubles bnbHostIn, bnbHostOut;   // page-locked staging of a node batch (8-byte words): the two copies of a round cost ~10 us each instead of ~25 pageable
-    // staged upload of a host X (api.hip: upload_matrix): 4 copier threads x 2 page-locked buffers, one stream each; wall time and bytes of
-    // the last one (0 when the inputs were device-resident)
-    char *upPin[8] = {};
-    hipStream_t upStream[4] = {};
-    hipEvent_t upEvent[8] = {};
+    // staged upload of a host X (upload_matrix); wall time and bytes of the last one (0 when the inputs were device-resident)
+    partls::UploadStaging up;
     double last_upload_ms = 0.0, last_upload_bytes = 0.0;
     partls::PinnedDoubles hG;                      // host copy of the augmented Gram (pinned: 0.8 MB per prepare at C3)
     partls::PinnedDoubles hScale;
@@ -175,8 +225,8 @@ struct partls_ctx {
     bool coop_state_valid = false;                 // scratch holds the tableau/basis of the previous cooperative solve
     bool coop_fallback = false;                    // the cooperative attempt of the current solve timed out at its grid barrier
     // final tableau of the last single-node solve on the register kernel (pinned host copies; see solve_nodes `want_tab`)
-    double *hTab = nullptr;
-    int8_t *hBasic = nullptr;
+    partls::PinnedArray<double> hTab;
+    partls::PinnedArray<int8_t> hBasic;
     size_t hTabDoubles = 0;
     bool tab_valid = false, tab_full = false;
     // partls_cv_opt (cv.hip): internal same-device contexts, created on first use and destroyed with this one.  cv_work holds one problem
@@ -210,10 +260,41 @@ partls_status ctx_prepare_tableau(partls_ctx *c);
 partls_status load_partition(partls_ctx *c, const int64_t *P, int64_t M, int64_t K, int64_t ldP);
 // host X (N x M, ldX, elements of `esz` bytes) -> packed device image (ld N) on c->stream, staged through page-locked buffers when large
 partls_status upload_matrix(partls_ctx *c, void *dst, const void *X, int64_t N, int64_t M, int64_t ldX, size_t esz = sizeof(double));
-// the Opt sweep's pieces that partls_cv_opt shares (api.hip)
+// ---- the set-up of a sweep launch (sweep_setup.hip): every launch of a sweep kernel goes through these
+constexpr double SWEEP_PIV_EPS = 1e-11;                      // SweepParams::piv_eps of every launch
+inline int sweep_max_rounds(int n) { return 20 * (n + 1); }  // SweepParams::max_rounds unless the caller overrides it
+// The fields every launch shares: n, kbits, mask, scratch (ensure it first: ensure_sweep_scratch), tol, piv_eps, max_rounds, rbit.
+// internal_order (chain mode): patterns run in the calibrated bit order — mask = maskInt and rbit = the inverse of c->order unless that
+// order is the identity; otherwise mask = maskTabP and rbit = identity.  The caller sets what is its own: the range, the chain
+// length, the outputs, the node pointers, the snapshot arrays, the batch fields, the fault hooks, a max_rounds override.
+SweepParams sweep_params(const partls_ctx *c, bool internal_order);
+// the one scratch-sizing rule: the register kernels take 64 doubles, the global-memory kernels a tableau per workgroup
+partls_status ensure_sweep_scratch(partls_ctx *c, int grid);
+// Node mode (SweepParams::node_code): sweep_params plus the range [0, nodes) in chains of chain_len, and bestObj / bestPat (sized for the
+// grid) for the per-workgroup minima, which the kernels rank in node mode too and nobody reads.  Ensure the scratch first.
+partls_status node_sweep_params(partls_ctx *c, size_t nodes, int64_t chain_len, int grid, SweepParams *p);
+// the counter words of a launch: [unconverged | pivots | vetoes | (cooperative kernel) blocks], 8 bytes each, zeroed by the caller
+inline void bind_counters(SweepParams &p, unsigned long long *w) { p.n_unconverged = w; p.n_pivots = w + 1; p.n_vetoes = w + 2; }
+// The per-workgroup result block of a chain-mode sweep, 8-byte words: [counters (4) | best objective (grid) | best pattern (grid)] and,
+// with runner_up, [runner-up objective (grid) | runner-up pattern (grid)]; patterns in the internal bit order.
+struct SweepBlock { unsigned long long *counters; double *best_obj; int64_t *best_pat; double *second_obj; int64_t *second_pat; };
+inline size_t sweep_block_words(int grid, bool runner_up) { return 4 + (runner_up ? 4 : 2) * (size_t)grid; }
+inline SweepBlock sweep_block(double *base, int grid, bool runner_up)
+{
+    double *b = base + 4;
+    const size_t g = (size_t)grid;
+    return {reinterpret_cast<unsigned long long *>(base), b, reinterpret_cast<int64_t *>(b + g), runner_up ? b + 2 * g : nullptr,
+            runner_up ? reinterpret_cast<int64_t *>(b + 3 * g) : nullptr};
+}
+void bind_sweep_block(SweepParams &p, double *base, int grid, bool runner_up);   // counters, best_*, second_* of p -> the block at base
+// The only place that picks a sweep kernel: the register kernel (T0reg), else the deferred-update or, with PARTLS_EAGER_GENERIC, the
+// eager global-memory kernel (Tfull).  models: the export instantiation (partls_opt_models; see launch_sweep_blk in common.h)
+hipError_t launch_any_sweep(partls_ctx *c, SweepParams &p, int grid, bool models = false);
+// the Opt sweep's pieces that partls_cv_opt shares
 partls_status calibrate_bit_order(partls_ctx *c);
 bool sweep_plan(partls_ctx *c, int64_t total, int64_t *chain_len_out, int *grid_out, const char *who);
 int64_t reference_pattern(const partls_ctx *c, int64_t q);
+// sweep_out: the host copy of a result block with runner-up columns (sweep_block)
 void install_sweep_result(partls_ctx *c, const double *sweep_out, int grid, bool has_sol, double *bobj_out, int64_t *bpat_out);
 
 // Solve a batch of `cnt` independent subproblems ("nodes") from the fresh tableau.  codes[i * n + v] is the constraint on

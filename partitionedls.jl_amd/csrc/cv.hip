@@ -43,7 +43,7 @@ static partls_status make_internal(partls_ctx *c, partls_ctx **slot)
 }
 
 // the working context sees the training rows of problem fold f (f == F: all rows): its own rows are the first training fold, the
-// other training folds are its peers (data_pass, api.hip, sums context then peers in order)
+// other training folds are its peers (data_pass, refine.hip, sums context then peers in order)
 static void point_rows(partls_ctx *c, partls_ctx *W, const int64_t *fold_ptr, int64_t F, int64_t f)
 {
     W->peers.clear();
@@ -270,10 +270,7 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
     const bool want_sol = (sweep_reg_small(T) || sweep_reg_exports(T)) && !c->knobs.no_export;
     PARTLS_HIP_CHECK(c->cvEta.ensure((size_t)E * sizeof(double)));
     PARTLS_HIP_CHECK(hipMemcpyAsync(c->cvEta.p, eta, (size_t)E * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    PARTLS_HIP_CHECK(c->scratch.ensure(64 * sizeof(double)));
-    BitOrder rbit;
-    for (int k = 0; k < 40; ++k) rbit.gbit[k] = (uint8_t)k;
-    if (!W->order_identity) for (int k = 0; k < W->kbits; ++k) rbit.gbit[W->order.gbit[k]] = (uint8_t)k;
+    PARTLS_HIP_CHECK(c->scratch.ensure(64 * sizeof(double)));      // the register kernels' share (ensure_sweep_scratch goes by W, the prepared context)
     hipEvent_t ev[4];
     for (int i = 0; i < 4; ++i) PARTLS_HIP_CHECK(hipEventCreate(&ev[i]));
     struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; ++i) (void)hipEventDestroy(e[i]); } } evg{ev};
@@ -284,7 +281,7 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
         if (!sweep_plan(W, npat * bc, &chain_len, &grid_all, "partls_cv_opt")) return PARTLS_ERR_UNSUPPORTED;
         const int64_t nch = (npat + chain_len - 1) / chain_len;
         const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(nch, (grid_all + bc - 1) / bc));
-        const size_t out_w = 4 + 4 * (size_t)gx;
+        const size_t out_w = sweep_block_words(gx, true);
         // [scale (bc x n) | Tfull (bc x (n+1)^2) | T0reg (bc x t0d) | tol (bc) | sweep blocks (bc x out_w) | best_sol (bc x gx x n)]
         const size_t o_scale = 0, o_tf = o_scale + (size_t)bc * n, o_t0 = o_tf + (size_t)bc * tfd, o_tol = o_t0 + (size_t)bc * t0d,
                      o_out = o_tol + (size_t)bc, o_sol = o_out + (size_t)bc * out_w, words = o_sol + (want_sol ? (size_t)bc * gx * n : 0);
@@ -296,20 +293,12 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
         PARTLS_HIP_CHECK(launch_layout_reg_batch(base + o_tf, n, T, bc, base + o_t0, c->stream));
         PARTLS_HIP_CHECK(hipMemsetAsync(base + o_out, 0, (size_t)bc * out_w * sizeof(double), c->stream));
         PARTLS_HIP_CHECK(hipEventRecord(ev[1], c->stream));
-        SweepParams p{};
-        p.n = n; p.kbits = W->kbits;
-        p.mask = W->order_identity ? W->maskTabP : W->maskInt.as<uint64_t>();
+        SweepParams p = sweep_params(W, /*internal_order=*/true);
         p.T0 = base + o_t0;
         p.scratch = c->scratch.as<double>();
         p.g_begin = 0; p.g_end = npat; p.chain_len = chain_len;
-        p.tol = 0.0; p.piv_eps = 1e-11; p.max_rounds = 20 * (n + 1);
-        double *ob = base + o_out;
-        p.n_unconverged = reinterpret_cast<unsigned long long *>(ob);
-        p.n_pivots = reinterpret_cast<unsigned long long *>(ob) + 1;
-        p.n_vetoes = reinterpret_cast<unsigned long long *>(ob) + 2;
-        p.best_obj = ob + 4; p.best_pat = reinterpret_cast<int64_t *>(ob + 4 + gx);
-        p.second_obj = ob + 4 + 2 * (size_t)gx; p.second_pat = reinterpret_cast<int64_t *>(ob + 4 + 3 * (size_t)gx);
-        p.rbit = rbit;
+        p.tol = 0.0;                                             // every problem has its own: batch_tol
+        bind_sweep_block(p, base + o_out, gx, true);             // problem 0's block; problem q's lies q * batch_out words further
         if (want_sol) { p.best_sol = base + o_sol; p.node_ld = n; }
         p.batch_t0 = (int64_t)t0d; p.batch_out = (int64_t)out_w; p.batch_tol = base + o_tol;
         PARTLS_HIP_CHECK(launch_sweep_blk_batch(p, T, gx, bc, c->stream));
@@ -420,8 +409,7 @@ try {
     return cv_opt(c, X, N, M, ldX, y, nullptr, x_on_device, P, K, ldP, fold_ptr, F, eta, E, flags, alpha, ld_alpha, beta, ld_beta, t, opt,
                   best_index, heldout_sse, status);
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 partls_status partls_cv_opt_weighted(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w,
                                      int x_on_device, const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F,
@@ -432,5 +420,4 @@ try {
     return cv_opt(c, X, N, M, ldX, y, w, x_on_device, P, K, ldP, fold_ptr, F, eta, E, flags, alpha, ld_alpha, beta, ld_beta, t, opt,
                   best_index, heldout_sse, status);
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD

@@ -577,8 +577,7 @@ try {
     *out = mc;
     return PARTLS_OK;
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 void partls_multi_destroy(partls_multi *mc)
 {
@@ -604,8 +603,7 @@ try {
     *ms = mc->t_ms[(size_t)rank][(size_t)which];
     return PARTLS_OK;
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 partls_status partls_fit_opt_multi(partls_multi *mc, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
                                    const int64_t *P, int64_t K, int64_t ldP, double eta, uint32_t flags,
@@ -634,8 +632,7 @@ try {
     if (unconv) { set_error("%lld subproblems hit the pivot cap", (long long)unconv); return PARTLS_ERR_NOT_CONVERGED; }
     return PARTLS_OK;
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 partls_status partls_fit_bnb_multi(partls_multi *mc, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
                                    const int64_t *P, int64_t K, int64_t ldP, double eta,
@@ -646,7 +643,6 @@ try {
     const FitArgs a{1, X, N, M, ldX, y, P, K, ldP, eta, PARTLS_OPT_FAITHFUL_INTERCEPT, alpha, beta, t, opt, nullptr, nullptr, nopen};
     return run_fit(mc, a);
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 }  // extern "C"

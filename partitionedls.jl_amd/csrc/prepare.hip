@@ -1,0 +1,254 @@
+// prepare.hip — from the caller's arrays to a prepared context: upload of X, y and the sample weights, the Gram products, the tableau.
+#include "ctx.h"
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <numeric>
+#include <thread>
+
+namespace partls {
+
+partls_status load_partition(partls_ctx *c, const int64_t *P, int64_t M, int64_t K, int64_t ldP)
+{
+    c->P.assign((size_t)M * K, 0);
+    c->mask_aug.assign((size_t)M + 2, 0);
+    for (int64_t k = 0; k < K; ++k)
+        for (int64_t m = 0; m < M; ++m) {
+            const int64_t v = P[m + k * ldP];
+            if (v != 0 && v != 1) { set_error("P[%lld,%lld] = %lld is not 0/1", (long long)m, (long long)k, (long long)v); return PARTLS_ERR_BAD_PARTITION; }
+            c->P[(size_t)m + (size_t)k * M] = v;
+            if (v) c->mask_aug[(size_t)m] |= (1ULL << k);
+        }
+    c->mask_aug[(size_t)M] = 1ULL << K;            // the intercept's own group (homogeneousCoords, PartitionedLS.jl:78)
+    c->mask_aug[(size_t)M + 1] = 0;                // y
+    return PARTLS_OK;
+}
+
+// Host -> device copy of a column-major matrix (N x M, leading dimension ldX) into a packed device image (leading dimension N).
+// Measured on the MI355X box (tools/ubench/h2d_paths.hip, profiles/r04_h2d_paths.txt): the link gives 57 GB/s from page-locked memory;
+// hipMemcpy2DAsync from PAGEABLE memory reaches that only when the runtime has pinned the very same pages before — a caller's fresh
+// array goes at 8 GB/s (205 MB, C3) to 25 GB/s (4.1 GB, C4), the pinning itself costs as much as the transfer.  Staged through
+// page-locked buffers by a few copier threads the same array goes at 42-55 GB/s whatever its history: UP_T threads, each with its own
+// stream and two staging buffers, own a contiguous range of columns; a thread packs a batch of columns into one buffer (memcpy) while
+// the DMA of its previous batch runs from the other.  Small matrices (< 8 MB) take the plain copy.
+namespace {
+constexpr int UP_T = 4;
+constexpr size_t UP_BUF = (size_t)8 << 20;
+}
+partls_status upload_matrix(partls_ctx *c, void *dst_, const void *X_, int64_t N, int64_t M, int64_t ldX, size_t esz)
+{
+    char *dst = static_cast<char *>(dst_);                 // everything below goes by bytes: esz = 8 (double) or 4 (float)
+    const char *X = static_cast<const char *>(X_);
+    const size_t bytes = (size_t)N * M * esz;
+    if (bytes < ((size_t)8 << 20) || c->knobs.no_staged_upload) {
+        PARTLS_HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)N * esz, X, (size_t)ldX * esz, (size_t)N * esz, (size_t)M,
+                                          hipMemcpyHostToDevice, c->stream));
+        return PARTLS_OK;
+    }
+    if (!c->up.pin[0]) {
+        for (int i = 0; i < 2 * UP_T; ++i) PARTLS_HIP_CHECK(hipHostMalloc((void **)&c->up.pin[i], UP_BUF, hipHostMallocDefault));
+        for (int t = 0; t < UP_T; ++t) PARTLS_HIP_CHECK(hipStreamCreateWithFlags(&c->up.stream[t], hipStreamNonBlocking));
+        for (int i = 0; i < 2 * UP_T; ++i) PARTLS_HIP_CHECK(hipEventCreateWithFlags(&c->up.event[i], hipEventDisableTiming));
+    }
+    // rows per piece of a column (a column longer than a staging buffer goes in pieces), columns per batch otherwise
+    const size_t col_bytes = (size_t)N * esz, ld_bytes = (size_t)ldX * esz;
+    hipError_t err[UP_T];
+    for (int t = 0; t < UP_T; ++t) err[t] = hipSuccess;
+    const int device = c->device;
+    auto worker = [&](int t) {
+        hipError_t e = hipSetDevice(device);
+        const int64_t c0 = M * t / UP_T, c1 = M * (t + 1) / UP_T;
+        char *pin[2] = {c->up.pin[2 * t], c->up.pin[2 * t + 1]};
+        bool used[2] = {false, false};
+        int b = 0;
+        auto flush = [&](char *d, size_t n) {           // DMA of the buffer just filled; the other buffer is filled meanwhile
+            if (e == hipSuccess) e = hipMemcpyAsync(d, pin[b], n, hipMemcpyHostToDevice, c->up.stream[t]);
+            if (e == hipSuccess) e = hipEventRecord(c->up.event[2 * t + b], c->up.stream[t]);
+            used[b] = true;
+            b ^= 1;
+            if (used[b] && e == hipSuccess) e = hipEventSynchronize(c->up.event[2 * t + b]);      // the buffer about to be refilled is free again
+        };
+        if (col_bytes <= UP_BUF) {
+            const int64_t per = (int64_t)(UP_BUF / col_bytes);
+            for (int64_t j0 = c0; j0 < c1 && e == hipSuccess; j0 += per) {
+                const int64_t j1 = j0 + per < c1 ? j0 + per : c1;
+                for (int64_t j = j0; j < j1; ++j) std::memcpy(pin[b] + (size_t)(j - j0) * col_bytes, X + (size_t)j * ld_bytes, col_bytes);
+                flush(dst + (size_t)j0 * col_bytes, (size_t)(j1 - j0) * col_bytes);
+            }
+        } else {
+            const int64_t rows = (int64_t)(UP_BUF / esz);
+            for (int64_t j = c0; j < c1 && e == hipSuccess; ++j)
+                for (int64_t r0 = 0; r0 < N && e == hipSuccess; r0 += rows) {
+                    const int64_t r1 = r0 + rows < N ? r0 + rows : N;
+                    std::memcpy(pin[b], X + (size_t)j * ld_bytes + (size_t)r0 * esz, (size_t)(r1 - r0) * esz);
+                    flush(dst + (size_t)j * col_bytes + (size_t)r0 * esz, (size_t)(r1 - r0) * esz);
+                }
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(c->up.stream[t]);
+        err[t] = e;
+    };
+    {
+        std::vector<std::thread> th;
+        th.reserve(UP_T);
+        bool spawned = true;
+        try { for (int t = 1; t < UP_T; ++t) th.emplace_back(worker, t); }
+        catch (...) { spawned = false; }
+        worker(0);
+        for (std::thread &w : th) w.join();
+        if (!spawned) for (int t = (int)th.size() + 1; t < UP_T; ++t) worker(t);      // out of threads: the caller's thread takes the rest
+    }
+    PARTLS_HIP_CHECK(hipSetDevice(c->device));
+    for (int t = 0; t < UP_T; ++t) if (err[t] != hipSuccess) { set_error("staged upload of X failed: %s", hipGetErrorString(err[t])); return PARTLS_ERR_HIP; }
+    return PARTLS_OK;                                    // every copier has synchronised its stream: the image is complete for c->stream
+}
+
+partls_status prepare_weights(partls_ctx *c, const double *w, int64_t N, int on_device)
+{
+    c->dw = nullptr; c->ds = nullptr;
+    const double *dw = w;
+    if (!on_device) {
+        PARTLS_HIP_CHECK(c->ownW.ensure((size_t)N * sizeof(double)));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(c->ownW.p, w, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        dw = c->ownW.as<double>();
+    }
+    const int nb = weight_prep_blocks(N);
+    PARTLS_HIP_CHECK(c->ownS.ensure((size_t)N * sizeof(double)));
+    PARTLS_HIP_CHECK(c->wPart.ensure((size_t)3 * nb * sizeof(double)));
+    PARTLS_HIP_CHECK(c->hPart.resize((size_t)3 * nb));
+    PARTLS_HIP_CHECK(launch_weight_prep(dw, N, c->ownS.as<double>(), c->wPart.as<double>(), c->stream));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->hPart.data(), c->wPart.p, (size_t)3 * nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    bool neg = false, bad = false;
+    double sum = 0.0;
+    for (int b = 0; b < nb; ++b) {
+        neg = neg || c->hPart[(size_t)3 * b] != 0.0;
+        bad = bad || c->hPart[(size_t)3 * b + 1] != 0.0;
+        sum += c->hPart[(size_t)3 * b + 2];
+    }
+    if (bad) { set_error("the sample weights contain NaN/Inf"); return PARTLS_ERR_NONFINITE; }
+    if (neg) { set_error("a sample weight is negative"); return PARTLS_ERR_BAD_ARG; }
+    if (!(sum > 0.0)) { set_error("the sample weights sum to 0"); return PARTLS_ERR_BAD_ARG; }
+    if (!std::isfinite(sum)) { set_error("the sum of the sample weights overflows"); return PARTLS_ERR_NONFINITE; }
+    c->dw = dw; c->ds = c->ownS.as<double>();
+    return PARTLS_OK;
+}
+
+partls_status ctx_prepare(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
+                          const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags, const double *w, bool x_f32)
+{
+    partls_status st = check_common(c, X, N, M, ldX, P, K, ldP);
+    if (st != PARTLS_OK) return st;
+    if (!y) { set_error("y is NULL"); return PARTLS_ERR_BAD_ARG; }
+    if (!(eta >= 0.0)) { set_error("eta must be >= 0"); return PARTLS_ERR_BAD_ARG; }
+    c->prepared = false;
+    c->peers.clear();                              // a row-sharded fit sets them again after every rank has prepared its block
+    c->near_for = -1; c->near_pat.clear(); c->cand.clear();
+    c->last_upload_ms = 0.0; c->last_upload_bytes = 0.0;
+    c->sweep_vetoes = 0;
+    c->coop_state_valid = false;
+    c->order_ready = false; c->order_identity = true; c->flip_cost.clear(); c->ms[PARTLS_T_CALIB] = 0.0;
+    c->dw = nullptr; c->ds = nullptr;
+    c->x_f32 = false;
+    if (x_f32 && c->multi_rank) { set_error("float X: a context of a partls_multi is not supported (row-sharded multi-GPU fits are fp64)"); return PARTLS_ERR_UNSUPPORTED; }
+    PARTLS_HIP_CHECK(hipSetDevice(c->device));
+    if (w) {
+        if (c->multi_rank) { set_error("sample weights: a context of a partls_multi is not supported (multi-GPU fits are unweighted)"); return PARTLS_ERR_UNSUPPORTED; }
+        st = prepare_weights(c, w, N, x_on_device);
+        if (st != PARTLS_OK) return st;
+    }
+    st = load_partition(c, P, M, K, ldP);
+    if (st != PARTLS_OK) return st;
+    c->N = N; c->M = M; c->K = K; c->eta = eta; c->flags = flags; c->faithful = faithful;
+
+    if (x_on_device) {
+        c->dX = X; c->dy = y; c->ldX = ldX;
+    } else {
+        const size_t esz = x_f32 ? sizeof(float) : sizeof(double);
+        PARTLS_HIP_CHECK(c->ownX.ensure((size_t)N * M * esz));
+        PARTLS_HIP_CHECK(c->ownY.ensure((size_t)N * sizeof(double)));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(c->ownY.p, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        const auto u0 = std::chrono::steady_clock::now();
+        st = upload_matrix(c, c->ownX.p, X, N, M, ldX, esz);
+        if (st != PARTLS_OK) return st;
+        c->last_upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+        c->last_upload_bytes = (double)N * (double)M * (double)esz;
+        c->dX = c->ownX.p; c->dy = c->ownY.as<double>(); c->ldX = N;
+    }
+    c->x_f32 = x_f32;
+
+    // Gram products (fp64 MFMA)
+    const size_t slabd = gram_slab_doubles(N, M, c->knobs.gram_S, c->knobs.gram_cr, &c->chunks, &c->ldg);
+    PARTLS_HIP_CHECK(c->slab.ensure(slabd * sizeof(double)));
+    PARTLS_HIP_CHECK(c->G.ensure((size_t)c->ldg * c->ldg * sizeof(double)));
+    t_begin(c, PARTLS_T_GRAM);
+    PARTLS_HIP_CHECK(launch_gram(c->dX, N, M, c->ldX, c->dy, c->slab.as<double>(), c->chunks, c->ldg, c->knobs.gram_S, c->knobs.gram_cr,
+                                 c->G.as<double>(), c->stream, c->ds, c->x_f32));
+    t_end(c, PARTLS_T_GRAM);
+    // rows of X sharded over several devices: the Gram products of the blocks are summed here (partls_fit_opt_multi, multi.hip)
+    if (c->gram_hook) { st = c->gram_hook(c); if (st != PARTLS_OK) return st; }
+    return ctx_prepare_tableau(c);
+}
+
+partls_status ctx_prepare_tableau(partls_ctx *c)
+{
+    const int64_t M = c->M, K = c->K;
+    const double eta = c->eta;
+    const bool faithful = c->faithful;
+    const uint32_t flags = c->flags;
+    // tableau variables, grouped by partition (stable sort on the lowest group a variable belongs to) so that the
+    // variables one Gray-code flip touches sit in as few 16-wide tile columns as possible
+    c->n = faithful ? (int)M + 1 : (int)M;
+    c->kbits = faithful ? (int)K + 1 : (int)K;
+    c->perm.resize((size_t)c->n);
+    std::iota(c->perm.begin(), c->perm.end(), 0);
+    auto key = [&](int v) { const uint64_t m = c->mask_aug[(size_t)v]; return m ? __builtin_ctzll(m) : 64; };
+    std::stable_sort(c->perm.begin(), c->perm.end(), [&](int a, int b) { return key(a) < key(b); });
+    c->mask_tab.resize((size_t)c->n);
+    for (int i = 0; i < c->n; ++i) c->mask_tab[(size_t)i] = c->mask_aug[(size_t)c->perm[(size_t)i]];
+
+    // one upload: [group masks of the augmented variables (M + 2) | group masks in tableau order (n) | permutation (n ints)]
+    {
+        const size_t words = (size_t)M + 2 + (size_t)c->n + ((size_t)c->n + 1) / 2;
+        c->pack.assign(words, 0);
+        std::memcpy(c->pack.data(), c->mask_aug.data(), ((size_t)M + 2) * sizeof(uint64_t));
+        std::memcpy(c->pack.data() + M + 2, c->mask_tab.data(), (size_t)c->n * sizeof(uint64_t));
+        std::memcpy(c->pack.data() + M + 2 + c->n, c->perm.data(), (size_t)c->n * sizeof(int));
+        PARTLS_HIP_CHECK(c->maskAugD.ensure(words * sizeof(uint64_t)));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(c->maskAugD.p, c->pack.data(), words * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        c->maskTabP = c->maskAugD.as<uint64_t>() + M + 2;
+        c->permP = reinterpret_cast<int *>(c->maskAugD.as<uint64_t>() + M + 2 + c->n);
+    }
+    PARTLS_HIP_CHECK(c->scale.ensure((size_t)c->n * sizeof(double)));
+    PARTLS_HIP_CHECK(c->Tfull.ensure((size_t)(c->n + 1) * (c->n + 1) * sizeof(double)));
+    t_begin(c, PARTLS_T_PREP);
+    PARTLS_HIP_CHECK(launch_prep(c->G.as<double>(), c->ldg, (int)M, eta, c->maskAugD.as<uint64_t>(), faithful ? 0 : 1,
+                                 c->permP, c->scale.as<double>(), c->Tfull.as<double>(), c->n, c->stream));
+    c->use_reg = sweep_reg_supported(c->n) && c->n <= 16 * c->knobs.reg_maxt && !(flags & PARTLS_OPT_GENERIC_KERNEL);
+    if (c->use_reg) {
+        c->T = sweep_reg_tiles(c->n);
+        PARTLS_HIP_CHECK(c->T0reg.ensure(sweep_reg_t0_doubles(c->T) * sizeof(double)));
+        PARTLS_HIP_CHECK(launch_layout_reg(c->Tfull.as<double>(), c->n, c->T, c->T0reg.as<double>(), c->stream));
+    }
+    t_end(c, PARTLS_T_PREP);
+    PARTLS_HIP_CHECK(c->hG.resize((size_t)c->ldg * c->ldg));
+    PARTLS_HIP_CHECK(c->hScale.resize((size_t)c->n));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->hG.data(), c->G.p, c->hG.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->hScale.data(), c->scale.p, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    t_collect(c);
+    // NaN / Inf anywhere in column m of [X y] makes the diagonal Gram entry sum_i z_im^2 non-finite (so does a finite column whose
+    // squares overflow — equally outside the Gram form): M + 2 host compares instead of a separate pass over X, which cost 0.87 ms
+    // of the 4.1 GB read at C4 before the Gram kernel read the same bytes again
+    for (int64_t i = 0; i < M + 2; ++i) {
+        if (i == M) continue;                                    // the ones column
+        if (!std::isfinite(c->hG[(size_t)i * c->ldg + i])) { set_error("X or y contains NaN/Inf (or overflows in X'X)"); return PARTLS_ERR_NONFINITE; }
+    }
+    const double yy = c->hG[(size_t)(M + 1) * c->ldg + (M + 1)];
+    c->tol = c->knobs.tol_rel * std::sqrt(yy > 0.0 ? yy : 0.0);
+    if (!(c->tol > 0.0)) c->tol = 1e-300;
+    c->prepared = true;
+    return PARTLS_OK;
+}
+
+}  // namespace partls

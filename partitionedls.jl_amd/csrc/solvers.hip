@@ -1,7 +1,7 @@
 // solvers.hip — fit(Alt) and fit(BnB) on the Gram / tableau kernels (SURVEY.md §8f-1,2).
 //
 // Both reduce to batches of sign-constrained least-squares "nodes" on the shared Gram block, solved on the device by the
-// sweep kernels in node mode (solve_nodes, api.hip):
+// sweep kernels in node mode (solve_nodes, sweep_setup.hip):
 //   * Alt α-step (Alt.jl:80-90):  nonneg_lsq(Xo .* f', y) with f_m = sum_k Po[m,k] β_k has the constraint set
 //     {Xo w : sign(f_m) w_m >= 0} (f_m == 0: zero column, α_m stays 0); α_m = w_m / f_m.  Any 0/1 partition matrix, as in the
 //     reference: for a feature in several groups f_m is not a function of the sign pattern of β, hence per-variable codes.
@@ -66,8 +66,7 @@ struct SnapshotPool {                                              // a view of 
     {
         const size_t slot_bytes = (bytes + 255) & ~(size_t)255;
         if (c->bnbSlotBytes != slot_bytes) {                       // another tableau size: the old chunks are useless
-            for (void *q : c->bnbChunks) (void)hipFree(q);
-            c->bnbChunks.clear();
+            c->bnbChunks.release();
             c->bnbSlotBytes = slot_bytes;
             c->bnbChunkSlots = (int)std::max<size_t>(8, std::min<size_t>(512, ((size_t)160 << 20) / slot_bytes));
         }
@@ -131,16 +130,16 @@ partls_status bnb_bound_batch(partls_ctx *c, size_t cnt, const uint64_t *pat, co
     PARTLS_HIP_CHECK(c->bnbOut.ensure(out_bytes));
     PARTLS_HIP_CHECK(c->nodeCode.ensure(cnt * (size_t)n));
     PARTLS_HIP_CHECK(c->nodeSol.ensure((4 + cnt + cnt * (size_t)n) * sizeof(double)));
-    PARTLS_HIP_CHECK(c->bestObj.ensure(sizeof(double) * (4 + 4 * 4096)));
-    PARTLS_HIP_CHECK(c->bestPat.ensure(sizeof(int64_t) * 4096));
     // workgroups of the batch's grid: the 512-thread kernel runs one per CU at a time and the dispatcher balances nodes of different cost
     // best with one node per workgroup (tools/experiments/README.md); the global-memory kernel needs a scratch tableau per workgroup
-    int ncu = 256;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || ncu < 1) ncu = 256;
+    const int ncu = c->ncu;
     const size_t wg_cap = c->use_reg ? (size_t)ncu * (size_t)std::max(1, sweep_reg_concurrency(c->T)) * (size_t)std::max(1, c->knobs.bnb_wg_per_cu)
                                      : (size_t)2 * ncu;
     const int grid = (int)std::min<size_t>(cnt, wg_cap);
-    PARTLS_HIP_CHECK(c->scratch.ensure(c->use_reg ? 64 * sizeof(double) : (size_t)grid * (n + 1) * (n + 1) * sizeof(double)));
+    SweepParams p;
+    partls_status st = ensure_sweep_scratch(c, grid);
+    if (st == PARTLS_OK) st = node_sweep_params(c, cnt, 1, grid, &p);
+    if (st != PARTLS_OK) return st;
     PARTLS_HIP_CHECK(c->bnbHostIn.resize(in_words));
     PARTLS_HIP_CHECK(c->bnbHostOut.resize((out_bytes + 7) / 8));
     uint64_t *hin = reinterpret_cast<uint64_t *>(c->bnbHostIn.data());
@@ -157,29 +156,14 @@ partls_status bnb_bound_batch(partls_ctx *c, size_t cnt, const uint64_t *pat, co
     PARTLS_HIP_CHECK(hipMemcpyAsync(din, hin, in_words * 8, hipMemcpyHostToDevice, c->stream));
     PARTLS_HIP_CHECK(hipMemsetAsync(dout, 0, 32, c->stream));
     PARTLS_HIP_CHECK(launch_bnb_codes(c->maskTabP, n, din, din + cnt, (int)cnt, c->nodeCode.as<int8_t>(), c->stream));
-    SweepParams p{};
-    p.n = n; p.kbits = c->kbits;
-    p.mask = c->maskTabP;
-    p.scratch = c->scratch.as<double>();
-    p.g_begin = 0; p.g_end = (int64_t)cnt; p.chain_len = 1;
-    p.tol = c->tol; p.piv_eps = 1e-11; p.max_rounds = 20 * (n + 1);
-    p.best_obj = c->bestObj.as<double>(); p.best_pat = c->bestPat.as<int64_t>();
-    p.n_unconverged = reinterpret_cast<unsigned long long *>(dout);
-    p.n_pivots = p.n_unconverged + 1;
-    p.n_vetoes = p.n_unconverged + 2;
+    bind_counters(p, reinterpret_cast<unsigned long long *>(dout));
     p.node_code = c->nodeCode.as<int8_t>();
     p.node_obj2 = c->nodeSol.as<double>() + 4; p.node_sol = c->nodeSol.as<double>() + 4 + cnt; p.node_ld = n;
     if (snaps) {
         p.node_src = reinterpret_cast<const double *const *>(din + 2 * cnt);
         p.node_dst = reinterpret_cast<double *const *>(din + 3 * cnt);
     }
-    if (c->use_reg) {
-        p.T0 = c->T0reg.as<double>();
-        PARTLS_HIP_CHECK(launch_sweep_blk(p, c->T, grid, c->stream));
-    } else {
-        p.T0 = c->Tfull.as<double>();
-        PARTLS_HIP_CHECK(launch_sweep_lazy(p, grid, c->stream));
-    }
+    PARTLS_HIP_CHECK(launch_any_sweep(c, p, grid));          // snapshots_supported(c): the register or the deferred-update kernel
     double *dlb = reinterpret_cast<double *>(dout + 32);
     int *dbr = reinterpret_cast<int *>(dout + 32 + cnt * 8);
     PARTLS_HIP_CHECK(launch_bnb_nu(p.node_sol, p.node_obj2, n, c->scale.as<double>(), c->maskTabP, Kp, din + cnt, (int)cnt, dlb, dbr, c->stream));
@@ -293,8 +277,7 @@ try {
     if (st != PARTLS_OK) return st;
     return partls_alt_prepared(c, eps, T, alpha0, beta0, alpha, beta, t, opt, iters);
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 partls_status partls_alt_prepared(partls_ctx *c, double eps, int64_t T, const double *alpha0, const double *beta0,
                                   double *alpha, double *beta, double *t, double *opt, int64_t *iters)
@@ -394,8 +377,7 @@ try {
     }
     return alt_finish(c, a, b, wv, vcode_last, hdiag, gersh, optval, i - 1, unconv_total, alpha, beta, t, opt, iters);
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 partls_status partls_fit_bnb(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
                              const int64_t *P, int64_t K, int64_t ldP, double eta,
@@ -405,8 +387,7 @@ try {
     if (st != PARTLS_OK) return st;
     return partls_bnb_prepared(c, alpha, beta, t, opt, nopen);
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 // ---- BnB primitives (shared by the single-rank driver below and the rank-sharded search of partitionedls.jl_amd/dist.py) -------
 // A node is (pat, free): group k is branched iff bit k of `free` is clear, and then constrained to alpha_pk >= 0 (bit k of pat
@@ -465,8 +446,7 @@ try {
     if (unconv) { set_error("partls_bnb_bound: a node bound hit the pivot cap"); return PARTLS_ERR_NOT_CONVERGED; }
     return PARTLS_OK;
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 // The same with tableau snapshots, for a host that runs the search itself (partitionedls.jl_amd/dist.py: the rank-sharded search deals
 // every node to the rank that holds its parent's snapshot).  src_slot[i]: snapshot node i starts from (-1: the fresh tableau);
@@ -482,8 +462,7 @@ try {
     PARTLS_HIP_CHECK(pool.begin(snapshot_bytes(c)));
     return PARTLS_OK;
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 static partls_status bnb_bound_snap_impl(partls_ctx *c, int64_t count, const uint64_t *pat, const uint64_t *free_, const int32_t *src_slot,
                                          int32_t *dst_slot, double *lb, int32_t *branch, const std::function<void()> &between);
@@ -492,8 +471,7 @@ partls_status partls_bnb_bound_snap(partls_ctx *c, int64_t count, const uint64_t
 try {
     return bnb_bound_snap_impl(c, count, pat, free_, src_slot, dst_slot, lb, branch, {});
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 static partls_status bnb_bound_snap_impl(partls_ctx *c, int64_t count, const uint64_t *pat, const uint64_t *free_, const int32_t *src_slot,
                                          int32_t *dst_slot, double *lb, int32_t *branch, const std::function<void()> &between)
@@ -548,8 +526,7 @@ try {
         }
     return PARTLS_OK;
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 // The model of one (feasible) node: re-solve, data-space refinement, BnB.jl:36-39 normalisation, objective from the data.
 partls_status partls_bnb_leaf(partls_ctx *c, uint64_t pat, uint64_t free_, double *alpha, double *beta, double *t, double *opt)
@@ -586,7 +563,7 @@ try {
     st = data_objective(c, w, opt, &g);
     if (st != PARTLS_OK) return st;
     if (unconv) { set_error("partls_bnb_leaf: the node solve hit the pivot cap"); return PARTLS_ERR_NOT_CONVERGED; }
-    // the leaf's KKT conditions against the data, as partls_opt_finish checks its winner (api.hip: kkt_violation_data)
+    // the leaf's KKT conditions against the data, as partls_opt_finish checks its winner (refine.hip: kkt_violation_data)
     std::vector<int8_t> vcode((size_t)Mp, 0);
     for (int v = 0; v < n; ++v) vcode[(size_t)c->perm[(size_t)v]] = codes[(size_t)v];
     int worst = -1;
@@ -598,8 +575,7 @@ try {
     }
     return PARTLS_OK;
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 // fit_BnB (BnB.jl:94-132) as a best-first search: frontier ordered by the parent's bound, nodes bounded in device batches, the
 // incumbent prunes (BnB.jl:102).  Same optimum as the reference's depth-first recursion; the node count is not.  On the register
@@ -655,8 +631,7 @@ try {
     if (nodes_out) *nodes_out = f.bounded;
     return PARTLS_OK;
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 // ---- the frontier behind the C ABI: what a host that shards the search over processes drives (partitionedls.jl_amd/dist.py) ------------
 partls_status partls_frontier_create(int n_groups, int rank, int world, int64_t batch, partls_frontier **out)
@@ -720,7 +695,6 @@ try {
     if (nopen) *nopen = bounded;
     return partls_bnb_leaf(c, best_pat, best_free, alpha, beta, t, opt);
 }
-catch (const std::bad_alloc &) { partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }
-catch (...) { partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
+PARTLS_ABI_GUARD
 
 }  // extern "C"

@@ -1,0 +1,395 @@
+// sweep_setup.hip — everything between a prepared context and a sweep launch: the shared launch parameters, the scratch rule, the
+// per-workgroup result block, the choice of the kernel, the bit-order calibration, the chain plan and the node-mode solves.  Host only.
+#include "ctx.h"
+#include "near_tie.h"
+#include "sweep_rules.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <numeric>
+
+namespace partls {
+
+SweepParams sweep_params(const partls_ctx *c, bool internal_order)
+{
+    SweepParams p{};
+    const bool permuted = internal_order && !c->order_identity;
+    p.n = c->n; p.kbits = c->kbits;
+    p.mask = permuted ? c->maskInt.as<uint64_t>() : c->maskTabP;
+    p.scratch = c->scratch.as<double>();
+    p.tol = c->tol; p.piv_eps = SWEEP_PIV_EPS; p.max_rounds = sweep_max_rounds(c->n);
+    for (int k = 0; k < 40; ++k) p.rbit.gbit[k] = (uint8_t)k;
+    if (permuted) for (int k = 0; k < c->kbits; ++k) p.rbit.gbit[c->order.gbit[k]] = (uint8_t)k;   // exact ties: first REFERENCE index
+    return p;
+}
+
+partls_status ensure_sweep_scratch(partls_ctx *c, int grid)
+{
+    const size_t ld = (size_t)c->n + 1;
+    PARTLS_HIP_CHECK(c->scratch.ensure((c->use_reg ? 64 : (size_t)grid * ld * ld) * sizeof(double)));
+    return PARTLS_OK;
+}
+
+partls_status node_sweep_params(partls_ctx *c, size_t nodes, int64_t chain_len, int grid, SweepParams *p)
+{
+    const size_t wgs = (size_t)std::max(grid, 4096);
+    PARTLS_HIP_CHECK(c->bestObj.ensure(sizeof(double) * wgs));
+    PARTLS_HIP_CHECK(c->bestPat.ensure(sizeof(int64_t) * wgs));
+    *p = sweep_params(c, false);
+    p->g_begin = 0; p->g_end = (int64_t)nodes; p->chain_len = chain_len;
+    p->best_obj = c->bestObj.as<double>(); p->best_pat = c->bestPat.as<int64_t>();
+    return PARTLS_OK;
+}
+
+void bind_sweep_block(SweepParams &p, double *base, int grid, bool runner_up)
+{
+    const SweepBlock b = sweep_block(base, grid, runner_up);
+    bind_counters(p, b.counters);
+    p.best_obj = b.best_obj; p.best_pat = b.best_pat;
+    p.second_obj = b.second_obj; p.second_pat = b.second_pat;
+}
+
+// (bnb_bound_batch, solvers.hip, needs tableau snapshots, which the eager global-memory kernel does not keep: it is only reached when
+// snapshots_supported(c), i.e. use_reg || !eager_generic, so it never gets the third kernel here)
+hipError_t launch_any_sweep(partls_ctx *c, SweepParams &p, int grid, bool models)
+{
+    if (c->use_reg) {
+        p.T0 = c->T0reg.as<double>();
+        return launch_sweep_blk(p, c->T, grid, c->stream, models);
+    }
+    p.T0 = c->Tfull.as<double>();
+    return c->knobs.eager_generic ? launch_sweep_generic(p, grid, c->stream, models) : launch_sweep_lazy(p, grid, c->stream, models);
+}
+
+void opt_codes(const partls_ctx *c, uint64_t pattern, std::vector<int8_t> &codes)
+{
+    // multiplier of Opt.jl:28-29: f_m = sum_k P[m,k] s_k; only its sign matters for the constraint f_m w_m >= 0 (0: column is zero)
+    codes.resize((size_t)c->n);
+    for (int i = 0; i < c->n; ++i) {
+        const int f = sign_of_var(c->mask_tab[(size_t)i], pattern);
+        codes[(size_t)i] = (int8_t)((f > 0) - (f < 0));
+    }
+}
+
+partls_status solve_nodes(partls_ctx *c, const std::vector<int8_t> &codes, size_t cnt, std::vector<double> &sols,
+                          std::vector<double> &obj2, unsigned long long *unconv, bool resume, bool want_tab)
+{
+    c->tab_valid = false;
+    const int n = c->n, ld = n + 1;
+    sols.assign(cnt * (size_t)n, 0.0);
+    obj2.assign(cnt, 0.0);
+    if (unconv) *unconv = 0;
+    if (cnt == 0) return PARTLS_OK;
+    if (codes.size() != cnt * (size_t)n) { set_error("solve_nodes: code array has the wrong size"); return PARTLS_ERR_BAD_ARG; }
+    const int grid = (int)std::min<size_t>(cnt, c->use_reg ? 2048 : 512);
+    PARTLS_HIP_CHECK(c->nodeCode.ensure(cnt * (size_t)n));
+    // one output block on the device, one copy back: [counters (4 x 8 B) | objective^2 (cnt) | solutions (cnt x n)]
+    const size_t out_words = 4 + cnt + cnt * (size_t)n;
+    PARTLS_HIP_CHECK(c->nodeSol.ensure(out_words * sizeof(double)));
+    // one large problem: many workgroups on a single global-memory tableau (sweep_coop.hip) — unless a previous attempt of this very
+    // call found the device too crowded for its grid barrier (`coop_fallback`, set below)
+    const bool coop = !c->use_reg && cnt == 1 && !c->knobs.no_coop && !c->coop_fallback;
+    c->coop_fallback = false;
+    if (coop) {
+        const size_t need = ((size_t)2 * ld * ld + (size_t)n / 8 + 2) * sizeof(double);  // two tableau images + basis flags + current image
+        if (c->scratch.bytes < need) c->coop_state_valid = false;
+        PARTLS_HIP_CHECK(c->scratch.ensure(need));
+    } else {
+        c->coop_state_valid = false;
+        const partls_status ss = ensure_sweep_scratch(c, grid);
+        if (ss != PARTLS_OK) return ss;
+    }
+    PARTLS_HIP_CHECK(hipMemsetAsync(c->nodeSol.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->nodeCode.p, codes.data(), cnt * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    SweepParams p;
+    const partls_status ps = node_sweep_params(c, cnt, 1, grid, &p);
+    if (ps != PARTLS_OK) return ps;
+    bind_counters(p, c->nodeSol.as<unsigned long long>());
+    p.node_code = c->nodeCode.as<int8_t>();
+    p.node_obj2 = c->nodeSol.as<double>() + 4; p.node_sol = c->nodeSol.as<double>() + 4 + cnt; p.node_ld = n;
+    // the caller will refine this one solution: have the register kernel leave its final tableau (refine_solution's solver)
+    // (the cooperative kernel's tableau already lives in global memory: the current image and its basis flags are copied below)
+    const bool dump_reg = want_tab && cnt == 1 && c->use_reg, dump_coop = want_tab && coop;
+    const bool dump = dump_reg || dump_coop;
+    const size_t tabd = dump_reg ? sweep_reg_t0_doubles(c->T) : (dump_coop ? (size_t)ld * ld : 0);
+    if (dump) {
+        if (dump_reg) {
+            PARTLS_HIP_CHECK(c->nodeTab.ensure(tabd * sizeof(double)));
+            PARTLS_HIP_CHECK(c->nodeBasic.ensure((size_t)16 * c->T));
+        }
+        if (c->hTabDoubles < tabd) {                                   // pinned: the 0.3 MB copy then costs ~20 us instead of ~150
+            c->hTabDoubles = 0;
+            PARTLS_HIP_CHECK(c->hTab.alloc(tabd));
+            PARTLS_HIP_CHECK(c->hBasic.alloc(1024 + 16 /* >= 16 x MAXT of sweep_blk.hip, >= n + 1 <= 1024 flags of the cooperative kernel */));
+            c->hTabDoubles = tabd;
+        }
+        if (dump_reg) { p.node_tab = c->nodeTab.as<double>(); p.node_basic = c->nodeBasic.as<int8_t>(); }
+    }
+    if (coop) {
+        // one large problem: many workgroups cooperate on a single global-memory tableau (sweep_coop.hip)
+        p.T0 = c->Tfull.as<double>();
+        p.resume = (resume && c->coop_state_valid) ? 1 : 0;
+        PARTLS_HIP_CHECK(c->gridCtr.ensure(64));
+        p.grid_ctr = c->gridCtr.as<unsigned>();
+        p.coop_fault = c->knobs.coop_fault;
+        c->coop_state_valid = false;                                   // until this launch is known to have completed
+        // 6 rows per workgroup (measured at n = 513: 0.87 / 0.81 / 0.79 / 0.85 ms per alpha-step with 16 / 8 / 6 / 4): its 16 waves take
+        // half a row each in the fused update (gj_apply); more workgroups than that only lengthen the grid barrier
+        const int rows_wg = c->knobs.coop_rows > 0 ? c->knobs.coop_rows : 6;
+        int nwg = (ld + rows_wg - 1) / rows_wg;
+        if (nwg > 128) nwg = 128;
+        PARTLS_HIP_CHECK(launch_sweep_coop(p, nwg, c->stream));
+    } else {
+        PARTLS_HIP_CHECK(launch_any_sweep(c, p, grid));
+    }
+    unsigned long long counters[4] = {0, 0, 0, 0};                 // unconverged, pivots, vetoes, (cooperative kernel) blocks
+    // page-locked up to 64 MB (a fit's single solves and node batches: KBs to a few MB); a caller that bounds a million nodes in one cold
+    // batch gets a pageable buffer instead of gigabytes of pinned host memory
+    std::vector<double> outw_big;
+    double *outw_buf;
+    if (out_words <= ((size_t)64 << 20) / sizeof(double)) { PARTLS_HIP_CHECK(c->nodeOut.resize(out_words)); outw_buf = c->nodeOut.data(); }
+    else { outw_big.resize(out_words); outw_buf = outw_big.data(); }
+    const double *outw = outw_buf;
+    PARTLS_HIP_CHECK(hipMemcpyAsync(outw_buf, c->nodeSol.p, out_words * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (dump_reg) {
+        PARTLS_HIP_CHECK(hipMemcpyAsync(c->hTab, c->nodeTab.p, tabd * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(c->hBasic, c->nodeBasic.p, (size_t)16 * c->T, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (dump_coop) {                                               // flags [n] + index of the current tableau image, then that image
+        const char *flagbuf = static_cast<const char *>(c->scratch.p) + (size_t)2 * ld * ld * sizeof(double);
+        PARTLS_HIP_CHECK(hipMemcpyAsync(c->hBasic, flagbuf, (size_t)n + 1, hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        const size_t img = (size_t)(c->hBasic[n] & 1) * ld * ld;
+        PARTLS_HIP_CHECK(hipMemcpyAsync(c->hTab, c->scratch.as<double>() + img, tabd * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    std::memcpy(counters, outw, sizeof(counters));
+    if (coop && (counters[0] >> 40)) {
+        // grid-barrier timeout: some workgroups of the cooperative grid were not resident (the device is shared with another
+        // context or process).  Nothing of that attempt is used; the same node is solved again by ONE workgroup, which needs no
+        // co-residency (slower, never hangs).
+        c->coop_fallback = true;
+        return solve_nodes(c, codes, cnt, sols, obj2, unconv, false, want_tab);
+    }
+    if (coop) c->coop_state_valid = counters[0] == 0;
+    std::copy(outw + 4, outw + 4 + cnt, obj2.begin());
+    std::copy(outw + 4 + cnt, outw + out_words, sols.begin());
+    if (unconv) *unconv = counters[0];
+    c->last_pivots = counters[1]; c->last_vetoes = counters[2]; c->last_blocks = counters[3];
+    c->tab_valid = dump && counters[0] == 0;
+    c->tab_full = dump_coop;                                       // layout of hTab: full (n+1)^2 matrix, or the register kernel's tiles
+    return PARTLS_OK;
+}
+
+partls_status solve_nodes_device(partls_ctx *c, size_t cnt, const int8_t *code, double *obj2, double *sol,
+                                 unsigned long long *counters, int max_rounds)
+{
+    c->tab_valid = false;
+    c->coop_state_valid = false;
+    if (cnt == 0) return PARTLS_OK;
+    const int n = c->n;
+    const int grid = (int)std::min<size_t>(cnt, c->use_reg ? 2048 : 512);
+    SweepParams p;
+    partls_status st = ensure_sweep_scratch(c, grid);
+    if (st == PARTLS_OK) st = node_sweep_params(c, cnt, 1, grid, &p);
+    if (st != PARTLS_OK) return st;
+    p.max_rounds = max_rounds;
+    bind_counters(p, counters);
+    p.node_code = code; p.node_obj2 = obj2; p.node_sol = sol; p.node_ld = n;
+    PARTLS_HIP_CHECK(launch_any_sweep(c, p, grid));
+    return PARTLS_OK;
+}
+
+}  // namespace partls
+
+using namespace partls;
+
+// Which group sits on which bit of the Gray index.  Bit b flips in 2^-(b+1) of all transitions and a flip exchanges roughly the
+// variables of its group that carry signal, so the cheap groups belong on the fast bits: on C3 the reference's order (group k on
+// bit k) costs 16.9 M pivots / 74.9 ms, the measured-cost order 13.2 M / 51.0 ms for the same 2^20 subproblems.  The cost of a flip
+// is MEASURED on the prepared problem: `ncu` chains of nodes on the kernel the sweep will use, chain c solving a pseudo-random pattern from
+// scratch and then flipping the groups of its half of the bits one after the other (each node warm-started from its predecessor,
+// exactly as in the sweep); pivots per flip are averaged per group.  Wall time = one chain = (8 + K'/2) patterns' worth, paid once
+// per prepare and only when the sweep is long enough to repay it.  Deterministic (fixed walks, no atomics in the solves), so every
+// rank of a sharded sweep derives the same order from the same data; dist.py cross-checks that before trusting the shards.
+partls_status partls::calibrate_bit_order(partls_ctx *c)
+{
+    const int kb = c->kbits, n = c->n;
+    c->order_ready = true;
+    c->order_identity = true;
+    c->flip_cost.clear();
+    for (int k = 0; k < 40; ++k) c->order.gbit[k] = (uint8_t)k;
+    if (kb < 2 || c->knobs.bit_order == 1) return PARTLS_OK;
+    const int ncu = c->ncu;
+    const int nseg = kb >= 8 ? 2 : 1;
+    const int seg_len = (kb + nseg - 1) / nseg, L = seg_len + 1;
+    // one calibration chain costs about (8 + seg_len) patterns (8: the solve from scratch); the sweep gives every CU 2^kb / ncu of them.
+    // What it buys depends on the data (nothing when the groups cost the same, a third of the sweep on C3): run it when it costs <= 3 %
+    if (c->knobs.bit_order != 2 && ((int64_t)1 << kb) < (int64_t)ncu * 32 * (8 + seg_len)) return PARTLS_OK;
+    const int chains = std::max(ncu - ncu % nseg, 2 * nseg);
+    const size_t steps = (size_t)chains * L;
+
+    PARTLS_HIP_CHECK(c->nodeCode.ensure(steps * (size_t)n));
+    PARTLS_HIP_CHECK(c->nodePiv.ensure((3 * steps + 8) * sizeof(unsigned)));
+    PARTLS_HIP_CHECK(c->nodeSol.ensure((4 + (size_t)chains + (size_t)chains * n) * sizeof(double)));
+    SweepParams p;
+    partls_status st = ensure_sweep_scratch(c, chains);
+    if (st == PARTLS_OK) st = node_sweep_params(c, steps, L, chains, &p);
+    if (st != PARTLS_OK) return st;
+    PARTLS_HIP_CHECK(hipMemsetAsync(c->nodePiv.p, 0, 8 * sizeof(unsigned), c->stream));          // [unconverged (8 B) | ... | pivots per step]
+    t_begin(c, PARTLS_T_CALIB);
+    PARTLS_HIP_CHECK(launch_walk_codes(c->maskTabP, n, kb, chains, L, seg_len, nseg, c->nodeCode.as<int8_t>(), c->stream));
+    p.n_unconverged = c->nodePiv.as<unsigned long long>();
+    p.node_code = c->nodeCode.as<int8_t>();
+    p.node_obj2 = c->nodeSol.as<double>() + 4; p.node_sol = c->nodeSol.as<double>() + 4 + chains; p.node_ld = n;
+    p.node_piv = c->nodePiv.as<unsigned>() + 8;                    // 3 counters per step
+    PARTLS_HIP_CHECK(launch_any_sweep(c, p, chains));
+    t_end(c, PARTLS_T_CALIB);
+    std::vector<unsigned> piv(3 * steps + 8);
+    PARTLS_HIP_CHECK(hipMemcpyAsync(piv.data(), c->nodePiv.p, (3 * steps + 8) * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    t_collect(c);
+    c->coop_state_valid = false;
+    c->tab_valid = false;
+    unsigned long long unconv = 0;
+    std::memcpy(&unconv, piv.data(), sizeof(unconv));
+    if (unconv) return PARTLS_OK;                            // a walk hit the pivot cap: the sample says nothing, keep the plain order
+
+    // Cost of a flip in pivot equivalents.  On the register kernel a pattern's cycles split (stamp build) into ~730 + 4.4 NS
+    // per pivot (panel step + update; NS = tile slots), ~4 400 per block pivot (gather, scatter, the update's start, barrier waits) and
+    // ~2 100 per KKT scan beyond the first, which every pattern pays: a group whose variables straddle tile columns so that a flip takes
+    // three blocks instead of two costs as much more as four extra pivots would.  All three counts are exact (no timing), so the
+    // order stays a deterministic function of the data.
+    const double ns = c->use_reg ? 0.5 * c->T * (c->T + 1) : 0.0;
+    const double per_pivot = 730.0 + 4.4 * ns;
+    const double w_block = c->use_reg ? c->knobs.cal_wb * 4400.0 / per_pivot : 0.0, w_scan = c->use_reg ? c->knobs.cal_ws * 2100.0 / per_pivot : 0.0;
+    std::vector<double> cost((size_t)kb, 0.0);
+    std::vector<int> cnt((size_t)kb, 0);
+    for (int ch = 0; ch < chains; ++ch)
+        for (int i = 1; i < L; ++i) {
+            const int k = walk_flipped_bit(ch, i, kb, seg_len, nseg);
+            const unsigned *now = &piv[8 + 3 * ((size_t)ch * L + i)], *was = now - 3;
+            const double scans = (double)(now[2] - was[2]);
+            cost[(size_t)k] += (double)(now[0] - was[0]) + w_block * (double)(now[1] - was[1]) + w_scan * (scans > 1.0 ? scans - 1.0 : 0.0);
+            ++cnt[(size_t)k];
+        }
+    for (int k = 0; k < kb; ++k) cost[(size_t)k] = cnt[(size_t)k] ? cost[(size_t)k] / cnt[(size_t)k] : 0.0;
+    std::vector<int> by_cost((size_t)kb);
+    std::iota(by_cost.begin(), by_cost.end(), 0);
+    std::stable_sort(by_cost.begin(), by_cost.end(), [&](int a, int b) { return cost[(size_t)a] < cost[(size_t)b]; });
+    c->flip_cost = cost;
+    // pivots per pattern the additive model predicts: sum_b 2^-(b+1) cost(group on bit b).  Sorting noisy estimates of equal costs always
+    // "predicts" a gain of about their standard error (~1 %): below 2 % the reference's order stays (measured on such problems: +-1 %)
+    double pred_ref = 0.0, pred_sorted = 0.0, wgt = 0.5;
+    for (int b = 0; b < kb; ++b, wgt *= 0.5) { pred_ref += wgt * cost[(size_t)b]; pred_sorted += wgt * cost[(size_t)by_cost[(size_t)b]]; }
+    if (c->knobs.bit_order != 2 && !(pred_sorted < 0.98 * pred_ref)) return PARTLS_OK;
+    bool ident = true;
+    for (int b = 0; b < kb; ++b) { c->order.gbit[by_cost[(size_t)b]] = (uint8_t)b; ident = ident && by_cost[(size_t)b] == b; }
+    if (ident) return PARTLS_OK;
+    std::vector<uint64_t> mi((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        uint64_t m = c->mask_tab[(size_t)i], q = 0;
+        for (; m; m &= m - 1) q |= 1ULL << c->order.gbit[__builtin_ctzll(m)];
+        mi[(size_t)i] = q;
+    }
+    PARTLS_HIP_CHECK(c->maskInt.ensure((size_t)n * sizeof(uint64_t)));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->maskInt.p, mi.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));     // `mi` is pageable and goes out of scope
+    c->order_identity = false;
+    return PARTLS_OK;
+}
+
+// internal pattern (group k on bit gbit[k]) -> the reference's pattern index (group k on bit k)
+int64_t partls::reference_pattern(const partls_ctx *c, int64_t q)
+{
+    if (q < 0 || c->order_identity) return q;
+    uint64_t r = 0;
+    for (int k = 0; k < c->kbits; ++k) r |= (((uint64_t)q >> c->order.gbit[k]) & 1ULL) << k;
+    return (int64_t)r;
+}
+
+// Chain length and grid of a sweep over `total` Gray indices (partls_opt_sweep; partls_opt_models per piece: the same plan for the same
+// range, so its rows carry the objectives all_opt gets).  false (error set): the range needs more than 2^31 chains.
+bool partls::sweep_plan(partls_ctx *c, int64_t total, int64_t *chain_len_out, int *grid_out, const char *who)
+{
+    // Chain length.  A chain start costs ~8 patterns' pivots, so chains should be long (~1024 patterns), but the register kernel runs ONE
+    // chain per CU at a time and the chains of a range take almost equally long: the sweep lasts ceil(chains / CUs) chain times, and a
+    // chain count that is not a multiple of the CU count pays for the whole last round (measured on C3, 256 CUs: 1024 chains of 1024
+    // patterns 74.9 ms, 768 of 1366 75.1, but 820 of 1280 90.6 and 1366 of 768 81.5).  So: a whole number k >= 2 of chains per CU.
+    int64_t chain_len;
+    if (c->knobs.chain_len > 0) chain_len = c->knobs.chain_len;
+    else if (c->use_reg) {
+        const int ncu = c->ncu;
+        // ~1024 patterns per chain; 2048 once that still leaves every CU 8 or more chains to balance with (C5, 2^24 patterns: 690.6 ->
+        // 686.7 ms; 4096: 686.6, 8192: 689.8)
+        const int64_t per_chain = total >= (int64_t)ncu * 2048 * 8 ? 2048 : 1024;
+        const int conc = sweep_reg_concurrency(c->T);           // chains a CU runs at once: 1, or the 256-thread kernel's occupancy
+        if (conc > 1) {
+            // small tableaus: `slots` chains run at the same time, so a short enumeration is cut into exactly that many chains — down to
+            // 4 patterns each: a chain start costs about 8 patterns' pivots, but an idle slot costs a whole chain (BASELINE config 2, 4096
+            // patterns on 256 x 3 slots: 683 chains of 6 instead of 256 of 16)
+            const int64_t slots = (int64_t)ncu * conc;
+            const int64_t k = std::max<int64_t>(1, (total + slots * per_chain - 1) / (slots * per_chain));
+            chain_len = std::max<int64_t>(4, (total + k * slots - 1) / (k * slots));
+        } else {
+        int64_t k = (total + (int64_t)ncu * per_chain - 1) / ((int64_t)ncu * per_chain);
+        if (k < 2) k = 2;
+        chain_len = (total + k * ncu - 1) / (k * ncu);
+        if (chain_len < 16) chain_len = 16;                     // tiny ranges: fewer chains than CUs rather than chains of a few patterns
+        }
+    } else {
+        // global-memory kernels (n > 320): a chain start costs ~n/2 pivots (the first pattern is solved from the empty basis) against ~25 per
+        // warm-started pattern, so chains are as long as still leaves every CU one (measured at D = 340, 2^16 / 2^18 patterns: 64 -> 3.79 /
+        // 4.17 M solves/s, 128 -> 3.90 / 4.37, 256 -> 4.01 / 4.46)
+        const int ncu = c->ncu;
+        chain_len = 256;
+        while (chain_len > 16 && (total + chain_len - 1) / chain_len < ncu) chain_len >>= 1;
+    }
+    if (chain_len < 1) chain_len = 1;
+    const int64_t nchains = (total + chain_len - 1) / chain_len;
+    if (nchains >= (1LL << 31) || chain_len >= (1LL << 31)) { set_error("%s: more than 2^31 chains in one call; split the Gray-index range", who); return false; }
+    int grid = (int)std::min<int64_t>(nchains, c->knobs.grid > 0 ? c->knobs.grid : (c->use_reg ? 4096 : 1024));
+    if (grid < 1) grid = 1;
+    *chain_len_out = chain_len;
+    *grid_out = grid;
+    return true;
+}
+
+// The host half of a sweep: counters, winner and near ties from the per-workgroup block the kernel left (sweep_out: the host copy of a
+// sweep_block with runner-up columns).  Installs what partls_opt_finish reads: export_wg (has_sol: the kernel wrote bestSol), near_for,
+// near_pat, cand.  partls_opt_sweep and the batched sweep of partls_cv_opt (cv.hip, one block per problem) share it.
+void partls::install_sweep_result(partls_ctx *c, const double *sweep_out, int grid, bool has_sol, double *bobj_out, int64_t *bpat_out)
+{
+    const SweepBlock b = sweep_block(const_cast<double *>(sweep_out), grid, true);     // read only
+    c->last_pivots = b.counters[1];
+    c->last_vetoes = b.counters[2];
+    c->sweep_vetoes = b.counters[2];
+    c->export_wg = -1;
+    std::vector<int64_t> bp((size_t)grid);
+    double bobj = INFINITY;
+    int64_t bpat = -1;
+    int best_wg = -1;
+    for (int i = 0; i < grid; ++i) {                     // argmin with first-index tie-break (Opt.jl:96)
+        bp[(size_t)i] = reference_pattern(c, b.best_pat[i]);
+        if (bp[(size_t)i] < 0) continue;
+        if (bpat < 0 || b.best_obj[i] < bobj || (b.best_obj[i] == bobj && bp[(size_t)i] < bpat)) { bobj = b.best_obj[i]; bpat = bp[(size_t)i]; best_wg = i; }
+    }
+    if (has_sol) c->export_wg = best_wg;                 // row of bestSol that holds the winner's solution (valid while near_for == winner)
+    // Near ties (near_tie.h): each workgroup reports its minimum and its runner-up; those within the Gram form's own error of the winner
+    // are remembered (at most 3, best first) and partls_opt_finish re-ranks them with the objective from the data.
+    c->near_pat.clear();
+    c->cand.clear();
+    c->near_for = bpat;
+    if (bpat >= 0) {
+        const double yy = h_reg(c, (int)c->M + 1, (int)c->M + 1);
+        const double lim2 = bobj * bobj + c->knobs.near_tie_rel * (yy > 0.0 ? yy : 0.0);
+        std::vector<std::pair<double, int64_t>> others;
+        for (int i = 0; i < grid; ++i) {
+            if (bp[(size_t)i] >= 0) others.emplace_back(b.best_obj[i], bp[(size_t)i]);
+            if (b.second_pat[i] >= 0) others.emplace_back(b.second_obj[i], reference_pattern(c, b.second_pat[i]));
+        }
+        install_near_ties({bobj, bpat}, std::move(others), lim2, 3, c->cand, c->near_pat, c->near_for);
+    }
+    *bobj_out = bobj;
+    *bpat_out = bpat;
+}

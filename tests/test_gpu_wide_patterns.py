@@ -3,7 +3,7 @@
 Gray index 2^32; these tests run the device and host paths that carry a pattern, a Gray index or a bit position there: the register
 kernels' 32-bit loop state (sweep_blk.hip), the 64-bit walks of sweep_lazy.hip / sweep_generic.hip, ref_index_less (common.h), the
 cleanup kernel's Gray index -> internal pattern -> reference index (models.hip), the calibration's walk over bits 20-39 (misc.hip),
-reference_pattern / install_sweep_result / partls_opt_finish / _pattern / _candidates / _merge_candidates (api.hip), the wrappers (api.py).
+reference_pattern / install_sweep_result / partls_opt_finish / _pattern / _candidates / _merge_candidates (sweep_setup.hip, opt.hip), the wrappers (api.py).
 
 SAFETY: a full sweep at 40 bits would keep a card busy for half a day and a running kernel cannot be stopped from Python.  Every
 opt_sweep / opt_models call of this file goes through wide_reference.guarded (an explicit range of at most 4096 indices inside the
