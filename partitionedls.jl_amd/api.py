@@ -8,7 +8,9 @@ import atexit
 import ctypes as C
 import warnings
 import weakref
+from contextlib import contextmanager
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
@@ -81,47 +83,128 @@ def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int64))
 
 
-def _is_f32(dtype):
-    """float32 is the one element type besides float64 that X may keep on its way to the device"""
-    return dtype is not None and np.dtype(dtype) == np.float32
+def _i32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
-def _x_host(X):
-    """host X as the library takes it — the ONE place that decides: a float32 array stays float32, every other dtype becomes float64;
-    F-contiguous either way (a C-ordered or strided input is copied, never widened; an array already in that form is returned as it is)"""
-    return np.asfortranarray(X, dtype=np.float32 if _is_f32(getattr(X, "dtype", None)) else np.float64)
+def _u64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint64))
 
 
-def _x_dtype(dtype, who):
-    if dtype is None or np.dtype(dtype) == np.float64:
-        return np.float64
-    if np.dtype(dtype) == np.float32:
-        return np.float32
-    raise TypeError("%s: dtype must be float64 or float32, got %s" % (who, np.dtype(dtype)))
+def _inputs(X, y, P, f32=True):
+    """host X, y (or None), P as the library takes them — the ONE place that decides dtype and layout.  X: a float32 array stays float32
+    where the entry has a float32 form (f32), every other dtype becomes float64; F-contiguous either way (a C-ordered or
+    strided input is copied, never widened; an array already in that form is returned as it is).  y: float64.  P: F-contiguous int64."""
+    xt = np.float32 if f32 and getattr(X, "dtype", None) == np.float32 else np.float64
+    return (np.asfortranarray(X, dtype=xt), None if y is None else np.ascontiguousarray(y, dtype=np.float64),
+            np.asfortranarray(P, dtype=np.int64))
+
+
+def _weights(weights, N, who=None):
+    """per-row sample weights as the library takes them: a contiguous float64 vector of length N, or None.  who ("fit",
+    "cross_validate"): checked in full on the host before any device work — floating, finite, >= 0, sum > 0 (ValueError otherwise)."""
+    if weights is None:
+        return None
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (N,):
+        raise ValueError("weights: expected shape (%d,), got %s" % (N, w.shape))
+    if who:
+        if not np.issubdtype(np.asarray(weights).dtype, np.floating):
+            raise ValueError("%s: weights must be floating point, got %s" % (who, np.asarray(weights).dtype))
+        if not np.all(np.isfinite(w)):
+            raise ValueError("%s: weights must be finite" % who)
+        if np.any(w < 0):
+            raise ValueError("%s: weights must be >= 0" % who)
+        if not w.sum() > 0:
+            raise ValueError("%s: the weights sum to 0" % who)
+    return w
+
+
+def _f32(dtype, who):
+    """element type of a device-resident X, declared by the caller: True for float32, False for float64 (or None)"""
+    dtype = np.dtype(np.float64 if dtype is None else dtype)
+    if dtype not in (np.float64, np.float32):
+        raise TypeError("%s: dtype must be float64 or float32, got %s" % (who, dtype))
+    return dtype == np.float32
+
+
+class _Model:
+    """The output set of a call that returns one model: alpha[M], beta[K], t, opt and one int64 (best_index / iters / nopen)."""
+
+    def __init__(self, M, K):
+        self.a, self.b = np.zeros(M), np.zeros(K)
+        self.t, self.o, self.n = C.c_double(), C.c_double(), C.c_int64()
+        self.ptrs = (_dp(self.a), _dp(self.b), C.byref(self.t), C.byref(self.o), C.byref(self.n))     # in the order of the C ABI
+
+    def result(self):
+        return self.a, self.b, self.t.value, self.o.value, self.n.value
+
+
+def _ill(obj, st):
+    """status of a call on obj (Context / MultiContext) whose outputs are filled even when it reports PARTLS_ERR_ILL_CONDITIONED
+    (include/partls.h): raised, or with obj.tolerate_ill recorded in obj.last_ill"""
+    _check(st, (L.ERR_ILL_CONDITIONED,) if obj.tolerate_ill else ())
+    obj.last_ill = st == L.ERR_ILL_CONDITIONED
+
+
+@contextmanager
+def _tolerating(on_ill_conditioned, *objs):
+    """fit's on_ill_conditioned ("warn": tolerate status 9) holds on objs (Context / MultiContext, or None) inside the block only: what
+    their user set comes back on every way out"""
+    saved = [(o, o.tolerate_ill) for o in objs if o is not None]
+    try:
+        for o, _ in saved:
+            o.tolerate_ill = on_ill_conditioned == "warn"
+        yield
+    finally:
+        for o, was in saved:
+            o.tolerate_ill = was
+
+
+def _host_fit(obj, entry, X, y, P, eta, *options, all_opt=()):
+    """One-call fit of marshalled host float64 inputs on obj (Context / MultiContext): partls_fit_alt, partls_fit_bnb, partls_fit_opt_multi
+    and partls_fit_bnb_multi share the argument list up to η, take their options next, write one model (_Model) and, Opt, all_opt last"""
+    N, M = X.shape
+    K = P.shape[1]
+    out = _Model(M, K)
+    obj.generation += 1
+    _ill(obj, entry(obj._h, X.ctypes.data, N, M, N, y.ctypes.data, P.ctypes.data, K, M, float(eta), *options, *out.ptrs, *all_opt))
+    obj._shape = (N, M, K)
+    return out.result()
 
 
 class Context:
     """Thin owner of a partls_ctx (one per device)."""
 
-    def __init__(self, device=0):
-        self._h = C.c_void_p()
-        _check(L.lib().partls_create(int(device), C.byref(self._h)))
-        self.device = device
+    def __init__(self, device=0, *, _owner=None, _handle=None):
+        """_owner, _handle: a non-owning view of the rank context _handle of the MultiContext _owner (MultiContext.context)"""
+        self._h = C.c_void_p(_handle)
+        self._owner, self._borrowed = _owner, _owner is not None
+        if not self._borrowed:
+            _check(L.lib().partls_create(int(device), C.byref(self._h)))
+            _live_contexts.add(self)
+        self.device = None if self._borrowed else device
         self.generation = 0          # bumped by every prepare: lazily rebuilt results check it (see _Solutions)
-        self.tolerate_ill = False    # True: status 9 (outputs hold the best Gram-form model) is recorded in last_ill instead of raised
+        self._tolerate_ill = False
         self.last_ill = False
-        _live_contexts.add(self)
 
-    def _ill(self, st):
-        """status of a call whose outputs are filled even when it reports PARTLS_ERR_ILL_CONDITIONED (include/partls.h)"""
-        _check(st, (L.ERR_ILL_CONDITIONED,) if getattr(self, "tolerate_ill", False) else ())
-        self.last_ill = st == L.ERR_ILL_CONDITIONED
+    @property
+    def tolerate_ill(self):
+        """True: status 9 (outputs hold the best Gram-form model) is recorded in last_ill instead of raised.  A view has no setting of
+        its own: it reads its MultiContext's at every call."""
+        return self._tolerate_ill if self._owner is None else self._owner.tolerate_ill
+
+    @tolerate_ill.setter
+    def tolerate_ill(self, value):
+        if self._owner is not None:
+            raise AttributeError("a view takes tolerate_ill from its MultiContext: set it there")
+        self._tolerate_ill = bool(value)
 
     def close(self):
         """Release the device objects now.  Also run for every live context by an atexit hook, i.e. BEFORE interpreter
         finalisation and before the HIP runtime (or a profiler layered on it) tears itself down — a context destroyed later,
         from a module-global's __del__ during exit(), made HIP calls into a dead runtime (round-1 rocprofv3 crash)."""
-        if self._h and not getattr(self, "_borrowed", False):      # a view of a MultiContext's rank does not own the handle
+        if self._h and not self._borrowed:      # a view of a MultiContext's rank does not own the handle
             L.lib().partls_destroy(self._h)
         self._h = C.c_void_p()
 
@@ -137,49 +220,34 @@ class Context:
         partls_opt_prepare_weighted, after which every staged call on the problem is weighted.
         A float32 X stays float32 — uploaded and read as such through partls_opt_prepare_f32, with or without weights; the results are
         those of X.astype(float64) bit for bit.  Every other dtype is converted to float64; y always is."""
-        X = _x_host(X)
-        f32 = X.dtype == np.float32
-        y = np.ascontiguousarray(y, dtype=np.float64)
-        P = np.asfortranarray(P, dtype=np.int64)
+        X, y, P = _inputs(X, y, P)
         N, M = X.shape
-        self._shape = (N, M, P.shape[1])
-        self.generation += 1
-        if f32:
-            w = None
-            if weights is not None:
-                w = np.ascontiguousarray(weights, dtype=np.float64)
-                if w.shape != (N,):
-                    raise ValueError("weights: expected shape (%d,), got %s" % (N, w.shape))
-            _check(L.lib().partls_opt_prepare_f32(self._h, X.ctypes.data, N, M, N, y.ctypes.data, None if w is None else w.ctypes.data, 0,
-                                                  P.ctypes.data, P.shape[1], P.shape[0], float(eta), int(flags)))
-        elif weights is None:
-            _check(L.lib().partls_opt_prepare(self._h, X.ctypes.data, N, M, N, y.ctypes.data, 0, P.ctypes.data, P.shape[1],
-                                              P.shape[0], float(eta), int(flags)))
-        else:
-            w = np.ascontiguousarray(weights, dtype=np.float64)
-            if w.shape != (N,):
-                raise ValueError("weights: expected shape (%d,), got %s" % (N, w.shape))
-            _check(L.lib().partls_opt_prepare_weighted(self._h, X.ctypes.data, N, M, N, y.ctypes.data, w.ctypes.data, 0, P.ctypes.data,
-                                                       P.shape[1], P.shape[0], float(eta), int(flags)))
+        w = _weights(weights, N)
+        self._prepare(X.ctypes.data, y.ctypes.data, None if w is None else w.ctypes.data, 0, X.dtype == np.float32, N, M, N, P, eta,
+                      flags)
 
     def opt_prepare_device(self, dX_ptr, dy_ptr, N, M, ldX, P, eta=0.0, flags=0, dw_ptr=None, dtype=np.float64):
         """dX_ptr, dy_ptr (and dw_ptr, optional per-row sample weights, N doubles): raw device addresses (e.g. torch tensor
         .data_ptr()) that stay owned by the caller.  dtype: element type of X — float64, or float32 (a float32 tensor; ldX counts
         elements; y and the weights stay float64): partls_opt_prepare_f32."""
-        P = np.asfortranarray(P, dtype=np.int64)
-        f32 = _x_dtype(dtype, "opt_prepare_device") == np.float32
+        f32 = _f32(dtype, "opt_prepare_device")
+        self._prepare(C.c_void_p(dX_ptr), C.c_void_p(dy_ptr), None if dw_ptr is None else C.c_void_p(dw_ptr), 1, f32, N, M, ldX,
+                      np.asfortranarray(P, dtype=np.int64), eta, flags)
+
+    def _prepare(self, xp, yp, wp, on_device, f32, N, M, ldX, P, eta, flags):
+        """The one prepare behind opt_prepare and opt_prepare_device.  xp, yp, wp (or None): addresses, on the host or (on_device) in
+        HBM; f32: X holds float32 (partls_opt_prepare_f32, weighted or not); P: F-contiguous int64."""
+        lib = L.lib()
+        head = (self._h, xp, N, M, ldX, yp)
+        tail = (on_device, P.ctypes.data, P.shape[1], P.shape[0], float(eta), int(flags))
         self._shape = (N, M, P.shape[1])
         self.generation += 1
         if f32:
-            _check(L.lib().partls_opt_prepare_f32(self._h, C.c_void_p(dX_ptr), N, M, ldX, C.c_void_p(dy_ptr),
-                                                  None if dw_ptr is None else C.c_void_p(dw_ptr), 1, P.ctypes.data, P.shape[1], P.shape[0],
-                                                  float(eta), int(flags)))
-        elif dw_ptr is None:
-            _check(L.lib().partls_opt_prepare(self._h, C.c_void_p(dX_ptr), N, M, ldX, C.c_void_p(dy_ptr), 1, P.ctypes.data,
-                                              P.shape[1], P.shape[0], float(eta), int(flags)))
+            _check(lib.partls_opt_prepare_f32(*head, wp, *tail))
+        elif wp is None:
+            _check(lib.partls_opt_prepare(*head, *tail))
         else:
-            _check(L.lib().partls_opt_prepare_weighted(self._h, C.c_void_p(dX_ptr), N, M, ldX, C.c_void_p(dy_ptr), C.c_void_p(dw_ptr), 1,
-                                                       P.ctypes.data, P.shape[1], P.shape[0], float(eta), int(flags)))
+            _check(lib.partls_opt_prepare_weighted(*head, wp, *tail))
 
     def num_patterns(self):
         return int(L.lib().partls_opt_num_patterns(self._h))
@@ -203,14 +271,9 @@ class Context:
         return bo.value, bp.value, allopt, nu.value
 
     def opt_finish(self, pattern):
-        N, M, K = self._shape
-        a = np.zeros(M)
-        b = np.zeros(K)
-        t = C.c_double()
-        o = C.c_double()
-        bi = C.c_int64()
-        self._ill(L.lib().partls_opt_finish(self._h, int(pattern), _dp(a), _dp(b), C.byref(t), C.byref(o), C.byref(bi)))
-        return a, b, t.value, o.value, bi.value
+        out = _Model(*self._shape[1:])
+        _ill(self, L.lib().partls_opt_finish(self._h, int(pattern), *out.ptrs))
+        return out.result()
 
     def opt_candidates(self):
         """(obj, pattern) arrays: this context's winner of the last sweep and its near ties (tracked objectives), best first."""
@@ -227,9 +290,7 @@ class Context:
         return wo.value, wp.value
 
     def near_ties_evaluated(self):
-        n = C.c_int64()
-        _check(L.lib().partls_get_near_ties(self._h, C.byref(n)))
-        return n.value
+        return self._count(L.lib().partls_get_near_ties)
 
     def opt_pattern(self, pattern):
         N, M, K = self._shape
@@ -265,28 +326,23 @@ class Context:
         (None or [] for the path only).  weights (host inputs) / dw_ptr (device inputs): optional per-row sample weights
         (partls_cv_opt_weighted).  Returns a dict of column-major results, one problem per column, q = f * E + e: alpha (M x B), beta (K x B),
         t, opt, best_index, heldout_sse, status (all length B)."""
-        P = np.asfortranarray(P, dtype=np.int64)
-        M, K = P.shape
         wp = None
         if device_ptrs is None:
-            X = np.asfortranarray(X, dtype=np.float64)
-            y = np.ascontiguousarray(y, dtype=np.float64)
-            N, M2 = X.shape
-            if M2 != M:
+            X, y, P = _inputs(X, y, P, f32=False)
+            N, ldX, on_dev = X.shape[0], X.shape[0], 0
+            if X.shape[1] != P.shape[0]:
                 raise ValueError("DimensionMismatch: X is %s, P is %s" % (X.shape, P.shape))
-            xp, yp, ldX, on_dev = X.ctypes.data, y.ctypes.data, N, 0
-            if weights is not None:
-                w = np.ascontiguousarray(weights, dtype=np.float64)
-                if w.shape != (N,):
-                    raise ValueError("weights: expected shape (%d,), got %s" % (N, w.shape))
-                wp = w.ctypes.data
+            w = _weights(weights, N)
+            xp, yp, wp = X.ctypes.data, y.ctypes.data, None if w is None else w.ctypes.data
         else:
             if weights is not None:
                 raise ValueError("cv_opt: device inputs take their weights as the fifth entry of device_ptrs")
+            P = np.asfortranarray(P, dtype=np.int64)
             dX, dy, N, ldX = device_ptrs[:4]
             xp, yp, on_dev = C.c_void_p(dX), C.c_void_p(dy), 1
             if len(device_ptrs) > 4 and device_ptrs[4] is not None:
                 wp = C.c_void_p(device_ptrs[4])
+        M, K = P.shape
         fp = np.ascontiguousarray([] if fold_ptr is None else fold_ptr, dtype=np.int64)
         F = max(len(fp) - 1, 0)
         et = np.ascontiguousarray(np.atleast_1d(etas), dtype=np.float64)
@@ -298,25 +354,22 @@ class Context:
         bi = np.zeros(B, dtype=np.int64)
         stat = np.zeros(B, dtype=np.int32)
         self.generation += 1
+        head = (self._h, xp, int(N), int(M), int(ldX), yp)
+        tail = (on_dev, P.ctypes.data, K, M, _ip(fp) if F else None, F, _dp(et), E, int(flags), _dp(alpha), M, _dp(beta), K, _dp(t), _dp(opt),
+                _ip(bi), _dp(sse), _i32p(stat))
         if wp is None:
-            _check(L.lib().partls_cv_opt(self._h, xp, int(N), int(M), int(ldX), yp, on_dev, P.ctypes.data, K, M, _ip(fp) if F else None, F,
-                                         _dp(et), E, int(flags), _dp(alpha), M, _dp(beta), K, _dp(t), _dp(opt), _ip(bi), _dp(sse),
-                                         stat.ctypes.data_as(C.POINTER(C.c_int32))))
+            _check(L.lib().partls_cv_opt(*head, *tail))
         else:
-            _check(L.lib().partls_cv_opt_weighted(self._h, xp, int(N), int(M), int(ldX), yp, wp, on_dev, P.ctypes.data, K, M,
-                                                  _ip(fp) if F else None, F, _dp(et), E, int(flags), _dp(alpha), M, _dp(beta), K, _dp(t),
-                                                  _dp(opt), _ip(bi), _dp(sse), stat.ctypes.data_as(C.POINTER(C.c_int32))))
+            _check(L.lib().partls_cv_opt_weighted(*head, wp, *tail))
         return dict(alpha=alpha, beta=beta, t=t, opt=opt, best_index=bi, heldout_sse=sse, status=stat, F=F, E=E)
 
     def alt_prepared(self, alpha0, beta0, eps=1e-6, T=100):
         """Alt on a context prepared with OPT_FAITHFUL_INTERCEPT (e.g. device-resident inputs)."""
         N, M, K = self._shape
         a0 = np.ascontiguousarray(alpha0, dtype=np.float64); b0 = np.ascontiguousarray(beta0, dtype=np.float64)
-        a = np.zeros(M); b = np.zeros(K)
-        t = C.c_double(); o = C.c_double(); it = C.c_int64()
-        self._ill(L.lib().partls_alt_prepared(self._h, float(eps), int(T), _dp(a0), _dp(b0), _dp(a), _dp(b), C.byref(t),
-                                              C.byref(o), C.byref(it)))
-        return a, b, t.value, o.value, it.value
+        out = _Model(M, K)
+        _ill(self, L.lib().partls_alt_prepared(self._h, float(eps), int(T), _dp(a0), _dp(b0), *out.ptrs))
+        return out.result()
 
     def alt_multistart(self, alpha0s, beta0s, eps=1e-6, T=100, raise_if_none=True):
         """Alt from R starting points in one batched device call (partls_alt_multistart) on a context prepared with
@@ -331,25 +384,22 @@ class Context:
             raise ValueError("alt_multistart: alpha0s must be (R, %d) and beta0s (R, %d) with R >= 1, got %s and %s"
                              % (M + 1, K + 1, a0.shape, b0.shape))
         R = a0.shape[0]
-        a = np.zeros(M); b = np.zeros(K)
-        t = C.c_double(); o = C.c_double(); it = C.c_int64(); best = C.c_int64()
+        out = _Model(M, K)
+        best = C.c_int64()
         aa = np.zeros((R, M)); ba = np.zeros((R, K)); ta = np.zeros(R); oa = np.zeros(R)
         ia = np.zeros(R, dtype=np.int64); sa = np.zeros(R, dtype=np.int32)
-        st = L.lib().partls_alt_multistart(self._h, float(eps), int(T), R, _dp(a0), M + 1, _dp(b0), K + 1, _dp(a), _dp(b), C.byref(t),
-                                           C.byref(o), C.byref(it), C.byref(best), _dp(aa), M, _dp(ba), K, _dp(ta), _dp(oa), _ip(ia),
-                                           sa.ctypes.data_as(C.POINTER(C.c_int32)))
+        st = L.lib().partls_alt_multistart(self._h, float(eps), int(T), R, _dp(a0), M + 1, _dp(b0), K + 1, *out.ptrs, C.byref(best),
+                                           _dp(aa), M, _dp(ba), K, _dp(ta), _dp(oa), _ip(ia), _i32p(sa))
         if st == L.ERR_NOT_CONVERGED and not raise_if_none:
             self.last_ill = False
         else:
-            self._ill(st)
-        return a, b, t.value, o.value, it.value, best.value, dict(opt=oa, iters=ia, status=sa, alpha=aa, beta=ba, t=ta)
+            _ill(self, st)
+        return out.result() + (best.value, dict(opt=oa, iters=ia, status=sa, alpha=aa, beta=ba, t=ta))
 
     def bnb_prepared(self):
-        N, M, K = self._shape
-        a = np.zeros(M); b = np.zeros(K)
-        t = C.c_double(); o = C.c_double(); no = C.c_int64()
-        self._ill(L.lib().partls_bnb_prepared(self._h, _dp(a), _dp(b), C.byref(t), C.byref(o), C.byref(no)))
-        return a, b, t.value, o.value, no.value
+        out = _Model(*self._shape[1:])
+        _ill(self, L.lib().partls_bnb_prepared(self._h, *out.ptrs))
+        return out.result()
 
     def bnb_bound(self, pats, frees):
         """Bound a batch of BnB nodes (pat[i], free[i]) on a prepared faithful context: (lb[count], branch[count])."""
@@ -359,9 +409,7 @@ class Context:
         lb = np.zeros(n)
         br = np.zeros(n, dtype=np.int32)
         if n:
-            _check(L.lib().partls_bnb_bound(self._h, n, pats.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                            frees.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(lb),
-                                            br.ctypes.data_as(C.POINTER(C.c_int32))))
+            _check(L.lib().partls_bnb_bound(self._h, n, _u64p(pats), _u64p(frees), _dp(lb), _i32p(br)))
         return lb, br
 
     def bnb_snap_begin(self):
@@ -375,16 +423,13 @@ class Context:
         n = len(pats)
         lb = np.zeros(n); br = np.zeros(n, dtype=np.int32); dst = np.full(n, -1, dtype=np.int32)
         if n:
-            i32 = C.POINTER(C.c_int32)
-            _check(L.lib().partls_bnb_bound_snap(self._h, n, pats.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                 frees.ctypes.data_as(C.POINTER(C.c_uint64)), src.ctypes.data_as(i32),
-                                                 dst.ctypes.data_as(i32), _dp(lb), br.ctypes.data_as(i32)))
+            _check(L.lib().partls_bnb_bound_snap(self._h, n, _u64p(pats), _u64p(frees), _i32p(src), _i32p(dst), _dp(lb), _i32p(br)))
         return lb, br, dst
 
     def bnb_snap_release(self, slots):
         sl = np.ascontiguousarray(slots, dtype=np.int32)
         if len(sl):
-            _check(L.lib().partls_bnb_snap_release(self._h, len(sl), sl.ctypes.data_as(C.POINTER(C.c_int32))))
+            _check(L.lib().partls_bnb_snap_release(self._h, len(sl), _i32p(sl)))
 
     def bnb_search(self, max_nodes=0):
         """The BnB search on a prepared faithful context (warm-started node bounds): (mu, pat, free, nodes_bounded)."""
@@ -393,35 +438,40 @@ class Context:
         return mu.value, pat.value, fr.value, nn.value
 
     def bnb_leaf(self, pat, free):
-        N, M, K = self._shape
-        a = np.zeros(M); b = np.zeros(K)
-        t = C.c_double(); o = C.c_double()
-        self._ill(L.lib().partls_bnb_leaf(self._h, C.c_uint64(int(pat)), C.c_uint64(int(free)), _dp(a), _dp(b), C.byref(t), C.byref(o)))
-        return a, b, t.value, o.value
+        out = _Model(*self._shape[1:])
+        _ill(self, L.lib().partls_bnb_leaf(self._h, C.c_uint64(int(pat)), C.c_uint64(int(free)), *out.ptrs[:4]))
+        return out.result()[:4]
 
     def predict(self, X, P, alpha, beta, t):
         """yhat = X (P .* alpha) beta .+ t for a host X of any layout (partls_predict).  A float32 X stays float32 — copied F-contiguous
         when it is C-ordered or strided, never widened — and is uploaded and read as such (partls_predict_f32); every
         other dtype is converted to float64."""
-        X = _x_host(X)
-        f32 = X.dtype == np.float32
-        P = np.asfortranarray(P, dtype=np.int64)
-        a = np.ascontiguousarray(alpha, dtype=np.float64)
-        b = np.ascontiguousarray(beta, dtype=np.float64)
+        X, _, P = _inputs(X, None, P)
         N, M = X.shape
         yh = np.zeros(N)
-        fn = L.lib().partls_predict_f32 if f32 else L.lib().partls_predict
-        _check(fn(self._h, X.ctypes.data, N, M, N, P.ctypes.data, P.shape[1], M, _dp(a), _dp(b), float(t), _dp(yh)))
+        self._predict(X.ctypes.data, 0, X.dtype == np.float32, N, M, N, P, alpha, beta, t, _dp(yh))
         return yh
 
     def predict_device(self, dX_ptr, N, M, ldX, P, alpha, beta, t, dyhat_ptr, dtype=np.float64):
         """the same with X (N x M, ldX, elements of `dtype`: float64 or float32) and yhat (N doubles) in HBM: raw device addresses"""
-        P = np.asfortranarray(P, dtype=np.int64)
+        self._predict(C.c_void_p(dX_ptr), 1, _f32(dtype, "predict_device"), int(N), int(M), int(ldX), np.asfortranarray(P, dtype=np.int64),
+                      alpha, beta, t, C.c_void_p(dyhat_ptr))
+
+    def _predict(self, xp, on_device, f32, N, M, ldX, P, alpha, beta, t, yhat):
+        """The one predict behind predict and predict_device: xp and yhat are addresses on the host or (on_device) in HBM"""
         a = np.ascontiguousarray(alpha, dtype=np.float64)
         b = np.ascontiguousarray(beta, dtype=np.float64)
-        fn = L.lib().partls_predict_device_f32 if _x_dtype(dtype, "predict_device") == np.float32 else L.lib().partls_predict_device
-        _check(fn(self._h, C.c_void_p(dX_ptr), int(N), int(M), int(ldX), P.ctypes.data, P.shape[1], int(M), _dp(a), _dp(b), float(t),
-                  C.c_void_p(dyhat_ptr)))
+        lib = L.lib()
+        if on_device:
+            fn = lib.partls_predict_device_f32 if f32 else lib.partls_predict_device
+        else:
+            fn = lib.partls_predict_f32 if f32 else lib.partls_predict
+        _check(fn(self._h, xp, N, M, ldX, P.ctypes.data, P.shape[1], M, _dp(a), _dp(b), float(t), yhat))
+
+    def _count(self, getter):
+        n = C.c_int64()
+        _check(getter(self._h, C.byref(n)))
+        return n.value
 
     def timing(self, which):
         ms = C.c_double()
@@ -435,20 +485,14 @@ class Context:
         return ms.value, b.value
 
     def pivots(self):
-        n = C.c_int64()
-        _check(L.lib().partls_get_pivots(self._h, C.byref(n)))
-        return n.value
+        return self._count(L.lib().partls_get_pivots)
 
     def vetoes(self):
-        n = C.c_int64()
-        _check(L.lib().partls_get_vetoes(self._h, C.byref(n)))
-        return n.value
+        return self._count(L.lib().partls_get_vetoes)
 
     def blocks(self):
         """pivot blocks of the cooperative kernel in the last single-node solve (0: the solve ran on another kernel)"""
-        n = C.c_int64()
-        _check(L.lib().partls_get_blocks(self._h, C.byref(n)))
-        return n.value
+        return self._count(L.lib().partls_get_blocks)
 
     def sweep_route(self):
         """(kernel, T): the sweep kernel of the prepared problem (or of the last cv_opt's problems) — L.ROUTE_REG_256, ROUTE_REG_512,
@@ -506,9 +550,8 @@ class Frontier:
     def next(self):
         """(total, pats, frees, src_slots, per_rank): this rank's share of the next round (views valid until the next call)"""
         tot = C.c_int64(); mine = C.c_int64()
-        u64 = C.POINTER(C.c_uint64); i32 = C.POINTER(C.c_int32)
-        _check(L.lib().partls_frontier_next(self._h, C.byref(tot), C.byref(mine), self._pat.ctypes.data_as(u64), self._free.ctypes.data_as(u64),
-                                            self._src.ctypes.data_as(i32), self._per.ctypes.data_as(i32)))
+        _check(L.lib().partls_frontier_next(self._h, C.byref(tot), C.byref(mine), _u64p(self._pat), _u64p(self._free), _i32p(self._src),
+                                            _i32p(self._per)))
         m = mine.value
         return tot.value, self._pat[:m], self._free[:m], self._src[:m], self._per.copy()
 
@@ -517,9 +560,7 @@ class Frontier:
         lb = np.ascontiguousarray(lb, dtype=np.float64); br = np.ascontiguousarray(branch, dtype=np.int32)
         ds = np.ascontiguousarray(dst, dtype=np.int32)
         nd = C.c_int64()
-        i32 = C.POINTER(C.c_int32)
-        _check(L.lib().partls_frontier_ingest(self._h, _dp(lb), br.ctypes.data_as(i32), ds.ctypes.data_as(i32),
-                                              self._dead.ctypes.data_as(i32), len(self._dead), C.byref(nd)))
+        _check(L.lib().partls_frontier_ingest(self._h, _dp(lb), _i32p(br), _i32p(ds), _i32p(self._dead), len(self._dead), C.byref(nd)))
         return self._dead[:nd.value].copy()
 
     def result(self):
@@ -580,46 +621,19 @@ class MultiContext:
         h = L.lib().partls_multi_context(self._h, int(rank))
         if not h:
             raise IndexError("rank out of range")
-        view = Context.__new__(Context)
-        view._h, view.device, view.generation, view._borrowed, view._owner = C.c_void_p(h), None, 0, True, self
-        view.tolerate_ill, view.last_ill = self.tolerate_ill, False
+        view = Context(_owner=self, _handle=h)
         self._views.add(view)
         return view
 
     def fit_opt(self, X, y, P, eta=0.0, flags=0, want_all=False):
-        X = np.asfortranarray(X, dtype=np.float64)
-        y = np.ascontiguousarray(y, dtype=np.float64)
-        P = np.asfortranarray(P, dtype=np.int64)
-        N, M = X.shape
-        K = P.shape[1]
-        a = np.zeros(M); b = np.zeros(K)
-        t = C.c_double(); o = C.c_double(); bi = C.c_int64()
-        allopt = np.full(1 << (K + 1), np.nan) if want_all else None
-        self.generation += 1
-        st = _check(L.lib().partls_fit_opt_multi(self._h, X.ctypes.data, N, M, N, y.ctypes.data, P.ctypes.data, K, M, float(eta),
-                                                 int(flags), _dp(a), _dp(b), C.byref(t), C.byref(o), C.byref(bi),
-                                                 _dp(allopt) if want_all else None),
-                    (L.ERR_ILL_CONDITIONED,) if self.tolerate_ill else ())
-        self.last_ill = st == L.ERR_ILL_CONDITIONED
-        self._shape = (N, M, K)
-        return a, b, t.value, o.value, bi.value, allopt
+        X, y, P = _inputs(X, y, P, f32=False)
+        allopt = np.full(1 << (P.shape[1] + 1), np.nan) if want_all else None
+        return _host_fit(self, L.lib().partls_fit_opt_multi, X, y, P, eta, int(flags),
+                         all_opt=(_dp(allopt) if want_all else None,)) + (allopt,)
 
     def fit_bnb(self, X, y, P, eta=0.0):
         """fit(BnB) with the frontier search sharded over the ranks (include/partls.h: partls_fit_bnb_multi): (alpha, beta, t, opt, nopen)"""
-        X = np.asfortranarray(X, dtype=np.float64)
-        y = np.ascontiguousarray(y, dtype=np.float64)
-        P = np.asfortranarray(P, dtype=np.int64)
-        N, M = X.shape
-        K = P.shape[1]
-        a = np.zeros(M); b = np.zeros(K)
-        t = C.c_double(); o = C.c_double(); no = C.c_int64()
-        self.generation += 1
-        st = _check(L.lib().partls_fit_bnb_multi(self._h, X.ctypes.data, N, M, N, y.ctypes.data, P.ctypes.data, K, M, float(eta),
-                                                 _dp(a), _dp(b), C.byref(t), C.byref(o), C.byref(no)),
-                    (L.ERR_ILL_CONDITIONED,) if self.tolerate_ill else ())
-        self.last_ill = st == L.ERR_ILL_CONDITIONED
-        self._shape = (N, M, K)
-        return a, b, t.value, o.value, no.value
+        return _host_fit(self, L.lib().partls_fit_bnb_multi, *_inputs(X, y, P, f32=False), eta)
 
     def timing(self, rank, which):
         ms = C.c_double()
@@ -688,9 +702,10 @@ def regularizeProblem(X, y, P, η):
 # ---------------------------------------------------------------------------------------------------------------------
 # fit / predict
 # ---------------------------------------------------------------------------------------------------------------------
-def _marshal(X, y, P, keep_f32=False):
-    """keep_f32: a float32 X stays float32 (F-contiguous: a C-ordered or strided input is copied, never widened) for the entry points
-    that read it as such; every other floating dtype, and every caller without keep_f32, gets float64."""
+def _fit_inputs(X, y, P, f32=False):
+    """fit's and cross_validate's argument checks (the reference's method signatures), then _inputs.  Float32 inputs
+    (test/runtests.jl:123-146): y is widened (N numbers), X only where the device path has no float32 form (f32 False); result fields
+    are abstract floats in the reference."""
     X = np.asarray(X)
     y = np.asarray(y)
     P = np.asarray(P)
@@ -702,31 +717,20 @@ def _marshal(X, y, P, keep_f32=False):
         raise TypeError("fit: P must be an integer matrix (P::Array{Int,2})")
     if X.shape[0] != y.shape[0] or P.shape[0] != X.shape[1]:
         raise ValueError("DimensionMismatch: X is %s, y is %s, P is %s" % (X.shape, y.shape, P.shape))
-    # Float32 inputs (test/runtests.jl:123-146): y is widened (N numbers), X only where the device path has no float32 form; result
-    # fields are abstract floats in the reference
-    xt = np.float32 if (keep_f32 and X.dtype == np.float32) else np.float64
-    return (np.asfortranarray(X, dtype=xt), np.ascontiguousarray(y, dtype=np.float64),
-            np.asfortranarray(P, dtype=np.int64))
+    return _inputs(X, y, P, f32)
 
 
-def _weights(weights, N, who):
-    """sample weights of fit / cross_validate, checked on the host before any device work: 1-D, length N, floating, finite, >= 0,
-    sum > 0 (ValueError otherwise) -> contiguous float64, or None"""
-    if weights is None:
-        return None
-    w = np.asarray(weights)
-    if w.ndim != 1 or w.shape[0] != N:
-        raise ValueError("%s: weights must be a vector of length N = %d, got shape %s" % (who, N, w.shape))
-    if not np.issubdtype(w.dtype, np.floating):
-        raise ValueError("%s: weights must be floating point, got %s" % (who, w.dtype))
-    w = np.ascontiguousarray(w, dtype=np.float64)
-    if not np.all(np.isfinite(w)):
-        raise ValueError("%s: weights must be finite" % who)
-    if np.any(w < 0):
-        raise ValueError("%s: weights must be >= 0" % who)
-    if not w.sum() > 0:
-        raise ValueError("%s: the weights sum to 0" % who)
-    return w
+def _generator(rng):
+    """rng as fit, cross_validate and cv_folds take it: None (fresh entropy), an int seed, or a numpy Generator (used as it is)"""
+    if rng is None or isinstance(rng, (int, np.integer)):
+        return np.random.default_rng(None if rng is None else int(rng))
+    return rng
+
+
+def _draw_start(gen, M, K):
+    """one starting point of Alt, (alpha0[M+1], beta0[K+1]), as the reference draws it"""
+    alpha0 = gen.random(M + 1)                                # Alt.jl:65
+    return alpha0, (gen.random(K + 1) - 0.5) * 10             # Alt.jl:66
 
 
 def _alt_starts(alg, M, K, restarts, alpha0, beta0, rng):
@@ -757,19 +761,21 @@ def _alt_starts(alg, M, K, restarts, alpha0, beta0, rng):
         if not (np.all(np.isfinite(a0)) and np.all(np.isfinite(b0))):
             raise ValueError("fit: the starting points must be finite")
         return a0, b0
-    if rng is None:
-        gen = np.random.default_rng()
-    elif isinstance(rng, (int, np.integer)):
-        gen = np.random.default_rng(int(rng))
-    else:
-        gen = rng
-    R = int(restarts)
-    a0 = np.empty((R, M + 1))
-    b0 = np.empty((R, K + 1))
-    for r in range(R):
-        a0[r] = gen.random(M + 1)                             # Alt.jl:65
-        b0[r] = (gen.random(K + 1) - 0.5) * 10                # Alt.jl:66
-    return a0, b0
+    gen = _generator(rng)
+    a0, b0 = zip(*[_draw_start(gen, M, K) for _ in range(int(restarts))])
+    return np.array(a0), np.array(b0)
+
+
+class _Problem(NamedTuple):
+    """What a _Solutions object keeps of its fit, to prepare the problem again: the marshalled inputs and the options"""
+    X: np.ndarray
+    y: np.ndarray
+    P: np.ndarray
+    eta: float
+    flags: int
+    device: int
+    weights: object = None                 # sample weights of a weighted fit
+    on_ill_conditioned: str = "raise"      # of the fit; the default is what a Context does on its own
 
 
 class _Solutions:
@@ -778,8 +784,9 @@ class _Solutions:
     the shared context over, the problem is prepared once more on a private context owned by this object."""
 
     def __init__(self, ctx, all_opt, P, problem):
-        self._ctx, self._all, self._P, self._problem = ctx, all_opt, P, problem
-        self._owner = getattr(ctx, "_owner", ctx)      # a view of a MultiContext's rank 0: the owner counts the fits
+        self._ctx, self._all, self._P, self._problem = ctx, all_opt, P, _Problem(*problem)
+        # a view of a MultiContext's rank 0: the owner counts the fits and holds the tolerance
+        self._owner = getattr(ctx, "_owner", None) or ctx
         self._gen = self._owner.generation
 
     def __len__(self):
@@ -787,17 +794,18 @@ class _Solutions:
 
     def _context(self):
         if self._owner.generation != self._gen:        # the shared context now holds another problem
-            Xf, yf, Pf, eta, flags, device = self._problem[:6]
-            w = self._problem[6] if len(self._problem) > 6 else None         # sample weights of a weighted fit
-            self._ctx = self._owner = Context(device)
-            self._ctx.opt_prepare(Xf, yf, Pf, eta, flags, weights=w)
+            p = self._problem
+            self._ctx = self._owner = Context(p.device)
+            self._ctx.opt_prepare(p.X, p.y, p.P, p.eta, p.flags, weights=p.weights)
             self._gen = self._ctx.generation
         return self._ctx
 
     def __getitem__(self, b):
         if b < 0:
             b += len(self)
-        a, bt, t, opt, _ = self._context().opt_finish(b)
+        ctx = self._context()
+        with _tolerating(self._problem.on_ill_conditioned, self._owner):     # of the fit that made this object, whatever was fitted since
+            a, bt, t, opt, _ = ctx.opt_finish(b)
         return float(self._all[b]), PartLSFitResult(a, bt, t, self._P)
 
     def __iter__(self):
@@ -881,7 +889,7 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
         raise ValueError("nnlsalg must be one of :nnls, :pivot, :fnnls")
     if on_ill_conditioned not in ("warn", "raise"):
         raise ValueError('on_ill_conditioned must be "warn" or "raise"')
-    Xf, yf, Pf = _marshal(X, y, P, keep_f32=devices is None)
+    Xf, yf, Pf = _fit_inputs(X, y, P, f32=devices is None)
     N, M = Xf.shape
     K = Pf.shape[1]
     wf = _weights(weights, N, "fit")
@@ -890,88 +898,69 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
     if wf is not None and devices is not None:
         raise NotImplementedError("fit: sample weights are not supported on several devices (devices=)")
     ctx = default_context(device)
-    ctx.tolerate_ill = on_ill_conditioned == "warn"
+    mc = default_multi(devices) if devices is not None and alg is not Alt else None
     ctx.last_ill = False
-    lib = L.lib()
     Pout = np.array(Pf, dtype=np.int64, order="C")
+    faithful = L.OPT_FAITHFUL_INTERCEPT
 
-    def report(owner, **kw):
-        """the NamedTuple of the reference + what the data-space check said"""
+    def result(owner, a, b, t, **kw):
+        """the reference's result tuple: the NamedTuple third element carries what the data-space check said as well"""
         if owner.last_ill:
             kkt = ctx.kkt_violation() if owner is ctx else float("nan")
             warnings.warn("partitionedls: the model's KKT conditions do not hold in data space (X is too ill-conditioned for the fp64 "
                           "Gram form); the returned model is the best Gram-form one — " + L.lib().partls_last_error().decode(),
                           IllConditionedWarning, stacklevel=3)
             kw.update(ill_conditioned=True, kkt_violation=kkt)
-        return Report(**kw)
+        return PartLSFitResult(a, b, t, Pout), None, Report(**kw)
 
-    if alg is Opt:
-        flags = (L.OPT_FAITHFUL_INTERCEPT if (faithful_intercept or returnAllSolutions) else 0) | \
-                (L.OPT_GENERIC_KERNEL if generic_kernel else 0)
-        if devices is not None:
-            mc = default_multi(devices)
-            mc.tolerate_ill = ctx.tolerate_ill
-            a, b, t, opt, bi, allopt = mc.fit_opt(Xf, yf, Pf, eta_v, flags, want_all=returnAllSolutions)
-            model = PartLSFitResult(a, b, t, Pout)
+    def solutions(c, allopt, flags, dev):
+        return _Solutions(c, allopt, Pout, _Problem(Xf, yf, Pf, eta_v, flags, dev, wf, on_ill_conditioned))
+
+    # on_ill_conditioned holds on the shared objects for the span of this call only
+    with _tolerating(on_ill_conditioned, ctx, mc):
+        if alg is Opt:
+            flags = (faithful if (faithful_intercept or returnAllSolutions) else 0) | (L.OPT_GENERIC_KERNEL if generic_kernel else 0)
+            if mc is not None:
+                a, b, t, opt, bi, allopt = mc.fit_opt(Xf, yf, Pf, eta_v, flags, want_all=returnAllSolutions)
+                if returnAllSolutions:
+                    c0 = mc.context(0)
+                    c0._shape = (N, M, K)
+                    return result(mc, a, b, t, solutions=solutions(c0, allopt, flags, mc.devices[0]))
+                return result(mc, a, b, t, opt=opt, best_index=bi)
+            ctx.opt_prepare(Xf, yf, Pf, eta_v, flags, weights=wf)
+            bobj, bpat, allopt, unconv = ctx.opt_sweep(0, -1, want_all=returnAllSolutions)
+            if unconv:
+                raise PartlsError(L.ERR_NOT_CONVERGED, f"{unconv} subproblems hit the pivot cap")
+            a, b, t, opt, bi = ctx.opt_finish(bpat)
             if returnAllSolutions:
-                c0 = mc.context(0)
-                c0._shape = (N, M, K)
-                return model, None, report(mc, solutions=_Solutions(c0, allopt, Pout, (Xf, yf, Pf, eta_v, flags, mc.devices[0])))
-            return model, None, report(mc, opt=opt, best_index=bi)
-        ctx.opt_prepare(Xf, yf, Pf, eta_v, flags, weights=wf)
-        bobj, bpat, allopt, unconv = ctx.opt_sweep(0, -1, want_all=returnAllSolutions)
-        if unconv:
-            raise PartlsError(L.ERR_NOT_CONVERGED, f"{unconv} subproblems hit the pivot cap")
-        a, b, t, opt, bi = ctx.opt_finish(bpat)
-        model = PartLSFitResult(a, b, t, Pout)
-        if returnAllSolutions:
-            return model, None, report(ctx, solutions=_Solutions(ctx, allopt, Pout, (Xf, yf, Pf, eta_v, flags, device, wf)))
-        return model, None, report(ctx, opt=opt, best_index=bi)
-    if alg is Alt and starts is not None:
-        ctx.opt_prepare(Xf, yf, Pf, eta_v, L.OPT_FAITHFUL_INTERCEPT, weights=wf)
-        a, b, t, o, it, best, per = ctx.alt_multistart(starts[0], starts[1], eps_v, int(T))
-        return PartLSFitResult(a, b, t, Pout), None, report(ctx, opt=o, iters=it, best_start=best, starts=Report(**per))
-    if alg is Alt:
-        if alpha0 is None or beta0 is None:
-            if rng is None:
-                gen = np.random.default_rng()
-            elif isinstance(rng, (int, np.integer)):
-                gen = np.random.default_rng(int(rng))
+                return result(ctx, a, b, t, solutions=solutions(ctx, allopt, flags, device))
+            return result(ctx, a, b, t, opt=opt, best_index=bi)
+        if alg is Alt and starts is not None:
+            ctx.opt_prepare(Xf, yf, Pf, eta_v, faithful, weights=wf)
+            a, b, t, o, it, best, per = ctx.alt_multistart(starts[0], starts[1], eps_v, int(T))
+            return result(ctx, a, b, t, opt=o, iters=it, best_start=best, starts=Report(**per))
+        if alg is Alt:
+            if alpha0 is None or beta0 is None:
+                alpha0, beta0 = _draw_start(_generator(rng), M, K)
+            a0 = np.ascontiguousarray(alpha0, dtype=np.float64)
+            b0 = np.ascontiguousarray(beta0, dtype=np.float64)
+            if a0.shape != (M + 1,) or b0.shape != (K + 1,):
+                raise ValueError("alpha0 must have M+1 and beta0 K+1 entries")
+            if staged:                                        # partls_fit_alt = prepare (faithful) + partls_alt_prepared
+                ctx.opt_prepare(Xf, yf, Pf, eta_v, faithful, weights=wf)
+                a, b, t, o, it = ctx.alt_prepared(a0, b0, eps_v, int(T))
             else:
-                gen = rng
-            alpha0 = gen.random(M + 1)                    # Alt.jl:65
-            beta0 = (gen.random(K + 1) - 0.5) * 10        # Alt.jl:66
-        a0 = np.ascontiguousarray(alpha0, dtype=np.float64)
-        b0 = np.ascontiguousarray(beta0, dtype=np.float64)
-        if a0.shape != (M + 1,) or b0.shape != (K + 1,):
-            raise ValueError("alpha0 must have M+1 and beta0 K+1 entries")
-        if staged:                                        # partls_fit_alt = prepare (faithful) + partls_alt_prepared
-            ctx.opt_prepare(Xf, yf, Pf, eta_v, L.OPT_FAITHFUL_INTERCEPT, weights=wf)
-            a, b, t, o, it = ctx.alt_prepared(a0, b0, eps_v, int(T))
-            return PartLSFitResult(a, b, t, Pout), None, report(ctx, opt=o, iters=it)
-        a = np.zeros(M); b = np.zeros(K)
-        t = C.c_double(); o = C.c_double(); it = C.c_int64()
-        ctx.generation += 1
-        ctx._ill(lib.partls_fit_alt(ctx._h, Xf.ctypes.data, N, M, N, yf.ctypes.data, Pf.ctypes.data, K, M, eta_v, eps_v,
-                                    int(T), _dp(a0), _dp(b0), _dp(a), _dp(b), C.byref(t), C.byref(o), C.byref(it)))
-        return PartLSFitResult(a, b, t.value, Pout), None, report(ctx, opt=o.value, iters=it.value)
-    if alg is BnB:
-        if devices is not None:
-            mc = default_multi(devices)
-            mc.tolerate_ill = ctx.tolerate_ill
-            a, b, t, opt, nopen = mc.fit_bnb(Xf, yf, Pf, eta_v)
-            return PartLSFitResult(a, b, t, Pout), None, report(mc, opt=opt, nopen=nopen)
-        if staged:                                        # partls_fit_bnb = prepare (faithful) + partls_bnb_prepared
-            ctx.opt_prepare(Xf, yf, Pf, eta_v, L.OPT_FAITHFUL_INTERCEPT, weights=wf)
+                a, b, t, o, it = _host_fit(ctx, L.lib().partls_fit_alt, Xf, yf, Pf, eta_v, eps_v, int(T), _dp(a0), _dp(b0))
+            return result(ctx, a, b, t, opt=o, iters=it)
+        if mc is not None:
+            a, b, t, o, no = mc.fit_bnb(Xf, yf, Pf, eta_v)
+            return result(mc, a, b, t, opt=o, nopen=no)
+        if staged:                                            # partls_fit_bnb = prepare (faithful) + partls_bnb_prepared
+            ctx.opt_prepare(Xf, yf, Pf, eta_v, faithful, weights=wf)
             a, b, t, o, no = ctx.bnb_prepared()
-            return PartLSFitResult(a, b, t, Pout), None, report(ctx, opt=o, nopen=no)
-        a = np.zeros(M); b = np.zeros(K)
-        t = C.c_double(); o = C.c_double(); no = C.c_int64()
-        ctx.generation += 1
-        ctx._ill(lib.partls_fit_bnb(ctx._h, Xf.ctypes.data, N, M, N, yf.ctypes.data, Pf.ctypes.data, K, M, eta_v,
-                                    _dp(a), _dp(b), C.byref(t), C.byref(o), C.byref(no)))
-        return PartLSFitResult(a, b, t.value, Pout), None, report(ctx, opt=o.value, nopen=no.value)
-    raise TypeError("fit: first argument must be Opt, Alt or BnB")
+        else:
+            a, b, t, o, no = _host_fit(ctx, L.lib().partls_fit_bnb, Xf, yf, Pf, eta_v)
+        return result(ctx, a, b, t, opt=o, nopen=no)
 
 
 def cv_folds(N, nfolds=5, shuffle=False, rng=None):
@@ -992,8 +981,7 @@ def cv_folds(N, nfolds=5, shuffle=False, rng=None):
     sizes = np.array([len(a) for a in np.array_split(np.arange(N), F)], dtype=np.int64)
     fold_ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     if shuffle:
-        gen = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(None if rng is None else int(rng))
-        perm = gen.permutation(N).astype(np.int64)
+        perm = _generator(rng).permutation(N).astype(np.int64)
     else:
         perm = np.arange(N, dtype=np.int64)
     return fold_ptr, perm
@@ -1038,7 +1026,7 @@ def cross_validate(alg, X, y, P, *, η=None, eta=None, nfolds=5, shuffle=False, 
         raise ValueError('on_ill_conditioned must be "warn" or "raise"')
     grid = [0.0] if (η is None and eta is None) else (η if η is not None else eta)
     etas = np.ascontiguousarray(np.atleast_1d(np.asarray(grid, dtype=np.float64)))
-    Xf, yf, Pf = _marshal(X, y, P)
+    Xf, yf, Pf = _fit_inputs(X, y, P)
     N, M = Xf.shape
     wf = _weights(weights, N, "cross_validate")
     fold_ptr, perm = cv_folds(N, nfolds, shuffle, rng)
@@ -1107,10 +1095,9 @@ def predict(*args, device=0):
     X = np.asarray(X)
     if not np.issubdtype(X.dtype, np.floating) or X.ndim != 2:
         raise TypeError("predict: X must be a floating-point matrix")
-    Pf = np.asfortranarray(P, dtype=np.int64)
+    Xf, _, Pf = _inputs(X, None, P)                     # what the context is handed is what goes up (Context.predict takes it as it is)
     a = np.ascontiguousarray(α, dtype=np.float64)
     b = np.ascontiguousarray(β, dtype=np.float64)
-    Xf = _x_host(X)                                     # what the context is handed is what goes up (Context.predict takes it as it is)
     M = Xf.shape[1]
     if Pf.shape[0] != M or a.shape != (M,) or b.shape != (Pf.shape[1],):
         raise ValueError("DimensionMismatch in predict")

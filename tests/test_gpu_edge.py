@@ -371,3 +371,37 @@ def test_winner_from_the_512_thread_kernel_mid_sizes(partls, oracle, monkeypatch
         np.testing.assert_allclose(partls.predict(partls.PartLSFitResult(a, b, t, P), X), oracle.predict(X, P, ref["alpha"], ref["beta"], ref["t"]),
                                    atol=1e-6 * np.linalg.norm(y), err_msg=mode)
     assert res["export"][4] == res["resolve"][4] and abs(res["export"][3] - res["resolve"][3]) <= 1e-12 * res["resolve"][3]
+
+
+def test_fit_takes_its_tolerance_of_status_9_with_it(partls):
+    """fit(on_ill_conditioned="warn") tolerates status 9 for the span of its own calls: the shared default context raises again as
+    soon as the fit has returned, while the returnAllSolutions result keeps the choice of its fit — on the shared context, and on the
+    private one it prepares once another fit has taken the shared context over (same model bit for bit).  Data of
+    test_beyond_the_gram_form_the_call_reports_it at its worst level."""
+    ILL = partls.lowlevel.ERR_ILL_CONDITIONED
+    rng = np.random.default_rng(42)
+    N, D, K = 2000, 24, 4
+    Z = rng.standard_normal((N, 6))
+    X = Z @ rng.standard_normal((6, D)) + 1e-7 * rng.standard_normal((N, D))
+    grp = np.arange(D) % K
+    P = np.zeros((D, K), dtype=np.int64); P[np.arange(D), grp] = 1
+    y = X @ (rng.random(D) * np.array([1., -2, 3, -1])[grp]) + 0.3 + 0.05 * rng.standard_normal(N)
+    with pytest.raises(partls.PartlsError) as ei:                  # the precondition: this input reports status 9
+        partls.fit(partls.Opt, X, y, P, returnAllSolutions=True, on_ill_conditioned="raise")
+    assert ei.value.status == ILL
+    ctx = partls.default_context()
+    assert ctx.tolerate_ill is False
+    with pytest.warns(partls.IllConditionedWarning):
+        _, _, rep = partls.fit(partls.Opt, X, y, P, returnAllSolutions=True)
+    assert rep.ill_conditioned and ctx.tolerate_ill is False
+    best = int(np.argmin(rep.solutions._all))                      # the winner: the pattern the fit finished
+    with pytest.raises(partls.PartlsError) as ei:
+        ctx.opt_finish(best)
+    assert ei.value.status == ILL
+    o1, m1 = rep.solutions[best]
+    assert np.isfinite(o1) and np.all(np.isfinite(m1.α)) and np.all(np.isfinite(m1.β)) and np.isfinite(m1.t)
+    X2 = np.random.default_rng(7).standard_normal((200, 6))
+    partls.fit(partls.Opt, X2, X2 @ np.arange(1.0, 7.0) + 0.5, np.repeat(np.eye(2, dtype=np.int64), 3, axis=0))
+    o2, m2 = rep.solutions[best]                                   # prepared again on a private context
+    assert rep.solutions._ctx is not ctx and ctx.tolerate_ill is False
+    assert o2 == o1 and np.array_equal(m2.α, m1.α) and np.array_equal(m2.β, m1.β) and m2.t == m1.t
