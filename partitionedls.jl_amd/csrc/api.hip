@@ -91,6 +91,7 @@ try {
     if (const char *e = getenv("PARTLS_GRAM_S")) c->knobs.gram_S = atoi(e);
     if (const char *e = getenv("PARTLS_GRAM_CR")) c->knobs.gram_cr = atoi(e);
     if (const char *e = getenv("PARTLS_COOP_ROWS")) c->knobs.coop_rows = atoi(e);
+    if (const char *e = getenv("PARTLS_PAIR")) c->knobs.pair = atoi(e) != 0 ? 1 : 0;
     if (const char *e = getenv("PARTLS_BIT_ORDER")) c->knobs.bit_order = !strcmp(e, "identity") ? 1 : (!strcmp(e, "calibrate") ? 2 : 0);
     if (const char *e = getenv("PARTLS_ALT_MS_MAX_ROUNDS")) c->knobs.alt_ms_max_rounds = atoi(e);
     if (const char *e = getenv("PARTLS_ALT_MS_CHUNK")) c->knobs.alt_ms_chunk = atoll(e);

@@ -42,6 +42,11 @@ struct SweepParams {
     double tol;                  // feasibility tolerance on the rhs column (scaled units)
     double piv_eps;              // an entering pivot below this is treated as a dependent column and skipped
     int max_rounds;              // cap on exchange rounds per pattern
+    int pair;                    // host only (launch_sweep_blk picks the instantiation; no kernel reads it): != 0: the pair walk — of two patterns that
+                                 // differ in internal bit 0 the tableau visits one, the other is priced from its violators' columns (chain mode
+                                 // of the 512-thread register kernel up to T = 16, sweep_blk.hip).  It sits in the padding behind max_rounds: no
+                                 // field moves and the kernel argument keeps its size — appended at the end it grew the argument by 8 bytes and
+                                 // the BATCH kernels' scratch from 320 to 328 bytes
     double *all_opt;             // optional [2^kbits] objective per pattern index
     double *best_obj;            // [gridDim.x] per-workgroup minimum objective
     int64_t *best_pat;           // [gridDim.x] its pattern index (internal bit order; ties broken on the REFERENCE index, see rbit)

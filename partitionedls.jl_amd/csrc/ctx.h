@@ -135,6 +135,7 @@ struct partls_knobs {
     double near_tie_rel = 1e-13; // PARTLS_NEAR_TIE_REL (tests): width of the near-tie window of the sweep, in units of y'y on the objective^2
     double cal_wb = 1.0, cal_ws = 1.0;  // PARTLS_CAL_WB / PARTLS_CAL_WS: multipliers of the block / scan weights of the bit-order cost model (experiments)
     bool cv_serial = false;      // PARTLS_CV_SERIAL: partls_cv_opt sweeps its problems one after another through partls_opt_sweep (A/B tests, timing)
+    int pair = -1;               // PARTLS_PAIR: 0 / 1 force the pair walk of the 512-thread register kernel off / on; -1 automatic (sweep_pairs, sweep_setup.hip)
     int bit_order = 0;           // PARTLS_BIT_ORDER: 0 automatic (calibrate when the sweep is long enough to repay it), "identity" = 1
                                  // (group k on Gray bit k), "calibrate" = 2 (always measure; small problems in the tests)
 };
@@ -293,6 +294,7 @@ hipError_t launch_any_sweep(partls_ctx *c, SweepParams &p, int grid, bool models
 // the Opt sweep's pieces that partls_cv_opt shares
 partls_status calibrate_bit_order(partls_ctx *c);
 bool sweep_plan(partls_ctx *c, int64_t total, int64_t *chain_len_out, int *grid_out, const char *who);
+bool sweep_pairs(const partls_ctx *c, int64_t total);   // does partls_opt_sweep walk a range of `total` Gray indices in pairs on this context?
 int64_t reference_pattern(const partls_ctx *c, int64_t q);
 // sweep_out: the host copy of a result block with runner-up columns (sweep_block)
 void install_sweep_result(partls_ctx *c, const double *sweep_out, int grid, bool has_sol, double *bobj_out, int64_t *bpat_out);

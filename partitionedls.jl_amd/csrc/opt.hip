@@ -115,6 +115,7 @@ try {
 
     SweepParams p = sweep_params(c, /*internal_order=*/true);
     p.g_begin = g_begin; p.g_end = g_end; p.chain_len = chain_len;
+    p.pair = sweep_pairs(c, total) ? 1 : 0;
     p.all_opt = all_opt ? c->allOpt.as<double>() : nullptr;
     bind_sweep_block(p, c->bestObj.as<double>(), grid, true);
     if (!c->use_reg && c->knobs.lz_fault) p.coop_fault = 77;   // test hook of the deferred-update kernel's panel (SweepParams::coop_fault)
@@ -154,9 +155,9 @@ try {
         if (hipMemcpy(st, c->scratch.p, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess)
             fprintf(stderr, "[partls stamps] scan: pre %.0f barrier %.0f post %.0f | gather: work %.0f barrier %.0f | panel: work %.0f barrier %.0f | "
                             "update %.0f | scatter %.0f | chain-load %.0f/%.0f | pivots %llu || gather split: block setup %.0f chain %.0f rhs/myj %.0f"
-                            " || workgroup 0: %.0f blocks, %.0f scans, %.0f pivots\n",
+                            " || workgroup 0: %.0f blocks, %.0f scans, %.0f pivots || pair walk: twin scan %.0f, solve + rows + scan %.0f\n",
                     st[9], st[10], st[0], st[12] + st[13] + st[8], st[1], st[11], st[2], st[3], st[4], st[5], st[6], cnt[1], st[12], st[13], st[8],
-                    st[24], st[25], st[26]);
+                    st[24], st[25], st[26], st[15], st[14]);
     }
     double bobj = INFINITY;
     int64_t bpat = -1;

@@ -58,9 +58,19 @@ static constexpr int MB = 8;                    // pivots per block (a tile colu
 #ifndef PARTLS_MB_BIG
 #define PARTLS_MB_BIG 8
 #endif
+#ifndef PARTLS_PAIR
+#define PARTLS_PAIR 1            // 0: the pair walk of the 512-thread chain kernel is not compiled (every Gray flip is exchanged on the tableau)
+#endif
 static constexpr int EXPORT_MAXT = 17;          // ... up to this tile count (beyond it the two live registers of the export start spilling: 22 -> 32 spilled VGPRs at T = 18)
 static constexpr int MBB = PARTLS_MB_BIG;       // ... of the 512-thread kernel (8..16; experiments: tools/experiments/README.md)
 static constexpr int NO_VETO = 99;
+static constexpr int PAIR_MAXC = 16;            // pair walk: most violators a twin is priced with (the two panel buffers hold 2 MBB >= 16 columns)
+static constexpr int PAIR_PIV_MIN_HI = 0x3f1a36e2;   // ... and the smallest entering pivot (unit-diagonal scale) it is priced with: the high word of 1e-4
+                                                // (0x3f1a36e2eb1c432d) — a pivot is accepted when its high word, as a signed integer, is ABOVE this one, i.e.
+                                                // d >= 1.00000000055e-4: a scalar compare with a literal, where the double constant costs two VGPRs the
+                                                // compiler keeps live through the whole kernel.  The rounds' dependent-column rule, d <= 1e-11 max(1, cmax^2),
+                                                // needs the whole panel; a twin below the guard is left to the rounds
+static constexpr int F64_EXP_HI = 0x7ff00000;   // the exponent bits of a double's high word: all set = inf or NaN (whose high word lies ABOVE the guard's)
 
 constexpr int nslots(int T) { return T * (T + 1) / 2; }
 constexpr int tri(int g) { return g * (g + 1) / 2; }
@@ -140,6 +150,7 @@ struct LdsImage {
     unsigned long long s_vmask[16 * MAXT];     // group mask of variable v
     double Pbase[2 * MBB * CWMAX];             // [2][MB][CW] panel, double buffered by block parity
 };
+static_assert(2 * MBB >= PAIR_MAXC, "the pair walk gathers up to PAIR_MAXC columns into the two panel buffers");
 __shared__ LdsImage lds_image;
 __shared__ LdsImageT<CW_S, MAXT_S> lds_small;              // the 256-thread kernel's image (~51 KB: three workgroups per CU)
 
@@ -286,6 +297,63 @@ __device__ __forceinline__ int panel_block(double *P, double *Z, double *U, doub
     return veto;
 }
 
+// ---- pair walk: the twin's |C| x |C| solve on ONE wave, no workgroup barrier inside ------------------------------------------
+// The m gathered columns of C (panel columns 0..m-1, ascending variable index) are eliminated by the m sequential pivots of
+// panel_block, restricted to what decides: the m pivot rows and, as a column of its own, their rhs entries q_C (the panel's rhs row,
+// by symmetry).  The rhs column ends as the twin's rhs entries q'_C of the pivot rows (what scatter takes from the final panel), and
+// these ARE the coefficients of the rank-m update of every other row: with T_ik / |d|, T_kk = -1/d a single pivot gives
+// q_i - T_ik q_k / d and q'_k = q_k / |d|, i.e. q_i - T_ik a_k with a_k = +q'_k for an entering and -q'_k for a leaving variable, and
+// so for the block (the sweeps of distinct variables commute); the rhs row itself is such a row: corner' = corner - sum_k q_k a_k.
+// Checked against sequential pivots in tools/pair_emul.py.
+// Layout: lane = r + 16 h holds row r of the four columns 4 h .. 4 h + 3, as ROTATED: at step s register jj of quarter h is column
+// (s + 4 h + jj) mod 16, so the pivot column is always register 0 of quarter 0 and the step loop stays rolled with static register
+// indices.  8 VGPRs of matrix per lane: with a whole row per lane (32) the chain kernel of T = 16 spilled.
+// out: [0..16) a_j, [16..32) q'_C, [33] != 0: an entering pivot at or below the guard, or a pivot that is not finite (nothing else of `out` is
+// then meaningful)
+template <int CW>
+__device__ __forceinline__ void pair_solve(const double *P, const int *cpos, int m, int lane, int rhspos, double *out)
+{
+    const int r = lane & 15, h = lane >> 4;
+    const int code = cpos[r < m ? r : 0];
+    const unsigned basm = (unsigned)__ballot(code < 0 && lane < m);
+    const int pos = code < 0 ? ~code : code;
+    double pv[4];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+        const int c = 4 * h + jj;
+        const double v = P[c * CW + pos];
+        pv[jj] = (r < m && c < m) ? v : 0.0;
+    }
+    double qc = P[r * CW + rhspos];
+    if (r >= m) qc = 0.0;
+    bool hard = false;
+#pragma unroll 1
+    for (int s = 0; s < m; ++s) {
+        const double d = readlane_f64(pv[0], s);
+        const int dh = __double2hiint(d);                       // (wave-uniform: scalar compares)
+        if ((!((basm >> s) & 1u) && !(dh > PAIR_PIV_MIN_HI)) || (dh & F64_EXP_HI) == F64_EXP_HI) { hard = true; break; }
+        const double inv = rcp_newton(d), ainv = fabs(inv);
+        const double pvs = __shfl(pv[0], r);                    // this row's entry of the pivot column
+        const double fz = -pvs * inv;
+        const double qs = readlane_f64(qc, s);
+        double val[4];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            const double u = __shfl(pv[0], (s + 4 * h + jj) & 15);     // the pivot row's entry, from the pivot COLUMN (panel_block's NUMERICS)
+            val[jj] = (r == s) ? u * ainv : fma(fz, u, pv[jj]);
+        }
+        if (h == 0) val[0] = (r == s) ? -inv : pvs * ainv;      // the pivot column itself
+        qc = (r == s) ? qs * ainv : fma(fz, qs, qc);
+        const double nx = __shfl(val[0], (lane + 16) & 63);
+        pv[0] = val[1]; pv[1] = val[2]; pv[2] = val[3]; pv[3] = nx;
+    }
+    if (lane < PAIR_MAXC) {
+        out[PAIR_MAXC + lane] = qc;
+        out[lane] = ((basm >> lane) & 1u) ? -qc : qc;
+    }
+    if (lane == 0) out[2 * PAIR_MAXC + 1] = hard ? 1.0 : 0.0;
+}
+
 #define PARTLS_CASES(M) M(0) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15) M(16) M(17) M(18) M(19)
 
 // NODE: node mode (Alt alpha-steps, BnB bounds: one subproblem per chain, free / zero groups) is a separate instantiation, so
@@ -294,7 +362,7 @@ __device__ __forceinline__ int panel_block(double *P, double *Z, double *U, doub
 // row g - g_begin of p.node_sol (leading dimension p.node_ld) and sqrt(obj2) in p.node_obj2[g - g_begin]; a pattern that hit the pivot
 // cap leaves NaN in both.  The row follows from the chain and pattern counters alone (no live register beyond the default build's); the
 // export instantiation writes no best_sol.  A separate instantiation: the default ones keep their code.
-template <int T, int H, bool NODE, int W = 2, bool MODELS = false, bool BATCH = false>
+template <int T, int H, bool NODE, int W = 2, bool MODELS = false, bool BATCH = false, bool PAIRK = false>
 __device__ __forceinline__ void sweep_body(const SweepParams &p)
 {
     using L = Half<T, H, W>;
@@ -308,6 +376,12 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
     static_assert(!(NODE && MODELS), "node mode exports no per-pattern models (finish_pattern's capped flag is chain mode's)");
     constexpr bool MERGED = PARTLS_MERGED_SCAN && !NODE && !BATCH && T <= 17;
     constexpr bool LANE_MASKS = PARTLS_LANE_MASKS && !BATCH && T <= 16;
+    // PAIR: the pair walk — chain mode of the 512-thread kernel wherever both of the above are on, i.e. up to T = 16 (T = 17
+    // has no lane-held masks; from T = 18 on the chain kernel spills as it is and stays unpaired).  An instantiation of its own (PAIRK),
+    // launched when SweepParams::pair is set: compiled into the one chain kernel and switched at run time, the walk costs the plain one
+    // 3 % (C3 sweep 49.3 against 47.8 ms with the pairing off: the pricing's edges in the round loop move its code and 5 VGPRs).
+    constexpr bool PAIR = PAIRK && PARTLS_PAIR && MERGED && LANE_MASKS && W == 2 && !MODELS;
+    static_assert(PAIR == PAIRK, "the pair walk is launched only where it is compiled (pair_compiled)");
     static_assert(W == 2 || RHSPOS < 256, "the 256-thread kernel needs every panel row position (and the rhs row) below 256");
     auto &lds_image = *image_of<W>();
     const int tid = threadIdx.x, t8 = tid & 255, a = t8 & 15, b = t8 >> 4, lane = tid & 63, wave = tid >> 6;
@@ -320,6 +394,14 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
     unsigned long long *const s_sum = lds_image.s_sum;
     int *const s_veto = lds_image.s_veto;
     double *const s_best = lds_image.s_best;
+    // pair walk: U and Dinv are idle while a twin is priced (the panel steps rewrite what they read) and lie in the first 64 KB — fields of
+    // their own behind the panel each cost an address register that lives through the whole kernel.  s_pair: the solve's results (pair_solve's
+    // `out`); s_cpos[j]: panel row position of the twin's j-th violator (~position: the variable is basic); s_tw[w]: wave w still sees a violator
+    [[maybe_unused]] double *const s_pair = U;
+    [[maybe_unused]] int *const s_cpos = reinterpret_cast<int *>(Dinv);
+    [[maybe_unused]] int *const s_tw = s_cpos + PAIR_MAXC;
+    static_assert(2 * (MB + 64) >= 2 * PAIR_MAXC + 2, "pair_solve's `out` (doubles) fits U");
+    static_assert(2 * (MB + 64) >= PAIR_MAXC + 8, "s_cpos and s_tw (PAIR_MAXC + 8 ints) fit Dinv (MB + 64 doubles)");
     for (int i = tid; i < 2 * MB * CW; i += THREADS) Pbase[i] = 0.0;                   // padding rows are never gathered
     for (int i = tid; i < MB * CW; i += THREADS) Z[i] = 0.0;
     if (tid < 2 * (MB + 64)) U[tid] = 0.0;
@@ -438,7 +520,68 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                 } else if (obj2 < s_best[2]) { s_best[2] = obj2; reinterpret_cast<long long *>(s_best)[3] = (long long)pat; }
             }
         };
+        // the same bookkeeping for a pattern the tableau does not hold — a twin of the pair walk (PAIR: chain mode, no export of models): its
+        // objective^2, this thread's rhs entry and basis flag come as values (the twin's temporaries, or the tableau's own where C is empty).
+        // A recorder of its own: with these three as parameters of finish_pattern the node-mode kernels, which never price, lose their allocation
+        [[maybe_unused]] auto record_twin = [&](int gi, double cornerv, double qv, bool bv) {
+            const uint64_t g = (uint64_t)g0 + (unsigned)gi;
+            const uint64_t pat = g ^ (g >> 1);
+            const double obj2 = cornerv > 0.0 ? cornerv : 0.0;
+            if (p.all_opt && tid == THREADS - 1) p.all_opt[pat] = sqrt(obj2);
+            if constexpr (PARTLS_EXPORT_BIG && T <= EXPORT_MAXT) {
+                if (p.best_sol && obj2 < mybest) {
+                    mybest = obj2;
+                    if (has_var) p.best_sol[(size_t)blockIdx.x * p.node_ld + tid] = bv ? qv : 0.0;
+                }
+            }
+            if (tid == THREADS - 1) {                                // finish_pattern's ranking
+                const double bo = s_best[0];
+                const long long bp = reinterpret_cast<long long *>(s_best)[1];
+                if (obj2 < bo || (obj2 == bo && ref_index_less(pat, (unsigned long long)bp, lds_image.s_rbit))) {
+                    s_best[2] = bo; reinterpret_cast<long long *>(s_best)[3] = bp;
+                    s_best[0] = obj2; reinterpret_cast<long long *>(s_best)[1] = (long long)pat;
+                } else if (obj2 < s_best[2]) { s_best[2] = obj2; reinterpret_cast<long long *>(s_best)[3] = (long long)pat; }
+            }
+        };
         int gi = 0;
+        // ---- pair walk (PAIR) ----------------------------------------------------------------------------------------
+        // Patterns g and g ^ 1 (Gray indices) differ in internal bit 0 only: a PAIR when both lie in the chain.  The tableau visits ONE
+        // member per pair — the one whose bit 0 is the committed state's, so a step from pair to pair flips one group on a bit >= 1 — and
+        // once that member is confirmed its twin is PRICED from the columns of its violators C: nothing of the tableau is written.  A twin
+        // that pricing cannot finish (more than PAIR_MAXC violators, a small entering pivot, violators left after the block pivot on C) is
+        // solved by the ordinary rounds from the current tableau instead; a pattern without its partner in the chain (odd chain ends) is
+        // an ordinary pattern.  All of this state is wave-uniform and the same in both halves (the barrier invariant below).
+        [[maybe_unused]] bool tw_pending = false;                         // the pattern being solved has a twin that is still to come
+        [[maybe_unused]] int pr_ncol = -1;                                // >= 0: the exchange loop is gathering a twin's columns; columns so far
+        // index of the partner of chain pattern i, -1 if it has none
+        [[maybe_unused]] auto pair_partner = [&](int i) -> int {
+            const int j = (((unsigned)g0 + (unsigned)i) & 1u) ? i - 1 : i + 1;
+            return (PAIR && j >= 0 && j < glen) ? j : -1;
+        };
+        [[maybe_unused]] auto pair_unit_end = [&](int i) -> int { const int j = pair_partner(i); return (j > i ? j : i) + 1; };
+        // the pattern the tableau visits of the unit that starts at chain index u, with the committed state at chain pattern i
+        [[maybe_unused]] auto pair_target = [&](int u, int i) -> int {
+            const unsigned gu = (unsigned)g0 + (unsigned)u, gc = (unsigned)g0 + (unsigned)i;
+            if (pair_partner(u) < 0 || (gu & 1u)) return u;
+            return (((gu >> 1) ^ gu ^ (gc >> 1) ^ gc) & 1u) ? u + 1 : u;      // bit 0 of gray(g) = bit 0 of g ^ (g >> 1)
+        };
+        // after pattern gi: on to its twin (`to_twin`: by the ordinary rounds), or to the next unit; false: the chain is finished
+        [[maybe_unused]] auto pair_next = [&](bool to_twin, int &f, int &fn) -> bool {
+            if (to_twin) gi = pair_partner(gi);
+            else {
+                const int u = pair_unit_end(gi);
+                if (u >= glen) return false;
+                gi = pair_target(u, gi);
+            }
+            tw_pending = !to_twin && pair_partner(gi) >= 0;
+            const uint64_t vmask = s_vmask[tid < 16 * T ? tid : 0] & (has_var ? ~0ULL : 0ULL);
+            const uint64_t g = (uint64_t)g0 + (unsigned)gi;
+            f = sign_of_var(vmask, g ^ (g >> 1));
+            const int u2 = pair_unit_end(gi);                             // the merged scan looks ahead to the next pattern the TABLEAU visits
+            fn = f;
+            if (u2 < glen) { const uint64_t gn = (uint64_t)g0 + (unsigned)pair_target(u2, gi); fn = sign_of_var(vmask, gn ^ (gn >> 1)); }
+            return true;
+        };
         for (;;) {                                                    // !MERGED: one turn per pattern; MERGED: one turn
             [[maybe_unused]] const unsigned nunconv0 = nunconv;           // !MERGED: did this pattern hit the pivot cap?
             bool isfree = false;
@@ -453,6 +596,12 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                 const uint64_t g = (uint64_t)g0 + (unsigned)gi, gn = g + 1;                 // MERGED: gi = 0 here
                 f = sign_of_var(vmask, g ^ (g >> 1));
                 if constexpr (MERGED) fn = glen > 1 ? sign_of_var(vmask, gn ^ (gn >> 1)) : f;
+                if constexpr (PAIR) {                                     // gi = 0: the chain's first pattern is visited whatever its bit 0
+                    tw_pending = pair_partner(0) >= 0;
+                    const int u2 = pair_unit_end(0);
+                    fn = f;
+                    if (u2 < glen) { const uint64_t g2 = (uint64_t)g0 + (unsigned)pair_target(u2, 0); fn = sign_of_var(vmask, g2 ^ (g2 >> 1)); }
+                }
             }
             blocked = false;
             int ninf_best = n + 1, patience = 3, rounds = 0;
@@ -534,21 +683,76 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                     // ---- pattern gi is finished (converged, or the pivot cap: count != 0) ---------------------------------------
                     if constexpr (!MERGED) break;                         // the turn of the outer loop ends
                     finish_pattern(gi, count != 0);
+                    if constexpr (PAIR) {
+                        // 0: no twin to come (second member of a pair, a pattern without partner, or a twin with empty C: done)
+                        // 2: the twin goes to the ordinary rounds  3: its columns are gathered, pricing goes on inside the exchange loop
+                        int tw = 0;
+                        if (tw_pending) {
+                            tw = 2;                                   // (a capped pattern's pair is finished by the ordinary path)
+                            if (count == 0) {
+                                // ---- violators C of the twin's signs on the current rhs column and basis: a scan of its own ----
+                                const int part = sc & 1;
+                                ++sc;
+                                const uint64_t vmask = s_vmask[tid < 16 * T ? tid : 0] & (has_var ? ~0ULL : 0ULL);
+                                const uint64_t gt = (uint64_t)g0 + (unsigned)pair_partner(gi);
+                                const int ft = sign_of_var(vmask, gt ^ (gt >> 1));
+                                const double fqt = q * (double)(ft > 1 ? 1 : (ft < -1 ? -1 : ft));
+                                const bool badt = has_var && (basic ? ((ft == 0) || (fqt < -p.tol)) : (fqt > p.tol));   // kkt_violates (sweep_rules.h), written out
+                                const unsigned long long bt = __ballot(badt);
+                                unsigned summt = (unsigned)__popcll(bt);
+#pragma unroll
+                                for (int sub = 0; sub < 4; ++sub)
+                                    if ((bt >> (16 * sub)) & 0xFFFFull) summt |= 0x100u << sub;
+                                if (lane == 0 && wave < nwords) { s_inf[part * 8 + wave] = bt; s_sum[part * 8 + wave] = summt; }
+                                __syncthreads();
+                                STAMP(15);
+                                int countt = 0;
+                                unsigned tilest = 0;
+#pragma unroll
+                                for (int w = 0; w < NW; ++w) {
+                                    const unsigned sw = (unsigned)__builtin_amdgcn_readfirstlane((int)s_sum[part * 8 + w]);
+                                    countt += (int)(sw & 0xFFu);
+                                    tilest |= (sw >> 8) << (4 * w);
+                                }
+                                if (countt == 0) {                    // C is empty: the twin's optimum is the current corner
+                                    record_twin(pair_partner(gi), corner, q, basic);
+                                    tw = 0;                           // ... and the confirming scan's look-ahead still holds
+                                } else if (countt <= PAIR_MAXC) {     // gather C through the exchange loop's own gather
+                                    tw = 3;
+                                    pr_ncol = 0;
+                                    all = true;
+                                    tiles = tilest;
+                                    soff = part * 8;
+                                }
+                            }
+                        }
+                        if (tw == 2) {                                // a fresh scan starts the twin
+                            if (!pair_next(true, f, fn)) break;
+                            blocked = false;
+                            ninf_best = n + 1; patience = 3; rounds = 0;
+                            continue;
+                        }
+                    }
+                    if (!(PAIR && pr_ncol >= 0)) {
                     // ---- ... and the next one starts: from this very scan where it can ---------------------------------------------
-                    if (++gi >= glen) break;
+                    if constexpr (PAIR) { if (!pair_next(false, f, fn)) break; }       // (f and fn: the next visited pattern's and its successor's)
+                    else if (++gi >= glen) break;
                     blocked = false;
                     ninf_best = n + 1; patience = 3; rounds = 0;
                     if constexpr (MERGED) {
+                        if constexpr (!PAIR) {
                         const uint64_t vmask = s_vmask[tid < 16 * T ? tid : 0] & (has_var ? ~0ULL : 0ULL);
                         const uint64_t gn = (uint64_t)g0 + (unsigned)gi + 1;
                         f = fn;
                         fn = gi + 1 < glen ? sign_of_var(vmask, gn ^ (gn >> 1)) : f;
+                        }
                         // count2 == 0: the new pattern is optimal as it stands — the next scan records it (and looks one pattern further)
                         if (count2 == 0 || p.max_rounds < 1) continue;
                         ninf_best = count2; rounds = 1;                   // ExchangeRule::next of a first round: count2 < n + 1, 1 <= max_rounds
                         all = true;
                         tiles = tiles2;
                         soff += 16;
+                    }
                     }
                 }
                 int single_k = -1;
@@ -572,6 +776,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                     tmask = (unsigned)((s_inf[soff + wl] >> shl) & 0xFFFFull) | ((unsigned)((s_bas[par * 8 + wl] >> shl) & 0xFFFFull) << 16);
                 }
 
+                [[maybe_unused]] bool chain_end = false;                  // PAIR: the chain's last pattern was a priced twin
                 while (tiles) {
                     const int kappa = __builtin_ctz(tiles);
                     unsigned pmall, basm;
@@ -590,7 +795,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                     while (pmall) {
                         // ---- block: the lowest <= MB violators of tile column kappa -------------------------------------
                         unsigned rest = 0;
-                        if (__builtin_expect(__builtin_popcount(pmall) > MB, 0)) {
+                        if (__builtin_expect(__builtin_popcount(pmall) > MB && !(PAIR && pr_ncol >= 0), 0)) {       // (pricing gathers a tile column's violators at once)
                             rest = pmall;
 #pragma unroll
                             for (int i = 0; i < MB; ++i) rest &= rest - 1;
@@ -600,7 +805,12 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                         const int m = __builtin_popcount(pm);
                         const int bpar = bc & 1;
                         double *P = Pbase + bpar * MB * CW;
-                        ++bc;
+                        if constexpr (PAIR) {
+                            // pricing: no block — only its gather, into the next free columns of the two panel buffers (both idle at a confirmed
+                            // pattern; bc, bpar and s_veto stay as they are for the block that follows)
+                            if (pr_ncol >= 0) P = Pbase + pr_ncol * CW;
+                            else ++bc;
+                        } else ++bc;
                         // the tile index is invariant in this loop: left alone, the compiler hoists all 17 `kappa == i` tests out of it
                         // as 64-bit lane masks (34 SGPRs, spilled to VGPR lanes and reloaded per block); the opaque copy keeps each
                         // test a plain s_cmp at its use (C3 sweep 93.0 -> 85.3 ms)
@@ -614,6 +824,10 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                         STAMP(13);
                         if (tid < 16 * T && (tid >> 4) == kappa && ((pm >> (tid & 15)) & 1u))
                             P[__builtin_popcount(pm & ((1u << (tid & 15)) - 1u)) * CW + RHSPOS] = q;
+                        if constexpr (PAIR) {
+                            if (pr_ncol >= 0 && tid < 16 * T && (tid >> 4) == kappa && ((pm >> (tid & 15)) & 1u))
+                                s_cpos[pr_ncol + __builtin_popcount(pm & ((1u << (tid & 15)) - 1u))] = basic ? ~mypos : mypos;
+                        }
                         // is this thread's panel row a pivot row?  row position t <-> variable 16*rowrho + rowc
                         int myj = -1;
                         bool my_basic = false;
@@ -626,7 +840,9 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                         STAMP(1);
                         if (tid == 0) s_veto[bpar ^ 1] = NO_VETO;              // the other slot: last read before this barrier
                         // ---- 2. panel elimination -----------------------------------------------------------------------
-                        {
+                        // (pricing: the gathered columns stay as they are — no panel, and below no pivot: the block body runs empty, as after a veto;
+                        // a `continue` behind the gather instead makes the allocator spill 770 VGPRs of the tableau)
+                        if (!(PAIR && pr_ncol >= 0)) {
                             int veto;
                             switch (m) {
 #define PARTLS_PB(i) case i: if constexpr (i <= MB) veto = panel_block<(i <= MB ? i : 1), CW, MB>(P, Z, U, Dinv, myj, my_basic, p.piv_eps, tid, tid, idle_wave); else veto = 0; break;
@@ -655,6 +871,12 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                             pmx = 0;
                             mx = 0;
                             ++nveto;
+                        }
+                        if constexpr (PAIR) {
+                            const bool pr = pr_ncol >= 0;
+                            pmx = pr ? 0u : pmx;
+                            mx = pr ? 0 : mx;
+                            pr_ncol += pr ? m : 0;
                         }
                         // ---- 3. fused rank-m update of the register tableau ------------------------------------------------
                         bool blk_ok = false;
@@ -693,6 +915,80 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                         STAMP(4);
                     }
                     tiles &= tiles - 1;
+                if constexpr (PAIR) {
+                    // (inside the loop over the tile columns, behind the last one: an easy twin hands the loop the NEXT pattern's tile columns,
+                    // those of the confirming scan's look-ahead, and its exchange starts without a scan, as it does behind an ordinary pattern)
+                    if (pr_ncol >= 0 && tiles == 0) {
+                        // ---- pricing the twin of pattern gi: its m violators' columns are panel columns 0..m-1 (after this barrier) ----------
+                        const int m = pr_ncol;
+                        pr_ncol = -1;
+                        const int part = (sc - 1) & 1;                    // the twin's scan was the last one
+                        // the thread's coordinates once more, opaque: everything derived from `tid` itself is hoisted out of the chain loop and
+                        // held in registers through the whole kernel (lane masks, row positions: 8 spilled VGPRs at T = 16)
+                        int tidp = tid;
+                        asm volatile("" : "+v"(tidp));
+                        const int lanep = tidp & 63, wavep = __builtin_amdgcn_readfirstlane(tidp >> 6);
+                        __syncthreads();
+                        // One wave solves while the other seven wait at the barrier: nothing else of the pricing can start before the coefficients
+                        // exist (every row's FMAs need all of them).  The panel is not in use, so no wave owns a panel row here and any wave will
+                        // do — wave 3, of half 0 rather than the blocks' idle wave of half 1: half 0 holds fewer tile slots (66 against 70 at
+                        // T = 16), so the solve's ten live registers land where the allocation has room.
+                        if (H == 0 && wavep == 3) pair_solve<CW>(Pbase, s_cpos, m, lanep, RHSPOS, s_pair);
+                        __syncthreads();
+                        const bool guard = __builtin_amdgcn_readfirstlane(__double2hiint(s_pair[2 * PAIR_MAXC + 1])) != 0;
+                        // every thread forms its twin rhs entry: the pivot rows take the solve's, the others m FMAs on their own panel row
+                        const unsigned long long cw = s_inf[part * 8 + wavep];
+                        const bool in_c = has_var && ((cw >> lanep) & 1ull);
+                        double qt = q, cornert = corner;
+                        {
+                            const int rp = tidp < 16 * T ? (tidp & 15) * RS + (tidp >> 4) : RHSPOS;
+                            for (int j = 0; j < m; ++j) {
+                                const double aj = s_pair[j];
+                                qt = fma(-Pbase[j * CW + rp], aj, qt);
+                                cornert = fma(-Pbase[j * CW + RHSPOS], aj, cornert);       // the rhs row's own entry: the objective
+                            }
+                        }
+                        if (in_c) {
+                            int rank = __popcll(cw & ((1ull << lanep) - 1ull));
+#pragma unroll
+                            for (int w = 0; w < NW; ++w)
+                                if (w < wavep) rank += __popcll(s_inf[part * 8 + w]);
+                            qt = s_pair[PAIR_MAXC + rank];
+                        }
+                        const bool bt = basic != in_c;
+                        const uint64_t vmask = s_vmask[tidp < 16 * T ? tidp : 0] & (has_var ? ~0ULL : 0ULL);
+                        const uint64_t gt = (uint64_t)g0 + (unsigned)pair_partner(gi);
+                        const int ft = sign_of_var(vmask, gt ^ (gt >> 1));
+                        const double fqt = qt * (double)(ft > 1 ? 1 : (ft < -1 ? -1 : ft));
+                        const bool bad2 = has_var && (bt ? ((ft == 0) || (fqt < -p.tol)) : (fqt > p.tol));   // kkt_violates (sweep_rules.h), written out
+                        const unsigned long long b2 = __ballot(bad2);
+                        if (lanep == 0) s_tw[wavep] = b2 != 0ull;
+                        __syncthreads();
+                        int left = guard ? 1 : 0;
+#pragma unroll
+                        for (int w = 0; w < 8; ++w) left |= s_tw[w];
+                        left = __builtin_amdgcn_readfirstlane(left);
+                        // easy: the block pivot on C is the whole story — recorded as finish_pattern records; else nothing of the pricing is kept
+                        if (!left) record_twin(pair_partner(gi), cornert, qt, bt);
+                        STAMP(14);
+                        if (!pair_next(left != 0, f, fn)) chain_end = true;
+                        else {
+                            blocked = false;
+                            ninf_best = n + 1; patience = 3; rounds = 0;
+                            if (!left && count2 != 0 && p.max_rounds >= 1) {          // as behind finish_pattern above
+                                ninf_best = count2; rounds = 1;
+                                all = true;
+                                tiles = (unsigned)__builtin_amdgcn_readfirstlane((int)tiles2);
+                                soff = par * 8 + 16;
+                                const int tl = lanep < T ? lanep : 0, wl = tl >> 2, shl = 16 * (tl & 3);
+                                tmask = (unsigned)((s_inf[soff + wl] >> shl) & 0xFFFFull) | ((unsigned)((s_bas[par * 8 + wl] >> shl) & 0xFFFFull) << 16);
+                            }
+                        }
+                    }
+                }
+                }
+                if constexpr (PAIR) {
+                    if (chain_end) break;
                 }
             }
             if constexpr (!MERGED) {
@@ -756,14 +1052,15 @@ __device__ __forceinline__ void batch_select(SweepParams &p)
     if (p.best_sol) p.best_sol += q * (int64_t)gridDim.x * p.node_ld;
 }
 
-template <int T, bool NODE, bool MODELS = false, bool BATCH = false>
+template <int T, bool NODE, bool MODELS = false, bool BATCH = false, bool PAIRK = false>
 __global__ __launch_bounds__(THREADS, 2) void sweep_blk_kernel(SweepParams p)
 {
     if constexpr (BATCH) batch_select(p);
     const int half = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
-    if (half == 0) sweep_body<T, 0, NODE, 2, MODELS, BATCH>(p);
-    else sweep_body<T, 1, NODE, 2, MODELS, BATCH>(p);
+    if (half == 0) sweep_body<T, 0, NODE, 2, MODELS, BATCH, PAIRK>(p);
+    else sweep_body<T, 1, NODE, 2, MODELS, BATCH, PAIRK>(p);
 }
+constexpr bool pair_compiled(int T) { return PARTLS_PAIR && PARTLS_MERGED_SCAN && PARTLS_LANE_MASKS && T > MAXT_S && T <= 16; }
 
 #ifndef PARTLS_SMALL_OCC
 #define PARTLS_SMALL_OCC(T) ((T) <= 8 ? 3 : 2)          // waves per SIMD = workgroups per CU the allocator is asked to leave room for
@@ -864,6 +1161,7 @@ static hipError_t launch_blk_T(const SweepParams &p, int grid, hipStream_t s, bo
     } else {
         if (p.node_code) hipLaunchKernelGGL((blk::sweep_blk_kernel<T, true>), dim3(grid), dim3(blk::THREADS), 0, s, p);     // ~100 KB of static LDS
         else if (models) hipLaunchKernelGGL((blk::sweep_blk_kernel<T, false, true>), dim3(grid), dim3(blk::THREADS), 0, s, p);
+        else if (blk::pair_compiled(T) && p.pair) hipLaunchKernelGGL((blk::sweep_blk_kernel<T, false, false, false, blk::pair_compiled(T)>), dim3(grid), dim3(blk::THREADS), 0, s, p);
         else hipLaunchKernelGGL((blk::sweep_blk_kernel<T, false>), dim3(grid), dim3(blk::THREADS), 0, s, p);
     }
     return hipGetLastError();

@@ -16,7 +16,9 @@
 //                   rounds = 1), and the ranking at the end of a pattern (finish_pattern, on objective^2 in LDS, its own form);
 //   sweep_lazy.hip  sweep_lazy_kernel: the KKT scan, the exchange and the ranking;
 //   sweep_coop.hip  sweep_coop_kernel: the KKT scan and the exchange (a single solve ranks nothing).
-// A change to kkt_violates, ExchangeRule or rank_pattern is made here AND in those places (ten with the merged scan's two).
+// A change to kkt_violates, ExchangeRule or rank_pattern is made here AND in those places (ten with the merged scan's two; the pair walk of
+// sweep_blk.hip adds kkt_violates twice more, under the twin's signs: the scan for its violators and the scan of its priced rhs column, and
+// the ranking once more: record_twin, the bookkeeping of a priced twin).
 #pragma once
 #include "common.h"
 

@@ -308,6 +308,30 @@ int64_t partls::reference_pattern(const partls_ctx *c, int64_t q)
     return (int64_t)r;
 }
 
+// The pair walk (sweep_blk.hip, PAIR) runs on the 512-thread register kernel up to T = 16.  PARTLS_PAIR forces it off or on; left alone it
+// is on where all of this holds:
+//   * the bit-order calibration's length rule (calibrate_bit_order: K' >= 18 on 256 CUs) — the enumerations whose cheapest group sits on
+//     bit 0 and that are long enough for the walk to matter; short ones keep the plain walk and their pivot counts;
+//   * the range itself gives every CU 32 patterns or more: a short range of a long enumeration (partls_opt_models' companion sweeps,
+//     whose winner is promised bit for bit among the export's rows: include/partls.h) keeps the plain walk;
+//   * the group on bit 0 has 12..16 live variables.  A heuristic fitted to the two long enumerations the benchmark has, one each: with 12
+//     (C3, K = 20) the walk gains 4.1 % (sweep 47.61 -> 45.65 ms), with 10 (C5, K = 24) it LOSES 3.3 % (669.2 -> 691.6 ms with the walk
+//     forced) — pricing a twin (a scan, a gather pass through the block body, the solve on one wave, the rows, a scan: ~16k cycles in
+//     the stamp build) costs about what 10 pivots in two block pivots cost (profiles/pair_ab_c3.txt).  Nothing between 10 and 12 was
+//     measured; the rule stays on the side that was seen to win.  Beyond 16 every twin goes to the rounds and only its scan is added.
+bool partls::sweep_pairs(const partls_ctx *c, int64_t total)
+{
+    if (!c->use_reg || sweep_reg_small(c->T) || c->T > 16 || c->knobs.pair == 0) return false;
+    if (c->knobs.pair == 1) return true;
+    const int kb = c->kbits, seg_len = (kb + (kb >= 8 ? 2 : 1) - 1) / (kb >= 8 ? 2 : 1);
+    if (kb < 2 || ((int64_t)1 << kb) < (int64_t)c->ncu * 32 * (8 + seg_len) || total < (int64_t)c->ncu * 32) return false;
+    int live = 0;
+    for (int k = 0; k < kb; ++k)
+        if (c->order.gbit[k] == 0)
+            for (int i = 0; i < c->n; ++i) live += ((c->mask_tab[(size_t)i] >> k) & 1ULL) != 0 && c->hScale[(size_t)i] != 0.0;
+    return live >= 12 && live <= 16;
+}
+
 // Chain length and grid of a sweep over `total` Gray indices (partls_opt_sweep; partls_opt_models per piece: the same plan for the same
 // range, so its rows carry the objectives all_opt gets).  false (error set): the range needs more than 2^31 chains.
 bool partls::sweep_plan(partls_ctx *c, int64_t total, int64_t *chain_len_out, int *grid_out, const char *who)
@@ -346,6 +370,9 @@ bool partls::sweep_plan(partls_ctx *c, int64_t total, int64_t *chain_len_out, in
         while (chain_len > 16 && (total + chain_len - 1) / chain_len < ncu) chain_len >>= 1;
     }
     if (chain_len < 1) chain_len = 1;
+    // pair walk: chains of even length (an odd one leaves a pattern without its partner at every chain end: solved the ordinary way).
+    // A range with an odd g_begin keeps such end patterns; PARTLS_CHAIN_LEN is taken as given.
+    if (c->knobs.chain_len <= 0 && sweep_pairs(c, total)) chain_len += chain_len & 1;
     const int64_t nchains = (total + chain_len - 1) / chain_len;
     if (nchains >= (1LL << 31) || chain_len >= (1LL << 31)) { set_error("%s: more than 2^31 chains in one call; split the Gray-index range", who); return false; }
     int grid = (int)std::min<int64_t>(nchains, c->knobs.grid > 0 ? c->knobs.grid : (c->use_reg ? 4096 : 1024));

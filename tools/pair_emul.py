@@ -1,0 +1,265 @@
+"""numpy emulation of the PAIR WALK of sweep_blk.hip (development aid; never imported by the product or the tests).
+
+The walk, the pricing of a twin and its guards follow the kernel statement by statement (sweep_body's pair_partner / pair_unit_end /
+pair_target / pair_next and pair_solve), on tools/tableau_emul.py's dense tableau and its sequential pivot():
+
+  * patterns g and g ^ 1 of a chain are a pair; the tableau visits the member whose bit 0 is the committed state's;
+  * the twin is priced from the columns T[:, C] of its violators C: the |C| x |C| system of the pivot rows with the rhs entries q_C
+    as a column, sequential pivots in ascending order (T_ik / |d|, T_kk = -1/d), a_k = +q'_k (entering) / -q'_k (leaving),
+    q_i' = q_i - sum_k T_ik a_k, corner' = corner - sum_k q_k a_k;  every priced twin is ALSO pivoted sequentially on a copy of the
+    tableau and the two results are compared (`formula error`: the check of the sign conventions);
+  * hard twins (|C| > 16, an entering pivot at or below the guard, violators left) go to the ordinary rounds.
+
+Reports, per problem: committed pivots against the plain walk's, easy / hard twins, |C|, tile columns of C, the smallest pivot, the
+largest error against the oracle, and the twins that were priced although the ordinary path (the leave-one-out rule of the rounds)
+rejects a column for them — that count must be 0.
+
+  python tools/pair_emul.py tests            the problems of tests/test_gpu_pair.py
+  python tools/pair_emul.py fuzz [count]     problems drawn by tests/test_gpu_fuzz.py's _random_problem (default 200)
+"""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.getcwd())
+sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
+sys.path.insert(0, os.path.join(os.getcwd(), "tools"))
+
+from tableau_emul import pivot, prepare  # noqa: E402
+
+PAIR_MAXC = 16
+PIV_MIN = 1.00000000055e-4          # sweep_blk.hip: PAIR_PIV_MIN_HI (the high word of the pivot above that of 1e-4)
+PIV_EPS = 1e-11
+
+
+def pop(v):
+    return bin(int(v)).count("1")
+
+
+def signs(mask, n, pat):
+    return np.array([2 * pop(int(mask[v]) & pat) - pop(mask[v]) for v in range(n)])
+
+
+def violators(T, n, basic, f, tol, blocked=None):
+    q = T[:n, n]
+    fq = np.where(f > 0, q, np.where(f < 0, -q, 0.0))
+    nb = (fq > tol) if blocked is None else ((fq > tol) & ~blocked)
+    return np.where(basic, (f == 0) | (fq < -tol), nb)
+
+
+def rounds(T, n, basic, f, tol, stats):
+    """the ordinary exchange rounds (tableau_emul.sweep's body, leave-one-out rule); returns pivots applied"""
+    blocked = np.zeros(n, dtype=bool)
+    ninf_best, patience, nr, progress, npiv = n + 1, 3, 0, False, 0
+    while True:
+        if progress:
+            blocked[:] = False
+        progress = False
+        viol = np.nonzero(violators(T, n, basic, f, tol, blocked))[0]
+        if len(viol) == 0:
+            return npiv
+        if len(viol) < ninf_best:
+            ninf_best, patience, allv = len(viol), 3, True
+        elif patience > 0:
+            patience -= 1
+            allv = True
+        else:
+            allv = False
+        nr += 1
+        if nr > 20 * (n + 1):
+            stats["capped"] += 1
+            return npiv
+        if not allv:
+            viol = viol[-1:]
+        for k in viol:
+            d = T[k, k]
+            if not basic[k]:
+                col = np.delete(T[:n, k], k)
+                cmax2 = float(np.max(col ** 2)) if len(col) else 0.0
+                if d <= PIV_EPS * max(1.0, cmax2):
+                    blocked[k] = True
+                    stats["rejections"] += 1
+                    continue
+            pivot(T, k, d)
+            basic[k] = not basic[k]
+            progress = True
+            npiv += 1
+
+
+def price(T, n, basic, C):
+    """pair_solve + the row phase: (guard fired, q', corner', smallest entering pivot)"""
+    m = len(C)
+    A = T[np.ix_(C, C)].copy()
+    qc = T[C, n].copy()
+    dmin = np.inf
+    for s in range(m):
+        d = A[s, s]
+        if not basic[C[s]]:
+            dmin = min(dmin, d)
+            if not d >= PIV_MIN:
+                return True, None, None, dmin
+        inv = 1.0 / d
+        ainv = abs(inv)
+        col = A[:, s].copy()                      # the pivot COLUMN: u_j = col[j]
+        qs = qc[s]
+        for r in range(m):
+            fz = -col[r] * inv
+            if r == s:
+                A[r, :] = col * ainv
+                qc[r] = qs * ainv
+            else:
+                A[r, :] += fz * col
+                qc[r] += fz * qs
+        A[:, s] = col * ainv
+        A[s, s] = -inv
+    a = np.where(basic[C], -qc, qc)
+    qt = T[:n, n] - T[:n][:, C] @ a
+    qt[C] = qc
+    return False, qt, T[n, n] - T[C, n] @ a, dmin
+
+
+def pair_sweep(pr, chain_len, g_begin=0, g_end=None, pairing=True):
+    n, T0, mask, kbits, tol = pr["n"], pr["T0"], pr["mask"], pr["kbits"], pr["tol"]
+    g_end = (1 << kbits) if g_end is None else g_end
+    out = np.full(1 << kbits, np.nan)
+    st = dict(pivots=0, easy=0, empty=0, hard_wide=0, hard_guard=0, hard_left=0, capped=0, rejections=0, csize=[], ctiles=[],
+              dmin=np.inf, formula_err=0.0, priced_but_rejected=0)
+    gray = lambda g: g ^ (g >> 1)
+    for g0 in range(g_begin, g_end, chain_len):
+        glen = min(chain_len, g_end - g0)
+        T = T0.copy()
+        basic = np.zeros(n, dtype=bool)
+
+        def partner(i):
+            j = i - 1 if (g0 + i) & 1 else i + 1
+            return j if pairing and 0 <= j < glen else -1
+
+        def unit_end(i):
+            return max(i, partner(i)) + 1
+
+        def target(u, i):
+            if partner(u) < 0 or (g0 + u) & 1:
+                return u
+            return u + 1 if (gray(g0 + u) ^ gray(g0 + i)) & 1 else u
+
+        gi, pending = 0, partner(0) >= 0
+        while True:
+            f = signs(mask, n, gray(g0 + gi))
+            st["pivots"] += rounds(T, n, basic, f, tol, st)
+            out[gray(g0 + gi)] = np.sqrt(max(T[n, n], 0.0))
+            to_twin = False
+            if pending:
+                ft = signs(mask, n, gray(g0 + partner(gi)))
+                C = np.nonzero(violators(T, n, basic, ft, tol))[0]
+                to_twin = True
+                if len(C) == 0:
+                    st["empty"] += 1
+                    out[gray(g0 + partner(gi))] = np.sqrt(max(T[n, n], 0.0))
+                    to_twin = False
+                elif len(C) > PAIR_MAXC:
+                    st["hard_wide"] += 1
+                else:
+                    guard, qt, ct, dmin = price(T, n, basic, C)
+                    st["dmin"] = min(st["dmin"], dmin)
+                    if guard:
+                        st["hard_guard"] += 1
+                    else:
+                        bt = basic.copy()
+                        bt[C] = ~bt[C]
+                        T2 = T.copy()
+                        T2[:n, n] = qt
+                        if violators(T2, n, bt, ft, tol).any():
+                            st["hard_left"] += 1
+                        else:
+                            st["easy"] += 1
+                            st["csize"].append(len(C))
+                            st["ctiles"].append(len(set(int(k) // 16 for k in C)))
+                            out[gray(g0 + partner(gi))] = np.sqrt(max(ct, 0.0))
+                            to_twin = False
+                            # the sign conventions: sequential pivot() of the same block on a copy; and what the rounds would reject
+                            T3 = T.copy()
+                            rej = False
+                            for k in C:
+                                d = T3[k, k]
+                                if not basic[k]:
+                                    col = np.delete(T3[:n, k], k)
+                                    rej = rej or d <= PIV_EPS * max(1.0, float(np.max(col ** 2)))
+                                pivot(T3, k, d)
+                            st["priced_but_rejected"] += int(rej)
+                            scale = max(1.0, float(np.max(np.abs(T3[:n, n]))))
+                            st["formula_err"] = max(st["formula_err"], float(np.max(np.abs(T3[:n, n] - qt))) / scale,
+                                                    abs(T3[n, n] - ct) / max(1.0, abs(ct)))
+            if to_twin:
+                gi, pending = partner(gi), False
+                continue
+            u = unit_end(gi)
+            if u >= glen:
+                break
+            gi = target(u, gi)
+            pending = partner(gi) >= 0
+    return out, st
+
+
+def report(tag, pr, ref, chain_len, **kw):
+    plain, sp = pair_sweep(pr, chain_len, pairing=False, **kw)
+    got, st = pair_sweep(pr, chain_len, **kw)
+    seen = ~np.isnan(got)
+    err = float(np.max(np.abs(got[seen] - ref[seen]) / np.maximum(1.0, ref[seen]))) if ref is not None else float("nan")
+    hard = st["hard_wide"] + st["hard_guard"] + st["hard_left"]
+    cs = st["csize"]
+    print("%-28s pivots %6d (plain walk %6d)  twins: easy %4d empty %4d hard %4d (wide %d guard %d left %d)  |C| %s  tiles %s  min pivot %.3g  "
+          "formula err %.2g  oracle err %.2g  priced-but-rejected %d  capped %d" % (
+              tag, st["pivots"], sp["pivots"], st["easy"], st["empty"], hard, st["hard_wide"], st["hard_guard"], st["hard_left"],
+              ("%d..%d" % (min(cs), max(cs))) if cs else "-", ("%d..%d" % (min(st["ctiles"]), max(st["ctiles"]))) if cs else "-",
+              st["dmin"], st["formula_err"], err, st["priced_but_rejected"], st["capped"]))
+    return st, err
+
+
+def main():
+    from oracle import oracle as O
+    O.build()
+    what = sys.argv[1] if len(sys.argv) > 1 else "tests"
+    bad = 0
+    if what == "tests":
+        import test_gpu_pair as tp
+        for kind, n, flags in tp.CASES:
+            X, y, P = tp.problem(kind, n, flags)
+            faithful = bool(flags & tp.FAITHFUL)
+            ref = None
+            if faithful:
+                Xo, Po = O.homogeneous(X, P)
+                R, z = O.compress(Xo, y)
+                ref = O.opt_patterns(R, z, Po, np.arange(1 << (tp.K + 1)))
+            pr = prepare(np.asarray(X), y, np.asarray(P), 0.0, faithful=faithful)
+            for cl in (16, 7):
+                st, err = report("%s n=%d flags=%d chain %d" % (kind, n, flags, cl), pr, ref, cl)
+                bad += st["priced_but_rejected"] + (faithful and not err <= 1e-9) + (st["formula_err"] > 1e-9)
+                # what each kind is there for (chains of 16 are the plan the tests run on; `plain walk` here is the emulation's own)
+                hard = st["hard_wide"] + st["hard_guard"] + st["hard_left"]
+                priced = st["easy"] + st["empty"]
+                want = {"plain": st["easy"] >= 1 and hard >= 1,
+                        "straddle": st["easy"] >= 1 and max(st["ctiles"], default=0) >= 2,
+                        "wide": priced == 0 and hard == st["hard_wide"] >= 1,       # every twin is hard: none can be priced
+                        "null": st["empty"] >= 1,
+                        "dup": st["easy"] >= 1 and hard >= 1 and st["hard_guard"] >= 1,
+                        "overlap": st["easy"] >= 1}[kind]
+                if not want:
+                    print("    ^ %s lacks the twins it is there for" % kind)
+                    bad += 1
+    else:
+        from test_gpu_fuzz import _random_problem
+        cnt = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+        rng = np.random.default_rng(9000)
+        for i in range(cnt):
+            X, y, P, eta = _random_problem(rng)
+            ref = O.fit_opt(X, y, P, eta=eta, return_all=True)["all_opt"]
+            pr = prepare(X, y, P, eta)
+            st, err = report("fuzz %d %s K=%d" % (i, X.shape, P.shape[1]), pr, ref, 16)
+            bad += st["priced_but_rejected"]
+    print("priced-but-rejected / failed checks in total: %d" % bad)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
