@@ -511,13 +511,17 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                 }
             }
             // the ranking of rank_pattern (sweep_rules.h) on objective^2 held in LDS, in this kernel's own form: it has no `best_pat >= 0` guard
-            if (tid == THREADS - 1) {                                // lexicographic (objective, pattern) minimum: argmin's first-index rule
+            // lexicographic (objective, pattern) minimum and runner-up: argmin's first-index rule for both.  The minimum is never above the
+            // runner-up, so a pattern above the runner-up — nearly every one — is done after one comparison
+            if (tid == THREADS - 1 && obj2 <= s_best[2]) {
                 const double bo = s_best[0];
                 const long long bp = reinterpret_cast<long long *>(s_best)[1];
                 if (obj2 < bo || (obj2 == bo && ref_index_less(pat, (unsigned long long)bp, lds_image.s_rbit))) {
                     s_best[2] = bo; reinterpret_cast<long long *>(s_best)[3] = bp;             // the old minimum becomes the runner-up
                     s_best[0] = obj2; reinterpret_cast<long long *>(s_best)[1] = (long long)pat;
-                } else if (obj2 < s_best[2]) { s_best[2] = obj2; reinterpret_cast<long long *>(s_best)[3] = (long long)pat; }
+                } else if (obj2 < s_best[2] || ref_index_less(pat, (unsigned long long)reinterpret_cast<long long *>(s_best)[3], lds_image.s_rbit)) {
+                    s_best[2] = obj2; reinterpret_cast<long long *>(s_best)[3] = (long long)pat;     // (equal to the runner-up's here)
+                }
             }
         };
         // the same bookkeeping for a pattern the tableau does not hold — a twin of the pair walk (PAIR: chain mode, no export of models): its
@@ -534,13 +538,15 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                     if (has_var) p.best_sol[(size_t)blockIdx.x * p.node_ld + tid] = bv ? qv : 0.0;
                 }
             }
-            if (tid == THREADS - 1) {                                // finish_pattern's ranking
+            if (tid == THREADS - 1 && obj2 <= s_best[2]) {           // finish_pattern's ranking
                 const double bo = s_best[0];
                 const long long bp = reinterpret_cast<long long *>(s_best)[1];
                 if (obj2 < bo || (obj2 == bo && ref_index_less(pat, (unsigned long long)bp, lds_image.s_rbit))) {
                     s_best[2] = bo; reinterpret_cast<long long *>(s_best)[3] = bp;
                     s_best[0] = obj2; reinterpret_cast<long long *>(s_best)[1] = (long long)pat;
-                } else if (obj2 < s_best[2]) { s_best[2] = obj2; reinterpret_cast<long long *>(s_best)[3] = (long long)pat; }
+                } else if (obj2 < s_best[2] || ref_index_less(pat, (unsigned long long)reinterpret_cast<long long *>(s_best)[3], lds_image.s_rbit)) {
+                    s_best[2] = obj2; reinterpret_cast<long long *>(s_best)[3] = (long long)pat;
+                }
             }
         };
         int gi = 0;

@@ -735,7 +735,9 @@ __global__ __launch_bounds__(NT) void sweep_lazy_kernel(SweepParams p, int mb, i
             if (obj < best_obj || (obj == best_obj && best_pat >= 0 && ref_index_less(pat, (unsigned long long)best_pat, p.rbit.gbit))) {
                 second_obj = best_obj; second_pat = best_pat;
                 best_obj = obj; best_pat = (long long)pat;
-            } else if (obj < second_obj) { second_obj = obj; second_pat = (long long)pat; }
+            } else if (obj < second_obj || (obj == second_obj && second_pat >= 0 && ref_index_less(pat, (unsigned long long)second_pat, p.rbit.gbit))) {
+                second_obj = obj; second_pat = (long long)pat;
+            }
             // the workgroup's best pattern so far leaves its solution behind (as sweep_blk.hip's 256-thread kernel does): the host takes
             // the winner's from here instead of solving that pattern again — at n > 320 a 1.2 ms solve on the many-workgroup kernel
             if (!MODELS && p.best_sol && !code && obj2 < wg_best2) {

@@ -63,7 +63,9 @@ struct ExchangeRule {
 };
 
 // lexicographic (objective, pattern) minimum with its runner-up (near-tie re-rank on the host); exact ties go to the pattern that comes
-// first in the reference's visiting order (argmin's first-index rule).  (Works on copies and stores all four once: conditional stores
+// first in the reference's visiting order (argmin's first-index rule) — for the runner-up as for the minimum, so that the two are the two
+// smallest (objective, reference index) pairs whatever the order of the visits (the pair walk visits in another order than the plain
+// walk, and partls_opt_candidates lists the same patterns after both).  (Works on copies and stores all four once: conditional stores
 // through the references end up as one store to a selected address, which keeps the caller's variables in scratch memory.)
 __device__ __forceinline__ void rank_pattern(double obj, uint64_t pat, double &best_obj, long long &best_pat, double &second_obj,
                                              long long &second_pat, const unsigned char *rbit)
@@ -73,7 +75,7 @@ __device__ __forceinline__ void rank_pattern(double obj, uint64_t pat, double &b
     if (obj < bo || (obj == bo && bp >= 0 && ref_index_less(pat, (unsigned long long)bp, rbit))) {
         so = bo; sp = bp;
         bo = obj; bp = (long long)pat;
-    } else if (obj < so) { so = obj; sp = (long long)pat; }
+    } else if (obj < so || (obj == so && sp >= 0 && ref_index_less(pat, (unsigned long long)sp, rbit))) { so = obj; sp = (long long)pat; }
     best_obj = bo; best_pat = bp; second_obj = so; second_pat = sp;
 }
 

@@ -32,7 +32,8 @@ Every kind but wide and null also asserts pivots() strictly below the paired-off
 two-tile-column gather — and every case runs the finish on the sweep's winner with PARTLS_FINISH_TRACE: best_index equals the paired-off
 run's, the objective agrees within rtol 1e-10, and where the paired-off walk's best_sol was taken by the finish (it carries the
 winner's signs) the pair walk's is taken too — a best_sol written from a priced twin's temporaries (qt, bt) with the committed
-member's signs or basis would be refused there.  tools/pair_emul.py walks these very problems on the CPU, reports the priced and the
+member's signs or basis would be refused there — where the sweep's winner is a priced twin, which these problems do not guarantee:
+tests/test_gpu_pair_routes.py has the problems that do, the other tile counts and the automatic route.  tools/pair_emul.py walks these very problems on the CPU, reports the priced and the
 hard twins of each and fails unless every kind has the twins it is there for."""
 import sys
 
@@ -56,8 +57,9 @@ COUPLING = 0.01                                             # see problem()
 SEED = {"plain": 0, "straddle": 0, "wide": 0, "null": 0, "dup": 0, "overlap": 0}
 
 
-def problem(kind, n, flags=FAITHFUL):
-    """(X, y, P) of one kind"""
+def problem(kind, n, flags=FAITHFUL, K=K, coupling=COUPLING):
+    """(X, y, P) of one kind; K groups, the part of group 0's columns inside the span of the others scaled to `coupling` (the defaults
+    draw the problems of this file; tests/test_gpu_pair_routes.py asks for longer enumerations and other couplings)"""
     D = n - 1 if flags & FAITHFUL else n
     N = 2 * D + 50
     rng = np.random.default_rng(20262000 + 1000 * n + 100 * SEED[kind] + 17 * KINDS.index(kind) + (flags & FAITHFUL))
@@ -79,7 +81,7 @@ def problem(kind, n, flags=FAITHFUL):
     oth = np.flatnonzero(grp != 0)
     Q, _ = np.linalg.qr(np.column_stack([X[:, oth], np.ones(N)]))
     par = Q @ (Q.T @ X[:, g0])
-    X[:, g0] += (COUPLING - 1.0) * par
+    X[:, g0] += (coupling - 1.0) * par
     if kind == "straddle":
         X[:, g0[:10]] = 0.0                                             # tableau variables 0..9 never move; 10..21 straddle tile columns 0 and 1
     if kind == "null":

@@ -14,7 +14,7 @@ Reports, per problem: committed pivots against the plain walk's, easy / hard twi
 largest error against the oracle, and the twins that were priced although the ordinary path (the leave-one-out rule of the rounds)
 rejects a column for them — that count must be 0.
 
-  python tools/pair_emul.py tests            the problems of tests/test_gpu_pair.py
+  python tools/pair_emul.py tests            the problems of tests/test_gpu_pair.py and tests/test_gpu_pair_routes.py
   python tools/pair_emul.py fuzz [count]     problems drawn by tests/test_gpu_fuzz.py's _random_problem (default 200)
 """
 import os
@@ -204,6 +204,7 @@ def pair_sweep(pr, chain_len, g_begin=0, g_end=None, pairing=True):
 def report(tag, pr, ref, chain_len, **kw):
     plain, sp = pair_sweep(pr, chain_len, pairing=False, **kw)
     got, st = pair_sweep(pr, chain_len, **kw)
+    st["plain_pivots"] = sp["pivots"]
     seen = ~np.isnan(got)
     err = float(np.max(np.abs(got[seen] - ref[seen]) / np.maximum(1.0, ref[seen]))) if ref is not None else float("nan")
     hard = st["hard_wide"] + st["hard_guard"] + st["hard_left"]
@@ -247,6 +248,56 @@ def main():
                 if not want:
                     print("    ^ %s lacks the twins it is there for" % kind)
                     bad += 1
+        # the problems of tests/test_gpu_pair_routes.py, each with its purpose as a failing condition
+        import test_gpu_pair_routes as tr
+
+        def objectives(X, y, P, pats):
+            Xo, Po = O.homogeneous(X, P)
+            R, z = O.compress(Xo, y)
+            return O.opt_patterns(R, z, Po, pats)
+
+        # A: every instantiation T = 11 .. 16 prices twins AND sends some to the rounds
+        for n, flags in tr.TILE_CASES:
+            X, y, P = tp.problem("plain", n, flags)
+            faithful = bool(flags & tp.FAITHFUL)
+            ref = objectives(X, y, P, np.arange(1 << (tp.K + 1))) if faithful else None
+            pr = prepare(np.asarray(X), y, np.asarray(P), 0.0, faithful=faithful)
+            st, err = report("A plain n=%d flags=%d chain 16" % (n, flags), pr, ref, 16)
+            hard = st["hard_wide"] + st["hard_guard"] + st["hard_left"]
+            bad += st["priced_but_rejected"] + (faithful and not err <= 1e-9) + (st["formula_err"] > 1e-9)
+            if not (st["easy"] >= 1 and hard >= 1):
+                print("    ^ n=%d lacks easy or hard twins" % n)
+                bad += 1
+        # B: the global winner has an odd Gray index g and is priced as the twin of g - 1 in the range [g - 1, g + 1)
+        for kind, n, mirror, coupling in tr.TWIN_CASES:
+            X, y, P = tr.twin_problem(kind, n, mirror, coupling)
+            ref = objectives(X, y, P, np.arange(1 << (tp.K + 1)))
+            w = int(np.argmin(ref))
+            g = tr.gray_inverse(w)
+            pr = prepare(np.asarray(X), y, np.asarray(P), 0.0, faithful=True)
+            st, err = report("B %s n=%d%s coupling %g: winner %d = gray(%d)" % (kind, n, " mirrored" if mirror else "", coupling, w, g),
+                             pr, ref, 16, g_begin=g - 1 + (~g & 1), g_end=g + 1 + (~g & 1))
+            bad += st["priced_but_rejected"] + (not err <= 1e-9) + (st["formula_err"] > 1e-9)
+            if not (g & 1 and st["easy"] == 1):
+                print("    ^ the winner is no priced twin (Gray index %d, %d priced)" % (g, st["easy"]))
+                bad += 1
+        # C: the first 256 patterns of the long enumerations on which the automatic rule turns the walk on save pivots
+        for tag, n, flags, K, live, null, _ in tr.ROUTE_CASES:
+            if not 12 <= live <= 16 or n > 256 or K < 17:
+                continue
+            X, y, P = tr.route_problem(n, flags, K, live, null)
+            faithful = bool(flags & tp.FAITHFUL)
+            pr = prepare(np.asarray(X), y, np.asarray(P), 0.0, faithful=faithful)
+            pats = np.arange(256) ^ (np.arange(256) >> 1)
+            ref = None
+            if faithful:
+                ref = np.full(1 << (K + 1), np.nan)
+                ref[pats] = objectives(X, y, P, pats)
+            st, err = report("C %s K=%d n=%d flags=%d [0, 256)" % (tag, K, n, flags), pr, ref, 16, g_end=256)
+            bad += st["priced_but_rejected"] + (faithful and not err <= 1e-9) + (st["formula_err"] > 1e-9)
+            if not (st["easy"] >= 1 and st["pivots"] < st["plain_pivots"]):
+                print("    ^ %s: the pair walk saves no pivots" % tag)
+                bad += 1
     else:
         from test_gpu_fuzz import _random_problem
         cnt = int(sys.argv[2]) if len(sys.argv) > 2 else 200
