@@ -237,6 +237,37 @@ partls_status partls_cv_opt_weighted(partls_ctx *ctx, const double *X, int64_t N
                                      double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t, double *opt,
                                      int64_t *best_index, double *heldout_sse, int32_t *status);
 
+/* ---- fit(Opt) under B row weightings of one (X, y, P) in one call: bootstrap replicates (integer counts), jackknife and repeated
+ * train / validation splits (0/1 weights), any other reweighting --------------------------------------------------------------------
+ * Inputs as partls_opt_prepare (x_on_device: X, y AND W are device pointers), plus
+ *   W: N x B doubles, column-major, leading dimension ldW >= N; column b is weighting b (rules of partls_opt_prepare_weighted: finite,
+ *      >= 0, sum > 0; a row of weight 0 acts as an absent row of problem b);   eta: finite, >= 0;   flags: those of partls_fit_opt.
+ * Problem b is exactly partls_opt_prepare_weighted(w = W[:, b], eta, flags), partls_opt_sweep(0, -1), partls_opt_finish(winner): the
+ * meanings, the near-tie window and the data-space KKT check are a single weighted fit's.  Outputs, column b of each (caller-allocated):
+ *   alpha[b * ld_alpha + m], beta[b * ld_beta + k], t[b], opt[b], best_index[b], status[b]: as partls_cv_opt (status 0 / 9 / 6; NaN
+ *              outputs and best_index -1 on 6);
+ *   oob_rows[b] (optional, NULL to skip): the number of rows with W[i, b] == 0 — the out-of-bag rows of a bootstrap replicate;
+ *   oob_sse[b]  (optional, NULL to skip): sum over those rows of (predict(model_b, x_i) - y_i)^2, unweighted, from the data; NaN when
+ *              oob_rows[b] is 0 or the problem failed (status 6).
+ * Every column of W is checked before any output is written: NaN / Inf anywhere -> PARTLS_ERR_NONFINITE; a negative entry, a column of
+ * sum 0, B < 1, ldW < N or a NULL W / required output -> PARTLS_ERR_BAD_ARG; a context of a partls_multi -> PARTLS_ERR_UNSUPPORTED;
+ * other argument errors as partls_cv_opt.  Any failure of the whole call writes no output.
+ * One upload of X, y, W; one weighted Gram per column (the single fit's kernel and summation order: an all-ones column gives the
+ * unweighted fit bit for bit); prepare, layout and sweep batched as in partls_cv_opt (register kernels, n <= 288, chunks of up to 65535
+ * problems) or one problem after another (larger n, PARTLS_OPT_GENERIC_KERNEL, PARTLS_RESAMPLE_SERIAL=1 read at partls_create); the
+ * visiting order is calibrated once on weighting 0; each problem is finished like a single fit with its column's weights.  The same call
+ * twice is bitwise equal.  The chain plan of a sweep goes by the size of the batch, so a problem swept in another batch (or alone) may
+ * start its finish from another chain's solution of the same winner: equal within a single fit's tolerances, not always bit for bit.
+ * oob_sse is a function of the model and the column alone (fixed blocks, fixed order, no atomics).  The device holds W, sqrt(W) (16 N B bytes) and one Gram per column for the call.
+ * Context state afterwards as after partls_cv_opt: no prepared problem; partls_get_sweep_route reports this call's route;
+ * partls_get_timing its phases (GRAM: the B Gram builds, PREP, SWEEP, FINISH: host wall time of the per-problem finishes, OOB: the
+ * out-of-bag pass). */
+partls_status partls_opt_weightings(partls_ctx *ctx, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
+                                    int x_on_device, const int64_t *P, int64_t K, int64_t ldP,
+                                    const double *W, int64_t ldW, int64_t B, double eta, uint32_t flags,
+                                    double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t, double *opt,
+                                    int64_t *best_index, double *oob_sse, int64_t *oob_rows, int32_t *status);
+
 /* ---- fit(Alt, X, y, P; η, ϵ, T)  — replaces Alt.jl:50-124 ------------------------------------------------------------
  * alpha0[M+1], beta0[K+1]: the random initial point the Julia shim draws exactly as Alt.jl:58-66 does.
  * Outputs as Alt.jl:119: alpha[M], beta[K], *t = β[end]*α[end], *opt, *iters = completed iterations. */
@@ -351,7 +382,8 @@ typedef enum {
     PARTLS_T_SWEEP = 2,     /* the sign-pattern sweep kernel          */
     PARTLS_T_FINISH = 3,    /* winner re-solve + residual from data   */
     PARTLS_T_CALIB = 4,     /* bit-order calibration of the sweep (0 when it did not run) */
-    PARTLS_T_COUNT = 5
+    PARTLS_T_OOB = 5,       /* out-of-bag pass of partls_opt_weightings (0 after every other call) */
+    PARTLS_T_COUNT = 6
 } partls_timer;
 partls_status partls_get_timing(const partls_ctx *ctx, partls_timer which, double *ms);
 /* host -> device upload of X inside the last prepare / fit on this context: wall time (ms) and bytes (0 / 0 when the inputs were device
@@ -375,8 +407,8 @@ partls_status partls_get_blocks(const partls_ctx *ctx, int64_t *blocks);
 partls_status partls_get_kkt_violation(const partls_ctx *ctx, double *violation, double *min_pivot);
 /* debugging / tests: the sweep kernel the prepared problem runs on (partls_opt_sweep, partls_opt_models, the node solves of
  * partls_bnb_bound* / fit(Alt) / partls_opt_finish) and its tile count T = ceil(n / 16) on the register kernels (0 on the global-memory
- * kernels).  After a partls_cv_opt (which leaves no prepared problem on ctx): the route of that call's problems, which are swept in one
- * batched launch on the register kernels unless PARTLS_CV_SERIAL is set.  Read-only: the prepare decides it from n, the flags and the
+ * kernels).  After a partls_cv_opt or partls_opt_weightings (which leave no prepared problem on ctx): the route of that call's
+ * problems, which are swept in one batched launch on the register kernels unless PARTLS_CV_SERIAL / PARTLS_RESAMPLE_SERIAL is set.  Read-only: the prepare decides it from n, the flags and the
  * knobs read at partls_create.  PARTLS_ERR_STATE when neither holds. */
 typedef enum {
     PARTLS_ROUTE_REG_256 = 1,   /* register-resident tableau, 256-thread workgroups (T <= 10)                            */

@@ -10,7 +10,7 @@ CSRC = os.path.join(_HERE, "csrc")
 OK, ERR_BAD_ARG, ERR_BAD_PARTITION, ERR_NONFINITE, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_CONVERGED, ERR_UNSUPPORTED, ERR_STATE, ERR_ILL_CONDITIONED = range(10)
 OPT_FAITHFUL_INTERCEPT = 1
 OPT_GENERIC_KERNEL = 2
-T_GRAM, T_PREP, T_SWEEP, T_FINISH, T_CALIB = range(5)
+T_GRAM, T_PREP, T_SWEEP, T_FINISH, T_CALIB, T_OOB = range(6)
 ROUTE_REG_256, ROUTE_REG_512, ROUTE_DEFERRED, ROUTE_EAGER = range(1, 5)
 
 _dp = C.POINTER(C.c_double)
@@ -51,6 +51,9 @@ SYMBOLS = [
     ("partls_cv_opt_weighted", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64,
                                          _i64, _ip, _i64, _dp, _i64, C.c_uint32, _dp, _i64, _dp, _i64, _dp, _dp, _ip, _dp,
                                          C.POINTER(C.c_int32)]),
+    ("partls_opt_weightings", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, C.c_int, C.c_void_p, _i64, _i64,
+                                        C.c_void_p, _i64, _i64, C.c_double, C.c_uint32, _dp, _i64, _dp, _i64, _dp, _dp, _ip, _dp, _ip,
+                                        C.POINTER(C.c_int32)]),
     ("partls_opt_num_patterns", _i64, [C.c_void_p]),
     ("partls_opt_bit_order", C.c_int, [C.c_void_p, _ip, _dp]),
     ("partls_fit_alt", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, C.c_void_p, _i64, _i64, C.c_double,

@@ -363,6 +363,41 @@ class Context:
             _check(L.lib().partls_cv_opt_weighted(*head, wp, *tail))
         return dict(alpha=alpha, beta=beta, t=t, opt=opt, best_index=bi, heldout_sse=sse, status=stat, F=F, E=E)
 
+    def opt_weightings(self, X, y, P, W, eta=0.0, flags=0, device_ptrs=None, oob=True):
+        """partls_opt_weightings: fit(Opt) under every column of W (N x B row weightings: bootstrap counts, 0/1 masks, any weights
+        that are finite, >= 0 and sum to more than 0 per column) in one call.  X, y, W: host arrays, or
+        device_ptrs=(dX_ptr, dy_ptr, N, ldX, dW_ptr, ldW, B) for device-resident float64 inputs (X, y, W then ignored; pass None).
+        A float32 X is widened to float64 on the host (this entry has no float32 form).  oob=False skips the out-of-bag pass.
+        Returns a dict of column-major results, one problem per column: alpha (M x B), beta (K x B), t, opt, best_index, status,
+        oob_sse (NaN where a column has no zero-weight row, the problem failed, or oob=False) and oob_rows (all length B)."""
+        if device_ptrs is None:
+            X, y, P = _inputs(X, y, P, f32=False)
+            N, ldX, on_dev = X.shape[0], X.shape[0], 0
+            if X.shape[1] != P.shape[0]:
+                raise ValueError("DimensionMismatch: X is %s, P is %s" % (X.shape, P.shape))
+            Wf = np.asfortranarray(W, dtype=np.float64)
+            if Wf.ndim != 2 or Wf.shape[0] != N or Wf.shape[1] < 1:
+                raise ValueError("opt_weightings: W must be (%d, B) with B >= 1, got %s" % (N, Wf.shape))
+            B, ldW = Wf.shape[1], N
+            xp, yp, wp = X.ctypes.data, y.ctypes.data, Wf.ctypes.data
+        else:
+            P = np.asfortranarray(P, dtype=np.int64)
+            dX, dy, N, ldX, dW, ldW, B = device_ptrs
+            xp, yp, wp, on_dev = C.c_void_p(dX), C.c_void_p(dy), C.c_void_p(dW), 1
+        M, K = P.shape
+        nB = max(int(B), 1)
+        alpha = np.zeros((M, nB), order="F")
+        beta = np.zeros((K, nB), order="F")
+        t = np.zeros(nB); opt = np.zeros(nB); sse = np.full(nB, np.nan)
+        bi = np.zeros(nB, dtype=np.int64)
+        rows = np.zeros(nB, dtype=np.int64)
+        stat = np.zeros(nB, dtype=np.int32)
+        self.generation += 1
+        _check(L.lib().partls_opt_weightings(self._h, xp, int(N), int(M), int(ldX), yp, on_dev, P.ctypes.data, K, M, wp, int(ldW), int(B),
+                                             float(eta), int(flags), _dp(alpha), M, _dp(beta), K, _dp(t), _dp(opt), _ip(bi),
+                                             _dp(sse) if oob else None, _ip(rows), _i32p(stat)))
+        return dict(alpha=alpha, beta=beta, t=t, opt=opt, best_index=bi, status=stat, oob_sse=sse, oob_rows=rows)
+
     def alt_prepared(self, alpha0, beta0, eps=1e-6, T=100):
         """Alt on a context prepared with OPT_FAITHFUL_INTERCEPT (e.g. device-resident inputs)."""
         N, M, K = self._shape
@@ -1081,6 +1116,151 @@ def cross_validate(alg, X, y, P, *, η=None, eta=None, nfolds=5, shuffle=False, 
                     best_index_eta=be, models=models, path=path, model=path[be] if be >= 0 else None,
                     opt=r["opt"].reshape(F + 1, E).copy(), best_index=r["best_index"].reshape(F + 1, E).copy(), status=st.copy(),
                     ill_conditioned=(st == L.ERR_ILL_CONDITIONED))
+
+
+@dataclass
+class BootstrapResult:
+    """What bootstrap and resample return: one fit(Opt) per weighting (replicate) b, as arrays — nothing here refers to a context.
+    counts: the N x B int64 multinomial draws of bootstrap (None from resample); alpha[B, M], beta[B, K], t[B], opt[B], best_index[B];
+    models[b]: PartLSFitResult, or None where status[b] is 6 (pivot cap: NaN rows); status[B] (0 / 9 / 6); oob_sse[b] / oob_rows[b]:
+    squared error and number of the rows replicate b left out (weight 0).  The statistics below go over the successful replicates
+    (status 0 or 9) and are plain numpy on B rows."""
+    counts: object
+    alpha: np.ndarray
+    beta: np.ndarray
+    t: np.ndarray
+    opt: np.ndarray
+    best_index: np.ndarray
+    models: list
+    status: np.ndarray
+    oob_sse: np.ndarray
+    oob_rows: np.ndarray
+
+    @property
+    def ok(self):
+        """replicates that returned a model"""
+        return np.asarray(self.status) != L.ERR_NOT_CONVERGED
+
+    @property
+    def ill_conditioned(self):
+        return np.asarray(self.status) == L.ERR_ILL_CONDITIONED
+
+    @property
+    def oob_mse(self):
+        """pooled out-of-bag error: sum of oob_sse over sum of oob_rows, over the successful replicates that left rows out"""
+        use = self.ok & (np.asarray(self.oob_rows) > 0) & np.isfinite(self.oob_sse)
+        return float(np.sum(self.oob_sse[use]) / np.sum(self.oob_rows[use])) if use.any() else float("nan")
+
+    @property
+    def sign_frequency(self):
+        """[K, 3]: share of the successful replicates with β_k < 0, = 0, > 0"""
+        b = np.asarray(self.beta)[self.ok]
+        if not len(b):
+            return np.full((np.asarray(self.beta).shape[1], 3), np.nan)
+        return np.stack([(b < 0).mean(0), (b == 0).mean(0), (b > 0).mean(0)], axis=1)
+
+    @property
+    def pattern_frequency(self):
+        """{best_index: share of the successful replicates whose winner it is}"""
+        bi = np.asarray(self.best_index)[self.ok]
+        v, c = np.unique(bi, return_counts=True)
+        return {int(p): float(n) / len(bi) for p, n in zip(v, c)}
+
+    def interval(self, level=0.95):
+        """percentile bounds over the successful replicates: dict(alpha=(lo[M], hi[M]), beta=(lo[K], hi[K]), t=(lo, hi))"""
+        level = float(level)
+        if not 0.0 < level < 1.0:
+            raise ValueError("interval: level must lie in (0, 1), got %r" % level)
+        ok = self.ok
+        if not ok.any():
+            raise ValueError("interval: no successful replicate")
+        q = [50.0 * (1.0 - level), 100.0 - 50.0 * (1.0 - level)]
+        out = {}
+        for k in ("alpha", "beta", "t"):
+            lo, hi = np.percentile(np.asarray(getattr(self, k))[ok], q, axis=0)
+            out[k] = (float(lo), float(hi)) if k == "t" else (lo, hi)
+        return out
+
+
+def _resample(who, alg, X, y, P, make_W, eta, faithful_intercept, generic_kernel, device, on_ill_conditioned):
+    """bootstrap and resample after their own argument checks.  make_W(N) -> (counts or None, W[N, B] float64) runs after the checks
+    of X, y, P and before any device work."""
+    if alg is not Opt:
+        raise TypeError("%s: only Opt is supported" % who)
+    if on_ill_conditioned not in ("warn", "raise"):
+        raise ValueError('on_ill_conditioned must be "warn" or "raise"')
+    Xf, yf, Pf = _fit_inputs(X, y, P)
+    N, M = Xf.shape
+    counts, W = make_W(N)
+    if not np.all(W.sum(axis=0) > 0):
+        raise ValueError("%s: a weighting sums to 0" % who)
+    B = W.shape[1]
+    flags = (L.OPT_FAITHFUL_INTERCEPT if faithful_intercept else 0) | (L.OPT_GENERIC_KERNEL if generic_kernel else 0)
+    r = default_context(device).opt_weightings(Xf, yf, Pf, W, eta, flags)
+    st = r["status"]
+    n_ill = int(np.sum(st == L.ERR_ILL_CONDITIONED))
+    if n_ill and on_ill_conditioned == "raise":
+        raise PartlsError(L.ERR_ILL_CONDITIONED, "%d replicate(s) failed the data-space KKT check" % n_ill)
+    if n_ill:
+        warnings.warn("partitionedls: %d replicate(s) failed the data-space KKT check (X too ill-conditioned for the fp64 Gram form under "
+                      "their weights); their models are the best Gram-form ones" % n_ill, IllConditionedWarning, stacklevel=3)
+    Pout = np.array(Pf, dtype=np.int64, order="C")
+    alpha, beta = np.ascontiguousarray(r["alpha"].T), np.ascontiguousarray(r["beta"].T)
+    models = [None if st[b] == L.ERR_NOT_CONVERGED else PartLSFitResult(alpha[b].copy(), beta[b].copy(), float(r["t"][b]), Pout)
+              for b in range(B)]
+    return BootstrapResult(counts=counts, alpha=alpha, beta=beta, t=r["t"], opt=r["opt"], best_index=r["best_index"], models=models,
+                           status=st, oob_sse=r["oob_sse"], oob_rows=r["oob_rows"])
+
+
+def _eta(η, eta):
+    return 0.0 if (η is None and eta is None) else float(η if η is not None else eta)
+
+
+def bootstrap(alg, X, y, P, *, B=100, rng=None, η=None, eta=None, weights=None, faithful_intercept=False, generic_kernel=False, device=0,
+              on_ill_conditioned="warn"):
+    """Nonparametric bootstrap of fit(Opt): B replicates in one device call (partls_opt_weightings) -> BootstrapResult.
+
+    Replicate b is fit(Opt, X, y, P; η, weights=counts[:, b]) with counts = _generator(rng).multinomial(N, np.full(N, 1/N), size=B).T
+    (int64, N x B; rng: None, an int seed or a numpy Generator) — returned as result.counts, so any replicate can be reproduced with
+    fit(..., weights=result.counts[:, b].astype(float)).  weights (as fit): the replicate's weights are counts[:, b] * weights.
+    The rows a replicate did not draw are its out-of-bag rows: result.oob_sse, oob_rows, oob_mse.  on_ill_conditioned as
+    cross_validate.  Only Opt (TypeError otherwise); single device.  A float32 X is widened to float64 on the host.
+    ValueError before any device work: B not an integer >= 1, bad weights (floating, finite, >= 0, sum > 0)."""
+    if alg is not Opt:
+        raise TypeError("bootstrap: only Opt is supported")
+    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or int(B) < 1:
+        raise ValueError("bootstrap: B must be an integer >= 1, got %r" % (B,))
+
+    def make_W(N):
+        wf = _weights(weights, N, "bootstrap")
+        counts = _generator(rng).multinomial(N, np.full(N, 1.0 / N), size=int(B)).T.astype(np.int64)
+        W = np.asfortranarray(counts, dtype=np.float64)
+        return counts, W if wf is None else np.asfortranarray(W * wf[:, None])
+
+    return _resample("bootstrap", alg, X, y, P, make_W, _eta(η, eta), faithful_intercept, generic_kernel, device, on_ill_conditioned)
+
+
+def resample(alg, X, y, P, W, *, η=None, eta=None, faithful_intercept=False, generic_kernel=False, device=0, on_ill_conditioned="warn"):
+    """fit(Opt) under the caller's own row weightings W (N x B: jackknife or repeated train / validation splits as 0/1 columns, any
+    reweighting) in one device call -> BootstrapResult with counts=None.  W: floating, finite, >= 0, every column sum > 0 (ValueError
+    otherwise, before any device work).  Otherwise as bootstrap; a column's zero-weight rows are its out-of-bag rows."""
+    if alg is not Opt:
+        raise TypeError("resample: only Opt is supported")
+
+    def make_W(N):
+        Wa = np.asarray(W)
+        if not np.issubdtype(Wa.dtype, np.floating):
+            raise ValueError("resample: W must be floating point, got %s" % Wa.dtype)
+        if Wa.ndim != 2 or Wa.shape[0] != N or Wa.shape[1] < 1:
+            raise ValueError("resample: W must have shape (%d, B) with B >= 1, got %s" % (N, Wa.shape))
+        Wf = np.asfortranarray(Wa, dtype=np.float64)
+        if not np.all(np.isfinite(Wf)):
+            raise ValueError("resample: W must be finite")
+        if np.any(Wf < 0):
+            raise ValueError("resample: W must be >= 0")
+        return None, Wf
+
+    return _resample("resample", alg, X, y, P, make_W, _eta(η, eta), faithful_intercept, generic_kernel, device, on_ill_conditioned)
 
 
 def predict(*args, device=0):

@@ -60,7 +60,7 @@ using namespace partls;
 
 extern "C" {
 
-int partls_version(void) { return 103; }
+int partls_version(void) { return 104; }
 const char *partls_last_error(void) { return g_err; }
 
 int partls_device_count(void)
@@ -116,6 +116,7 @@ try {
     c->knobs.alt_always_check = getenv("PARTLS_ALT_ALWAYS_CHECK") != nullptr;
     c->knobs.print_stamps = getenv("PARTLS_PRINT_STAMPS") != nullptr;
     c->knobs.cv_serial = getenv("PARTLS_CV_SERIAL") != nullptr && strcmp(getenv("PARTLS_CV_SERIAL"), "0") != 0;
+    c->knobs.resample_serial = getenv("PARTLS_RESAMPLE_SERIAL") != nullptr && strcmp(getenv("PARTLS_RESAMPLE_SERIAL"), "0") != 0;
     // a failure below must not leak the context (or the objects already created)
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     for (int w = 0; w < PARTLS_T_COUNT && e == hipSuccess; ++w) {
@@ -135,7 +136,7 @@ PARTLS_ABI_GUARD
 void partls_destroy(partls_ctx *c)
 {
     if (!c) return;
-    partls_destroy(c->cv_work);                           // partls_cv_opt's internal contexts (NULL when it never ran)
+    partls_destroy(c->cv_work);                           // partls_cv_opt's / partls_opt_weightings' internal contexts (NULL when neither ran)
     for (partls_ctx *v : c->cv_view) partls_destroy(v);
     c->cv_work = nullptr;
     c->cv_view.clear();
@@ -314,7 +315,7 @@ PARTLS_ABI_GUARD
 partls_status partls_get_sweep_route(const partls_ctx *c, int *kernel, int *tiles)
 try {
     if (!c || !kernel || !tiles) { set_error("partls_get_sweep_route: bad argument"); return PARTLS_ERR_BAD_ARG; }
-    // partls_cv_opt prepares its problems on the working context (cv.hip), which carries this context's knobs
+    // partls_cv_opt and partls_opt_weightings prepare their problems on the working context (cv.hip), which carries this context's knobs
     const partls_ctx *p = c->prepared ? c : (c->cv_work && c->cv_work->prepared ? c->cv_work : nullptr);
     if (!p) { set_error("partls_get_sweep_route: context not prepared"); return PARTLS_ERR_STATE; }
     *kernel = p->use_reg ? (sweep_reg_small(p->T) ? PARTLS_ROUTE_REG_256 : PARTLS_ROUTE_REG_512)

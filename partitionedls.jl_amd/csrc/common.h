@@ -146,10 +146,23 @@ size_t     gram_slab_doubles(int64_t N, int64_t M, int gram_S, int gram_cr, int 
 // loaded, so the results are those of the widened matrix bit for bit
 hipError_t launch_gram(const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, double *slab, int chunks,
                        int ldg, int gram_S, int gram_cr, double *G, hipStream_t s, const double *sw = nullptr, bool x_f32 = false);
+// `batch` weighted Grams of one X in one launch pair (partls_opt_weightings): weighting b stages sw + b N, uses the slab
+// slab + b slab_stride (slab_stride >= gram_slab_doubles) and writes G + b gstride; each is launch_gram(..., sw + b N)'s result bit for
+// bit (the same workgroup body, decomposition and reduction order).  Double X only; batch <= 65535.
+hipError_t launch_gram_weightings(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, double *slab, int64_t slab_stride,
+                                  int chunks, int ldg, int gram_S, int gram_cr, double *G, int64_t gstride, const double *sw, int batch,
+                                  hipStream_t s);
 // sample weights (misc.hip): s[i] = sqrt(w[i]) and, per block b of weight_prep_blocks(N), part[3 b ..] = (any w < 0, any non-finite w,
 // sum of w) — the host adds the blocks in index order
 int        weight_prep_blocks(int64_t N);
 hipError_t launch_weight_prep(const double *w, int64_t N, double *s, double *part, hipStream_t st);
+// `batch` weightings at once (partls_opt_weightings): column b of W (N x batch, ld ldW) -> column b of S = sqrt(W) (ld N) and, per block
+// x of weight_prep_blocks(N), part[4 (b nb + x) ..] = (any w < 0, any non-finite w, sum of w, rows with w == 0); batch <= 65535
+hipError_t launch_weightings_prep(const double *W, int64_t N, int64_t ldW, int batch, double *S, double *part, hipStream_t st);
+// out-of-bag SSE of `batch` models: part[b nb + x] = sum over block x's rows with W[i, b] == 0 of (X[i,:] wv_b[0..M) + wv_b[M] - y_i)^2,
+// wv: batch x (M + 1), nb = weight_prep_blocks(N); the host adds a problem's blocks in index order; batch <= 65535
+hipError_t launch_oob_sse(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *W, int64_t ldW,
+                          const double *wv, int batch, double *part, hipStream_t st);
 
 // tableau prep: B = regularised (and, free-intercept mode, intercept-eliminated) Gram; Tfull = unit-diagonal scaled
 // perm[i] = augmented-Gram index of tableau variable i (variables are grouped by partition so a flip touches few tiles)

@@ -135,6 +135,7 @@ struct partls_knobs {
     double near_tie_rel = 1e-13; // PARTLS_NEAR_TIE_REL (tests): width of the near-tie window of the sweep, in units of y'y on the objective^2
     double cal_wb = 1.0, cal_ws = 1.0;  // PARTLS_CAL_WB / PARTLS_CAL_WS: multipliers of the block / scan weights of the bit-order cost model (experiments)
     bool cv_serial = false;      // PARTLS_CV_SERIAL: partls_cv_opt sweeps its problems one after another through partls_opt_sweep (A/B tests, timing)
+    bool resample_serial = false; // PARTLS_RESAMPLE_SERIAL: the same for partls_opt_weightings (resample.hip)
     int pair = -1;               // PARTLS_PAIR: 0 / 1 force the pair walk of the 512-thread register kernel off / on; -1 automatic (sweep_pairs, sweep_setup.hip)
     int bit_order = 0;           // PARTLS_BIT_ORDER: 0 automatic (calibrate when the sweep is long enough to repay it), "identity" = 1
                                  // (group k on Gray bit k), "calibrate" = 2 (always measure; small problems in the tests)
@@ -238,6 +239,11 @@ struct partls_ctx {
     std::vector<partls_ctx *> cv_view;
     partls::DevBuf cvG, cvBatch, cvEta;
     partls::PinnedDoubles cvHost, cvHostG;
+    // partls_opt_weightings (resample.hip) shares cv_work and the cv* buffers above (cvG: one Gram per weighting) and
+    // adds: rsW, the upload of a host W (N x B, ld N); rsS = sqrt(W) (ld N); rsPart / rsHost, the per-block partials of
+    // weightings_prep_kernel and of oob_sse_kernel and their host copies; rsWv, the models of a chunk of problems as weight vectors
+    partls::DevBuf rsW, rsS, rsPart, rsWv;
+    partls::PinnedDoubles rsHost;
 };
 
 namespace partls {
@@ -298,6 +304,48 @@ bool sweep_pairs(const partls_ctx *c, int64_t total);   // does partls_opt_sweep
 int64_t reference_pattern(const partls_ctx *c, int64_t q);
 // sweep_out: the host copy of a result block with runner-up columns (sweep_block)
 void install_sweep_result(partls_ctx *c, const double *sweep_out, int grid, bool has_sol, double *bobj_out, int64_t *bpat_out);
+
+// ---- many fit(Opt) problems over one (X, y, P) in one call (cv.hip): what partls_cv_opt and partls_opt_weightings (resample.hip) share.
+// The caller's context c keeps the upload and the Gram products (c->cvG) and holds no prepared problem afterwards; c->cv_work, an
+// internal context on the same device, holds one problem at a time for its finish.
+// what the caller gets per problem (host staging; nothing reaches the caller's arrays before the whole call has succeeded); sse: the
+// held-out SSE of a cross-validation problem, the out-of-bag SSE of a weighting
+struct CvOut {
+    std::vector<double> alpha, beta, t, opt, sse;
+    std::vector<int64_t> best;
+    std::vector<int32_t> status;
+    void assign(int64_t B, int64_t M, int64_t K);
+    // column q of every array -> the caller's (sse to sse_out unless that is NULL)
+    void deliver(int64_t B, int64_t M, int64_t K, double *alpha_out, int64_t ld_alpha, double *beta_out, int64_t ld_beta, double *t_out,
+                 double *opt_out, int64_t *best_out, double *sse_out, int32_t *status_out) const;
+};
+// B problems: problem q reads the Gram G + (q / E) * gs (device; hostG: the host copies at the same stride) with eta[q % E] (host).
+// finish(q, bpat, unconv): cv_work holds problem q prepared and swept (winner bpat, -1 when none; unconv patterns hit the pivot cap).
+struct ProblemBatch {
+    int64_t B = 0, E = 1;
+    const double *eta = nullptr;
+    const double *G = nullptr, *hostG = nullptr;
+    int64_t gs = 0;
+    bool serial = false;                           // the entry's serial knob: every problem through ctx_prepare_tableau + partls_opt_sweep
+    const char *who = "";
+    std::function<partls_status(int64_t q, int64_t bpat, int64_t unconv)> finish;
+};
+partls_status make_internal(partls_ctx *c, partls_ctx **slot);
+// c forgets its prepared problem and takes the shape of the batch's; then X, y go up once (or the caller's device arrays are adopted)
+void batch_reset(partls_ctx *c, int64_t N, int64_t M, int64_t K, uint32_t flags);
+partls_status batch_upload(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device);
+// cv_work takes the batch's shape, partition and Gram layout, is prepared for Gram `cal_gram` at eta[0] with its rows set by
+// point_rows(cv_work), and the visiting order of the whole batch is calibrated there (the rule of a single fit decides whether that pays)
+partls_status batch_calibrate(partls_ctx *c, const int64_t *P, int64_t ldP, uint32_t flags, int ldg, int chunks, const ProblemBatch &pb,
+                              int64_t cal_gram, const std::function<void(partls_ctx *)> &point_rows);
+// prepare and sweep every problem — batched on the register kernels (chunks bounded by PARTLS_OPT_MODELS_PIECE_BYTES and 65535
+// problems), or one after another (n > 288, PARTLS_OPT_GENERIC_KERNEL, pb.serial) — and call pb.finish on each; fills c->ms
+partls_status batch_sweep(partls_ctx *c, const ProblemBatch &pb);
+// the tested single-fit finish of problem q on cv_work (its rows already set): partls_opt_finish into column q of o, o.status[q] =
+// 0 / PARTLS_ERR_ILL_CONDITIONED / PARTLS_ERR_NOT_CONVERGED (then NaN outputs, best -1); any other status fails the call
+partls_status finish_model(partls_ctx *c, int64_t q, int64_t bpat, int64_t unconv, CvOut &o);
+// w_m = alpha_m sum_k P[m,k] beta_k over the features and w_M = t: the model of column q of o as predict applies it (PartitionedLS.jl:132)
+void model_weights(const partls_ctx *work, const CvOut &o, int64_t q, double *w);
 
 // Solve a batch of `cnt` independent subproblems ("nodes") from the fresh tableau.  codes[i * n + v] is the constraint on
 // tableau variable v in node i: +1 (w >= 0), -1 (w <= 0), 0 (w = 0), 2 (free) — see SweepParams::node_code.  sols: cnt x n

@@ -4,6 +4,9 @@
 // and swept in one launch of the BATCH instantiation of the register kernels (blockIdx.y = problem).  Each problem is then finished as
 // partls_opt_finish finishes a single fit (near-tie re-rank from the data, refinement, KKT check, cleanupResult), on an internal working
 // context whose data passes cover exactly its training rows (row-block views of the folds as its peers).  DESIGN.md §4.6.
+// The parts that do not know about folds — the reset and upload, the calibration on the working context, the batched / serial sweep of
+// B problems over Grams at a fixed stride with the finish as a callback, the finish of one model — are the batch_* helpers of ctx.h,
+// which partls_opt_weightings (resample.hip) shares.
 #include "ctx.h"
 #include <chrono>
 #include <cmath>
@@ -33,7 +36,7 @@ static hipError_t launch_fold_gram_combine(const double *Gf, int nf, int F, int6
     return hipGetLastError();
 }
 
-static partls_status make_internal(partls_ctx *c, partls_ctx **slot)
+partls_status make_internal(partls_ctx *c, partls_ctx **slot)
 {
     if (*slot) return PARTLS_OK;
     partls_status st = partls_create(c->device, slot);
@@ -62,44 +65,71 @@ static void point_rows(partls_ctx *c, partls_ctx *W, const int64_t *fold_ptr, in
     }
 }
 
-// what the caller gets per problem (host staging; nothing reaches the caller's arrays before the whole call has succeeded)
-struct CvOut {
-    std::vector<double> alpha, beta, t, opt, sse;
-    std::vector<int64_t> best;
-    std::vector<int32_t> status;
-};
+void CvOut::assign(int64_t B, int64_t M, int64_t K)
+{
+    alpha.assign((size_t)B * M, 0.0); beta.assign((size_t)B * K, 0.0);
+    t.assign((size_t)B, 0.0); opt.assign((size_t)B, 0.0); sse.assign((size_t)B, NAN);
+    best.assign((size_t)B, -1); status.assign((size_t)B, 0);
+}
 
-// Finish problem q on W (prepared state already installed): the tested single-fit finish, then the held-out SSE on fold f's rows.
-static partls_status finish_one(partls_ctx *c, partls_ctx *W, const int64_t *fold_ptr, int64_t F, int64_t f, int64_t q, int64_t bpat,
-                                int64_t unconv, CvOut &o)
+void CvOut::deliver(int64_t B, int64_t M, int64_t K, double *alpha_out, int64_t ld_alpha, double *beta_out, int64_t ld_beta, double *t_out,
+                    double *opt_out, int64_t *best_out, double *sse_out, int32_t *status_out) const
+{
+    for (int64_t q = 0; q < B; ++q) {
+        std::memcpy(alpha_out + q * ld_alpha, alpha.data() + (size_t)q * M, (size_t)M * sizeof(double));
+        std::memcpy(beta_out + q * ld_beta, beta.data() + (size_t)q * K, (size_t)K * sizeof(double));
+    }
+    std::memcpy(t_out, t.data(), (size_t)B * sizeof(double));
+    std::memcpy(opt_out, opt.data(), (size_t)B * sizeof(double));
+    std::memcpy(best_out, best.data(), (size_t)B * sizeof(int64_t));
+    if (sse_out) std::memcpy(sse_out, sse.data(), (size_t)B * sizeof(double));
+    std::memcpy(status_out, status.data(), (size_t)B * sizeof(int32_t));
+}
+
+partls_status finish_model(partls_ctx *c, int64_t q, int64_t bpat, int64_t unconv, CvOut &o)
 {
     const int64_t M = c->M, K = c->K;
     double *a = o.alpha.data() + (size_t)q * M, *b = o.beta.data() + (size_t)q * K;
     partls_status st = PARTLS_ERR_NOT_CONVERGED;
     if (bpat >= 0) {
-        point_rows(c, W, fold_ptr, F, f);
-        st = partls_opt_finish(W, bpat, a, b, &o.t[(size_t)q], &o.opt[(size_t)q], &o.best[(size_t)q]);
-        W->peers.clear();
+        st = partls_opt_finish(c->cv_work, bpat, a, b, &o.t[(size_t)q], &o.opt[(size_t)q], &o.best[(size_t)q]);
         if (st == PARTLS_OK && unconv) st = PARTLS_ERR_NOT_CONVERGED;
     }
     if (st != PARTLS_OK && st != PARTLS_ERR_ILL_CONDITIONED && st != PARTLS_ERR_NOT_CONVERGED) return st;
     o.status[(size_t)q] = (int32_t)st;
+    o.sse[(size_t)q] = NAN;
     if (st == PARTLS_ERR_NOT_CONVERGED) {
         std::fill(a, a + M, NAN);
         std::fill(b, b + K, NAN);
-        o.t[(size_t)q] = NAN; o.opt[(size_t)q] = NAN; o.best[(size_t)q] = -1; o.sse[(size_t)q] = NAN;
-        return PARTLS_OK;
+        o.t[(size_t)q] = NAN; o.opt[(size_t)q] = NAN; o.best[(size_t)q] = -1;
     }
-    o.sse[(size_t)q] = NAN;
-    if (f < F) {
-        // predict (PartitionedLS.jl:132): yhat = X (P .* alpha) beta .+ t, i.e. w_m = alpha_m sum_k P[m,k] beta_k, on fold f's rows
-        std::vector<double> w((size_t)M + 1, 0.0);
-        for (int64_t m = 0; m < M; ++m) {
-            double s = 0.0;
-            for (int64_t k = 0; k < K; ++k) if (c->cv_work->P[(size_t)m + (size_t)k * M]) s += b[k];
-            w[(size_t)m] = a[m] * s;
-        }
-        w[(size_t)M] = o.t[(size_t)q];
+    return PARTLS_OK;
+}
+
+void model_weights(const partls_ctx *work, const CvOut &o, int64_t q, double *w)
+{
+    const int64_t M = work->M, K = work->K;
+    const double *a = o.alpha.data() + (size_t)q * M, *b = o.beta.data() + (size_t)q * K;
+    for (int64_t m = 0; m < M; ++m) {
+        double s = 0.0;
+        for (int64_t k = 0; k < K; ++k) if (work->P[(size_t)m + (size_t)k * M]) s += b[k];
+        w[m] = a[m] * s;
+    }
+    w[M] = o.t[(size_t)q];
+}
+
+// Finish problem q on W (prepared state already installed): the tested single-fit finish, then the held-out SSE on fold f's rows.
+static partls_status finish_one(partls_ctx *c, partls_ctx *W, const int64_t *fold_ptr, int64_t F, int64_t f, int64_t q, int64_t bpat,
+                                int64_t unconv, CvOut &o)
+{
+    if (bpat >= 0) point_rows(c, W, fold_ptr, F, f);
+    const partls_status st = finish_model(c, q, bpat, unconv, o);
+    W->peers.clear();
+    if (st != PARTLS_OK) return st;
+    if (o.status[(size_t)q] != PARTLS_ERR_NOT_CONVERGED && f < F) {
+        // predict (PartitionedLS.jl:132): yhat = X (P .* alpha) beta .+ t on fold f's rows
+        std::vector<double> w((size_t)c->M + 1, 0.0);
+        model_weights(W, o, q, w.data());
         partls_ctx *v = c->cv_view[(size_t)f];
         double s2 = 0.0;
         const partls_status ds = data_pass(v, w, true, false, &s2, nullptr, {});
@@ -109,23 +139,197 @@ static partls_status finish_one(partls_ctx *c, partls_ctx *W, const int64_t *fol
     return PARTLS_OK;
 }
 
-static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w,
-                            int x_on_device, const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F, const double *eta,
-                            int64_t E, uint32_t flags, CvOut &o)
+void batch_reset(partls_ctx *c, int64_t N, int64_t M, int64_t K, uint32_t flags)
 {
-    const int64_t B = (F + 1) * E;
-    const int nf = F > 0 ? (int)F : 1;
-    const bool faithful = (flags & PARTLS_OPT_FAITHFUL_INTERCEPT) != 0;
     for (int w = 0; w < PARTLS_T_COUNT; ++w) c->ms[w] = 0.0;
-    PARTLS_HIP_CHECK(hipSetDevice(c->device));
     // this context keeps the upload and the Gram products; it holds no prepared problem afterwards
     c->prepared = false;
     c->peers.clear();
     c->near_for = -1; c->near_pat.clear(); c->cand.clear();
     c->last_upload_ms = 0.0; c->last_upload_bytes = 0.0;
-    c->N = N; c->M = M; c->K = K; c->flags = flags; c->faithful = faithful;
+    c->N = N; c->M = M; c->K = K; c->flags = flags; c->faithful = (flags & PARTLS_OPT_FAITHFUL_INTERCEPT) != 0;
     c->dw = nullptr; c->ds = nullptr;
-    c->x_f32 = false;                              // cross-validation reads X as double (no float form)
+    c->x_f32 = false;                              // the batched entries read X as double (no float form)
+}
+
+partls_status batch_upload(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device)
+{
+    if (x_on_device) {
+        c->dX = X; c->dy = y; c->ldX = ldX;
+        return PARTLS_OK;
+    }
+    PARTLS_HIP_CHECK(c->ownX.ensure((size_t)N * M * sizeof(double)));
+    PARTLS_HIP_CHECK(c->ownY.ensure((size_t)N * sizeof(double)));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->ownY.p, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const auto u0 = std::chrono::steady_clock::now();
+    partls_status st = upload_matrix(c, c->ownX.as<double>(), X, N, M, ldX);
+    if (st != PARTLS_OK) return st;
+    c->last_upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+    c->last_upload_bytes = (double)N * (double)M * sizeof(double);
+    c->dX = c->ownX.as<double>(); c->dy = c->ownY.as<double>(); c->ldX = N;
+    return PARTLS_OK;
+}
+
+partls_status batch_calibrate(partls_ctx *c, const int64_t *P, int64_t ldP, uint32_t flags, int ldg, int chunks, const ProblemBatch &pb,
+                              int64_t cal_gram, const std::function<void(partls_ctx *)> &point_rows)
+{
+    partls_ctx *W = c->cv_work;
+    const int64_t M = c->M, K = c->K;
+    W->knobs = c->knobs;
+    W->prepared = false;
+    W->peers.clear();
+    W->near_for = -1; W->near_pat.clear(); W->cand.clear();
+    W->sweep_vetoes = 0;
+    W->coop_state_valid = false;
+    W->order_ready = false; W->order_identity = true; W->flip_cost.clear();
+    W->gram_hook = nullptr;
+    partls_status st = load_partition(W, P, M, K, ldP);
+    if (st != PARTLS_OK) return st;
+    W->M = M; W->K = K; W->flags = flags; W->faithful = c->faithful;
+    W->ldg = ldg; W->chunks = chunks;
+    PARTLS_HIP_CHECK(W->G.ensure((size_t)pb.gs * sizeof(double)));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(W->G.p, pb.G + (size_t)cal_gram * pb.gs, (size_t)pb.gs * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+    W->eta = pb.eta[0];
+    point_rows(W);
+    st = ctx_prepare_tableau(W);
+    if (st != PARTLS_OK) return st;
+    W->peers.clear();
+    if ((int64_t)W->kbits > 40) { set_error("%s: %d sign bits: the enumeration is out of range (K <= 39)", pb.who, W->kbits); return PARTLS_ERR_UNSUPPORTED; }
+    st = calibrate_bit_order(W);
+    if (st != PARTLS_OK) return st;
+    c->ms[PARTLS_T_CALIB] = W->ms[PARTLS_T_CALIB];
+    return PARTLS_OK;
+}
+
+partls_status batch_sweep(partls_ctx *c, const ProblemBatch &pb)
+{
+    partls_ctx *W = c->cv_work;
+    const int64_t B = pb.B, E = pb.E, gs = pb.gs, M = c->M;
+    const double *Gc = pb.G, *eta = pb.eta;
+    const bool faithful = c->faithful;
+    const int ldg = W->ldg;
+    const int n = W->n;
+    const int64_t npat = (int64_t)1 << W->kbits;
+    partls_status st = PARTLS_OK;
+
+    double ms_prep = 0.0, ms_sweep = 0.0, ms_finish = 0.0;
+    // ---- every problem on its own through the existing launchers: n > 288, PARTLS_OPT_GENERIC_KERNEL, the entry's serial knob
+    if (!W->use_reg || pb.serial) {
+        for (int64_t q = 0; q < B; ++q) {
+            const int64_t f = q / E, e = q % E;
+            PARTLS_HIP_CHECK(hipMemcpyAsync(W->G.p, Gc + (size_t)f * gs, (size_t)gs * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+            W->eta = eta[e];
+            st = ctx_prepare_tableau(W);
+            if (st != PARTLS_OK) return st;
+            ms_prep += W->ms[PARTLS_T_PREP];
+            double bobj = 0.0;
+            int64_t bpat = -1, unconv = 0;
+            st = partls_opt_sweep(W, 0, -1, &bobj, &bpat, nullptr, &unconv);
+            if (st != PARTLS_OK) return st;
+            ms_sweep += W->ms[PARTLS_T_SWEEP];
+            const auto f0 = std::chrono::steady_clock::now();
+            st = pb.finish(q, bpat, unconv);
+            if (st != PARTLS_OK) return st;
+            ms_finish += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
+        }
+        c->ms[PARTLS_T_PREP] = ms_prep; c->ms[PARTLS_T_SWEEP] = ms_sweep; c->ms[PARTLS_T_FINISH] = ms_finish;
+        return PARTLS_OK;
+    }
+
+    // ---- batched: chunks of problems whose stacked tableaux stay below PARTLS_OPT_MODELS_PIECE_BYTES and whose count fits gridDim.y
+    const int T = W->T;
+    const size_t t0d = sweep_reg_t0_doubles(T), tfd = (size_t)(n + 1) * (n + 1);
+    const size_t tab_bytes = (tfd + t0d + (size_t)n + 1) * sizeof(double);
+    const int64_t bc_max = std::max<int64_t>(1, std::min<int64_t>(65535, (int64_t)(PARTLS_OPT_MODELS_PIECE_BYTES / tab_bytes)));
+    const bool want_sol = (sweep_reg_small(T) || sweep_reg_exports(T)) && !c->knobs.no_export;
+    PARTLS_HIP_CHECK(c->cvEta.ensure((size_t)E * sizeof(double)));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->cvEta.p, eta, (size_t)E * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    PARTLS_HIP_CHECK(c->scratch.ensure(64 * sizeof(double)));      // the register kernels' share (ensure_sweep_scratch goes by W, the prepared context)
+    hipEvent_t ev[4];
+    for (int i = 0; i < 4; ++i) PARTLS_HIP_CHECK(hipEventCreate(&ev[i]));
+    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; ++i) (void)hipEventDestroy(e[i]); } } evg{ev};
+    for (int64_t q0 = 0; q0 < B; q0 += bc_max) {
+        const int bc = (int)std::min<int64_t>(bc_max, B - q0);
+        int64_t chain_len = 0;
+        int grid_all = 0;
+        if (!sweep_plan(W, npat * bc, &chain_len, &grid_all, pb.who)) return PARTLS_ERR_UNSUPPORTED;
+        const int64_t nch = (npat + chain_len - 1) / chain_len;
+        const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(nch, (grid_all + bc - 1) / bc));
+        const size_t out_w = sweep_block_words(gx, true);
+        // [scale (bc x n) | Tfull (bc x (n+1)^2) | T0reg (bc x t0d) | tol (bc) | sweep blocks (bc x out_w) | best_sol (bc x gx x n)]
+        const size_t o_scale = 0, o_tf = o_scale + (size_t)bc * n, o_t0 = o_tf + (size_t)bc * tfd, o_tol = o_t0 + (size_t)bc * t0d,
+                     o_out = o_tol + (size_t)bc, o_sol = o_out + (size_t)bc * out_w, words = o_sol + (want_sol ? (size_t)bc * gx * n : 0);
+        PARTLS_HIP_CHECK(c->cvBatch.ensure(words * sizeof(double)));
+        double *base = c->cvBatch.as<double>();
+        PARTLS_HIP_CHECK(hipEventRecord(ev[0], c->stream));
+        PARTLS_HIP_CHECK(launch_prep_batch(Gc, gs, (int)E, q0, c->cvEta.as<double>(), ldg, (int)M, W->maskAugD.as<uint64_t>(), faithful ? 0 : 1,
+                                           W->permP, c->knobs.tol_rel, base + o_scale, base + o_tf, base + o_tol, n, bc, c->stream));
+        PARTLS_HIP_CHECK(launch_layout_reg_batch(base + o_tf, n, T, bc, base + o_t0, c->stream));
+        PARTLS_HIP_CHECK(hipMemsetAsync(base + o_out, 0, (size_t)bc * out_w * sizeof(double), c->stream));
+        PARTLS_HIP_CHECK(hipEventRecord(ev[1], c->stream));
+        SweepParams p = sweep_params(W, /*internal_order=*/true);
+        p.T0 = base + o_t0;
+        p.scratch = c->scratch.as<double>();
+        p.g_begin = 0; p.g_end = npat; p.chain_len = chain_len;
+        p.tol = 0.0;                                             // every problem has its own: batch_tol
+        bind_sweep_block(p, base + o_out, gx, true);             // problem 0's block; problem q's lies q * batch_out words further
+        if (want_sol) { p.best_sol = base + o_sol; p.node_ld = n; }
+        p.batch_t0 = (int64_t)t0d; p.batch_out = (int64_t)out_w; p.batch_tol = base + o_tol;
+        PARTLS_HIP_CHECK(launch_sweep_blk_batch(p, T, gx, bc, c->stream));
+        PARTLS_HIP_CHECK(hipEventRecord(ev[2], c->stream));
+        // host copies: scale, tolerances, sweep blocks
+        const size_t hw = (size_t)bc * n + (size_t)bc + (size_t)bc * out_w;
+        PARTLS_HIP_CHECK(c->cvHost.resize(hw));
+        double *h = c->cvHost.data();
+        PARTLS_HIP_CHECK(hipMemcpyAsync(h, base + o_scale, (size_t)bc * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(h + (size_t)bc * n, base + o_tol, ((size_t)bc + (size_t)bc * out_w) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        float f01 = 0.f, f12 = 0.f;
+        if (hipEventElapsedTime(&f01, ev[0], ev[1]) == hipSuccess) ms_prep += f01;
+        if (hipEventElapsedTime(&f12, ev[1], ev[2]) == hipSuccess) ms_sweep += f12;
+        const double *hscale = h, *htol = h + (size_t)bc * n, *hout = htol + bc;
+        const auto f0 = std::chrono::steady_clock::now();
+        for (int j = 0; j < bc; ++j) {
+            const int64_t q = q0 + j, f = q / E, e = q % E;
+            // install problem q's prepared state on the working context: what ctx_prepare_tableau would have left (the batched kernels
+            // compute the same entries) and what partls_opt_sweep would have left (winner, near ties, the winner's exported solution)
+            W->eta = eta[e];
+            std::memcpy(W->hG.data(), pb.hostG + (size_t)f * gs, (size_t)gs * sizeof(double));
+            std::memcpy(W->hScale.data(), hscale + (size_t)j * n, (size_t)n * sizeof(double));
+            W->tol = htol[j];
+            PARTLS_HIP_CHECK(hipMemcpyAsync(W->G.p, Gc + (size_t)f * gs, (size_t)gs * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+            PARTLS_HIP_CHECK(hipMemcpyAsync(W->scale.p, base + o_scale + (size_t)j * n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+            PARTLS_HIP_CHECK(hipMemcpyAsync(W->Tfull.p, base + o_tf + (size_t)j * tfd, tfd * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+            PARTLS_HIP_CHECK(hipMemcpyAsync(W->T0reg.p, base + o_t0 + (size_t)j * t0d, t0d * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+            if (want_sol) {
+                PARTLS_HIP_CHECK(W->bestSol.ensure((size_t)gx * n * sizeof(double)));
+                PARTLS_HIP_CHECK(hipMemcpyAsync(W->bestSol.p, base + o_sol + (size_t)j * gx * n, (size_t)gx * n * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+            }
+            W->coop_state_valid = false;
+            W->tab_valid = false;
+            W->prepared = true;
+            double bobj = 0.0;
+            int64_t bpat = -1;
+            const double *blk = hout + (size_t)j * out_w;
+            install_sweep_result(W, blk, gx, want_sol, &bobj, &bpat);
+            unsigned long long unconv = 0;
+            std::memcpy(&unconv, blk, sizeof(unconv));
+            st = pb.finish(q, bpat, (int64_t)unconv);
+            if (st != PARTLS_OK) return st;
+        }
+        ms_finish += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
+    }
+    c->ms[PARTLS_T_PREP] = ms_prep; c->ms[PARTLS_T_SWEEP] = ms_sweep; c->ms[PARTLS_T_FINISH] = ms_finish;
+    return PARTLS_OK;
+}
+
+static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w,
+                            int x_on_device, const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F, const double *eta,
+                            int64_t E, uint32_t flags, CvOut &o)
+{
+    const int nf = F > 0 ? (int)F : 1;
+    PARTLS_HIP_CHECK(hipSetDevice(c->device));
+    batch_reset(c, N, M, K, flags);
     // ---- sample weights (partls_cv_opt_weighted): checked and square-rooted before anything else; every fold Gram and every data pass
     // (finish, held-out SSE) then reads its rows' slice of them
     if (w) {
@@ -134,26 +338,14 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
     }
 
     // ---- one upload
-    if (x_on_device) {
-        c->dX = X; c->dy = y; c->ldX = ldX;
-    } else {
-        PARTLS_HIP_CHECK(c->ownX.ensure((size_t)N * M * sizeof(double)));
-        PARTLS_HIP_CHECK(c->ownY.ensure((size_t)N * sizeof(double)));
-        PARTLS_HIP_CHECK(hipMemcpyAsync(c->ownY.p, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        const auto u0 = std::chrono::steady_clock::now();
-        partls_status st = upload_matrix(c, c->ownX.as<double>(), X, N, M, ldX);
-        if (st != PARTLS_OK) return st;
-        c->last_upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
-        c->last_upload_bytes = (double)N * (double)M * sizeof(double);
-        c->dX = c->ownX.as<double>(); c->dy = c->ownY.as<double>(); c->ldX = N;
-    }
+    partls_status st = batch_upload(c, X, N, M, ldX, y, x_on_device);
+    if (st != PARTLS_OK) return st;
     const double *Xd = static_cast<const double *>(c->dX);
 
     // ---- internal contexts: the working context and one row view per fold
-    partls_status st = make_internal(c, &c->cv_work);
+    st = make_internal(c, &c->cv_work);
     if (st != PARTLS_OK) return st;
     partls_ctx *W = c->cv_work;
-    W->knobs = c->knobs;
     if (c->cv_view.size() < (size_t)F) c->cv_view.resize((size_t)F, nullptr);
     for (int64_t g = 0; g < F; ++g) {
         st = make_internal(c, &c->cv_view[(size_t)g]);
@@ -205,148 +397,14 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
                 return PARTLS_ERR_BAD_ARG;
             }
 
-    // ---- the working context: the problem's shape, partition and Gram; prepared first for the full-data problem at eta[0], on which the
-    // visiting order of the whole batch is calibrated (the rule of a single fit decides whether that pays)
-    W->prepared = false;
-    W->peers.clear();
-    W->near_for = -1; W->near_pat.clear(); W->cand.clear();
-    W->sweep_vetoes = 0;
-    W->coop_state_valid = false;
-    W->order_ready = false; W->order_identity = true; W->flip_cost.clear();
-    W->gram_hook = nullptr;
-    st = load_partition(W, P, M, K, ldP);
+    // ---- the working context: prepared first for the full-data problem at eta[0], on which the visiting order is calibrated
+    ProblemBatch pb;
+    pb.B = (F + 1) * E; pb.E = E; pb.eta = eta; pb.G = Gc; pb.hostG = c->cvHostG.data(); pb.gs = gs;
+    pb.serial = c->knobs.cv_serial; pb.who = "partls_cv_opt";
+    pb.finish = [&](int64_t q, int64_t bpat, int64_t unconv) { return finish_one(c, W, fold_ptr, F, q / E, q, bpat, unconv, o); };
+    st = batch_calibrate(c, P, ldP, flags, ldg, chunks, pb, F, [&](partls_ctx *Wc) { point_rows(c, Wc, fold_ptr, F, F); });
     if (st != PARTLS_OK) return st;
-    W->M = M; W->K = K; W->flags = flags; W->faithful = faithful;
-    W->ldg = ldg; W->chunks = chunks;
-    PARTLS_HIP_CHECK(W->G.ensure((size_t)gs * sizeof(double)));
-    auto load_problem_gram = [&](int64_t f) -> partls_status {
-        PARTLS_HIP_CHECK(hipMemcpyAsync(W->G.p, Gc + (size_t)f * gs, (size_t)gs * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
-        return PARTLS_OK;
-    };
-    st = load_problem_gram(F);
-    if (st != PARTLS_OK) return st;
-    W->eta = eta[0];
-    point_rows(c, W, fold_ptr, F, F);
-    st = ctx_prepare_tableau(W);
-    if (st != PARTLS_OK) return st;
-    W->peers.clear();
-    if ((int64_t)W->kbits > 40) { set_error("partls_cv_opt: %d sign bits: the enumeration is out of range (K <= 39)", W->kbits); return PARTLS_ERR_UNSUPPORTED; }
-    st = calibrate_bit_order(W);
-    if (st != PARTLS_OK) return st;
-    c->ms[PARTLS_T_CALIB] = W->ms[PARTLS_T_CALIB];
-    const int n = W->n;
-    const int64_t npat = (int64_t)1 << W->kbits;
-
-    double ms_prep = 0.0, ms_sweep = 0.0, ms_finish = 0.0;
-    // ---- every problem on its own through the existing launchers: n > 288, PARTLS_OPT_GENERIC_KERNEL, PARTLS_CV_SERIAL
-    if (!W->use_reg || c->knobs.cv_serial) {
-        for (int64_t q = 0; q < B; ++q) {
-            const int64_t f = q / E, e = q % E;
-            st = load_problem_gram(f);
-            if (st != PARTLS_OK) return st;
-            W->eta = eta[e];
-            st = ctx_prepare_tableau(W);
-            if (st != PARTLS_OK) return st;
-            ms_prep += W->ms[PARTLS_T_PREP];
-            double bobj = 0.0;
-            int64_t bpat = -1, unconv = 0;
-            st = partls_opt_sweep(W, 0, -1, &bobj, &bpat, nullptr, &unconv);
-            if (st != PARTLS_OK) return st;
-            ms_sweep += W->ms[PARTLS_T_SWEEP];
-            const auto f0 = std::chrono::steady_clock::now();
-            st = finish_one(c, W, fold_ptr, F, f, q, bpat, unconv, o);
-            if (st != PARTLS_OK) return st;
-            ms_finish += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
-        }
-        c->ms[PARTLS_T_PREP] = ms_prep; c->ms[PARTLS_T_SWEEP] = ms_sweep; c->ms[PARTLS_T_FINISH] = ms_finish;
-        return PARTLS_OK;
-    }
-
-    // ---- batched: chunks of problems whose stacked tableaux stay below PARTLS_OPT_MODELS_PIECE_BYTES and whose count fits gridDim.y
-    const int T = W->T;
-    const size_t t0d = sweep_reg_t0_doubles(T), tfd = (size_t)(n + 1) * (n + 1);
-    const size_t tab_bytes = (tfd + t0d + (size_t)n + 1) * sizeof(double);
-    const int64_t bc_max = std::max<int64_t>(1, std::min<int64_t>(65535, (int64_t)(PARTLS_OPT_MODELS_PIECE_BYTES / tab_bytes)));
-    const bool want_sol = (sweep_reg_small(T) || sweep_reg_exports(T)) && !c->knobs.no_export;
-    PARTLS_HIP_CHECK(c->cvEta.ensure((size_t)E * sizeof(double)));
-    PARTLS_HIP_CHECK(hipMemcpyAsync(c->cvEta.p, eta, (size_t)E * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    PARTLS_HIP_CHECK(c->scratch.ensure(64 * sizeof(double)));      // the register kernels' share (ensure_sweep_scratch goes by W, the prepared context)
-    hipEvent_t ev[4];
-    for (int i = 0; i < 4; ++i) PARTLS_HIP_CHECK(hipEventCreate(&ev[i]));
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; ++i) (void)hipEventDestroy(e[i]); } } evg{ev};
-    for (int64_t q0 = 0; q0 < B; q0 += bc_max) {
-        const int bc = (int)std::min<int64_t>(bc_max, B - q0);
-        int64_t chain_len = 0;
-        int grid_all = 0;
-        if (!sweep_plan(W, npat * bc, &chain_len, &grid_all, "partls_cv_opt")) return PARTLS_ERR_UNSUPPORTED;
-        const int64_t nch = (npat + chain_len - 1) / chain_len;
-        const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(nch, (grid_all + bc - 1) / bc));
-        const size_t out_w = sweep_block_words(gx, true);
-        // [scale (bc x n) | Tfull (bc x (n+1)^2) | T0reg (bc x t0d) | tol (bc) | sweep blocks (bc x out_w) | best_sol (bc x gx x n)]
-        const size_t o_scale = 0, o_tf = o_scale + (size_t)bc * n, o_t0 = o_tf + (size_t)bc * tfd, o_tol = o_t0 + (size_t)bc * t0d,
-                     o_out = o_tol + (size_t)bc, o_sol = o_out + (size_t)bc * out_w, words = o_sol + (want_sol ? (size_t)bc * gx * n : 0);
-        PARTLS_HIP_CHECK(c->cvBatch.ensure(words * sizeof(double)));
-        double *base = c->cvBatch.as<double>();
-        PARTLS_HIP_CHECK(hipEventRecord(ev[0], c->stream));
-        PARTLS_HIP_CHECK(launch_prep_batch(Gc, gs, (int)E, q0, c->cvEta.as<double>(), ldg, (int)M, W->maskAugD.as<uint64_t>(), faithful ? 0 : 1,
-                                           W->permP, c->knobs.tol_rel, base + o_scale, base + o_tf, base + o_tol, n, bc, c->stream));
-        PARTLS_HIP_CHECK(launch_layout_reg_batch(base + o_tf, n, T, bc, base + o_t0, c->stream));
-        PARTLS_HIP_CHECK(hipMemsetAsync(base + o_out, 0, (size_t)bc * out_w * sizeof(double), c->stream));
-        PARTLS_HIP_CHECK(hipEventRecord(ev[1], c->stream));
-        SweepParams p = sweep_params(W, /*internal_order=*/true);
-        p.T0 = base + o_t0;
-        p.scratch = c->scratch.as<double>();
-        p.g_begin = 0; p.g_end = npat; p.chain_len = chain_len;
-        p.tol = 0.0;                                             // every problem has its own: batch_tol
-        bind_sweep_block(p, base + o_out, gx, true);             // problem 0's block; problem q's lies q * batch_out words further
-        if (want_sol) { p.best_sol = base + o_sol; p.node_ld = n; }
-        p.batch_t0 = (int64_t)t0d; p.batch_out = (int64_t)out_w; p.batch_tol = base + o_tol;
-        PARTLS_HIP_CHECK(launch_sweep_blk_batch(p, T, gx, bc, c->stream));
-        PARTLS_HIP_CHECK(hipEventRecord(ev[2], c->stream));
-        // host copies: scale, tolerances, sweep blocks
-        const size_t hw = (size_t)bc * n + (size_t)bc + (size_t)bc * out_w;
-        PARTLS_HIP_CHECK(c->cvHost.resize(hw));
-        double *h = c->cvHost.data();
-        PARTLS_HIP_CHECK(hipMemcpyAsync(h, base + o_scale, (size_t)bc * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        PARTLS_HIP_CHECK(hipMemcpyAsync(h + (size_t)bc * n, base + o_tol, ((size_t)bc + (size_t)bc * out_w) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
-        float f01 = 0.f, f12 = 0.f;
-        if (hipEventElapsedTime(&f01, ev[0], ev[1]) == hipSuccess) ms_prep += f01;
-        if (hipEventElapsedTime(&f12, ev[1], ev[2]) == hipSuccess) ms_sweep += f12;
-        const double *hscale = h, *htol = h + (size_t)bc * n, *hout = htol + bc;
-        const auto f0 = std::chrono::steady_clock::now();
-        for (int j = 0; j < bc; ++j) {
-            const int64_t q = q0 + j, f = q / E, e = q % E;
-            // install problem q's prepared state on the working context: what ctx_prepare_tableau would have left (the batched kernels
-            // compute the same entries) and what partls_opt_sweep would have left (winner, near ties, the winner's exported solution)
-            W->eta = eta[e];
-            std::memcpy(W->hG.data(), c->cvHostG.data() + (size_t)f * gs, (size_t)gs * sizeof(double));
-            std::memcpy(W->hScale.data(), hscale + (size_t)j * n, (size_t)n * sizeof(double));
-            W->tol = htol[j];
-            PARTLS_HIP_CHECK(hipMemcpyAsync(W->G.p, Gc + (size_t)f * gs, (size_t)gs * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
-            PARTLS_HIP_CHECK(hipMemcpyAsync(W->scale.p, base + o_scale + (size_t)j * n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
-            PARTLS_HIP_CHECK(hipMemcpyAsync(W->Tfull.p, base + o_tf + (size_t)j * tfd, tfd * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
-            PARTLS_HIP_CHECK(hipMemcpyAsync(W->T0reg.p, base + o_t0 + (size_t)j * t0d, t0d * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
-            if (want_sol) {
-                PARTLS_HIP_CHECK(W->bestSol.ensure((size_t)gx * n * sizeof(double)));
-                PARTLS_HIP_CHECK(hipMemcpyAsync(W->bestSol.p, base + o_sol + (size_t)j * gx * n, (size_t)gx * n * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
-            }
-            W->coop_state_valid = false;
-            W->tab_valid = false;
-            W->prepared = true;
-            double bobj = 0.0;
-            int64_t bpat = -1;
-            const double *blk = hout + (size_t)j * out_w;
-            install_sweep_result(W, blk, gx, want_sol, &bobj, &bpat);
-            unsigned long long unconv = 0;
-            std::memcpy(&unconv, blk, sizeof(unconv));
-            st = finish_one(c, W, fold_ptr, F, f, q, bpat, (int64_t)unconv, o);
-            if (st != PARTLS_OK) return st;
-        }
-        ms_finish += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
-    }
-    c->ms[PARTLS_T_PREP] = ms_prep; c->ms[PARTLS_T_SWEEP] = ms_sweep; c->ms[PARTLS_T_FINISH] = ms_finish;
-    return PARTLS_OK;
+    return batch_sweep(c, pb);
 }
 
 }  // namespace partls
@@ -382,20 +440,10 @@ static partls_status cv_opt(partls_ctx *c, const double *X, int64_t N, int64_t M
     }
     const int64_t B = (F + 1) * E;
     CvOut o;
-    o.alpha.assign((size_t)B * M, 0.0); o.beta.assign((size_t)B * K, 0.0);
-    o.t.assign((size_t)B, 0.0); o.opt.assign((size_t)B, 0.0); o.sse.assign((size_t)B, NAN);
-    o.best.assign((size_t)B, -1); o.status.assign((size_t)B, 0);
+    o.assign(B, M, K);
     st = cv_run(c, X, N, M, ldX, y, w, x_on_device, P, K, ldP, fold_ptr, F, eta, E, flags, o);
     if (st != PARTLS_OK) return st;
-    for (int64_t q = 0; q < B; ++q) {
-        std::memcpy(alpha + q * ld_alpha, o.alpha.data() + (size_t)q * M, (size_t)M * sizeof(double));
-        std::memcpy(beta + q * ld_beta, o.beta.data() + (size_t)q * K, (size_t)K * sizeof(double));
-    }
-    std::memcpy(t, o.t.data(), (size_t)B * sizeof(double));
-    std::memcpy(opt, o.opt.data(), (size_t)B * sizeof(double));
-    std::memcpy(best_index, o.best.data(), (size_t)B * sizeof(int64_t));
-    std::memcpy(heldout_sse, o.sse.data(), (size_t)B * sizeof(double));
-    std::memcpy(status, o.status.data(), (size_t)B * sizeof(int32_t));
+    o.deliver(B, M, K, alpha, ld_alpha, beta, ld_beta, t, opt, best_index, heldout_sse, status);
     set_error("");
     return PARTLS_OK;
 }

@@ -345,15 +345,12 @@ __device__ __forceinline__ void gram_body(const XT *__restrict__ X, int64_t N, i
     }
 }
 
+// one workgroup of the Gram build: tile pair, XCD group and slice from blockIdx.x (gram_kernel and gram_weightings_kernel)
 template <class XT, bool WT>
-__global__ __launch_bounds__(64 * NWV, 4) void gram_kernel(      // 4 waves per SIMD (HIP: the second argument counts waves per EU): <= 128 VGPRs
-const XT *__restrict__ X, int64_t N, int M, int64_t ldX,
-                                                   const double *__restrict__ y, double *__restrict__ slab,
-                                                   int chunk_rows, int S, int np, const double *__restrict__ sw)
+__device__ __forceinline__ void gram_workgroup(const XT *__restrict__ X, int64_t N, int M, int64_t ldX, const double *__restrict__ y,
+                                               double *__restrict__ slab, int chunk_rows, int S, int np, const double *__restrict__ sw,
+                                               double *sA, double *sB, double *sV)
 {
-    __shared__ double sA[2 * GT * GLD];              // [2 buffers][128 columns][GLD]
-    __shared__ double sB[2 * GT * GLD];
-    __shared__ double sV[2 * 2 * GK];                // [2 buffers][ones, y][GK]
     const int nt = (M + GT - 1) / GT;                  // feature tiles only
     const int xg = blockIdx.x & 7, q = blockIdx.x >> 3;
     const int pair = q % np, sl = q / np;
@@ -372,16 +369,44 @@ const XT *__restrict__ X, int64_t N, int M, int64_t ldX,
     }
 }
 
+template <class XT, bool WT>
+__global__ __launch_bounds__(64 * NWV, 4) void gram_kernel(      // 4 waves per SIMD (HIP: the second argument counts waves per EU): <= 128 VGPRs
+const XT *__restrict__ X, int64_t N, int M, int64_t ldX,
+                                                   const double *__restrict__ y, double *__restrict__ slab,
+                                                   int chunk_rows, int S, int np, const double *__restrict__ sw)
+{
+    __shared__ double sA[2 * GT * GLD];              // [2 buffers][128 columns][GLD]
+    __shared__ double sB[2 * GT * GLD];
+    __shared__ double sV[2 * 2 * GK];                // [2 buffers][ones, y][GK]
+    gram_workgroup<XT, WT>(X, N, M, ldX, y, slab, chunk_rows, S, np, sw, sA, sB, sV);
+}
+
+// Several weightings of one X in one launch (partls_opt_weightings): blockIdx.y = weighting b, which stages
+// s = sw + b N and writes its partial tiles to slab + b slab_stride.  Everything else is gram_kernel<double, true> — the same workgroup
+// body on the same decomposition — so weighting b's partial tiles, and after the reduction its Gram, are those of a launch of its own,
+// bit for bit.
+__global__ __launch_bounds__(64 * NWV, 4) void gram_weightings_kernel(const double *__restrict__ X, int64_t N, int M, int64_t ldX,
+                                                                      const double *__restrict__ y, double *__restrict__ slab,
+                                                                      int chunk_rows, int S, int np, const double *__restrict__ sw,
+                                                                      int64_t slab_stride)
+{
+    __shared__ double sA[2 * GT * GLD];
+    __shared__ double sB[2 * GT * GLD];
+    __shared__ double sV[2 * 2 * GK];
+    const int64_t b = blockIdx.y;
+    gram_workgroup<double, true>(X, N, M, ldX, y, slab + b * slab_stride, chunk_rows, S, np, sw + b * N, sA, sB, sV);
+}
+
 // G[i][j] = sum over the slices of the computed entry: a feature pair lives in the tile of its upper 16 x 16 sub-tile pair
 // (diagonal tiles hold their upper triangle of sub-tiles only), an entry with a virtual index (ones = M, y = M + 1) in the virtual
 // columns of the slice.  Fixed summation order: bitwise reproducible, no float atomics.
-__global__ __launch_bounds__(256) void gram_reduce_kernel(const double *__restrict__ slab, int slices, int np, int nt, int ldg, int M, double *__restrict__ G)
+__device__ __forceinline__ void gram_reduce_workgroup(const double *__restrict__ slab, int slices, int np, int nt, int ldg, int M, double *__restrict__ G,
+                                                      double (*part)[64])
 {
     // Only the threads of STORED entries walk the slices (consecutive threads = consecutive columns of a tile row: coalesced) and write
     // the mirror entry too; in round 1/2a the thread of a mirrored entry walked the slices itself, 1 KB apart from its neighbours — one
     // cache line per lane and slice for half of the matrix (0.30 ms at C4, a quarter of the C3 build).  64 entries per workgroup: wave g
     // sums the slices c = g, g + 4, ... of its entries, wave 0 adds the four partial sums in order (fixed order; 4 x the loads in flight).
-    __shared__ double part[4][64];
     const int e = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int idx = blockIdx.x * 64 + e;
     const bool in = idx < ldg * ldg;
@@ -420,6 +445,21 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(const double *__restri
             if (mirror) G[(size_t)j * ldg + i] = t;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void gram_reduce_kernel(const double *__restrict__ slab, int slices, int np, int nt, int ldg, int M, double *__restrict__ G)
+{
+    __shared__ double part[4][64];
+    gram_reduce_workgroup(slab, slices, np, nt, ldg, M, G, part);
+}
+
+// ... of several weightings at once: blockIdx.y = weighting b, slab + b slab_stride -> G + b gstride (the same order per entry)
+__global__ __launch_bounds__(256) void gram_reduce_weightings_kernel(const double *__restrict__ slab, int slices, int np, int nt, int ldg, int M,
+                                                                     double *__restrict__ G, int64_t slab_stride, int64_t gstride)
+{
+    __shared__ double part[4][64];
+    const int64_t b = blockIdx.y;
+    gram_reduce_workgroup(slab + b * slab_stride, slices, np, nt, ldg, M, G + b * gstride, part);
 }
 
 static void gram_plan(int64_t N, int64_t M, int S_env, int cr_env, int *ldg_out, int *S_out, int *chunk_rows_out, int *np_out, int *nt_out)
@@ -487,6 +527,24 @@ hipError_t launch_gram(const void *X, int64_t N, int64_t M, int64_t ldX, const d
     if (e != hipSuccess) return e;
     const int tot = ldg * ldg;
     hipLaunchKernelGGL(gram_reduce_kernel, dim3((tot + 63) / 64), dim3(256), 0, s, slab, chunks, np, nt, ldg, (int)M, G);
+    return hipGetLastError();
+}
+
+
+hipError_t launch_gram_weightings(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, double *slab, int64_t slab_stride,
+                                  int chunks, int ldg, int gram_S, int gram_cr, double *G, int64_t gstride, const double *sw, int batch,
+                                  hipStream_t s)
+{
+    int ldg2, S, cr, np, nt;
+    gram_plan(N, M, gram_S, gram_cr, &ldg2, &S, &cr, &np, &nt);
+    if (ldX >= ((int64_t)1 << 30) || batch < 1 || batch > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gram_weightings_kernel, dim3(8 * S * np, batch), dim3(64 * NWV), 0, s, X, N, (int)M, ldX, y, slab, cr, S, np, sw,
+                       slab_stride);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int tot = ldg * ldg;
+    hipLaunchKernelGGL(gram_reduce_weightings_kernel, dim3((tot + 63) / 64, batch), dim3(256), 0, s, slab, chunks, np, nt, ldg, (int)M, G,
+                       slab_stride, gstride);
     return hipGetLastError();
 }
 

@@ -614,4 +614,103 @@ hipError_t launch_weight_prep(const double *w, int64_t N, double *s, double *par
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// B weightings of one data set (partls_opt_weightings): weight_prep_kernel with blockIdx.y = weighting b.  Column b of
+// W (N x B, leading dimension ldW) -> column b of S = sqrt(W) (leading dimension N) and, per block (b, x), four partials at
+// part[4 (b gridDim.x + x) ..]: the three of weight_prep_kernel and the number of rows whose weight is exactly 0 (the out-of-bag rows; a
+// count below 2^53 is exact in a double).  Same rows per block, same tree: column b's sum is weight_prep_kernel's for that column.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void weightings_prep_kernel(const double *__restrict__ W, int64_t N, int64_t ldW, double *__restrict__ S,
+                                                              double *__restrict__ part)
+{
+    __shared__ double red[4][256];
+    const int64_t b = blockIdx.y;
+    const double *w = W + b * ldW;
+    double *s = S + b * N;
+    double neg = 0.0, bad = 0.0, sum = 0.0, zero = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+        const double v = w[i];
+        const bool fin = isfinite(v);
+        if (!fin) bad = 1.0;
+        if (v < 0.0) neg = 1.0;
+        if (v == 0.0) zero += 1.0;
+        sum += fin ? v : 0.0;
+        s[i] = (fin && v >= 0.0) ? sqrt(v) : 0.0;
+    }
+    red[0][threadIdx.x] = neg; red[1][threadIdx.x] = bad; red[2][threadIdx.x] = sum; red[3][threadIdx.x] = zero;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+            red[0][threadIdx.x] = fmax(red[0][threadIdx.x], red[0][threadIdx.x + h]);
+            red[1][threadIdx.x] = fmax(red[1][threadIdx.x], red[1][threadIdx.x + h]);
+            red[2][threadIdx.x] += red[2][threadIdx.x + h];
+            red[3][threadIdx.x] += red[3][threadIdx.x + h];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double *p = part + 4 * (b * gridDim.x + blockIdx.x);
+        p[0] = red[0][0]; p[1] = red[1][0]; p[2] = red[2][0]; p[3] = red[3][0];
+    }
+}
+
+hipError_t launch_weightings_prep(const double *W, int64_t N, int64_t ldW, int batch, double *S, double *part, hipStream_t st)
+{
+    hipLaunchKernelGGL(weightings_prep_kernel, dim3(weight_prep_blocks(N), batch), dim3(256), 0, st, W, N, ldW, S, part);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Out-of-bag error of `batch` models at once (partls_opt_weightings): problem b = blockIdx.y has the model wv + b (M + 1) (features, then
+// the intercept) and the weights W + b ldW; part[b gridDim.x + x] = sum over the block's rows i with W[i, b] == 0 of
+// (sum_m X[i,m] w_m + t - y_i)^2, unweighted.  A row's prediction is accumulated exactly as residual_kernel does it (four chains over
+// m mod 4, ((a0 + a1) + (a2 + a3)) + t), the rows of a block and its tree are fixed by N alone, and the host adds the blocks in index
+// order: a problem's value does not depend on what else is in the batch.  No atomics.  Every workgroup of a column reads the rows of X
+// it owns once per problem; the problems of one launch share them through the caches.
+// Dynamic LDS only: [tree (256) | model (M + 1)].
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void oob_sse_kernel(const double *__restrict__ X, int64_t N, int64_t M, int64_t ldX,
+                                                      const double *__restrict__ y, const double *__restrict__ W, int64_t ldW,
+                                                      const double *__restrict__ wv, double *__restrict__ part)
+{
+    extern __shared__ double oob_lds[];
+    double *red = oob_lds, *sw = oob_lds + 256;
+    const int64_t b = blockIdx.y;
+    const double *wb = wv + b * (M + 1);
+    for (int64_t m = threadIdx.x; m <= M; m += blockDim.x) sw[m] = wb[m];
+    __syncthreads();
+    const double t = sw[M];
+    const double *wt = W + b * ldW;
+    double acc2 = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+        if (wt[i] != 0.0) continue;
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        int64_t m = 0;
+        for (; m + 3 < M; m += 4) {
+            a0 = fma(X[i + m * ldX], sw[m], a0);
+            a1 = fma(X[i + (m + 1) * ldX], sw[m + 1], a1);
+            a2 = fma(X[i + (m + 2) * ldX], sw[m + 2], a2);
+            a3 = fma(X[i + (m + 3) * ldX], sw[m + 3], a3);
+        }
+        for (; m < M; ++m) a0 = fma(X[i + m * ldX], sw[m], a0);
+        const double r = (((a0 + a1) + (a2 + a3)) + t) - y[i];
+        acc2 = fma(r, r, acc2);
+    }
+    red[threadIdx.x] = acc2;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[b * gridDim.x + blockIdx.x] = red[0];
+}
+
+hipError_t launch_oob_sse(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *W, int64_t ldW,
+                          const double *wv, int batch, double *part, hipStream_t st)
+{
+    hipLaunchKernelGGL(oob_sse_kernel, dim3(weight_prep_blocks(N), batch), dim3(256), (size_t)(256 + M + 1) * sizeof(double), st, X, N, M,
+                       ldX, y, W, ldW, wv, part);
+    return hipGetLastError();
+}
+
 }  // namespace partls

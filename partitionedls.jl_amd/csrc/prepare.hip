@@ -147,7 +147,7 @@ partls_status ctx_prepare(partls_ctx *c, const void *X, int64_t N, int64_t M, in
     c->last_upload_ms = 0.0; c->last_upload_bytes = 0.0;
     c->sweep_vetoes = 0;
     c->coop_state_valid = false;
-    c->order_ready = false; c->order_identity = true; c->flip_cost.clear(); c->ms[PARTLS_T_CALIB] = 0.0;
+    c->order_ready = false; c->order_identity = true; c->flip_cost.clear(); c->ms[PARTLS_T_CALIB] = 0.0; c->ms[PARTLS_T_OOB] = 0.0;
     c->dw = nullptr; c->ds = nullptr;
     c->x_f32 = false;
     if (x_f32 && c->multi_rank) { set_error("float X: a context of a partls_multi is not supported (row-sharded multi-GPU fits are fp64)"); return PARTLS_ERR_UNSUPPORTED; }

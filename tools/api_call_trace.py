@@ -57,6 +57,7 @@ SPEC = {
     "partls_opt_models": "h g_begin g_end out out out ld_raw out ld_alpha out ld_beta out out out",
     "partls_cv_opt": f"h {_XY} dev {_P} {_CV}",
     "partls_cv_opt_weighted": f"h {_XY} w:d:N dev {_P} {_CV}",
+    "partls_opt_weightings": f"h {_XY} dev {_P} w:d:ldW*B ldW B eta flags out ld_alpha out ld_beta out out out out out out",
     "partls_opt_num_patterns": "h", "partls_opt_bit_order": "h out out",
     "partls_fit_alt": f"h {_XY} {_P} eta eps T alpha0:d:M+1 beta0:d:K+1 {_OUT5}",
     "partls_fit_bnb": f"h {_XY} {_P} eta {_OUT5}",
@@ -176,7 +177,8 @@ class FakeLib:
     def _effect(self, name, h, env, args):
         """the few things control flow reads, and the return value"""
         if name in ("partls_opt_prepare", "partls_opt_prepare_weighted", "partls_opt_prepare_f32", "partls_fit_opt", "partls_fit_alt",
-                    "partls_fit_bnb", "partls_fit_opt_multi", "partls_fit_bnb_multi", "partls_cv_opt", "partls_cv_opt_weighted"):
+                    "partls_fit_bnb", "partls_fit_opt_multi", "partls_fit_bnb_multi", "partls_cv_opt", "partls_cv_opt_weighted",
+                    "partls_opt_weightings"):
             faithful = env.get("flags", 1) & 1               # partls_fit_alt / _bnb prepare with OPT_FAITHFUL_INTERCEPT
             for hh in [h] + self.ranks.get(h, []):
                 self.state[hh] = dict(M=env["M"], K=env["K"], npat=1 << (env["K"] + faithful))
