@@ -20,11 +20,11 @@
 // (lz_panel_stepwise), in two phases with three barriers per block on the 1024-thread plan (lz_panel_eliminate).
 // D = 340: 1.06 -> 4.0-4.5 M solves/s.  DESIGN.md §4 "Beyond n = 320".
 #include "gj_panel.h"
+#include "lazy_plan.h"
 
 namespace partls {
 
 static constexpr int LZ_MAXWORDS = 16;      // n <= 1024
-static constexpr int LZ_MAXR = 64;          // rows of the LDS pool at most
 #ifndef LZ_SPIN_SLEEP
 #define LZ_SPIN_SLEEP 1                     // s_sleep argument of the phase-2 waves' poll of the panel's progress word
 #endif
@@ -167,6 +167,7 @@ __device__ __forceinline__ void lz_fmac_bcast(double &acc, double y, double x, i
 // the block is redone from its (still untouched) panel image with that step marked "refused" — exactly what the step-by-step form does.
 // tab: [GJ_MB][GJ_MB] u, [GJ_MB][GJ_MB] final pivot rows, [GJ_MB] d, [GJ_MB] 1/d;  red: [GJ_MB] veto flags.
 static constexpr int LZ_MT = 8;
+static_assert(LAZY_PLAN_MB == GJ_MB && LAZY_PLAN_MT == LZ_MT, "lazy_plan.h plans for another block or panel width than this file compiles");
 template <int NT>
 __device__ __forceinline__ int lz_panel_eliminate(double *__restrict__ Pn, double *__restrict__ Zn, double *__restrict__ dinv,
                                                   double *__restrict__ tab, double *__restrict__ red, const int *__restrict__ ks, int m_,
@@ -786,24 +787,7 @@ __global__ __launch_bounds__(NT) void sweep_lazy_kernel(SweepParams p, int mb, i
     }
 }
 
-// LDS plan for leading dimension ld: pivots per block and rows of the pool (pending terms + panel).  false: no plan fits (never for n <= 1023)
-bool lazy_plan(int ld, int *mb_out, int *rows_out, size_t *shmem_out)
-{
-    const size_t budget = (size_t)151 * 1024;
-    const size_t fixed = (size_t)ld * 8 /* qs */ + 4 * (size_t)ld * 8 /* read-ahead rows */ + 3 * (size_t)ld /* flags, rowj */ + (2 * GJ_MB * GJ_MB + 8 * GJ_MB + 18) * 8 + 64;
-    const size_t row = (size_t)ld * 8;
-    if (budget < fixed + 6 * (row + 8 + GJ_MB * 8)) return false;
-    int rows = (int)((budget - fixed) / (row + 8 + GJ_MB * 8));              // each row: z or panel column, 1/d, Cj
-    if (rows > LZ_MAXR) rows = LZ_MAXR;
-    int mb = rows / 3;
-    if (mb > GJ_MB) mb = GJ_MB;
-    if (ld > 512 && mb > LZ_MT) mb = LZ_MT;                                  // the 1024-thread plan compiles the 8-column panel only
-    if (mb < 2) mb = 2;
-    *mb_out = mb; *rows_out = rows;
-    *shmem_out = ((size_t)(rows + 4) * ld + ld + rows + GJ_MB + (size_t)(rows + 4) * GJ_MB + 2 * GJ_MB * GJ_MB + 2 * GJ_MB + 18) * 8 + 3 * (size_t)ld + 16;
-    return true;
-}
-
+// the LDS plan (pivots per block, rows of the pool, dynamic LDS bytes) of a leading dimension: lazy_plan(), lazy_plan.h
 template <int NT, bool NODE, bool MODELS>
 static hipError_t launch_lazy_kernel(const SweepParams &p, int grid, int mb, int rows, size_t shmem, hipStream_t s)
 {

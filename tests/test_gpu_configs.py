@@ -73,7 +73,8 @@ def test_alt_d512_vs_oracle_same_start(partls, oracle):
 
 @pytest.mark.parametrize("D", [700, 1021])
 def test_global_memory_tableau_at_its_size_limit(partls, oracle, D):
-    """M = 700 and the documented maximum M + 1 = 1022 (check_common): every pattern of fit(Opt) on the global-memory kernels
+    """M = 700 and M = 1021 (n = M + 1 = 1022 tableau variables: one below the limit, check_common refuses M + 1 > 1023, so the
+    maximum is M = 1022, n = 1023; that size runs in test_gpu_lazy_plans.py): every pattern of fit(Opt) on the global-memory kernels
     (sweep_generic chains, sweep_coop winner re-solve) against the oracle; Alt from the same start."""
     rng = np.random.default_rng(D)
     K = 2
