@@ -1,4 +1,5 @@
-// common.h — internal declarations shared by the HIP translation units of libpartls_hip.so (gfx950 only).
+// common.h — internal declarations shared by the HIP translation units of libpartls_hip.so (gfx950 only).  (The rules that the prepare
+// path's kernels share with its host code are in prepare_rules.h, which needs no HIP.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -152,13 +153,12 @@ hipError_t launch_gram(const void *X, int64_t N, int64_t M, int64_t ldX, const d
 hipError_t launch_gram_weightings(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, double *slab, int64_t slab_stride,
                                   int chunks, int ldg, int gram_S, int gram_cr, double *G, int64_t gstride, const double *sw, int batch,
                                   hipStream_t s);
-// sample weights (misc.hip): s[i] = sqrt(w[i]) and, per block b of weight_prep_blocks(N), part[3 b ..] = (any w < 0, any non-finite w,
-// sum of w) — the host adds the blocks in index order
+// sample weights (misc.hip, one kernel): column b of W (N x batch, ld ldW) -> column b of S = sqrt(W) (ld N) and, per block x of
+// weight_prep_blocks(N) = nb, part[4 (b nb + x) ..] = (any w < 0, any non-finite w, sum of w, rows with w == 0); batch <= 65535.  The
+// host folds a column's blocks in index order (fold_weight_partials, prepare_rules.h).  launch_weight_prep: one column, ldW = N.
 int        weight_prep_blocks(int64_t N);
-hipError_t launch_weight_prep(const double *w, int64_t N, double *s, double *part, hipStream_t st);
-// `batch` weightings at once (partls_opt_weightings): column b of W (N x batch, ld ldW) -> column b of S = sqrt(W) (ld N) and, per block
-// x of weight_prep_blocks(N), part[4 (b nb + x) ..] = (any w < 0, any non-finite w, sum of w, rows with w == 0); batch <= 65535
 hipError_t launch_weightings_prep(const double *W, int64_t N, int64_t ldW, int batch, double *S, double *part, hipStream_t st);
+inline hipError_t launch_weight_prep(const double *w, int64_t N, double *s, double *part, hipStream_t st) { return launch_weightings_prep(w, N, N, 1, s, part, st); }
 // out-of-bag SSE of `batch` models: part[b nb + x] = sum over block x's rows with W[i, b] == 0 of (X[i,:] wv_b[0..M) + wv_b[M] - y_i)^2,
 // wv: batch x (M + 1), nb = weight_prep_blocks(N); the host adds a problem's blocks in index order; batch <= 65535
 hipError_t launch_oob_sse(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *W, int64_t ldW,
@@ -168,9 +168,9 @@ hipError_t launch_oob_sse(const double *X, int64_t N, int64_t M, int64_t ldX, co
 // perm[i] = augmented-Gram index of tableau variable i (variables are grouped by partition so a flip touches few tiles)
 hipError_t launch_prep(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, int free_intercept,
                        const int *perm, double *scale, double *Tfull, int n, hipStream_t s);
-// the same for `batch` problems at once (partls_cv_opt): slot q = blockIdx.y holds problem q0 + q, which reads the Gram
+// the same entries (prep_scale_entry, prep_tableau_entry) for `batch` problems at once: slot q = blockIdx.y holds problem q0 + q, which reads the Gram
 // G + ((q0 + q) / E) * gstride with eta[(q0 + q) % E] (device array); writes scale + q * n, Tfull + q * (n+1)^2 and
-// tol[q] = tol_rel * sqrt(max(y'y, 0)) (1e-300 when that is not > 0)
+// tol[q] = problem_tol(tol_rel, y'y of the problem's Gram) (prepare_rules.h)
 hipError_t launch_prep_batch(const double *G, int64_t gstride, int E, int64_t q0, const double *eta, int ldg, int M, const uint64_t *mask_aug,
                              int free_intercept, const int *perm, double tol_rel, double *scale, double *Tfull, double *tol, int n,
                              int batch, hipStream_t s);

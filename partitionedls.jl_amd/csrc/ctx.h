@@ -150,6 +150,10 @@ struct partls_ctx {
     bool timed[PARTLS_T_COUNT] = {};
     double ms[PARTLS_T_COUNT] = {};
 
+    // Reset by forget_problem (prepare.hip), the one reset of ctx_prepare, batch_reset and batch_calibrate — whatever below is derived
+    // from a prepared problem or its last sweep or solve: prepared, peers; near_for, near_pat, cand, export_wg; sweep_vetoes,
+    // coop_state_valid, coop_fallback; tab_valid; order_ready, order_identity, flip_cost; dw, ds, x_f32; last_upload_*; ms[CALIB], ms[OOB].
+    // (Not last_kkt / last_min_loo: partls_get_kkt_violation reports them, for the last model returned, without a prepared problem.)
     // problem
     bool prepared = false;
     int64_t N = 0, M = 0, K = 0, ldX = 0;
@@ -161,8 +165,9 @@ struct partls_ctx {
     const double *dy = nullptr;
     partls::DevBuf ownX, ownY;
     // sample weights of the prepared problem (partls_opt_prepare_weighted / partls_cv_opt_weighted; nullptr: unweighted): dw = w (the
-    // caller's device array, or ownW, the upload of a host one), ds = sqrt(w) (ownS, written by weight_prep_kernel).  Every Gram build
-    // and every data pass (data_pass) of the problem reads them; a plain prepare clears them.  DESIGN.md §4.7.
+    // caller's device array, or ownW, the upload of a host one), ds = sqrt(w) (ownS, written by weight_prep_kernel; wPart / hPart: its
+    // four partials per block).  Every Gram build and every data pass (data_pass) of the problem reads them; a plain prepare clears
+    // them.  DESIGN.md §4.7.
     const double *dw = nullptr, *ds = nullptr;
     partls::DevBuf ownW, ownS, wPart;
     bool multi_rank = false;                       // this context belongs to a partls_multi (weighted prepares are refused)
@@ -241,7 +246,7 @@ struct partls_ctx {
     partls::PinnedDoubles cvHost, cvHostG;
     // partls_opt_weightings (resample.hip) shares cv_work and the cv* buffers above (cvG: one Gram per weighting) and
     // adds: rsW, the upload of a host W (N x B, ld N); rsS = sqrt(W) (ld N); rsPart / rsHost, the per-block partials of
-    // weightings_prep_kernel and of oob_sse_kernel and their host copies; rsWv, the models of a chunk of problems as weight vectors
+    // weight_prep_kernel and of oob_sse_kernel and their host copies; rsWv, the models of a chunk of problems as weight vectors
     partls::DevBuf rsW, rsS, rsPart, rsWv;
     partls::PinnedDoubles rsHost;
 };
@@ -258,6 +263,10 @@ void t_collect(partls_ctx *c);
 partls_status ctx_prepare(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
                           const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags, const double *w = nullptr,
                           bool x_f32 = false);
+// c forgets its prepared problem and what its last sweep or solve left behind (the list: partls_ctx); buffers and the upload of X stay
+void forget_problem(partls_ctx *c);
+// X (elements of esz bytes: 8 or 4) and y: device arrays are adopted, host arrays go up into ownX (ld N) / ownY and the upload is timed
+partls_status adopt_or_upload(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device, size_t esz);
 // Sample weights w[N] (host, or device when on_device) -> c->dw, c->ds after one weight_prep_kernel pass, or the status of the first
 // failed check: NaN / Inf -> PARTLS_ERR_NONFINITE; a negative weight or a sum that is not > 0 -> PARTLS_ERR_BAD_ARG.
 partls_status prepare_weights(partls_ctx *c, const double *w, int64_t N, int on_device);
@@ -331,9 +340,8 @@ struct ProblemBatch {
     std::function<partls_status(int64_t q, int64_t bpat, int64_t unconv)> finish;
 };
 partls_status make_internal(partls_ctx *c, partls_ctx **slot);
-// c forgets its prepared problem and takes the shape of the batch's; then X, y go up once (or the caller's device arrays are adopted)
+// c forgets its prepared problem (forget_problem), zeroes every timer and takes the shape of the batch's
 void batch_reset(partls_ctx *c, int64_t N, int64_t M, int64_t K, uint32_t flags);
-partls_status batch_upload(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device);
 // cv_work takes the batch's shape, partition and Gram layout, is prepared for Gram `cal_gram` at eta[0] with its rows set by
 // point_rows(cv_work), and the visiting order of the whole batch is calibrated there (the rule of a single fit decides whether that pays)
 partls_status batch_calibrate(partls_ctx *c, const int64_t *P, int64_t ldP, uint32_t flags, int ldg, int chunks, const ProblemBatch &pb,

@@ -4,10 +4,12 @@
 // and swept in one launch of the BATCH instantiation of the register kernels (blockIdx.y = problem).  Each problem is then finished as
 // partls_opt_finish finishes a single fit (near-tie re-rank from the data, refinement, KKT check, cleanupResult), on an internal working
 // context whose data passes cover exactly its training rows (row-block views of the folds as its peers).  DESIGN.md §4.6.
-// The parts that do not know about folds — the reset and upload, the calibration on the working context, the batched / serial sweep of
-// B problems over Grams at a fixed stride with the finish as a callback, the finish of one model — are the batch_* helpers of ctx.h,
-// which partls_opt_weightings (resample.hip) shares.
+// The parts that do not know about folds — the reset, the calibration on the working context, the batched / serial sweep of B problems
+// over Grams at a fixed stride with the finish as a callback, the finish of one model — are the batch_* helpers of ctx.h, which
+// partls_opt_weightings (resample.hip) shares.  The steps a single prepare has too are the single prepare's (prepare.hip, prepare_rules.h):
+// forget_problem, adopt_or_upload, prepare_weights, gram_diag_finite, ctx_prepare_tableau and the preparation kernels.
 #include "ctx.h"
+#include "prepare_rules.h"
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -141,33 +143,10 @@ static partls_status finish_one(partls_ctx *c, partls_ctx *W, const int64_t *fol
 
 void batch_reset(partls_ctx *c, int64_t N, int64_t M, int64_t K, uint32_t flags)
 {
-    for (int w = 0; w < PARTLS_T_COUNT; ++w) c->ms[w] = 0.0;
     // this context keeps the upload and the Gram products; it holds no prepared problem afterwards
-    c->prepared = false;
-    c->peers.clear();
-    c->near_for = -1; c->near_pat.clear(); c->cand.clear();
-    c->last_upload_ms = 0.0; c->last_upload_bytes = 0.0;
+    forget_problem(c);
+    for (int w = 0; w < PARTLS_T_COUNT; ++w) c->ms[w] = 0.0;
     c->N = N; c->M = M; c->K = K; c->flags = flags; c->faithful = (flags & PARTLS_OPT_FAITHFUL_INTERCEPT) != 0;
-    c->dw = nullptr; c->ds = nullptr;
-    c->x_f32 = false;                              // the batched entries read X as double (no float form)
-}
-
-partls_status batch_upload(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device)
-{
-    if (x_on_device) {
-        c->dX = X; c->dy = y; c->ldX = ldX;
-        return PARTLS_OK;
-    }
-    PARTLS_HIP_CHECK(c->ownX.ensure((size_t)N * M * sizeof(double)));
-    PARTLS_HIP_CHECK(c->ownY.ensure((size_t)N * sizeof(double)));
-    PARTLS_HIP_CHECK(hipMemcpyAsync(c->ownY.p, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const auto u0 = std::chrono::steady_clock::now();
-    partls_status st = upload_matrix(c, c->ownX.as<double>(), X, N, M, ldX);
-    if (st != PARTLS_OK) return st;
-    c->last_upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
-    c->last_upload_bytes = (double)N * (double)M * sizeof(double);
-    c->dX = c->ownX.as<double>(); c->dy = c->ownY.as<double>(); c->ldX = N;
-    return PARTLS_OK;
 }
 
 partls_status batch_calibrate(partls_ctx *c, const int64_t *P, int64_t ldP, uint32_t flags, int ldg, int chunks, const ProblemBatch &pb,
@@ -175,13 +154,8 @@ partls_status batch_calibrate(partls_ctx *c, const int64_t *P, int64_t ldP, uint
 {
     partls_ctx *W = c->cv_work;
     const int64_t M = c->M, K = c->K;
+    forget_problem(W);
     W->knobs = c->knobs;
-    W->prepared = false;
-    W->peers.clear();
-    W->near_for = -1; W->near_pat.clear(); W->cand.clear();
-    W->sweep_vetoes = 0;
-    W->coop_state_valid = false;
-    W->order_ready = false; W->order_identity = true; W->flip_cost.clear();
     W->gram_hook = nullptr;
     partls_status st = load_partition(W, P, M, K, ldP);
     if (st != PARTLS_OK) return st;
@@ -338,7 +312,7 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
     }
 
     // ---- one upload
-    partls_status st = batch_upload(c, X, N, M, ldX, y, x_on_device);
+    partls_status st = adopt_or_upload(c, X, N, M, ldX, y, x_on_device, sizeof(double));
     if (st != PARTLS_OK) return st;
     const double *Xd = static_cast<const double *>(c->dX);
 
@@ -383,11 +357,10 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
     PARTLS_HIP_CHECK(hipMemcpyAsync(c->cvHostG.data(), Gc, (size_t)(F + 1) * gs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
     t_collect(c);
-    // NaN / Inf in [X y]: the diagonal of the all-rows Gram is non-finite (ctx_prepare's test; a sum of the folds' non-negative diagonals)
-    const double *Gall = c->cvHostG.data() + (size_t)F * gs;
-    for (int64_t i = 0; i < M + 2; ++i) {
-        if (i == M) continue;
-        if (!std::isfinite(Gall[(size_t)i * ldg + i])) { set_error("partls_cv_opt: X or y contains NaN/Inf (or overflows in X'X)"); return PARTLS_ERR_NONFINITE; }
+    // NaN / Inf in [X y]: the all-rows Gram decides (its diagonal is the sum of the folds' non-negative diagonals)
+    if (!gram_diag_finite(c->cvHostG.data() + (size_t)F * gs, ldg, M)) {
+        set_error("partls_cv_opt: X or y contains NaN/Inf (or overflows in X'X)");
+        return PARTLS_ERR_NONFINITE;
     }
     // weighted: every training set needs weight (its ones-column entry is sum_i s_i^2 over its rows)
     if (c->ds)

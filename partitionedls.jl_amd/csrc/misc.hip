@@ -1,7 +1,38 @@
 // misc.hip — the small kernels either side of the sweep: synthetic inputs, tableau preparation, residual from the data.
 #include "sweep_rules.h"
+#include "prepare_rules.h"
 
 namespace partls {
+
+// The block sum of the 256-thread kernels below: a fixed-order tree over red[256] (LDS).  Every thread calls it; all get the sum.
+__device__ __forceinline__ double block_sum_256(double *red, double v)
+{
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// Prediction of row i of column-major X (widened as it is loaded) under the weights sw[0..M) and intercept t: four chains over m mod 4,
+// ((a0 + a1) + (a2 + a3)) + t — the one order in which a row is predicted, so that a model's residual and its out-of-bag error agree
+// bit for bit on a row.  residual_kernel keeps a hand-written copy (see there).
+template <class XT>
+__device__ __forceinline__ double row_predict(const XT *X, int64_t i, int64_t M, int64_t ldX, const double *sw, double t)
+{
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    int64_t m = 0;
+    for (; m + 3 < M; m += 4) {
+        a0 = fma((double)X[i + m * ldX], sw[m], a0);
+        a1 = fma((double)X[i + (m + 1) * ldX], sw[m + 1], a1);
+        a2 = fma((double)X[i + (m + 2) * ldX], sw[m + 2], a2);
+        a3 = fma((double)X[i + (m + 3) * ldX], sw[m + 3], a3);
+    }
+    for (; m < M; ++m) a0 = fma((double)X[i + m * ldX], sw[m], a0);
+    return ((a0 + a1) + (a2 + a3)) + t;
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Synthetic inputs: integer-exact counter-based generator — the device twin of oracle_synth().
@@ -86,22 +117,19 @@ __device__ static inline double base_entry(const double *G, int ldg, int M, doub
     return v;
 }
 
-__global__ void prep_scale_kernel(const double *__restrict__ G, int ldg, int M, double eta,
-                                  const uint64_t *__restrict__ mask_aug, int free_intercept, const int *__restrict__ perm,
-                                  int n, double *__restrict__ scale)
+// The two steps, one entry per thread: the bodies of the single kernels and of the batched ones alike.  The tableau reads the scale.
+__device__ __forceinline__ void prep_scale_entry(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, int free_intercept,
+                                                 const int *perm, int n, double *scale)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const double d = base_entry(G, ldg, M, eta, mask_aug, free_intercept, perm, n, i, i);
     const double ref = G[(size_t)perm[i] * ldg + perm[i]];
-    // a (numerically) null column carries no information: scale 0 keeps it out of every basis
-    scale[i] = (d > 0.0 && d > 1e-14 * fabs(ref)) ? 1.0 / sqrt(d) : 0.0;
+    scale[i] = column_is_live(d, ref) ? 1.0 / sqrt(d) : 0.0;
 }
 
-__global__ void prep_tableau_kernel(const double *__restrict__ G, int ldg, int M, double eta,
-                                    const uint64_t *__restrict__ mask_aug, int free_intercept,
-                                    const int *__restrict__ perm, int n,
-                                    const double *__restrict__ scale, double *__restrict__ Tfull)
+__device__ __forceinline__ void prep_tableau_entry(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, int free_intercept,
+                                                   const int *perm, int n, const double *scale, double *Tfull)
 {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int ld = n + 1;
@@ -111,6 +139,19 @@ __global__ void prep_tableau_kernel(const double *__restrict__ G, int ldg, int M
     double v = base_entry(G, ldg, M, eta, mask_aug, free_intercept, perm, n, i, j) * si * sj;
     if (i == j && i < n && si == 0.0) v = 1.0;          // dead variable: harmless unit pivot, never selected
     Tfull[idx] = v;
+}
+
+// One problem: G and eta as passed (eta is a kernel argument: the single prepare pays no copy for it; a C2 fit is 0.58 ms end to end).
+__global__ void prep_scale_kernel(const double *__restrict__ G, int ldg, int M, double eta, const uint64_t *__restrict__ mask_aug,
+                                  int free_intercept, const int *__restrict__ perm, int n, double *__restrict__ scale)
+{
+    prep_scale_entry(G, ldg, M, eta, mask_aug, free_intercept, perm, n, scale);
+}
+
+__global__ void prep_tableau_kernel(const double *__restrict__ G, int ldg, int M, double eta, const uint64_t *__restrict__ mask_aug, int free_intercept,
+                                    const int *__restrict__ perm, int n, const double *__restrict__ scale, double *__restrict__ Tfull)
+{
+    prep_tableau_entry(G, ldg, M, eta, mask_aug, free_intercept, perm, n, scale, Tfull);
 }
 
 hipError_t launch_prep(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, int free_intercept,
@@ -126,46 +167,25 @@ hipError_t launch_prep(const double *G, int ldg, int M, double eta, const uint64
     return hipGetLastError();
 }
 
-// Batched preparation (partls_cv_opt): problem q = q0 + blockIdx.y reads the Gram G + (q / E) * gstride with eta[q % E] and writes slot
-// blockIdx.y of the outputs; the same entries as above.
-// Launched twice: scale (+ the tolerance from the problem's own y'y) first, then the tableau that reads it.
+// Batched: problem q = q0 + blockIdx.y reads the Gram G + (q / E) * gstride with eta[q % E] and writes slot blockIdx.y of the outputs;
+// the scale step also writes the problem's tolerance from its own y'y (problem_tol, the host's rule).
 __global__ void prep_scale_batch_kernel(const double *__restrict__ G, int64_t gstride, int E, int64_t q0, const double *__restrict__ eta, int ldg, int M,
                                         const uint64_t *__restrict__ mask_aug, int free_intercept, const int *__restrict__ perm, int n,
                                         double tol_rel, double *__restrict__ scale, double *__restrict__ tol)
 {
-    const int q = blockIdx.y;
-    const int64_t qq = q0 + q;
+    const int64_t qq = q0 + blockIdx.y;
     const double *Gq = G + (qq / E) * gstride;
-    const double e = eta[qq % E];
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const double yy = Gq[(size_t)(M + 1) * ldg + (M + 1)];
-        const double t = tol_rel * sqrt(yy > 0.0 ? yy : 0.0);
-        tol[q] = t > 0.0 ? t : 1e-300;
-    }
-    if (i >= n) return;
-    const double d = base_entry(Gq, ldg, M, e, mask_aug, free_intercept, perm, n, i, i);
-    const double ref = Gq[(size_t)perm[i] * ldg + perm[i]];
-    scale[(int64_t)q * n + i] = (d > 0.0 && d > 1e-14 * fabs(ref)) ? 1.0 / sqrt(d) : 0.0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) tol[blockIdx.y] = problem_tol(tol_rel, Gq[(size_t)(M + 1) * ldg + (M + 1)]);
+    prep_scale_entry(Gq, ldg, M, eta[qq % E], mask_aug, free_intercept, perm, n, scale + (int64_t)blockIdx.y * n);
 }
 
 __global__ void prep_tableau_batch_kernel(const double *__restrict__ G, int64_t gstride, int E, int64_t q0, const double *__restrict__ eta, int ldg,
                                           int M, const uint64_t *__restrict__ mask_aug, int free_intercept, const int *__restrict__ perm,
                                           int n, const double *__restrict__ scale, double *__restrict__ Tfull)
 {
-    const int q = blockIdx.y;
-    const int64_t qq = q0 + q;
-    const double *Gq = G + (qq / E) * gstride;
-    const double e = eta[qq % E];
-    const double *sq = scale + (int64_t)q * n;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int ld = n + 1;
-    if (idx >= ld * ld) return;
-    const int i = idx / ld, j = idx % ld;
-    const double si = (i < n) ? sq[i] : 1.0, sj = (j < n) ? sq[j] : 1.0;
-    double v = base_entry(Gq, ldg, M, e, mask_aug, free_intercept, perm, n, i, j) * si * sj;
-    if (i == j && i < n && si == 0.0) v = 1.0;
-    Tfull[(int64_t)q * ld * ld + idx] = v;
+    const int64_t qq = q0 + blockIdx.y;
+    prep_tableau_entry(G + (qq / E) * gstride, ldg, M, eta[qq % E], mask_aug, free_intercept, perm, n, scale + (int64_t)blockIdx.y * n,
+                       Tfull + (int64_t)blockIdx.y * (n + 1) * (n + 1));
 }
 
 hipError_t launch_prep_batch(const double *G, int64_t gstride, int E, int64_t q0, const double *eta, int ldg, int M, const uint64_t *mask_aug,
@@ -282,13 +302,8 @@ __global__ __launch_bounds__(256) void gersh_kernel(const double *__restrict__ T
     const int i = blockIdx.x;
     double s = 0.0;
     for (int j = threadIdx.x; j < n; j += 256) if (j != i) s += fabs(T[(size_t)i * ld + j]);
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[i] = red[0];
+    s = block_sum_256(red, s);
+    if (threadIdx.x == 0) out[i] = s;
 }
 hipError_t launch_gersh(const double *Tfull, int n, double *out, hipStream_t s)
 {
@@ -450,6 +465,8 @@ __global__ __launch_bounds__(256) void residual_kernel(const XT *__restrict__ X,
     __syncthreads();
     double acc2 = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+        // (row_predict), written out: through the helper this kernel — the data pass of C3 / C4 — is allocated one SGPR more (45 for 44;
+        // the same instructions in another allocation, profiles/prepare_path_resource_usage.txt).  A change is made in both.
         double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
         int64_t m = 0;
         for (; m + 3 < M; m += 4) {
@@ -468,13 +485,8 @@ __global__ __launch_bounds__(256) void residual_kernel(const XT *__restrict__ X,
         }
     }
     __shared__ double red[256];
-    red[threadIdx.x] = acc2;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && partial) partial[blockIdx.x] = red[0];
+    acc2 = block_sum_256(red, acc2);
+    if (threadIdx.x == 0 && partial) partial[blockIdx.x] = acc2;
 }
 
 template <class XT>
@@ -536,13 +548,8 @@ __global__ __launch_bounds__(256) void xtr_kernel(const XT *__restrict__ X, int6
         else for (; i < r1; i += 256) acc[0] += y[i] - yhat[i];
     }
     __shared__ double red[256];
-    red[threadIdx.x] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) gpart[(size_t)r * (M + 1) + m] = red[0];
+    const double g = block_sum_256(red, (acc[0] + acc[1]) + (acc[2] + acc[3]));
+    if (threadIdx.x == 0) gpart[(size_t)r * (M + 1) + m] = g;
 }
 
 int xtr_slices(int64_t N)
@@ -571,57 +578,17 @@ hipError_t launch_xtr(const void *X, int64_t N, int64_t M, int64_t ldX, const do
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Sample weights: one pass over w[N] on the device, for host and device weights alike.  Writes s = sqrt(w) (what the
-// Gram kernel stages; sqrt is correctly rounded, so sqrt(1) = 1 and sqrt(4) = 2 exactly) and, per block b, three partials:
-//   part[3b] = 1 if some w_i < 0,   part[3b + 1] = 1 if some w_i is NaN / Inf,   part[3b + 2] = sum of the block's w_i
-// (grid-stride rows, fixed-order tree over the block).  The host adds the blocks in index order and turns them into a status.
+// Sample weights: one pass over the columns of W (N x batch, leading dimension ldW) on the device, for host and
+// device weights alike; a single weighted fit is the batch of one.  Column b = blockIdx.y -> column b of S = sqrt(W) (leading
+// dimension N; what the Gram kernel stages; sqrt is correctly rounded, so sqrt(1) = 1 and sqrt(4) = 2 exactly) and, per block (b, x),
+// four partials at part[4 (b gridDim.x + x) ..]:
+//   [0] 1 if some w_i < 0,   [1] 1 if some w_i is NaN / Inf,   [2] the sum of the block's finite w_i,
+//   [3] the number of rows whose weight is exactly 0 (the out-of-bag rows of a weighting; a count below 2^53 is exact in a double)
+// (grid-stride rows, fixed-order trees over the block: a column's sum depends on N and the column alone).  The host folds a column's
+// blocks in index order (fold_weight_partials, prepare_rules.h) and turns them into a status.
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void weight_prep_kernel(const double *__restrict__ w, int64_t N, double *__restrict__ s,
+__global__ __launch_bounds__(256) void weight_prep_kernel(const double *__restrict__ W, int64_t N, int64_t ldW, double *__restrict__ S,
                                                           double *__restrict__ part)
-{
-    __shared__ double red[3][256];
-    double neg = 0.0, bad = 0.0, sum = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
-        const double v = w[i];
-        const bool fin = isfinite(v);
-        if (!fin) bad = 1.0;
-        if (v < 0.0) neg = 1.0;
-        sum += fin ? v : 0.0;
-        s[i] = (fin && v >= 0.0) ? sqrt(v) : 0.0;
-    }
-    red[0][threadIdx.x] = neg; red[1][threadIdx.x] = bad; red[2][threadIdx.x] = sum;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) {
-            red[0][threadIdx.x] = fmax(red[0][threadIdx.x], red[0][threadIdx.x + h]);
-            red[1][threadIdx.x] = fmax(red[1][threadIdx.x], red[1][threadIdx.x + h]);
-            red[2][threadIdx.x] += red[2][threadIdx.x + h];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { part[3 * blockIdx.x] = red[0][0]; part[3 * blockIdx.x + 1] = red[1][0]; part[3 * blockIdx.x + 2] = red[2][0]; }
-}
-
-int weight_prep_blocks(int64_t N)
-{
-    const int64_t b = (N + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
-}
-
-hipError_t launch_weight_prep(const double *w, int64_t N, double *s, double *part, hipStream_t st)
-{
-    hipLaunchKernelGGL(weight_prep_kernel, dim3(weight_prep_blocks(N)), dim3(256), 0, st, w, N, s, part);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// B weightings of one data set (partls_opt_weightings): weight_prep_kernel with blockIdx.y = weighting b.  Column b of
-// W (N x B, leading dimension ldW) -> column b of S = sqrt(W) (leading dimension N) and, per block (b, x), four partials at
-// part[4 (b gridDim.x + x) ..]: the three of weight_prep_kernel and the number of rows whose weight is exactly 0 (the out-of-bag rows; a
-// count below 2^53 is exact in a double).  Same rows per block, same tree: column b's sum is weight_prep_kernel's for that column.
-// ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void weightings_prep_kernel(const double *__restrict__ W, int64_t N, int64_t ldW, double *__restrict__ S,
-                                                              double *__restrict__ part)
 {
     __shared__ double red[4][256];
     const int64_t b = blockIdx.y;
@@ -637,36 +604,43 @@ __global__ __launch_bounds__(256) void weightings_prep_kernel(const double *__re
         sum += fin ? v : 0.0;
         s[i] = (fin && v >= 0.0) ? sqrt(v) : 0.0;
     }
-    red[0][threadIdx.x] = neg; red[1][threadIdx.x] = bad; red[2][threadIdx.x] = sum; red[3][threadIdx.x] = zero;
+    // the two flags: a max tree, written out (block_sum_256 adds); the two sums each have a row of red to themselves
+    red[0][threadIdx.x] = neg; red[1][threadIdx.x] = bad;
     __syncthreads();
     for (int h = 128; h > 0; h >>= 1) {
         if ((int)threadIdx.x < h) {
             red[0][threadIdx.x] = fmax(red[0][threadIdx.x], red[0][threadIdx.x + h]);
             red[1][threadIdx.x] = fmax(red[1][threadIdx.x], red[1][threadIdx.x + h]);
-            red[2][threadIdx.x] += red[2][threadIdx.x + h];
-            red[3][threadIdx.x] += red[3][threadIdx.x + h];
         }
         __syncthreads();
     }
+    sum = block_sum_256(red[2], sum);
+    zero = block_sum_256(red[3], zero);
     if (threadIdx.x == 0) {
         double *p = part + 4 * (b * gridDim.x + blockIdx.x);
-        p[0] = red[0][0]; p[1] = red[1][0]; p[2] = red[2][0]; p[3] = red[3][0];
+        p[0] = red[0][0]; p[1] = red[1][0]; p[2] = sum; p[3] = zero;
     }
+}
+
+int weight_prep_blocks(int64_t N)
+{
+    const int64_t b = (N + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
 }
 
 hipError_t launch_weightings_prep(const double *W, int64_t N, int64_t ldW, int batch, double *S, double *part, hipStream_t st)
 {
-    hipLaunchKernelGGL(weightings_prep_kernel, dim3(weight_prep_blocks(N), batch), dim3(256), 0, st, W, N, ldW, S, part);
+    hipLaunchKernelGGL(weight_prep_kernel, dim3(weight_prep_blocks(N), batch), dim3(256), 0, st, W, N, ldW, S, part);
     return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Out-of-bag error of `batch` models at once (partls_opt_weightings): problem b = blockIdx.y has the model wv + b (M + 1) (features, then
 // the intercept) and the weights W + b ldW; part[b gridDim.x + x] = sum over the block's rows i with W[i, b] == 0 of
-// (sum_m X[i,m] w_m + t - y_i)^2, unweighted.  A row's prediction is accumulated exactly as residual_kernel does it (four chains over
-// m mod 4, ((a0 + a1) + (a2 + a3)) + t), the rows of a block and its tree are fixed by N alone, and the host adds the blocks in index
-// order: a problem's value does not depend on what else is in the batch.  No atomics.  Every workgroup of a column reads the rows of X
-// it owns once per problem; the problems of one launch share them through the caches.
+// (sum_m X[i,m] w_m + t - y_i)^2, unweighted.  A row's prediction is residual_kernel's (row_predict), the rows of a block and its tree
+// are fixed by N alone, and the host adds the blocks in index order: a problem's value does not depend on what else is in the batch.
+// No atomics.  Every workgroup of a column reads the rows of X it owns once per problem; the problems of one launch share them through
+// the caches.
 // Dynamic LDS only: [tree (256) | model (M + 1)].
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void oob_sse_kernel(const double *__restrict__ X, int64_t N, int64_t M, int64_t ldX,
@@ -684,25 +658,11 @@ __global__ __launch_bounds__(256) void oob_sse_kernel(const double *__restrict__
     double acc2 = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
         if (wt[i] != 0.0) continue;
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-        int64_t m = 0;
-        for (; m + 3 < M; m += 4) {
-            a0 = fma(X[i + m * ldX], sw[m], a0);
-            a1 = fma(X[i + (m + 1) * ldX], sw[m + 1], a1);
-            a2 = fma(X[i + (m + 2) * ldX], sw[m + 2], a2);
-            a3 = fma(X[i + (m + 3) * ldX], sw[m + 3], a3);
-        }
-        for (; m < M; ++m) a0 = fma(X[i + m * ldX], sw[m], a0);
-        const double r = (((a0 + a1) + (a2 + a3)) + t) - y[i];
+        const double r = row_predict(X, i, M, ldX, sw, t) - y[i];
         acc2 = fma(r, r, acc2);
     }
-    red[threadIdx.x] = acc2;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[b * gridDim.x + blockIdx.x] = red[0];
+    acc2 = block_sum_256(red, acc2);
+    if (threadIdx.x == 0) part[b * gridDim.x + blockIdx.x] = acc2;
 }
 
 hipError_t launch_oob_sse(const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *W, int64_t ldW,

@@ -1,5 +1,8 @@
 // prepare.hip — from the caller's arrays to a prepared context: upload of X, y and the sample weights, the Gram products, the tableau.
+// The steps the batched entries (cv.hip, resample.hip) share with ctx_prepare are defined here once: forget_problem (the reset),
+// adopt_or_upload (X and y), prepare_weights, ctx_prepare_tableau; the rules they apply are those of prepare_rules.h.  DESIGN.md §4.
 #include "ctx.h"
+#include "prepare_rules.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -114,23 +117,50 @@ partls_status prepare_weights(partls_ctx *c, const double *w, int64_t N, int on_
     }
     const int nb = weight_prep_blocks(N);
     PARTLS_HIP_CHECK(c->ownS.ensure((size_t)N * sizeof(double)));
-    PARTLS_HIP_CHECK(c->wPart.ensure((size_t)3 * nb * sizeof(double)));
-    PARTLS_HIP_CHECK(c->hPart.resize((size_t)3 * nb));
+    PARTLS_HIP_CHECK(c->wPart.ensure((size_t)4 * nb * sizeof(double)));
+    PARTLS_HIP_CHECK(c->hPart.resize((size_t)4 * nb));
     PARTLS_HIP_CHECK(launch_weight_prep(dw, N, c->ownS.as<double>(), c->wPart.as<double>(), c->stream));
-    PARTLS_HIP_CHECK(hipMemcpyAsync(c->hPart.data(), c->wPart.p, (size_t)3 * nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->hPart.data(), c->wPart.p, (size_t)4 * nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    bool neg = false, bad = false;
-    double sum = 0.0;
-    for (int b = 0; b < nb; ++b) {
-        neg = neg || c->hPart[(size_t)3 * b] != 0.0;
-        bad = bad || c->hPart[(size_t)3 * b + 1] != 0.0;
-        sum += c->hPart[(size_t)3 * b + 2];
-    }
-    if (bad) { set_error("the sample weights contain NaN/Inf"); return PARTLS_ERR_NONFINITE; }
-    if (neg) { set_error("a sample weight is negative"); return PARTLS_ERR_BAD_ARG; }
-    if (!(sum > 0.0)) { set_error("the sample weights sum to 0"); return PARTLS_ERR_BAD_ARG; }
-    if (!std::isfinite(sum)) { set_error("the sum of the sample weights overflows"); return PARTLS_ERR_NONFINITE; }
+    const WeightFold f = fold_weight_partials(c->hPart.data(), nb);
+    if (f.nonfinite) { set_error("the sample weights contain NaN/Inf"); return PARTLS_ERR_NONFINITE; }
+    if (f.negative) { set_error("a sample weight is negative"); return PARTLS_ERR_BAD_ARG; }
+    if (!(f.sum > 0.0)) { set_error("the sample weights sum to 0"); return PARTLS_ERR_BAD_ARG; }
+    if (!std::isfinite(f.sum)) { set_error("the sum of the sample weights overflows"); return PARTLS_ERR_NONFINITE; }
     c->dw = dw; c->ds = c->ownS.as<double>();
+    return PARTLS_OK;
+}
+
+void forget_problem(partls_ctx *c)
+{
+    c->prepared = false;
+    c->peers.clear();                              // a row-sharded fit sets them again after every rank has prepared its block
+    c->near_for = -1; c->near_pat.clear(); c->cand.clear(); c->export_wg = -1;
+    c->sweep_vetoes = 0;
+    c->coop_state_valid = false; c->coop_fallback = false;
+    c->tab_valid = false;
+    c->order_ready = false; c->order_identity = true; c->flip_cost.clear();
+    c->dw = nullptr; c->ds = nullptr;
+    c->x_f32 = false;
+    c->last_upload_ms = 0.0; c->last_upload_bytes = 0.0;
+    c->ms[PARTLS_T_CALIB] = 0.0; c->ms[PARTLS_T_OOB] = 0.0;
+}
+
+partls_status adopt_or_upload(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device, size_t esz)
+{
+    if (x_on_device) {
+        c->dX = X; c->dy = y; c->ldX = ldX;
+        return PARTLS_OK;
+    }
+    PARTLS_HIP_CHECK(c->ownX.ensure((size_t)N * M * esz));
+    PARTLS_HIP_CHECK(c->ownY.ensure((size_t)N * sizeof(double)));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->ownY.p, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const auto u0 = std::chrono::steady_clock::now();
+    const partls_status st = upload_matrix(c, c->ownX.p, X, N, M, ldX, esz);
+    if (st != PARTLS_OK) return st;
+    c->last_upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+    c->last_upload_bytes = (double)N * (double)M * (double)esz;
+    c->dX = c->ownX.p; c->dy = c->ownY.as<double>(); c->ldX = N;
     return PARTLS_OK;
 }
 
@@ -141,15 +171,7 @@ partls_status ctx_prepare(partls_ctx *c, const void *X, int64_t N, int64_t M, in
     if (st != PARTLS_OK) return st;
     if (!y) { set_error("y is NULL"); return PARTLS_ERR_BAD_ARG; }
     if (!(eta >= 0.0)) { set_error("eta must be >= 0"); return PARTLS_ERR_BAD_ARG; }
-    c->prepared = false;
-    c->peers.clear();                              // a row-sharded fit sets them again after every rank has prepared its block
-    c->near_for = -1; c->near_pat.clear(); c->cand.clear();
-    c->last_upload_ms = 0.0; c->last_upload_bytes = 0.0;
-    c->sweep_vetoes = 0;
-    c->coop_state_valid = false;
-    c->order_ready = false; c->order_identity = true; c->flip_cost.clear(); c->ms[PARTLS_T_CALIB] = 0.0; c->ms[PARTLS_T_OOB] = 0.0;
-    c->dw = nullptr; c->ds = nullptr;
-    c->x_f32 = false;
+    forget_problem(c);
     if (x_f32 && c->multi_rank) { set_error("float X: a context of a partls_multi is not supported (row-sharded multi-GPU fits are fp64)"); return PARTLS_ERR_UNSUPPORTED; }
     PARTLS_HIP_CHECK(hipSetDevice(c->device));
     if (w) {
@@ -161,20 +183,8 @@ partls_status ctx_prepare(partls_ctx *c, const void *X, int64_t N, int64_t M, in
     if (st != PARTLS_OK) return st;
     c->N = N; c->M = M; c->K = K; c->eta = eta; c->flags = flags; c->faithful = faithful;
 
-    if (x_on_device) {
-        c->dX = X; c->dy = y; c->ldX = ldX;
-    } else {
-        const size_t esz = x_f32 ? sizeof(float) : sizeof(double);
-        PARTLS_HIP_CHECK(c->ownX.ensure((size_t)N * M * esz));
-        PARTLS_HIP_CHECK(c->ownY.ensure((size_t)N * sizeof(double)));
-        PARTLS_HIP_CHECK(hipMemcpyAsync(c->ownY.p, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        const auto u0 = std::chrono::steady_clock::now();
-        st = upload_matrix(c, c->ownX.p, X, N, M, ldX, esz);
-        if (st != PARTLS_OK) return st;
-        c->last_upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
-        c->last_upload_bytes = (double)N * (double)M * (double)esz;
-        c->dX = c->ownX.p; c->dy = c->ownY.as<double>(); c->ldX = N;
-    }
+    st = adopt_or_upload(c, X, N, M, ldX, y, x_on_device, x_f32 ? sizeof(float) : sizeof(double));
+    if (st != PARTLS_OK) return st;
     c->x_f32 = x_f32;
 
     // Gram products (fp64 MFMA)
@@ -237,16 +247,8 @@ partls_status ctx_prepare_tableau(partls_ctx *c)
     PARTLS_HIP_CHECK(hipMemcpyAsync(c->hScale.data(), c->scale.p, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
     t_collect(c);
-    // NaN / Inf anywhere in column m of [X y] makes the diagonal Gram entry sum_i z_im^2 non-finite (so does a finite column whose
-    // squares overflow — equally outside the Gram form): M + 2 host compares instead of a separate pass over X, which cost 0.87 ms
-    // of the 4.1 GB read at C4 before the Gram kernel read the same bytes again
-    for (int64_t i = 0; i < M + 2; ++i) {
-        if (i == M) continue;                                    // the ones column
-        if (!std::isfinite(c->hG[(size_t)i * c->ldg + i])) { set_error("X or y contains NaN/Inf (or overflows in X'X)"); return PARTLS_ERR_NONFINITE; }
-    }
-    const double yy = c->hG[(size_t)(M + 1) * c->ldg + (M + 1)];
-    c->tol = c->knobs.tol_rel * std::sqrt(yy > 0.0 ? yy : 0.0);
-    if (!(c->tol > 0.0)) c->tol = 1e-300;
+    if (!gram_diag_finite(c->hG.data(), c->ldg, M)) { set_error("X or y contains NaN/Inf (or overflows in X'X)"); return PARTLS_ERR_NONFINITE; }
+    c->tol = problem_tol(c->knobs.tol_rel, c->hG[(size_t)(M + 1) * c->ldg + (M + 1)]);
     c->prepared = true;
     return PARTLS_OK;
 }

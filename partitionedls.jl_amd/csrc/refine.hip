@@ -1,6 +1,7 @@
 // refine.hip — the data-space half of a fit: passes over X (objective, gradient), the KKT check of a winner and its iterative
 // refinement (final tableau of the node solve, or a host Cholesky of the Gram copy).
 #include "ctx.h"
+#include "prepare_rules.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -124,7 +125,7 @@ double kkt_violation_data(const partls_ctx *c, const std::vector<double> &w, con
     if (worst) *worst = -1;
     for (int m = 0; m <= M; ++m) {
         const double d = h_reg(c, m, m);
-        if (!(d > 0.0) || !(d > 1e-14 * std::fabs(c->hG[(size_t)m * c->ldg + m]))) continue;   // null column: never in any basis
+        if (!column_is_live(d, c->hG[(size_t)m * c->ldg + m])) continue;                       // null column: never in any basis
         const double gs = g[(size_t)m] / (std::sqrt(d) * (ynorm > 0.0 ? ynorm : 1.0));
         const int f = code[(size_t)m];
         double v = 0.0;

@@ -1,11 +1,13 @@
 // resample.hip — partls_opt_weightings (include/partls.h): fit(Opt) under B row weightings of one (X, y, P) in one call — bootstrap
-// replicates, jackknife, repeated splits.  X, y and W go up once; weightings_prep_kernel checks every column and writes sqrt(W);
+// replicates, jackknife, repeated splits.  X, y and W go up once; weight_prep_kernel — the single weighted fit's, one column per
+// blockIdx.y — checks every column and writes sqrt(W); fold_weight_partials (prepare_rules.h) reads its partials as prepare_weights does;
 // launch_gram_weightings — the weighted Gram kernel of a single fit with the weighting as a grid dimension (its summation order: an
 // all-ones column is the unweighted Gram bit for bit) — fills one Gram per problem at the stride launch_prep_batch indexes with E = 1;
 // the problems are then calibrated, prepared, swept and finished by the helpers partls_cv_opt uses (cv.hip: batch_calibrate,
 // batch_sweep, finish_model) — the working context's rows are all N rows with column b of W and of sqrt(W) as its weights — and
 // oob_sse_kernel evaluates every model on the rows its weighting left out.  DESIGN.md §4.10.
 #include "ctx.h"
+#include "prepare_rules.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -45,27 +47,19 @@ static partls_status weightings_run(partls_ctx *c, const double *X, int64_t N, i
     oob_rows.assign((size_t)B, 0);
     int64_t neg_col = -1, zero_col = -1, inf_col = -1;
     for (int64_t b = 0; b < B; ++b) {
-        bool neg = false, bad = false;
-        double sum = 0.0, zeros = 0.0;
-        for (int x = 0; x < nb; ++x) {                            // blocks in index order, as prepare_weights adds them
-            const double *p = c->rsHost.data() + (size_t)4 * ((size_t)b * nb + x);
-            neg = neg || p[0] != 0.0;
-            bad = bad || p[1] != 0.0;
-            sum += p[2];
-            zeros += p[3];
-        }
-        if (bad) { set_error("partls_opt_weightings: weighting %lld contains NaN/Inf", (long long)b); return PARTLS_ERR_NONFINITE; }
-        if (neg && neg_col < 0) neg_col = b;
-        if (!(sum > 0.0) && zero_col < 0) zero_col = b;
-        if (!std::isfinite(sum) && inf_col < 0) inf_col = b;
-        oob_rows[(size_t)b] = (int64_t)zeros;
+        const WeightFold f = fold_weight_partials(c->rsHost.data() + (size_t)4 * nb * b, nb);
+        if (f.nonfinite) { set_error("partls_opt_weightings: weighting %lld contains NaN/Inf", (long long)b); return PARTLS_ERR_NONFINITE; }
+        if (f.negative && neg_col < 0) neg_col = b;
+        if (!(f.sum > 0.0) && zero_col < 0) zero_col = b;
+        if (!std::isfinite(f.sum) && inf_col < 0) inf_col = b;
+        oob_rows[(size_t)b] = f.zero_rows;
     }
     if (inf_col >= 0) { set_error("partls_opt_weightings: the sum of weighting %lld overflows", (long long)inf_col); return PARTLS_ERR_NONFINITE; }
     if (neg_col >= 0) { set_error("partls_opt_weightings: weighting %lld has a negative weight", (long long)neg_col); return PARTLS_ERR_BAD_ARG; }
     if (zero_col >= 0) { set_error("partls_opt_weightings: weighting %lld sums to 0", (long long)zero_col); return PARTLS_ERR_BAD_ARG; }
 
     // ---- one upload of X, y
-    partls_status st = batch_upload(c, X, N, M, ldX, y, x_on_device);
+    partls_status st = adopt_or_upload(c, X, N, M, ldX, y, x_on_device, sizeof(double));
     if (st != PARTLS_OK) return st;
     const double *Xd = static_cast<const double *>(c->dX);
 
@@ -91,14 +85,11 @@ static partls_status weightings_run(partls_ctx *c, const double *X, int64_t N, i
     PARTLS_HIP_CHECK(hipMemcpyAsync(c->cvHostG.data(), Gc, (size_t)B * gs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
     t_collect(c);
-    // NaN / Inf in [X y] (ctx_prepare's test, on every weighting's Gram: a single weighted fit of that column fails the same way)
+    // NaN / Inf in [X y], on every weighting's Gram: a single weighted fit of that column fails the same way
     for (int64_t b = 0; b < B; ++b)
-        for (int64_t i = 0; i < M + 2; ++i) {
-            if (i == M) continue;
-            if (!std::isfinite(c->cvHostG[(size_t)b * gs + (size_t)i * ldg + i])) {
-                set_error("partls_opt_weightings: X or y contains NaN/Inf (or overflows in X'X)");
-                return PARTLS_ERR_NONFINITE;
-            }
+        if (!gram_diag_finite(c->cvHostG.data() + (size_t)b * gs, ldg, M)) {
+            set_error("partls_opt_weightings: X or y contains NaN/Inf (or overflows in X'X)");
+            return PARTLS_ERR_NONFINITE;
         }
 
     // ---- the working context: all N rows under the weights of column b; the visiting order is calibrated on weighting 0
