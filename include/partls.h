@@ -303,6 +303,34 @@ partls_status partls_alt_multistart(partls_ctx *ctx, double eps, int64_t T, int6
                                     double *alpha_all, int64_t ld_alpha_all, double *beta_all, int64_t ld_beta_all,
                                     double *t_all, double *opt_all, int64_t *iters_all, int32_t *status_all);
 
+/* ---- cross-validation of the multistart fit(Alt) over folds x an η grid, and the full-data path, in one call -------
+ * Beyond K = 39 groups fit(Opt) cannot enumerate and fit(Alt) from many starts is the tool; this entry chooses its η.  Data arguments,
+ * folds, grid and problem indexing (B = (F+1) E, q = f E + e, f = F: all rows) are partls_cv_opt_weighted's (w may be NULL); every
+ * problem is prepared with PARTLS_OPT_FAITHFUL_INTERCEPT whatever flags says (PARTLS_OPT_GENERIC_KERNEL is honoured).  eps, T, R,
+ * alpha0 ((M+1) x R, ld_alpha0 >= M+1), beta0 ((K+1) x R, ld_beta0 >= K+1) are partls_alt_multistart's; the SAME R starts are used for
+ * every problem.  Outputs, column q of each (caller-allocated, column-major):
+ *   alpha (ld_alpha >= M), beta (ld_beta >= K), t[q], opt[q], iters[q], best_start[q]: the problem's winner — its smallest final
+ *              Gram-form loss among the PARTLS_OK starts, lowest index on an exact tie — after the ending of partls_alt_prepared on
+ *              exactly the problem's training rows;
+ *   heldout_sse[q]: as partls_cv_opt_weighted (NaN for f = F);
+ *   status[q]: 0, PARTLS_ERR_ILL_CONDITIONED (outputs filled) or PARTLS_ERR_NOT_CONVERGED when no start of the problem finished
+ *              (NaN outputs, iters 0, best_start -1);
+ *   opt_all, iters_all, status_all (each optional, NULL to skip): R x B per-trajectory tables, entry q R + r = start r of problem q, with
+ *              the meanings of partls_alt_multistart (NaN / 0 rows for a failed start).
+ * Any other failure fails the whole call and writes no output; bad arguments (also eps <= 0, T < 1, R < 1, short leading dimensions)
+ * write nothing.  A trajectory's result does not depend on R, on the other η values, on its position in the batch or on the chunking
+ * (PARTLS_ALT_MS_CHUNK), bit for bit.  Register-kernel problems (n <= 288) advance all B R trajectories together; larger ones,
+ * PARTLS_OPT_GENERIC_KERNEL and PARTLS_CV_SERIAL=1 take one problem after another — the same per-trajectory results and the same
+ * winners' models, bit for bit.  Context state afterwards as after partls_cv_opt; partls_get_timing: GRAM, then host wall times of
+ * PREP, SWEEP (the iterations) and FINISH. */
+partls_status partls_cv_alt(partls_ctx *ctx, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w,
+                            int x_on_device, const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F,
+                            const double *eta, int64_t E, uint32_t flags, double eps, int64_t T, int64_t R,
+                            const double *alpha0, int64_t ld_alpha0, const double *beta0, int64_t ld_beta0,
+                            double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t, double *opt, int64_t *iters,
+                            int64_t *best_start, double *heldout_sse, int32_t *status,
+                            double *opt_all, int64_t *iters_all, int32_t *status_all);
+
 /* ---- fit(BnB, X, y, P; η)  — replaces BnB.jl:30-132 -------------------------------------------------------------------
  * Outputs as BnB.jl:36-40; *nopen = nodes bounded (search order differs from the reference's DFS, so it is not a
  * parity quantity). */

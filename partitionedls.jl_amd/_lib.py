@@ -64,6 +64,9 @@ SYMBOLS = [
     ("partls_bnb_prepared", C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _ip]),
     ("partls_alt_multistart", C.c_int, [C.c_void_p, C.c_double, _i64, _i64, _dp, _i64, _dp, _i64, _dp, _dp, _dp, _dp, _ip, _ip,
                                         _dp, _i64, _dp, _i64, _dp, _dp, _ip, C.POINTER(C.c_int32)]),
+    ("partls_cv_alt", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64, _i64, _ip,
+                                _i64, _dp, _i64, C.c_uint32, C.c_double, _i64, _i64, _dp, _i64, _dp, _i64,
+                                _dp, _i64, _dp, _i64, _dp, _dp, _ip, _ip, _dp, C.POINTER(C.c_int32), _dp, _ip, C.POINTER(C.c_int32)]),
     ("partls_bnb_bound", C.c_int, [C.c_void_p, _i64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _dp, C.POINTER(C.c_int32)]),
     ("partls_bnb_snap_begin", C.c_int, [C.c_void_p]),
     ("partls_bnb_bound_snap", C.c_int, [C.c_void_p, _i64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),

@@ -326,28 +326,8 @@ class Context:
         (None or [] for the path only).  weights (host inputs) / dw_ptr (device inputs): optional per-row sample weights
         (partls_cv_opt_weighted).  Returns a dict of column-major results, one problem per column, q = f * E + e: alpha (M x B), beta (K x B),
         t, opt, best_index, heldout_sse, status (all length B)."""
-        wp = None
-        if device_ptrs is None:
-            X, y, P = _inputs(X, y, P, f32=False)
-            N, ldX, on_dev = X.shape[0], X.shape[0], 0
-            if X.shape[1] != P.shape[0]:
-                raise ValueError("DimensionMismatch: X is %s, P is %s" % (X.shape, P.shape))
-            w = _weights(weights, N)
-            xp, yp, wp = X.ctypes.data, y.ctypes.data, None if w is None else w.ctypes.data
-        else:
-            if weights is not None:
-                raise ValueError("cv_opt: device inputs take their weights as the fifth entry of device_ptrs")
-            P = np.asfortranarray(P, dtype=np.int64)
-            dX, dy, N, ldX = device_ptrs[:4]
-            xp, yp, on_dev = C.c_void_p(dX), C.c_void_p(dy), 1
-            if len(device_ptrs) > 4 and device_ptrs[4] is not None:
-                wp = C.c_void_p(device_ptrs[4])
+        keep, xp, yp, wp, on_dev, N, ldX, P, fp, F, et, E, B = self._cv_inputs("cv_opt", X, y, P, fold_ptr, etas, device_ptrs, weights)
         M, K = P.shape
-        fp = np.ascontiguousarray([] if fold_ptr is None else fold_ptr, dtype=np.int64)
-        F = max(len(fp) - 1, 0)
-        et = np.ascontiguousarray(np.atleast_1d(etas), dtype=np.float64)
-        E = len(et)
-        B = (F + 1) * max(E, 1)
         alpha = np.zeros((M, B), order="F")
         beta = np.zeros((K, B), order="F")
         t = np.zeros(B); opt = np.zeros(B); sse = np.zeros(B)
@@ -362,6 +342,59 @@ class Context:
         else:
             _check(L.lib().partls_cv_opt_weighted(*head, wp, *tail))
         return dict(alpha=alpha, beta=beta, t=t, opt=opt, best_index=bi, heldout_sse=sse, status=stat, F=F, E=E)
+
+    @staticmethod
+    def _cv_inputs(who, X, y, P, fold_ptr, etas, device_ptrs, weights):
+        """the marshalling cv_opt and cv_alt share: (arrays to keep alive, X / y / w pointers, x_on_device, N, ldX, P, fold_ptr, F, etas, E, B)"""
+        wp = None
+        keep = None
+        if device_ptrs is None:
+            X, y, P = _inputs(X, y, P, f32=False)
+            N, ldX, on_dev = X.shape[0], X.shape[0], 0
+            if X.shape[1] != P.shape[0]:
+                raise ValueError("DimensionMismatch: X is %s, P is %s" % (X.shape, P.shape))
+            w = _weights(weights, N)
+            keep = (X, y, w)
+            xp, yp, wp = X.ctypes.data, y.ctypes.data, None if w is None else w.ctypes.data
+        else:
+            if weights is not None:
+                raise ValueError("%s: device inputs take their weights as the fifth entry of device_ptrs" % who)
+            P = np.asfortranarray(P, dtype=np.int64)
+            dX, dy, N, ldX = device_ptrs[:4]
+            xp, yp, on_dev = C.c_void_p(dX), C.c_void_p(dy), 1
+            if len(device_ptrs) > 4 and device_ptrs[4] is not None:
+                wp = C.c_void_p(device_ptrs[4])
+        fp = np.ascontiguousarray([] if fold_ptr is None else fold_ptr, dtype=np.int64)
+        F = max(len(fp) - 1, 0)
+        et = np.ascontiguousarray(np.atleast_1d(etas), dtype=np.float64)
+        E = len(et)
+        return keep, xp, yp, wp, on_dev, N, ldX, P, fp, F, et, E, (F + 1) * max(E, 1)
+
+    def cv_alt(self, X, y, P, fold_ptr, etas, alpha0s, beta0s, eps=1e-6, T=100, device_ptrs=None, weights=None, flags=0):
+        """partls_cv_alt: the multistart fit(Alt) on every (fold, η) training set and on all rows, in one call; inputs as
+        cv_opt, starts as alt_multistart — alpha0s (R, M+1), beta0s (R, K+1), the same R starts for every problem.  Returns cv_opt's dict
+        with best_start in place of best_index, plus iters (B) and starts = dict(opt, iters, status), each (B, R): row q = f * E + e,
+        column r = start r (meanings: alt_multistart)."""
+        keep, xp, yp, wp, on_dev, N, ldX, P, fp, F, et, E, B = self._cv_inputs("cv_alt", X, y, P, fold_ptr, etas, device_ptrs, weights)
+        M, K = P.shape
+        a0 = np.ascontiguousarray(alpha0s, dtype=np.float64); b0 = np.ascontiguousarray(beta0s, dtype=np.float64)
+        if a0.ndim != 2 or b0.ndim != 2 or a0.shape[1] != M + 1 or b0.shape[1] != K + 1 or a0.shape[0] != b0.shape[0]:
+            raise ValueError("cv_alt: alpha0s must be (R, %d) and beta0s (R, %d), got %s and %s" % (M + 1, K + 1, a0.shape, b0.shape))
+        R = a0.shape[0]
+        nR = max(R, 1)
+        alpha = np.zeros((M, B), order="F")
+        beta = np.zeros((K, B), order="F")
+        t = np.zeros(B); opt = np.zeros(B); sse = np.zeros(B)
+        it = np.zeros(B, dtype=np.int64); bs = np.zeros(B, dtype=np.int64)
+        stat = np.zeros(B, dtype=np.int32)
+        oa = np.zeros((B, nR)); ia = np.zeros((B, nR), dtype=np.int64); sa = np.zeros((B, nR), dtype=np.int32)
+        self.generation += 1
+        _check(L.lib().partls_cv_alt(self._h, xp, int(N), int(M), int(ldX), yp, wp, on_dev, P.ctypes.data, K, M, _ip(fp) if F else None, F,
+                                     _dp(et), E, int(flags), float(eps), int(T), R, _dp(a0), M + 1, _dp(b0), K + 1,
+                                     _dp(alpha), M, _dp(beta), K, _dp(t), _dp(opt), _ip(it), _ip(bs), _dp(sse), _i32p(stat),
+                                     _dp(oa), _ip(ia), _i32p(sa)))
+        return dict(alpha=alpha, beta=beta, t=t, opt=opt, iters=it, best_start=bs, heldout_sse=sse, status=stat, F=F, E=E,
+                    starts=dict(opt=oa, iters=ia, status=sa))
 
     def opt_weightings(self, X, y, P, W, eta=0.0, flags=0, device_ptrs=None, oob=True):
         """partls_opt_weightings: fit(Opt) under every column of W (N x B row weightings: bootstrap counts, 0/1 masks, any weights
@@ -1027,7 +1060,8 @@ class CVResult:
     """What cross_validate returns.  sse / mse: F x E held-out sums / means of squared errors; mse_mean[e] = sum_f sse[f, e] / N (pooled);
     with sample weights, sse is weighted and the means divide by the weight of the fold / of all rows instead of the row counts;
     best_eta: argmin of mse_mean over the η values whose problems all succeeded (first on ties); models[f][e] the training fits, path[e]
-    the full-data fits, model = path at best_eta; status[f][e] (F+1 rows: the last is the path) and ill_conditioned (status 9)."""
+    the full-data fits, model = path at best_eta; status[f][e] (F+1 rows: the last is the path) and ill_conditioned (status 9).
+    best_index: the winning patterns of Opt (None for Alt); iters, best_start, starts: cross_validate(Alt) only (see there)."""
     etas: np.ndarray
     folds: list
     fold_ptr: np.ndarray
@@ -1044,27 +1078,48 @@ class CVResult:
     best_index: np.ndarray
     status: np.ndarray
     ill_conditioned: np.ndarray
+    iters: np.ndarray = None               # Alt: completed iterations of every problem's winner
+    best_start: np.ndarray = None          # Alt: every problem's winning start (-1: none finished)
+    starts: object = None                  # Alt: Report(opt, iters, status), each [F+1, E, R]
 
 
 def cross_validate(alg, X, y, P, *, η=None, eta=None, nfolds=5, shuffle=False, rng=None, faithful_intercept=False, device=0,
-                   on_ill_conditioned="warn", generic_kernel=False, weights=None):
-    """K-fold cross-validation of fit(Opt) over an η grid, plus the full-data path, in one device call (partls_cv_opt).
+                   on_ill_conditioned="warn", generic_kernel=False, weights=None, restarts=None, alpha0=None, beta0=None, ϵ=None, eps=None,
+                   T=100):
+    """K-fold cross-validation of fit(Opt) — or of the multistart fit(Alt) — over an η grid, plus the full-data path, in one device
+    call (partls_cv_opt, partls_cv_alt).
 
     η/eta: the grid (default [0.0]); nfolds: F (0: the path only); shuffle / rng: rows permuted on the host first (CVResult.perm).
     Problem (f, e) is fit(Opt, X[train_f], y[train_f], P; η = η[e]) with train_f every row outside fold f in order.
     on_ill_conditioned: "warn" (default) keeps status-9 models and warns once, "raise" raises PartlsError(9).
     weights: optional per-row sample weights (as fit; permuted with the rows by shuffle): problem (f, e) is the weighted fit on train_f,
-    sse[f, e] = sum over fold f of w_i r_i^2, mse[f, e] = sse[f, e] / (weight of fold f), mse_mean[e] = sum_f sse[f, e] / sum_i w_i."""
-    if alg is not Opt:
-        raise TypeError("cross_validate: only Opt is supported")
+    sse[f, e] = sum over fold f of w_i r_i^2, mse[f, e] = sse[f, e] / (weight of fold f), mse_mean[e] = sum_f sse[f, e] / sum_i w_i.
+    Alt (the tool beyond K = 39 groups): problem (f, e) is fit(Alt, X[train_f], y[train_f], P; η = η[e], restarts=R, ϵ, T)
+    from the SAME R starts for every problem — restarts=R draws them (default 32), alpha0 (R, M+1) with beta0 (R, K+1) gives them; rules
+    and ValueErrors of fit.  One generator made from rng is consumed first by the shuffle permutation and then by R successive single
+    draws.  CVResult then carries iters, best_start ([F+1, E]) and starts = Report(opt, iters, status), each [F+1, E, R]; best_index is
+    None.  restarts or starts with Opt: ValueError."""
+    if alg not in (Opt, Alt):
+        raise TypeError("cross_validate: only Opt and Alt are supported")
+    if alg is Opt and (restarts is not None or alpha0 is not None or beta0 is not None):
+        raise ValueError("cross_validate: restarts, alpha0 and beta0 are options of Alt")
     if on_ill_conditioned not in ("warn", "raise"):
         raise ValueError('on_ill_conditioned must be "warn" or "raise"')
     grid = [0.0] if (η is None and eta is None) else (η if η is not None else eta)
     etas = np.ascontiguousarray(np.atleast_1d(np.asarray(grid, dtype=np.float64)))
     Xf, yf, Pf = _fit_inputs(X, y, P)
     N, M = Xf.shape
+    K = Pf.shape[1]
     wf = _weights(weights, N, "cross_validate")
+    if alg is Alt:
+        rng = _generator(rng)                                # one generator: the permutation first, then the starts
     fold_ptr, perm = cv_folds(N, nfolds, shuffle, rng)
+    starts = None
+    if alg is Alt:
+        if restarts is None and 2 not in [np.ndim(v) for v in (alpha0, beta0) if v is not None]:
+            restarts = 32
+        starts = _alt_starts(Alt, M, K, restarts, alpha0, beta0, rng)
+        eps_v = 1e-6 if (ϵ is None and eps is None) else float(ϵ if ϵ is not None else eps)
     if shuffle:
         Xf = np.asfortranarray(Xf[perm])
         yf = np.ascontiguousarray(yf[perm])
@@ -1078,7 +1133,15 @@ def cross_validate(alg, X, y, P, *, η=None, eta=None, nfolds=5, shuffle=False, 
     E = len(etas)
     flags = (L.OPT_FAITHFUL_INTERCEPT if faithful_intercept else 0) | (L.OPT_GENERIC_KERNEL if generic_kernel else 0)
     ctx = default_context(device)
-    r = ctx.cv_opt(Xf, yf, Pf, fold_ptr if F else None, etas, flags, weights=wf)
+    if alg is Opt:
+        r = ctx.cv_opt(Xf, yf, Pf, fold_ptr if F else None, etas, flags, weights=wf)
+        extra = dict(best_index=r["best_index"].reshape(F + 1, E).copy())
+    else:
+        r = ctx.cv_alt(Xf, yf, Pf, fold_ptr if F else None, etas, starts[0], starts[1], eps_v, int(T), weights=wf,
+                       flags=L.OPT_GENERIC_KERNEL if generic_kernel else 0)
+        per = {k: np.asarray(v).reshape(F + 1, E, -1).copy() for k, v in r["starts"].items()}
+        extra = dict(best_index=None, iters=r["iters"].reshape(F + 1, E).copy(), best_start=r["best_start"].reshape(F + 1, E).copy(),
+                     starts=Report(**per))
     st = r["status"].reshape(F + 1, E)
     if on_ill_conditioned == "raise" and np.any(st == L.ERR_ILL_CONDITIONED):
         raise PartlsError(L.ERR_ILL_CONDITIONED, "a cross-validation problem failed its data-space KKT check")
@@ -1114,8 +1177,7 @@ def cross_validate(alg, X, y, P, *, η=None, eta=None, nfolds=5, shuffle=False, 
     folds = [perm[fold_ptr[f]:fold_ptr[f + 1]] for f in range(F)]
     return CVResult(etas=etas, folds=folds, fold_ptr=fold_ptr, perm=perm, sse=sse, mse=mse, mse_mean=mse_mean, best_eta=best_eta,
                     best_index_eta=be, models=models, path=path, model=path[be] if be >= 0 else None,
-                    opt=r["opt"].reshape(F + 1, E).copy(), best_index=r["best_index"].reshape(F + 1, E).copy(), status=st.copy(),
-                    ill_conditioned=(st == L.ERR_ILL_CONDITIONED))
+                    opt=r["opt"].reshape(F + 1, E).copy(), status=st.copy(), ill_conditioned=(st == L.ERR_ILL_CONDITIONED), **extra)
 
 
 @dataclass

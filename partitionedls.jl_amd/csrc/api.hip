@@ -60,7 +60,7 @@ using namespace partls;
 
 extern "C" {
 
-int partls_version(void) { return 104; }
+int partls_version(void) { return 105; }
 const char *partls_last_error(void) { return g_err; }
 
 int partls_device_count(void)

@@ -200,6 +200,11 @@ hipError_t launch_alt_beta_system(const double *G, int ldg, int M, double eta, c
 // ... of `cnt` starts at once: start j reads a + slot[j] (M + 1), writes GA + j (M + 1) Kp and Hg + j Kp (Kp + 1)   (misc.hip)
 hipError_t launch_alt_beta_system_batch(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, const double *a, int Kp,
                                         const int *slot, int cnt, double *GA, double *Hg, hipStream_t s);
+// ... of starts of different problems of a batch (partls_cv_alt): start j belongs to problem q = q0 + prob[j] (device array) and reads the
+// Gram G + (q / E) gstride with eta[q % E] (device array), the indexing of launch_prep_batch; summed exactly as above
+hipError_t launch_alt_beta_system_problems(const double *G, int64_t gstride, int E, int64_t q0, const double *eta, const int *prob, int ldg,
+                                           int M, const uint64_t *mask_aug, const double *a, int Kp, const int *slot, int cnt, double *GA,
+                                           double *Hg, hipStream_t s);
 // wt (optional, device, N): sample weights -> sum_i wt[i] (...)^2
 hipError_t launch_residual(const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w, double t,
                            double *partial, int nblocks, double *yhat, hipStream_t s, const double *wt = nullptr, bool x_f32 = false);

@@ -340,6 +340,16 @@ struct ProblemBatch {
     std::function<partls_status(int64_t q, int64_t bpat, int64_t unconv)> finish;
 };
 partls_status make_internal(partls_ctx *c, partls_ctx **slot);
+// ---- what partls_cv_opt and partls_cv_alt (cv_alt.hip) share of a cross-validation call
+// the checks of the inputs (not of the outputs or of an entry's own options); who: the entry's name in the messages
+partls_status cv_check_inputs(const char *who, partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
+                              const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F, const double *eta, int64_t E);
+// batch_reset, the weights, the one upload, cv_work and one row view per fold, one Gram per fold and the combined training Grams:
+// c->cvG = [max(F, 1) fold Grams | F + 1 training Grams] at stride ldg^2 (the last is all rows'), c->cvHostG = host copy of the latter
+partls_status cv_grams(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w, int x_on_device,
+                       int64_t K, const int64_t *fold_ptr, int64_t F, uint32_t flags, const char *who, int *ldg_out, int *chunks_out);
+// W's data passes cover the training rows of fold f (f == F: all rows): its own rows are the first training fold, the others its peers
+void cv_point_rows(partls_ctx *c, partls_ctx *W, const int64_t *fold_ptr, int64_t F, int64_t f);
 // c forgets its prepared problem (forget_problem), zeroes every timer and takes the shape of the batch's
 void batch_reset(partls_ctx *c, int64_t N, int64_t M, int64_t K, uint32_t flags);
 // cv_work takes the batch's shape, partition and Gram layout, is prepared for Gram `cal_gram` at eta[0] with its rows set by
@@ -365,6 +375,42 @@ partls_status solve_nodes(partls_ctx *c, const std::vector<int8_t> &codes, size_
 // vetoes, -), zeroed by the caller.  Grid and scratch as solve_nodes; never the cooperative kernel; always from the fresh tableau.
 partls_status solve_nodes_device(partls_ctx *c, size_t cnt, const int8_t *code, double *obj2, double *sol,
                                  unsigned long long *counters, int max_rounds);
+// ... for ANOTHER problem of the context's shape, partition and kernel (partls_cv_alt): its tile-cyclic tableau T0reg (device) and its
+// tolerance instead of the context's.  Register-kernel contexts only.
+partls_status solve_nodes_device_at(partls_ctx *c, const double *T0reg, double tol, size_t cnt, const int8_t *code, double *obj2,
+                                    double *sol, unsigned long long *counters, int max_rounds);
+
+// ---- the multistart of fit(Alt) (alt_multi.hip), for one problem or for a batch of them
+// B problems of the context's shape at the strides of launch_prep_batch / launch_layout_reg_batch: problem p of the piece is problem
+// q0 + p of the whole batch and reads the Gram G + ((q0 + p) / E) gs with eta[(q0 + p) % E]
+struct AltProblems {
+    int64_t B = 1, E = 1, q0 = 0;
+    const double *G = nullptr;                     // device
+    int64_t gs = 0;
+    const double *eta = nullptr;                   // device, E values
+    const double *scale = nullptr;                 // device, B x n
+    const double *T0reg = nullptr;                 // device, B x t0d
+    size_t t0d = 0;
+    const double *tol = nullptr;                   // HOST, B
+    const double *yy = nullptr;                    // device, B: y'y of each problem's regularised Gram
+};
+// per-slot tables, slot = problem R + start (each optional); meanings: partls_alt_multistart
+struct AltTables {
+    double *alpha_all; int64_t ld_alpha_all; double *beta_all; int64_t ld_beta_all;
+    double *t_all, *opt_all; int64_t *iters_all; int32_t *status_all;
+};
+// a problem's best start (-1: none finished) and what alt_finish needs of it
+struct AltWinner {
+    int64_t start = -1, iters = 0;
+    double opt = 0.0;
+    std::vector<double> a, b, wv, hdiag;
+    std::vector<int8_t> vcode;
+};
+// pp == nullptr: the context's prepared problem (any kernel); else pp's B problems together (register-kernel context prepared for one
+// of them).  Start r of every problem begins at row r of alpha0 / beta0.  win: B winners.  No ending: the caller runs alt_finish.
+partls_status alt_multistart_core(partls_ctx *c, const AltProblems *pp, double eps, int64_t T, int64_t R,
+                                  const double *alpha0, int64_t ld_alpha0, const double *beta0, int64_t ld_beta0,
+                                  const AltTables &tb, AltWinner *win);
 // the ending of fit(Alt) (solvers.hip)
 partls_status alt_finish(partls_ctx *c, const std::vector<double> &a, const std::vector<double> &b, const std::vector<double> &wv,
                          const std::vector<int8_t> &vcode_last, const std::vector<double> &hdiag, const std::vector<double> &gersh,

@@ -49,7 +49,7 @@ partls_status make_internal(partls_ctx *c, partls_ctx **slot)
 
 // the working context sees the training rows of problem fold f (f == F: all rows): its own rows are the first training fold, the
 // other training folds are its peers (data_pass, refine.hip, sums context then peers in order)
-static void point_rows(partls_ctx *c, partls_ctx *W, const int64_t *fold_ptr, int64_t F, int64_t f)
+void cv_point_rows(partls_ctx *c, partls_ctx *W, const int64_t *fold_ptr, int64_t F, int64_t f)
 {
     W->peers.clear();
     W->ldX = c->ldX;
@@ -124,7 +124,7 @@ void model_weights(const partls_ctx *work, const CvOut &o, int64_t q, double *w)
 static partls_status finish_one(partls_ctx *c, partls_ctx *W, const int64_t *fold_ptr, int64_t F, int64_t f, int64_t q, int64_t bpat,
                                 int64_t unconv, CvOut &o)
 {
-    if (bpat >= 0) point_rows(c, W, fold_ptr, F, f);
+    if (bpat >= 0) cv_point_rows(c, W, fold_ptr, F, f);
     const partls_status st = finish_model(c, q, bpat, unconv, o);
     W->peers.clear();
     if (st != PARTLS_OK) return st;
@@ -297,9 +297,8 @@ partls_status batch_sweep(partls_ctx *c, const ProblemBatch &pb)
     return PARTLS_OK;
 }
 
-static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w,
-                            int x_on_device, const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F, const double *eta,
-                            int64_t E, uint32_t flags, CvOut &o)
+partls_status cv_grams(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w, int x_on_device,
+                       int64_t K, const int64_t *fold_ptr, int64_t F, uint32_t flags, const char *who, int *ldg_out, int *chunks_out)
 {
     const int nf = F > 0 ? (int)F : 1;
     PARTLS_HIP_CHECK(hipSetDevice(c->device));
@@ -319,7 +318,6 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
     // ---- internal contexts: the working context and one row view per fold
     st = make_internal(c, &c->cv_work);
     if (st != PARTLS_OK) return st;
-    partls_ctx *W = c->cv_work;
     if (c->cv_view.size() < (size_t)F) c->cv_view.resize((size_t)F, nullptr);
     for (int64_t g = 0; g < F; ++g) {
         st = make_internal(c, &c->cv_view[(size_t)g]);
@@ -359,25 +357,61 @@ static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M
     t_collect(c);
     // NaN / Inf in [X y]: the all-rows Gram decides (its diagonal is the sum of the folds' non-negative diagonals)
     if (!gram_diag_finite(c->cvHostG.data() + (size_t)F * gs, ldg, M)) {
-        set_error("partls_cv_opt: X or y contains NaN/Inf (or overflows in X'X)");
+        set_error("%s: X or y contains NaN/Inf (or overflows in X'X)", who);
         return PARTLS_ERR_NONFINITE;
     }
     // weighted: every training set needs weight (its ones-column entry is sum_i s_i^2 over its rows)
     if (c->ds)
         for (int64_t f = 0; f < F; ++f)
             if (!(c->cvHostG[(size_t)f * gs + (size_t)M * ldg + M] > 0.0)) {
-                set_error("partls_cv_opt_weighted: the training rows of fold %lld have zero total weight", (long long)f);
+                set_error("%s: the training rows of fold %lld have zero total weight", who, (long long)f);
                 return PARTLS_ERR_BAD_ARG;
             }
+    *ldg_out = ldg; *chunks_out = chunks;
+    return PARTLS_OK;
+}
+
+static partls_status cv_run(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w,
+                            int x_on_device, const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F, const double *eta,
+                            int64_t E, uint32_t flags, CvOut &o)
+{
+    int ldg = 0, chunks = 0;
+    partls_status st = cv_grams(c, X, N, M, ldX, y, w, x_on_device, K, fold_ptr, F, flags, "partls_cv_opt", &ldg, &chunks);
+    if (st != PARTLS_OK) return st;
+    partls_ctx *W = c->cv_work;
+    const int64_t gs = (int64_t)ldg * ldg;
+    const double *Gc = c->cvG.as<double>() + (size_t)(F > 0 ? F : 1) * gs;
 
     // ---- the working context: prepared first for the full-data problem at eta[0], on which the visiting order is calibrated
     ProblemBatch pb;
     pb.B = (F + 1) * E; pb.E = E; pb.eta = eta; pb.G = Gc; pb.hostG = c->cvHostG.data(); pb.gs = gs;
     pb.serial = c->knobs.cv_serial; pb.who = "partls_cv_opt";
     pb.finish = [&](int64_t q, int64_t bpat, int64_t unconv) { return finish_one(c, W, fold_ptr, F, q / E, q, bpat, unconv, o); };
-    st = batch_calibrate(c, P, ldP, flags, ldg, chunks, pb, F, [&](partls_ctx *Wc) { point_rows(c, Wc, fold_ptr, F, F); });
+    st = batch_calibrate(c, P, ldP, flags, ldg, chunks, pb, F, [&](partls_ctx *Wc) { cv_point_rows(c, Wc, fold_ptr, F, F); });
     if (st != PARTLS_OK) return st;
     return batch_sweep(c, pb);
+}
+
+// the input checks partls_cv_opt and partls_cv_alt share (everything but their outputs and their own options)
+partls_status cv_check_inputs(const char *who, partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
+                              const int64_t *P, int64_t K, int64_t ldP, const int64_t *fold_ptr, int64_t F, const double *eta, int64_t E)
+{
+    partls_status st = check_common(c, X, N, M, ldX, P, K, ldP);
+    if (st != PARTLS_OK) return st;
+    if (!y) { set_error("%s: y is NULL", who); return PARTLS_ERR_BAD_ARG; }
+    if (F < 0 || F == 1) { set_error("%s: F = %lld folds (need F = 0 for the path only, or F >= 2)", who, (long long)F); return PARTLS_ERR_BAD_ARG; }
+    if (F > 0) {
+        if (!fold_ptr) { set_error("%s: fold_ptr is NULL", who); return PARTLS_ERR_BAD_ARG; }
+        if (F > N) { set_error("%s: F = %lld folds for N = %lld rows", who, (long long)F, (long long)N); return PARTLS_ERR_BAD_ARG; }
+        if (fold_ptr[0] != 0 || fold_ptr[F] != N) { set_error("%s: fold_ptr must start at 0 and end at N", who); return PARTLS_ERR_BAD_ARG; }
+        for (int64_t g = 0; g < F; ++g)
+            if (!(fold_ptr[g] < fold_ptr[g + 1])) { set_error("%s: fold_ptr must be strictly increasing (fold %lld)", who, (long long)g); return PARTLS_ERR_BAD_ARG; }
+    }
+    if (E < 1 || !eta) { set_error("%s: need E >= 1 eta values", who); return PARTLS_ERR_BAD_ARG; }
+    for (int64_t e = 0; e < E; ++e)
+        if (!(eta[e] >= 0.0) || !std::isfinite(eta[e])) { set_error("%s: eta[%lld] = %g must be finite and >= 0", who, (long long)e, eta[e]); return PARTLS_ERR_BAD_ARG; }
+    if ((F + 1) > ((int64_t)1 << 40) / E) { set_error("%s: too many problems", who); return PARTLS_ERR_BAD_ARG; }
+    return PARTLS_OK;
 }
 
 }  // namespace partls
@@ -390,23 +424,10 @@ static partls_status cv_opt(partls_ctx *c, const double *X, int64_t N, int64_t M
                             double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t, double *opt,
                             int64_t *best_index, double *heldout_sse, int32_t *status)
 {
-    partls_status st = check_common(c, X, N, M, ldX, P, K, ldP);
+    partls_status st = cv_check_inputs("partls_cv_opt", c, X, N, M, ldX, y, P, K, ldP, fold_ptr, F, eta, E);
     if (st != PARTLS_OK) return st;
-    if (!y) { set_error("partls_cv_opt: y is NULL"); return PARTLS_ERR_BAD_ARG; }
-    if (F < 0 || F == 1) { set_error("partls_cv_opt: F = %lld folds (need F = 0 for the path only, or F >= 2)", (long long)F); return PARTLS_ERR_BAD_ARG; }
-    if (F > 0) {
-        if (!fold_ptr) { set_error("partls_cv_opt: fold_ptr is NULL"); return PARTLS_ERR_BAD_ARG; }
-        if (F > N) { set_error("partls_cv_opt: F = %lld folds for N = %lld rows", (long long)F, (long long)N); return PARTLS_ERR_BAD_ARG; }
-        if (fold_ptr[0] != 0 || fold_ptr[F] != N) { set_error("partls_cv_opt: fold_ptr must start at 0 and end at N"); return PARTLS_ERR_BAD_ARG; }
-        for (int64_t g = 0; g < F; ++g)
-            if (!(fold_ptr[g] < fold_ptr[g + 1])) { set_error("partls_cv_opt: fold_ptr must be strictly increasing (fold %lld)", (long long)g); return PARTLS_ERR_BAD_ARG; }
-    }
-    if (E < 1 || !eta) { set_error("partls_cv_opt: need E >= 1 eta values"); return PARTLS_ERR_BAD_ARG; }
-    for (int64_t e = 0; e < E; ++e)
-        if (!(eta[e] >= 0.0) || !std::isfinite(eta[e])) { set_error("partls_cv_opt: eta[%lld] = %g must be finite and >= 0", (long long)e, eta[e]); return PARTLS_ERR_BAD_ARG; }
     if (!alpha || !beta || !t || !opt || !best_index || !heldout_sse || !status) { set_error("partls_cv_opt: NULL output"); return PARTLS_ERR_BAD_ARG; }
     if (ld_alpha < M || ld_beta < K) { set_error("partls_cv_opt: leading dimension of alpha / beta too small"); return PARTLS_ERR_BAD_ARG; }
-    if ((F + 1) > ((int64_t)1 << 40) / E) { set_error("partls_cv_opt: too many problems"); return PARTLS_ERR_BAD_ARG; }
     if ((flags & PARTLS_OPT_FAITHFUL_INTERCEPT ? K + 1 : K) > 40) {
         set_error("partls_cv_opt: K = %lld: the enumeration of fit(Opt) is out of range (K <= 39)", (long long)K);
         return PARTLS_ERR_UNSUPPORTED;

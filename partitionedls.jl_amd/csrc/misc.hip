@@ -350,12 +350,24 @@ hipError_t launch_pattern_gather(const double *in, int64_t npat, int kbits, cons
 // kernel at D = 512 — latency of 513 dependent steps.)
 static constexpr int ALT_WAVES = 16;
 
+// PP (partls_cv_alt): start blockIdx.y belongs to problem q = pp.q0 + pp.prob[blockIdx.y] of a batch and reads that
+// problem's Gram G + (q / E) gstride with eta[q % E]; nothing else differs, and the PP = false instantiation ignores pp altogether.
+struct AltProblemOf { const int *prob; int64_t q0, gstride; int E; const double *eta; };
+#define ALT_PROBLEM_OPERANDS()                                                                                                        \
+    if constexpr (PP) {                                                                                                               \
+        const int64_t q = pp.q0 + pp.prob[blockIdx.y];                                                                                \
+        G += (q / pp.E) * pp.gstride;                                                                                                 \
+        eta = pp.eta[q % pp.E];                                                                                                       \
+    }
+
+template <bool PP>
 __global__ __launch_bounds__(64 * ALT_WAVES) void alt_ga_kernel(const double *__restrict__ G, int ldg, int M, double eta,
                                                                const uint64_t *__restrict__ mask_aug, const double *__restrict__ a, int Kp,
-                                                               double *__restrict__ GA, const int *__restrict__ slot)
+                                                               double *__restrict__ GA, const int *__restrict__ slot, AltProblemOf pp)
 {
     __shared__ double part[ALT_WAVES][64];
     const int m = blockIdx.x, k2 = threadIdx.x & 63, wave = threadIdx.x >> 6, Mp = M + 1;
+    ALT_PROBLEM_OPERANDS()
     if (slot) { a += (size_t)slot[blockIdx.y] * Mp; GA += (size_t)blockIdx.y * Mp * Kp; }      // start blockIdx.y of a batch (see below)
     // branch-free and unrolled: the loads of a step are wave-uniform (row m of G, alpha and the mask of variable m2), eight steps
     // are in flight together; a lane adds the product when variable m2 belongs to ITS group
@@ -385,12 +397,14 @@ __global__ __launch_bounds__(64 * ALT_WAVES) void alt_ga_kernel(const double *__
     }
 }
 
+template <bool PP>
 __global__ __launch_bounds__(64 * ALT_WAVES) void alt_h_kernel(const double *__restrict__ G, int ldg, int M, double eta,
                                                               const uint64_t *__restrict__ mask_aug, const double *__restrict__ a, int Kp,
                                                               const double *__restrict__ GA, double *__restrict__ Hg,
-                                                              const int *__restrict__ slot)
+                                                              const int *__restrict__ slot, AltProblemOf pp)
 {
     __shared__ double part[ALT_WAVES][65];
+    ALT_PROBLEM_OPERANDS()
     if (slot) { a += (size_t)slot[blockIdx.y] * (M + 1); GA += (size_t)blockIdx.y * (M + 1) * Kp; Hg += (size_t)blockIdx.y * Kp * (Kp + 1); }
     const int k = blockIdx.x, k2 = threadIdx.x & 63, wave = threadIdx.x >> 6, Mp = M + 1;     // column Kp of row k holds g[k] (Kp <= 64: lane Kp <= 64 ... handled by lane 63 when Kp == 64)
     // lanes 0..Kp-1: H[k][k2]; the g column is computed by lane Kp when Kp < 64, else by a second pass of lane 0
@@ -422,29 +436,49 @@ __global__ __launch_bounds__(64 * ALT_WAVES) void alt_h_kernel(const double *__r
 hipError_t launch_alt_beta_system(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, const double *a, int Kp,
                                   double *GA, double *Hg, hipStream_t s)
 {
-    hipLaunchKernelGGL(alt_ga_kernel, dim3(M + 1), dim3(64 * ALT_WAVES), 0, s, G, ldg, M, eta, mask_aug, a, Kp, GA, (const int *)nullptr);
+    hipLaunchKernelGGL(alt_ga_kernel<false>, dim3(M + 1), dim3(64 * ALT_WAVES), 0, s, G, ldg, M, eta, mask_aug, a, Kp, GA, (const int *)nullptr,
+                       AltProblemOf{});
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(alt_h_kernel, dim3(Kp), dim3(64 * ALT_WAVES), 0, s, G, ldg, M, eta, mask_aug, a, Kp, GA, Hg, (const int *)nullptr);
+    hipLaunchKernelGGL(alt_h_kernel<false>, dim3(Kp), dim3(64 * ALT_WAVES), 0, s, G, ldg, M, eta, mask_aug, a, Kp, GA, Hg, (const int *)nullptr,
+                       AltProblemOf{});
     return hipGetLastError();
 }
 
 // The same for `cnt` starts at once (partls_alt_multistart): start j of the batch = blockIdx.y reads alpha from a + slot[j] (M + 1) and
 // writes GA + j (M + 1) Kp and Hg + j Kp (Kp + 1).  Every start is summed exactly as a single one is: same workgroup shape, same orders.
-hipError_t launch_alt_beta_system_batch(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, const double *a, int Kp,
-                                        const int *slot, int cnt, double *GA, double *Hg, hipStream_t s)
+template <bool PP>
+static hipError_t alt_beta_system_batch(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, const double *a, int Kp,
+                                        const int *slot, int cnt, double *GA, double *Hg, AltProblemOf pp, hipStream_t s)
 {
     for (int j0 = 0; j0 < cnt; j0 += 65535) {                     // gridDim.y <= 65535
         const int nb = cnt - j0 < 65535 ? cnt - j0 : 65535;
         double *ga = GA + (size_t)j0 * (M + 1) * Kp, *hg = Hg + (size_t)j0 * Kp * (Kp + 1);
-        hipLaunchKernelGGL(alt_ga_kernel, dim3(M + 1, nb), dim3(64 * ALT_WAVES), 0, s, G, ldg, M, eta, mask_aug, a, Kp, ga, slot + j0);
+        AltProblemOf pj = pp;
+        if (PP) pj.prob += j0;
+        hipLaunchKernelGGL(alt_ga_kernel<PP>, dim3(M + 1, nb), dim3(64 * ALT_WAVES), 0, s, G, ldg, M, eta, mask_aug, a, Kp, ga, slot + j0, pj);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(alt_h_kernel, dim3(Kp, nb), dim3(64 * ALT_WAVES), 0, s, G, ldg, M, eta, mask_aug, a, Kp, ga, hg, slot + j0);
+        hipLaunchKernelGGL(alt_h_kernel<PP>, dim3(Kp, nb), dim3(64 * ALT_WAVES), 0, s, G, ldg, M, eta, mask_aug, a, Kp, ga, hg, slot + j0, pj);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+hipError_t launch_alt_beta_system_batch(const double *G, int ldg, int M, double eta, const uint64_t *mask_aug, const double *a, int Kp,
+                                        const int *slot, int cnt, double *GA, double *Hg, hipStream_t s)
+{
+    return alt_beta_system_batch<false>(G, ldg, M, eta, mask_aug, a, Kp, slot, cnt, GA, Hg, AltProblemOf{}, s);
+}
+
+// ... of starts that belong to different problems of a batch (partls_cv_alt): start j is of problem q0 + prob[j], which reads the Gram
+// G + (q / E) gstride with eta[q % E] (device array)
+hipError_t launch_alt_beta_system_problems(const double *G, int64_t gstride, int E, int64_t q0, const double *eta, const int *prob, int ldg,
+                                           int M, const uint64_t *mask_aug, const double *a, int Kp, const int *slot, int cnt, double *GA,
+                                           double *Hg, hipStream_t s)
+{
+    return alt_beta_system_batch<true>(G, ldg, M, 0.0, mask_aug, a, Kp, slot, cnt, GA, Hg, AltProblemOf{prob, q0, gstride, E, eta}, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

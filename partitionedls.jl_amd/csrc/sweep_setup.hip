@@ -181,8 +181,9 @@ partls_status solve_nodes(partls_ctx *c, const std::vector<int8_t> &codes, size_
     return PARTLS_OK;
 }
 
-partls_status solve_nodes_device(partls_ctx *c, size_t cnt, const int8_t *code, double *obj2, double *sol,
-                                 unsigned long long *counters, int max_rounds)
+// T0reg == nullptr: the context's own problem on whichever kernel it runs; else another problem of the same shape on the register kernel
+static partls_status nodes_on_stream(partls_ctx *c, const double *T0reg, double tol, size_t cnt, const int8_t *code, double *obj2,
+                                     double *sol, unsigned long long *counters, int max_rounds)
 {
     c->tab_valid = false;
     c->coop_state_valid = false;
@@ -196,8 +197,26 @@ partls_status solve_nodes_device(partls_ctx *c, size_t cnt, const int8_t *code, 
     p.max_rounds = max_rounds;
     bind_counters(p, counters);
     p.node_code = code; p.node_obj2 = obj2; p.node_sol = sol; p.node_ld = n;
-    PARTLS_HIP_CHECK(launch_any_sweep(c, p, grid));
+    if (T0reg) {
+        p.T0 = T0reg; p.tol = tol;
+        PARTLS_HIP_CHECK(launch_sweep_blk(p, c->T, grid, c->stream));
+    } else {
+        PARTLS_HIP_CHECK(launch_any_sweep(c, p, grid));
+    }
     return PARTLS_OK;
+}
+
+partls_status solve_nodes_device(partls_ctx *c, size_t cnt, const int8_t *code, double *obj2, double *sol,
+                                 unsigned long long *counters, int max_rounds)
+{
+    return nodes_on_stream(c, nullptr, 0.0, cnt, code, obj2, sol, counters, max_rounds);
+}
+
+partls_status solve_nodes_device_at(partls_ctx *c, const double *T0reg, double tol, size_t cnt, const int8_t *code, double *obj2,
+                                    double *sol, unsigned long long *counters, int max_rounds)
+{
+    if (!c->use_reg || !T0reg) { set_error("solve_nodes_device_at: needs a register-kernel context and a tableau"); return PARTLS_ERR_STATE; }
+    return nodes_on_stream(c, T0reg, tol, cnt, code, obj2, sol, counters, max_rounds);
 }
 
 }  // namespace partls

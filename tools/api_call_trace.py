@@ -64,6 +64,8 @@ SPEC = {
     "partls_alt_prepared": f"h eps T alpha0:d:M+1 beta0:d:K+1 {_OUT5}",
     "partls_bnb_prepared": f"h {_OUT5}",
     "partls_alt_multistart": f"h eps T R alpha0s:d:R*lda lda beta0s:d:R*ldb ldb {_OUT5} out out ld_alpha out ld_beta out out out out",
+    "partls_cv_alt": f"h {_XY} w:d:N dev {_P} fold_ptr:q:F+1 F etas:d:E E flags eps T R alpha0s:d:R*lda lda beta0s:d:R*ldb ldb "
+                     "out ld_alpha out ld_beta out out out out out out out out out",
     "partls_bnb_bound": "h n pats:Q:n frees:Q:n out out",
     "partls_bnb_snap_begin": "h",
     "partls_bnb_bound_snap": "h n pats:Q:n frees:Q:n src:i:n out out out",
