@@ -397,6 +397,34 @@ partls_status partls_predict_device(partls_ctx *ctx, const double *dX, int64_t N
 
 /* partls_predict_f32 / partls_predict_device_f32: the two predicts for an X stored as float (partls_f32.h). */
 
+/* ---- predict from B models in one pass over X; per-row order statistics and mean of the B predictions ------------
+ * Model b is (alpha[:, b], beta[:, b], t[b]) over the one partition P: alpha is M x B (leading dimension M), beta K x B (leading
+ * dimension K), t has B entries — the layouts partls_opt_weightings writes (with ld_alpha = M, ld_beta = K), all HOST arrays, as are P
+ * and ranks.  Column b of the N x B predictions is what partls_predict returns for model b, bit for bit (the same weights w_b, the same
+ * four chains over m mod 4, ((a0 + a1) + (a2 + a3)) + t_b); X is read once per PARTLS_PREDICT_MANY_CHUNK models, not once per model.
+ * Outputs, each optional, at least one of them wanted:
+ *   yhat  (N x B column-major, leading dimension ldY >= N; NULL: not wanted, ldY ignored): rows N .. ldY of a column are not written;
+ *   stats (N x nr column-major, leading dimension N; NULL if and only if nr == 0): stats[i, q] = the value at position ranks[q]
+ *         (0-based, 0 <= ranks[q] < B, nr <= PARTLS_PREDICT_MANY_MAX_B) of the ascending sort of row i's B predictions — exact, ties
+ *         included, for finite predictions;
+ *   mean  (N; NULL: not wanted): (((y_i0 + y_i1) + y_i2) + ... + y_i,B-1) / B, summed in that order.
+ * x_on_device = 0: X is a host array, uploaded once and released afterwards; the outputs are host arrays.  When only stats / mean are
+ * wanted no N x B array exists on the host or crosses PCIe.  x_on_device = 1 (as in partls_cv_opt): X and every non-NULL output are
+ * DEVICE addresses that stay owned by the caller.  Either way the rows are processed in chunks whose N x B intermediate in HBM stays
+ * within PARTLS_PREDICT_MANY_BYTES.
+ * Errors, all found before any device work: PARTLS_ERR_BAD_ARG for B < 1, no output wanted, stats and nr that disagree, a rank outside
+ * [0, B), ldY < N, a NaN / Inf in alpha, beta or t (a failed replicate's NaN row never reaches the selection); PARTLS_ERR_UNSUPPORTED
+ * for B or nr above PARTLS_PREDICT_MANY_MAX_B (predict a larger set of models in slices of columns); otherwise those of partls_predict.
+ * The context's prepared problem, if any, is untouched. */
+#define PARTLS_PREDICT_MANY_CHUNK 16                 /* models per pass over X                          */
+#define PARTLS_PREDICT_MANY_MAX_B 4096               /* most models (and most ranks) of one call        */
+#define PARTLS_PREDICT_MANY_BYTES (64ULL << 20)      /* 64 MiB: the N x B intermediate of a row chunk   */
+partls_status partls_predict_many(partls_ctx *ctx, const double *X, int64_t N, int64_t M, int64_t ldX, int x_on_device,
+                                  const int64_t *P, int64_t K, int64_t ldP, int64_t B, const double *alpha, const double *beta,
+                                  const double *t, double *yhat, int64_t ldY, int64_t nr, const int64_t *ranks, double *stats,
+                                  double *mean);
+/* partls_predict_many_f32: the same for an X stored as float (partls_f32_more.h). */
+
 /* ---- synthetic inputs of BASELINE.md §4, generated in HBM (bit-identical to oracle_synth on the host) -----------------
  * dX: device N x D (ld = N), dy: device N; wstar: HOST D doubles (alpha*_j beta*_g(j), from partls_synth_truth). */
 partls_status partls_synth_truth(uint64_t seed, int64_t D, int64_t K, int64_t *P, double *wstar);
@@ -452,8 +480,10 @@ partls_status partls_get_near_ties(const partls_ctx *ctx, int64_t *evaluated);
 partls_status partls_get_gram(const partls_ctx *ctx, double *G_aug);
 
 /* ---- float32 design matrices: one prepare and two predicts that take X as float (uploaded, kept and read as float; results equal the
- * fp64 path on the widened matrix bit for bit).  Part of this ABI; kept in a header of their own. */
+ * fp64 path on the widened matrix bit for bit).  Part of this ABI; kept in a header of their own.  partls_f32_more.h: the float32
+ * entry points added since (partls_predict_many_f32). */
 #include "partls_f32.h"
+#include "partls_f32_more.h"
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,8 @@ OPT_FAITHFUL_INTERCEPT = 1
 OPT_GENERIC_KERNEL = 2
 T_GRAM, T_PREP, T_SWEEP, T_FINISH, T_CALIB, T_OOB = range(6)
 ROUTE_REG_256, ROUTE_REG_512, ROUTE_DEFERRED, ROUTE_EAGER = range(1, 5)
+# partls_predict_many: models per pass over X, most models / ranks of a call, bytes of a row chunk's N x B intermediate (partls.h)
+PREDICT_MANY_CHUNK, PREDICT_MANY_MAX_B, PREDICT_MANY_BYTES = 16, 4096, 64 << 20
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -83,6 +85,8 @@ SYMBOLS = [
     ("partls_predict", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, _i64, _i64, _dp, _dp, C.c_double, _dp]),
     ("partls_predict_device", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, _i64, _i64, _dp, _dp, C.c_double,
                                         C.c_void_p]),
+    ("partls_predict_many", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_int, C.c_void_p, _i64, _i64, _i64, _dp, _dp, _dp,
+                                      C.c_void_p, _i64, _i64, _ip, C.c_void_p, C.c_void_p]),
     ("partls_synth_truth", C.c_int, [C.c_uint64, _i64, _i64, _ip, _dp]),
     ("partls_synth_device", C.c_int, [C.c_void_p, C.c_uint64, _i64, _i64, _dp, C.c_void_p, C.c_void_p]),
     ("partls_get_timing", C.c_int, [C.c_void_p, C.c_int, _dp]),
@@ -103,6 +107,12 @@ SYMBOLS_F32 = [
     ("partls_predict_f32", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, _i64, _i64, _dp, _dp, C.c_double, _dp]),
     ("partls_predict_device_f32", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, _i64, _i64, _dp, _dp, C.c_double,
                                             C.c_void_p]),
+]
+
+# ... and every symbol include/partls_f32_more.h declares (float32 entry points that came after those three)
+SYMBOLS_F32_MORE = [
+    ("partls_predict_many_f32", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_int, C.c_void_p, _i64, _i64, _i64, _dp, _dp, _dp,
+                                          C.c_void_p, _i64, _i64, _ip, C.c_void_p, C.c_void_p]),
 ]
 
 _lib = None
@@ -151,7 +161,7 @@ def lib():
                               f"(make -C '{CSRC}'); partitionedls.jl_amd has no CPU fallback")
         _preload_torch_hip_runtime()
         l = C.CDLL(SO_PATH)
-        for name, res, args in SYMBOLS + SYMBOLS_F32:
+        for name, res, args in SYMBOLS + SYMBOLS_F32 + SYMBOLS_F32_MORE:
             if os.environ.get("PARTLS_LIB") and not hasattr(l, name):
                 continue                   # diagnostic A/B builds of older sources may lack the newest entry points
             f = getattr(l, name)           # AttributeError here = header/library mismatch

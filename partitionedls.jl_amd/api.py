@@ -128,6 +128,23 @@ def _f32(dtype, who):
     return dtype == np.float32
 
 
+def _many_models(alpha, beta, t, M, K, ranks):
+    """B models as partls_predict_many takes them: alpha[B, M], beta[B, K], t[B] C-contiguous float64 (row b = model b) and the ranks as
+    an int64 vector (None: no order statistics).  ValueError for shapes that do not fit each other, M and K; a rank outside [0, B)."""
+    a = np.ascontiguousarray(alpha, dtype=np.float64)
+    b = np.ascontiguousarray(beta, dtype=np.float64)
+    tv = np.ascontiguousarray(t, dtype=np.float64)
+    if a.ndim != 2 or b.ndim != 2 or tv.ndim != 1 or a.shape[0] < 1 or a.shape != (tv.shape[0], M) or b.shape != (tv.shape[0], K):
+        raise ValueError("predict_many: expected alpha (B, %d), beta (B, %d) and t (B,) with B >= 1, got %s, %s and %s"
+                         % (M, K, a.shape, b.shape, tv.shape))
+    if ranks is None:
+        return a, b, tv, None
+    r = np.ascontiguousarray(ranks, dtype=np.int64)
+    if r.ndim != 1 or len(r) < 1 or r.min() < 0 or r.max() >= a.shape[0]:
+        raise ValueError("predict_many: ranks must be a non-empty vector of positions in [0, %d)" % a.shape[0])
+    return a, b, tv, r
+
+
 class _Model:
     """The output set of a call that returns one model: alpha[M], beta[K], t, opt and one int64 (best_index / iters / nopen)."""
 
@@ -535,6 +552,46 @@ class Context:
         else:
             fn = lib.partls_predict_f32 if f32 else lib.partls_predict
         _check(fn(self._h, xp, N, M, ldX, P.ctypes.data, P.shape[1], M, _dp(a), _dp(b), float(t), yhat))
+
+    def predict_many(self, X, P, alpha, beta, t, *, ranks=None, want_yhat=True, want_mean=False):
+        """The predictions of B models over one partition P in one upload of a host X (partls_predict_many).
+        alpha[B, M], beta[B, K], t[B]: row b = model b.  Returns dict(yhat, stats, mean): yhat[N, B] (None unless want_yhat), column b
+        = predict with model b bit for bit; stats[N, len(ranks)] (None without ranks), column q = the value at 0-based position
+        ranks[q] of each row's ascending sort of its B predictions; mean[N] (None unless want_mean), summed over b = 0 .. B-1 in that
+        order.  Without want_yhat no N x B array exists on the host.  X as in predict: float32 stays float32."""
+        X, _, P = _inputs(X, None, P)
+        N, M = X.shape
+        a, b, tv, r = _many_models(alpha, beta, t, M, P.shape[1], ranks)
+        B = a.shape[0]
+        yh = np.zeros((N, B), order="F") if want_yhat else None
+        st = None if r is None else np.zeros((N, len(r)), order="F")
+        mu = np.zeros(N) if want_mean else None
+        self._predict_many(X.ctypes.data, 0, X.dtype == np.float32, N, M, N, P, a, b, tv, None if yh is None else yh.ctypes.data, N, r,
+                           None if st is None else st.ctypes.data, None if mu is None else mu.ctypes.data)
+        return dict(yhat=yh, stats=st, mean=mu)
+
+    def predict_many_device(self, dX_ptr, N, M, ldX, P, alpha, beta, t, *, dyhat_ptr=None, ldY=0, ranks=None, dstats_ptr=None,
+                            dmean_ptr=None, dtype=np.float64):
+        """the same with X (N x M, ldX, elements of `dtype`: float64 or float32) and every wanted output in HBM, as raw device
+        addresses: dyhat_ptr (N x B doubles, column-major, leading dimension ldY >= N; rows N .. ldY are not written), dstats_ptr
+        (N x len(ranks), leading dimension N; wanted exactly when ranks is given), dmean_ptr (N)"""
+        f32 = _f32(dtype, "predict_many_device")
+        P = np.asfortranarray(P, dtype=np.int64)
+        a, b, tv, r = _many_models(alpha, beta, t, int(M), P.shape[1], ranks)
+        if (r is None) != (dstats_ptr is None):
+            raise ValueError("predict_many_device: dstats_ptr goes with ranks")
+        self._predict_many(C.c_void_p(dX_ptr), 1, f32, int(N), int(M), int(ldX), P, a, b, tv,
+                           None if dyhat_ptr is None else C.c_void_p(dyhat_ptr), int(ldY), r,
+                           None if dstats_ptr is None else C.c_void_p(dstats_ptr), None if dmean_ptr is None else C.c_void_p(dmean_ptr))
+
+    def _predict_many(self, xp, on_device, f32, N, M, ldX, P, a, b, tv, yhat, ldY, ranks, stats, mean):
+        """The one call behind predict_many and predict_many_device: xp and the outputs (or None) are addresses on the host or
+        (on_device) in HBM; a[B, M], b[B, K], tv[B] C-contiguous float64 (the M x B / K x B column-major layouts of the ABI); ranks:
+        int64 vector or None"""
+        lib = L.lib()
+        fn = lib.partls_predict_many_f32 if f32 else lib.partls_predict_many
+        _check(fn(self._h, xp, N, M, ldX, on_device, P.ctypes.data, P.shape[1], M, a.shape[0], _dp(a), _dp(b), _dp(tv), yhat, ldY,
+                  0 if ranks is None else len(ranks), None if ranks is None else _ip(ranks), stats, mean))
 
     def _count(self, getter):
         n = C.c_int64()
@@ -1185,8 +1242,8 @@ class BootstrapResult:
     """What bootstrap and resample return: one fit(Opt) per weighting (replicate) b, as arrays — nothing here refers to a context.
     counts: the N x B int64 multinomial draws of bootstrap (None from resample); alpha[B, M], beta[B, K], t[B], opt[B], best_index[B];
     models[b]: PartLSFitResult, or None where status[b] is 6 (pivot cap: NaN rows); status[B] (0 / 9 / 6); oob_sse[b] / oob_rows[b]:
-    squared error and number of the rows replicate b left out (weight 0).  The statistics below go over the successful replicates
-    (status 0 or 9) and are plain numpy on B rows."""
+    squared error and number of the rows replicate b left out (weight 0); P: the partition the replicates share.  The statistics below go
+    over the successful replicates (status 0 or 9) and are plain numpy on B rows; predict runs on the device."""
     counts: object
     alpha: np.ndarray
     beta: np.ndarray
@@ -1197,6 +1254,7 @@ class BootstrapResult:
     status: np.ndarray
     oob_sse: np.ndarray
     oob_rows: np.ndarray
+    P: object = None            # the partition of every replicate (predict needs no model object)
 
     @property
     def ok(self):
@@ -1243,6 +1301,57 @@ class BootstrapResult:
             out[k] = (float(lo), float(hi)) if k == "t" else (lo, hi)
         return out
 
+    def predict(self, X, level=0.95, *, return_all=False, device=0):
+        """Percentile band of the successful replicates' predictions for the rows of X, in one pass over X (partls_predict_many,
+        DESIGN.md §4.12): dict(mean[N], lo[N], hi[N]) — the mean over the replicates and the 50 (1 - level) and 100 - 50 (1 - level)
+        percentiles of each row's B_ok predictions as np.percentile defines them (linear interpolation), computed as 50 - 50 level
+        and 50 + 50 level: exactly 5 and 95 for level 0.9, 2.5 and 97.5 for 0.95.  The device returns the order
+        statistics either side of each percentile (at most four per row) and the mean; the interpolation between two neighbours
+        happens here, by np.percentile's own formula.  return_all=True adds yhat[N, B_ok], column j = predict with the j-th successful
+        replicate; without it no N x B array exists on the host.  X as in predict.  ValueError: level outside (0, 1), no
+        successful replicate, a result without its partition (P)."""
+        level = float(level)
+        if not 0.0 < level < 1.0:
+            raise ValueError("predict: level must lie in (0, 1), got %r" % level)
+        ok = self.ok
+        if not ok.any():
+            raise ValueError("predict: no successful replicate")
+        if self.P is None:
+            raise ValueError("predict: this result does not carry its partition P")
+        X = np.asarray(X)
+        if not np.issubdtype(X.dtype, np.floating) or X.ndim != 2:
+            raise TypeError("predict: X must be a floating-point matrix")
+        a, b, t = np.asarray(self.alpha)[ok], np.asarray(self.beta)[ok], np.asarray(self.t)[ok]
+        if X.shape[1] != a.shape[1]:
+            raise ValueError("DimensionMismatch in predict")
+        ranks, parts = _percentile_ranks(len(t), [50.0 - 50.0 * level, 50.0 + 50.0 * level])
+        r = default_context(device).predict_many(X, self.P, a, b, t, ranks=ranks, want_yhat=return_all, want_mean=True)
+        lo, hi = (_lerp(r["stats"][:, i], r["stats"][:, j], g) for i, j, g in parts)
+        out = dict(mean=r["mean"], lo=lo, hi=hi)
+        if return_all:
+            out["yhat"] = r["yhat"]
+        return out
+
+
+def _percentile_ranks(n, q):
+    """np.percentile(v, q) of n values by its default (linear) method, in two steps: the positions of the sorted values it reads —
+    (ranks, parts) with ranks the distinct positions in ascending order (int64) and parts[j] = (index into ranks of the lower
+    neighbour, of the upper one, weight gamma) for percentile q[j] — and _lerp below.  The virtual index is (n - 1) (q / 100), its
+    floor and ceiling the two neighbours (one position, gamma 0, when it is whole)."""
+    virtual = (n - 1) * np.true_divide(np.asarray(q, dtype=np.float64), 100)
+    lower = np.clip(np.floor(virtual), 0, n - 1)
+    upper = np.clip(np.ceil(virtual), 0, n - 1)
+    ranks = np.unique(np.concatenate([lower, upper])).astype(np.int64)
+    parts = [(int(np.searchsorted(ranks, lo)), int(np.searchsorted(ranks, up)), float(v - lo)) for lo, up, v in zip(lower, upper, virtual)]
+    return ranks, parts
+
+
+def _lerp(a, b, gamma):
+    """numpy's interpolation between neighbours a and b (numpy/lib/_function_base_impl.py, _lerp): a + (b - a) gamma, and from the upper
+    end, b - (b - a) (1 - gamma), when gamma >= 0.5"""
+    d = b - a
+    return b - d * (1 - gamma) if gamma >= 0.5 else a + d * gamma
+
 
 def _resample(who, alg, X, y, P, make_W, eta, faithful_intercept, generic_kernel, device, on_ill_conditioned):
     """bootstrap and resample after their own argument checks.  make_W(N) -> (counts or None, W[N, B] float64) runs after the checks
@@ -1271,7 +1380,7 @@ def _resample(who, alg, X, y, P, make_W, eta, faithful_intercept, generic_kernel
     models = [None if st[b] == L.ERR_NOT_CONVERGED else PartLSFitResult(alpha[b].copy(), beta[b].copy(), float(r["t"][b]), Pout)
               for b in range(B)]
     return BootstrapResult(counts=counts, alpha=alpha, beta=beta, t=r["t"], opt=r["opt"], best_index=r["best_index"], models=models,
-                           status=st, oob_sse=r["oob_sse"], oob_rows=r["oob_rows"])
+                           status=st, oob_sse=r["oob_sse"], oob_rows=r["oob_rows"], P=Pout)
 
 
 def _eta(η, eta):
@@ -1344,6 +1453,37 @@ def predict(*args, device=0):
     if Pf.shape[0] != M or a.shape != (M,) or b.shape != (Pf.shape[1],):
         raise ValueError("DimensionMismatch in predict")
     return default_context(device).predict(Xf, Pf, a, b, t)
+
+
+def predict_many(models, X, *, device=0):
+    """The predictions of many models for the rows of X in one upload of X (partls_predict_many)  ->  [N, B] float64,
+    column b = predict(models[b], X) bit for bit.  models: a sequence of PartLSFitResult over one common partition (bootstrap's
+    models, a cross-validation path, the starts of fit(Alt), solutions), or a tuple (alpha[B, M], beta[B, K], t[B], P) of arrays
+    (BootstrapResult's alpha, beta, t, P; solutions.arrays()).  X as in predict: float32 goes up as float32.  More than
+    lowlevel.PREDICT_MANY_MAX_B models are predicted in slices of that many columns (one upload of X per slice).
+    ValueError: an empty sequence, models over different partitions, shapes that do not fit; TypeError: X not a floating matrix."""
+    if isinstance(models, tuple) and len(models) == 4 and not isinstance(models[0], PartLSFitResult):
+        a, b, t, P = models
+    else:
+        ms = list(models)
+        if not ms or not all(isinstance(m, PartLSFitResult) for m in ms):
+            raise ValueError("predict_many: models must be a non-empty sequence of PartLSFitResult or a tuple (alpha, beta, t, P)")
+        P = np.asarray(ms[0].P)
+        if not all(m.P is ms[0].P or np.array_equal(np.asarray(m.P), P) for m in ms[1:]):
+            raise ValueError("predict_many: the models must share one partition P")
+        if len({np.shape(m.α) for m in ms}) != 1 or len({np.shape(m.β) for m in ms}) != 1:
+            raise ValueError("predict_many: the models differ in shape")
+        a, b, t = np.stack([m.α for m in ms]), np.stack([m.β for m in ms]), np.array([m.t for m in ms], dtype=np.float64)
+    X = np.asarray(X)
+    if not np.issubdtype(X.dtype, np.floating) or X.ndim != 2:
+        raise TypeError("predict_many: X must be a floating-point matrix")
+    Xf, _, Pf = _inputs(X, None, P)
+    if Pf.ndim != 2 or Pf.shape[0] != Xf.shape[1]:
+        raise ValueError("DimensionMismatch in predict_many")
+    a, b, t, _ = _many_models(a, b, t, Xf.shape[1], Pf.shape[1], None)
+    ctx, cap = default_context(device), L.PREDICT_MANY_MAX_B
+    parts = [ctx.predict_many(Xf, Pf, a[s:s + cap], b[s:s + cap], t[s:s + cap])["yhat"] for s in range(0, len(t), cap)]
+    return parts[0] if len(parts) == 1 else np.concatenate(parts, axis=1)
 
 
 def predict_device(model, dX_ptr, N, ldX, dyhat_ptr, device=0, dtype=np.float64):

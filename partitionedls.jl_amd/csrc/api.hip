@@ -54,6 +54,20 @@ double h_reg(const partls_ctx *c, int a, int b)
     return v;
 }
 
+partls_status predict_weights(const int64_t *P, int64_t M, int64_t K, int64_t ldP, const double *alpha, const double *beta, double *w)
+{
+    for (int64_t m = 0; m < M; ++m) {
+        double s = 0.0;
+        for (int64_t k = 0; k < K; ++k) {
+            const int64_t v = P[m + k * ldP];
+            if (v != 0 && v != 1) { set_error("P has an entry outside {0,1}"); return PARTLS_ERR_BAD_PARTITION; }
+            s += (double)v * alpha[m] * beta[k];
+        }
+        w[m] = s;
+    }
+    return PARTLS_OK;
+}
+
 }  // namespace partls
 
 using namespace partls;
@@ -158,7 +172,7 @@ void partls_destroy(partls_ctx *c)
     }
 }
 
-// predict: w_m = sum_k P[m,k] alpha_m beta_k on the host (M*K flops), yhat = X w + t on the device (one pass over X)
+// predict: w_m = sum_k P[m,k] alpha_m beta_k on the host (predict_weights: M*K flops), yhat = X w + t on the device (one pass over X)
 static partls_status predict_common(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, int x_on_device,
                                     const int64_t *P, int64_t K, int64_t ldP, const double *alpha, const double *beta, double t,
                                     double *yhat, bool x_f32 = false)
@@ -168,15 +182,8 @@ static partls_status predict_common(partls_ctx *c, const void *X, int64_t N, int
     if (!alpha || !beta || !yhat) { set_error("partls_predict: NULL argument"); return PARTLS_ERR_BAD_ARG; }
     PARTLS_HIP_CHECK(hipSetDevice(c->device));
     std::vector<double> w((size_t)M, 0.0);
-    for (int64_t m = 0; m < M; ++m) {
-        double s = 0.0;
-        for (int64_t k = 0; k < K; ++k) {
-            const int64_t v = P[m + k * ldP];
-            if (v != 0 && v != 1) { set_error("P has an entry outside {0,1}"); return PARTLS_ERR_BAD_PARTITION; }
-            s += (double)v * alpha[m] * beta[k];
-        }
-        w[(size_t)m] = s;
-    }
+    st = predict_weights(P, M, K, ldP, alpha, beta, w.data());
+    if (st != PARTLS_OK) return st;
     PARTLS_HIP_CHECK(c->wdev.ensure((size_t)(M + 1) * sizeof(double)));
     PARTLS_HIP_CHECK(hipMemcpyAsync(c->wdev.p, w.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const void *dX = X;

@@ -1,6 +1,6 @@
 // ctx.h — the context behind the opaque partls_ctx handle, the owning buffer types it is made of, and the host helpers the host
 // translation units share: api.hip (create / destroy / predict / getters), prepare.hip, sweep_setup.hip, opt.hip, refine.hip,
-// solvers.hip, multi.hip and the host halves of cv.hip and alt_multi.hip.
+// solvers.hip, multi.hip and the host halves of cv.hip, alt_multi.hip and predict_many.hip.
 #pragma once
 #include "common.h"
 #include <functional>
@@ -249,6 +249,10 @@ struct partls_ctx {
     // weight_prep_kernel and of oob_sse_kernel and their host copies; rsWv, the models of a chunk of problems as weight vectors
     partls::DevBuf rsW, rsS, rsPart, rsWv;
     partls::PinnedDoubles rsHost;
+    // partls_predict_many (predict_many.hip): pmW, the models of a call as chunk-blocked weight vectors and their
+    // intercepts; pmRanks, the ranks wanted; pmY, the N x B intermediate of a row chunk (at most PARTLS_PREDICT_MANY_BYTES); pmStats /
+    // pmMean, the device images of a host caller's stats (one row chunk) and mean
+    partls::DevBuf pmW, pmRanks, pmY, pmStats, pmMean;
 };
 
 namespace partls {
@@ -440,5 +444,9 @@ partls_status refine_solution(partls_ctx *c, std::vector<double> &w, bool free_i
 // regularised augmented Gram entry on the host copy
 double h_reg(const partls_ctx *c, int a, int b);
 partls_status check_common(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, const void *P, int64_t K, int64_t ldP);
+// The weights a prediction applies (api.hip), w[m] = sum over k = 0 .. K-1, in that order, of P[m,k] alpha[m] beta[k]: the ONE definition
+// behind partls_predict* and partls_predict_many*, whose columns equal the single predictions bit for bit.  Checks P on the way:
+// PARTLS_ERR_BAD_PARTITION for an entry outside {0,1}.
+partls_status predict_weights(const int64_t *P, int64_t M, int64_t K, int64_t ldP, const double *alpha, const double *beta, double *w);
 
 }  // namespace partls
