@@ -190,6 +190,32 @@ partls_status partls_opt_pattern(partls_ctx *ctx, int64_t pattern, double *raw_a
 partls_status partls_opt_models(partls_ctx *ctx, int64_t g_begin, int64_t g_end, int64_t *pattern, double *optval,
                                 double *raw_alpha, int64_t ld_raw, double *alpha, int64_t ld_alpha,
                                 double *beta, int64_t ld_beta, double *t, int64_t *n_unconverged, int64_t *n_vetoes);
+/* The k best patterns of a Gray-index range and their models, selected on the device: what partls_opt_models
+ * returns for the range, reduced to its k best rows before anything is copied back.  Preconditions, range rules and error statuses
+ * are those of partls_opt_models; additionally 1 <= k <= PARTLS_OPT_TOP_MAX_K (else PARTLS_ERR_BAD_ARG).
+ * Row i of every output (laid out as partls_opt_models' outputs; pattern and optval required, raw_alpha optional, alpha / beta / t all
+ * three or none) is the i-th best pattern of [g_begin, g_end) in the total order
+ *     a before b  iff  optval_a < optval_b, or optval_a == optval_b as doubles (-0.0 equals +0.0; +inf is an ordinary value) and
+ *                      pattern_a < pattern_b   (pattern: the reference index b).
+ * A pattern that hit the pivot cap (NaN objective) is never selected, only counted in *n_unconverged.
+ * *count = min(k, converged patterns of the range); rows at and beyond *count are not written.  Two calls with the same arguments
+ * return the same bits.  The models are the Gram-form models of partls_opt_models, bit for bit the rows it returns for the same
+ * patterns when both run the same piece; accuracy and the meaning of *n_vetoes are partls_opt_models'.
+ * The range is cut into equal pieces, ceil(total / npieces), whose scaled rows and objectives ((n + 1) doubles per pattern, n = M + 1)
+ * stay below PARTLS_OPT_MODELS_PIECE_BYTES (PARTLS_TOP_PIECE, read at partls_create: patterns per piece instead); each piece is one
+ * export sweep on the chain plan of partls_opt_sweep for its length, a selection, sort and gather of its k best rows on the device, the
+ * cleanup of those rows and one copy back; the host merges the pieces' lists by the same order.
+ * Leaves the state of the last partls_opt_sweep untouched, as partls_opt_models does. */
+#define PARTLS_OPT_TOP_MAX_K 4096
+partls_status partls_opt_top(partls_ctx *ctx, int64_t g_begin, int64_t g_end, int64_t k, int64_t *pattern, double *optval,
+                             double *raw_alpha, int64_t ld_raw, double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta,
+                             double *t, int64_t *count, int64_t *n_unconverged, int64_t *n_vetoes);
+/* The selection stage of partls_opt_top alone (tests, diagnosis): obj is a HOST array of cnt objectives of Gray indices
+ * g0 .. g0 + cnt - 1 of the prepared problem (g0 + cnt <= number of patterns, cnt < 2^31); it is uploaded and goes through the kernels
+ * partls_opt_top runs per piece, without a sweep.  index[i] (position in obj), pattern[i] (reference index) and optval[i] describe the
+ * i-th best entry in the order above; *count = min(k, non-NaN entries).  Needs a prepared context (any intercept mode). */
+partls_status partls_opt_top_select(partls_ctx *ctx, const double *obj, int64_t cnt, int64_t g0, int64_t k, int64_t *index,
+                                    int64_t *pattern, double *optval, int64_t *count);
 /* visiting order of the sweep: gbit[k] = Gray-index bit that carries group k (K' entries; identity unless calibrated);
  * flip_cost (optional, K' doubles): measured cost of a flip of group k in pivot equivalents (pivots + weighted block pivots and
  * extra KKT scans; exact counts, no timing), -1 when the calibration did not run (sweeps too short

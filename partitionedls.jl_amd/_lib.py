@@ -14,6 +14,7 @@ T_GRAM, T_PREP, T_SWEEP, T_FINISH, T_CALIB, T_OOB = range(6)
 ROUTE_REG_256, ROUTE_REG_512, ROUTE_DEFERRED, ROUTE_EAGER = range(1, 5)
 # partls_predict_many: models per pass over X, most models / ranks of a call, bytes of a row chunk's N x B intermediate (partls.h)
 PREDICT_MANY_CHUNK, PREDICT_MANY_MAX_B, PREDICT_MANY_BYTES = 16, 4096, 64 << 20
+OPT_TOP_MAX_K = 4096    # partls_opt_top: most patterns of a call (PARTLS_OPT_TOP_MAX_K, partls.h)
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -48,6 +49,8 @@ SYMBOLS = [
     ("partls_opt_merge_candidates", C.c_int, [C.c_void_p, _i64, _dp, _ip, _dp, _ip]),
     ("partls_opt_pattern", C.c_int, [C.c_void_p, _i64, _dp, _dp]),
     ("partls_opt_models", C.c_int, [C.c_void_p, _i64, _i64, _ip, _dp, _dp, _i64, _dp, _i64, _dp, _i64, _dp, _ip, _ip]),
+    ("partls_opt_top", C.c_int, [C.c_void_p, _i64, _i64, _i64, _ip, _dp, _dp, _i64, _dp, _i64, _dp, _i64, _dp, _ip, _ip, _ip]),
+    ("partls_opt_top_select", C.c_int, [C.c_void_p, _dp, _i64, _i64, _i64, _ip, _ip, _dp, _ip]),
     ("partls_cv_opt", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, C.c_int, C.c_void_p, _i64, _i64, _ip, _i64,
                                 _dp, _i64, C.c_uint32, _dp, _i64, _dp, _i64, _dp, _dp, _ip, _dp, C.POINTER(C.c_int32)]),
     ("partls_cv_opt_weighted", C.c_int, [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64,

@@ -337,6 +337,45 @@ class Context:
             out["raw_alpha"] = ra
         return out
 
+    def opt_top(self, k, g_begin=0, g_end=-1, raw=False):
+        """The k best patterns of the Gray-index range [g_begin, g_end) and their models, selected on the device (partls_opt_top):
+        dict of pattern[c], opt[c], alpha[c, M], beta[c, K], t[c] (raw_alpha[c, M+1] when raw=True), best first — by (opt, pattern),
+        -0.0 equal to +0.0, a pattern that hit the pivot cap never listed — with count = c = min(k, converged patterns of the range),
+        n_unconverged and n_vetoes.  The rows are opt_models' rows of those patterns (Gram form, not refined in data space)."""
+        N, M, K = self._shape
+        k = int(k)
+        B = max(k, 0)
+        pat = np.zeros(B, dtype=np.int64)
+        opt = np.zeros(B)
+        a = np.zeros((B, M))
+        b = np.zeros((B, K))
+        t = np.zeros(B)
+        ra = np.zeros((B, M + 1)) if raw else None
+        cn = C.c_int64()
+        nu = C.c_int64()
+        nv = C.c_int64()
+        _check(L.lib().partls_opt_top(self._h, int(g_begin), int(g_end), k, _ip(pat), _dp(opt), _dp(ra) if raw else None, M + 1,
+                                      _dp(a), M, _dp(b), K, _dp(t), C.byref(cn), C.byref(nu), C.byref(nv)))
+        c = cn.value
+        out = dict(pattern=pat[:c], opt=opt[:c], alpha=a[:c], beta=b[:c], t=t[:c], count=c, n_unconverged=nu.value, n_vetoes=nv.value)
+        if raw:
+            out["raw_alpha"] = ra[:c]
+        return out
+
+    def opt_top_select(self, obj, g0, k):
+        """The selection stage of opt_top alone (partls_opt_top_select): obj = objectives of Gray indices g0 .. g0 + len(obj) - 1 of the
+        prepared problem -> (index, pattern, opt) of the min(k, non-NaN) best entries in opt_top's order; index = positions in obj."""
+        o = np.ascontiguousarray(obj, dtype=np.float64)
+        k = int(k)
+        B = max(k, 0)
+        idx = np.zeros(B, dtype=np.int64)
+        pat = np.zeros(B, dtype=np.int64)
+        val = np.zeros(B)
+        cn = C.c_int64()
+        _check(L.lib().partls_opt_top_select(self._h, _dp(o), len(o), int(g0), k, _ip(idx), _ip(pat), _dp(val), C.byref(cn)))
+        c = cn.value
+        return idx[:c], pat[:c], val[:c]
+
     def cv_opt(self, X, y, P, fold_ptr, etas, flags=0, device_ptrs=None, weights=None):
         """partls_cv_opt: fit(Opt) on every (fold, η) training set and on all rows, in one call.  X, y: host arrays, or
         device_ptrs=(dX_ptr, dy_ptr, N, ldX[, dw_ptr]) for device-resident inputs (X then ignored; pass X=None).  fold_ptr: F+1 boundaries
@@ -978,9 +1017,67 @@ class _Solutions:
         return opt, alpha, beta, t
 
 
+@dataclass
+class TopPatterns:
+    """report.top of fit(Opt, ..., top=k): the k best sign patterns of the enumeration and their models, best first (partls_opt_top;
+    DESIGN.md §4.13).  pattern[k] (reference index b over the K groups and, bit K, the intercept), opt[k], alpha[k, M], beta[k, K], t[k];
+    models: the same as a list of PartLSFitResult; n_vetoes: the sweep's leave-one-out refusals (> 0: the models were rebuilt one by
+    one through opt_finish).  The order is that of the Gram-form objectives: (opt, pattern), -0.0 equal to +0.0.  fit's own winner is
+    re-ranked among its near ties in data space, so report.best_index is among the first entries of pattern, not necessarily the first."""
+    pattern: np.ndarray
+    opt: np.ndarray
+    alpha: np.ndarray
+    beta: np.ndarray
+    t: np.ndarray
+    models: list
+    n_vetoes: int = 0
+
+    def __len__(self):
+        return len(self.pattern)
+
+    @property
+    def gap(self):
+        """opt[1:] - opt[0]: how far behind the winner each runner-up is"""
+        return self.opt[1:] - self.opt[:1]
+
+    @property
+    def sign_agreement(self):
+        """[K, 3]: share of the listed models with beta_k < 0, = 0, > 0 (the layout of BootstrapResult.sign_frequency)"""
+        b = np.asarray(self.beta)
+        if len(b) == 0:
+            return np.full((b.shape[1], 3), np.nan)
+        return np.stack([(b < 0).mean(0), (b == 0).mean(0), (b > 0).mean(0)], axis=1)
+
+    def group_patterns(self):
+        """The list over the 2^K group patterns: the intercept's bit (bit K) dropped from every pattern, of the entries that then
+        coincide the better (earlier) one kept, the order preserved.  A TopPatterns whose pattern holds the group patterns."""
+        K = np.asarray(self.beta).shape[1]
+        gp = np.asarray(self.pattern, dtype=np.int64) & ((1 << K) - 1)
+        _, first = np.unique(gp, return_index=True)
+        keep = np.sort(first)
+        return TopPatterns(gp[keep], self.opt[keep], self.alpha[keep], self.beta[keep], self.t[keep], [self.models[i] for i in keep],
+                           self.n_vetoes)
+
+
+def _top_patterns(ctx, k, Pout):
+    """fit(Opt, ..., top=k) after the fit: opt_top(k) on the prepared context -> TopPatterns"""
+    r = ctx.opt_top(k)
+    if r["n_unconverged"] > 0:
+        raise PartlsError(L.ERR_NOT_CONVERGED, "%d subproblems hit the pivot cap" % r["n_unconverged"])
+    pat, opt, a, b, t = r["pattern"], r["opt"], r["alpha"], r["beta"], r["t"]
+    if r["n_vetoes"] > 0:
+        warnings.warn("partitionedls: the sweep refused dependent columns (%d leave-one-out vetoes): the Gram-form models carry no "
+                      "guarantee, the %d listed models are rebuilt on their own (the ranking is kept)" % (r["n_vetoes"], len(pat)),
+                      IllConditionedWarning, stacklevel=3)
+        for i in range(len(pat)):                              # (status 9 of a rebuilt model: as fit's on_ill_conditioned says)
+            a[i], b[i], t[i] = ctx.opt_finish(int(pat[i]))[:3]
+    models = [PartLSFitResult(a[i].copy(), b[i].copy(), float(t[i]), Pout) for i in range(len(pat))]
+    return TopPatterns(pat, opt, a, b, t, models, int(r["n_vetoes"]))
+
+
 def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="nnls", returnAllSolutions=False, rng=None,
         alpha0=None, beta0=None, device=0, devices=None, faithful_intercept=False, generic_kernel=False, on_ill_conditioned="warn",
-        weights=None, restarts=None):
+        weights=None, restarts=None, top=None):
     """fit(::Type{Opt|Alt|BnB}, X, y, P; η, ...) -> (PartLSFitResult, None, Report)   [Opt.jl:73, Alt.jl:50, BnB.jl:30]
 
     η/eta: regularisation (default 0.0);  Alt: ϵ/eps (1e-6), T (100), rng (None | int seed | numpy Generator) or an
@@ -1005,9 +1102,22 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
     one row per start (opt: the Gram-form loss of its last iteration; NaN rows where status != 0).  ValueError: 1-D starts together
     with restarts, mismatched shapes, non-finite starts, restarts < 1, restarts with Opt / BnB.  PartlsError(ERR_NOT_CONVERGED) when
     every start failed.
+    Opt, top=k (int in 1 .. lowlevel.OPT_TOP_MAX_K): report.top = TopPatterns, the k best sign patterns and their models, selected on
+    the device after the fit (partls_opt_top).  It forces the faithful enumeration, as returnAllSolutions does, and
+    combines with it, with weights= and with a float32 X.  The ranking is the Gram-form one: report.best_index, re-ranked among near
+    ties in data space, is among the first entries of top.pattern, not necessarily the first.  ValueError: top outside that range, or
+    with Alt / BnB; NotImplementedError with devices= (merge per-shard Context.opt_top lists with dist.merge_top).
     """
     if alg not in (Opt, Alt, BnB):
         raise TypeError("fit: first argument must be Opt, Alt or BnB")
+    if top is not None:
+        if isinstance(top, bool) or not isinstance(top, (int, np.integer)) or not 1 <= int(top) <= L.OPT_TOP_MAX_K:
+            raise ValueError("fit: top must be an int in 1 .. %d, got %r" % (L.OPT_TOP_MAX_K, top))
+        if alg is not Opt:
+            raise ValueError("fit: top= is an option of Opt (the enumeration), not of %s" % alg.__name__)
+        if devices is not None:
+            raise NotImplementedError("fit: top= is not supported on several devices (devices=); merge per-shard Context.opt_top lists "
+                                      "with dist.merge_top")
     eta_v = 0.0 if (η is None and eta is None) else float(η if η is not None else eta)
     eps_v = 1e-6 if (ϵ is None and eps is None) else float(ϵ if ϵ is not None else eps)
     if nnlsalg not in ("nnls", "pivot", "fnnls"):
@@ -1044,7 +1154,7 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
     # on_ill_conditioned holds on the shared objects for the span of this call only
     with _tolerating(on_ill_conditioned, ctx, mc):
         if alg is Opt:
-            flags = (faithful if (faithful_intercept or returnAllSolutions) else 0) | (L.OPT_GENERIC_KERNEL if generic_kernel else 0)
+            flags = (faithful if (faithful_intercept or returnAllSolutions or top is not None) else 0) | (L.OPT_GENERIC_KERNEL if generic_kernel else 0)
             if mc is not None:
                 a, b, t, opt, bi, allopt = mc.fit_opt(Xf, yf, Pf, eta_v, flags, want_all=returnAllSolutions)
                 if returnAllSolutions:
@@ -1057,9 +1167,10 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
             if unconv:
                 raise PartlsError(L.ERR_NOT_CONVERGED, f"{unconv} subproblems hit the pivot cap")
             a, b, t, opt, bi = ctx.opt_finish(bpat)
+            extra = {} if top is None else dict(top=_top_patterns(ctx, int(top), Pout))
             if returnAllSolutions:
-                return result(ctx, a, b, t, solutions=solutions(ctx, allopt, flags, device))
-            return result(ctx, a, b, t, opt=opt, best_index=bi)
+                return result(ctx, a, b, t, solutions=solutions(ctx, allopt, flags, device), **extra)
+            return result(ctx, a, b, t, opt=opt, best_index=bi, **extra)
         if alg is Alt and starts is not None:
             ctx.opt_prepare(Xf, yf, Pf, eta_v, faithful, weights=wf)
             a, b, t, o, it, best, per = ctx.alt_multistart(starts[0], starts[1], eps_v, int(T))

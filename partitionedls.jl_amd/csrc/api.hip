@@ -74,7 +74,7 @@ using namespace partls;
 
 extern "C" {
 
-int partls_version(void) { return 105; }
+int partls_version(void) { return 106; }
 const char *partls_last_error(void) { return g_err; }
 
 int partls_device_count(void)
@@ -109,6 +109,7 @@ try {
     if (const char *e = getenv("PARTLS_BIT_ORDER")) c->knobs.bit_order = !strcmp(e, "identity") ? 1 : (!strcmp(e, "calibrate") ? 2 : 0);
     if (const char *e = getenv("PARTLS_ALT_MS_MAX_ROUNDS")) c->knobs.alt_ms_max_rounds = atoi(e);
     if (const char *e = getenv("PARTLS_ALT_MS_CHUNK")) c->knobs.alt_ms_chunk = atoll(e);
+    if (const char *e = getenv("PARTLS_TOP_PIECE")) c->knobs.top_piece = atoll(e);
     if (const char *e = getenv("PARTLS_KKT_TOL")) c->knobs.kkt_tol = atof(e);
     if (const char *e = getenv("PARTLS_NEAR_TIE_REL")) c->knobs.near_tie_rel = atof(e);
     if (const char *e = getenv("PARTLS_CAL_WB")) c->knobs.cal_wb = atof(e);

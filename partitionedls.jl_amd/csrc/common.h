@@ -183,9 +183,30 @@ hipError_t launch_pattern_gather(const double *in, int64_t npat, int kbits, cons
 // partls_opt_models (models.hip): the sweep's scaled solutions of Gray indices [g0, g0 + cnt) -> reference pattern, raw alpha (in place
 // over the solution rows, ld n = M + 1), cleanupResult's alpha / beta / t; out = [pattern (cnt int64) | optval (cnt) | t (cnt) |
 // alpha (cnt x M) | beta (cnt x K)].  A row whose objective is NaN (pivot cap) gets NaN everywhere.
+// glist (optional, device, cnt): row i is Gray index glist[i] instead of g0 + i (partls_opt_top's compact rows)
 hipError_t launch_models_cleanup(double *sol, const double *obj, int64_t g0, int64_t cnt, int M, int K, int kbits, const BitOrder &order,
                                  bool order_identity, const int *perm, const double *scale, const uint64_t *mask_aug, bool want_raw,
-                                 double *out, hipStream_t s);
+                                 double *out, hipStream_t s, const int64_t *glist = nullptr);
+
+// partls_opt_top / partls_opt_top_select (topk.hip): the k smallest of obj[0 .. cnt) (device; Gray indices g0 + i) by (objective with
+// -0 = +0, reference index), NaN never selected, in that order.  work: topk_work_bytes(kk) device bytes, kk = min(k, cnt); after
+// launch_topk_select its first four 8-byte words are [threshold hi | threshold lo | 0 | count] and out_idx / out_pat hold the selected
+// positions and their reference indices.  launch_topk_gather: rows out_idx[i] of `rows` (cnt x n) -> crow (kk x n), their objectives ->
+// cobj and Gray indices -> glist; rows at and beyond the count get a NaN objective.
+constexpr int64_t TOPK_MAX_K = PARTLS_OPT_TOP_MAX_K;
+constexpr size_t  TOPK_STATE_BYTES = 2048;
+struct TopkWork { uint64_t *sel_hi, *sel_lo; int64_t *sel_idx, *out_idx, *out_pat; };
+inline TopkWork topk_work(void *work, int64_t kk)
+{
+    uint64_t *b = reinterpret_cast<uint64_t *>(static_cast<char *>(work) + TOPK_STATE_BYTES);
+    const size_t k = (size_t)kk;
+    return {b, b + k, reinterpret_cast<int64_t *>(b + 2 * k), reinterpret_cast<int64_t *>(b + 3 * k), reinterpret_cast<int64_t *>(b + 4 * k)};
+}
+size_t     topk_work_bytes(int64_t kk);
+hipError_t launch_topk_select(const double *obj, int64_t cnt, int64_t g0, int64_t k, int kbits, const BitOrder &order, bool order_identity,
+                              void *work, hipStream_t s);
+hipError_t launch_topk_gather(const double *rows, const double *obj, int n, int64_t g0, int64_t cnt, int64_t kk, const void *work, double *crow,
+                              double *cobj, int64_t *glist, hipStream_t s);
 
 // BnB node batches (misc.hip): per-variable constraint codes of the nodes (pat, free) and (bound, branch) from their solutions
 hipError_t launch_bnb_codes(const uint64_t *mask_tab, int n, const uint64_t *pat, const uint64_t *free_, int cnt, int8_t *codes, hipStream_t s);

@@ -137,6 +137,7 @@ struct partls_knobs {
     bool cv_serial = false;      // PARTLS_CV_SERIAL: partls_cv_opt sweeps its problems one after another through partls_opt_sweep (A/B tests, timing)
     bool resample_serial = false; // PARTLS_RESAMPLE_SERIAL: the same for partls_opt_weightings (resample.hip)
     int pair = -1;               // PARTLS_PAIR: 0 / 1 force the pair walk of the 512-thread register kernel off / on; -1 automatic (sweep_pairs, sweep_setup.hip)
+    long long top_piece = 0;     // PARTLS_TOP_PIECE: patterns per piece of partls_opt_top (0: what PARTLS_OPT_MODELS_PIECE_BYTES admits); tests
     int bit_order = 0;           // PARTLS_BIT_ORDER: 0 automatic (calibrate when the sweep is long enough to repay it), "identity" = 1
                                  // (group k on Gray bit k), "calibrate" = 2 (always measure; small problems in the tests)
 };
@@ -195,6 +196,9 @@ struct partls_ctx {
     // partls_opt_models: one piece's scaled rows + objectives, its cleaned outputs, the export's own counters, and their page-locked staging
     partls::DevBuf mdlRows, mdlOut, mdlCtr;
     partls::PinnedDoubles mdlStage;
+    // partls_opt_top (topk.hip) shares them (mdlRows: a piece's rows + objectives; mdlOut: the cleaned outputs of its k
+    // rows) and adds: topWork, the selection's state and survivor lists; topRows, the k selected rows, objectives and Gray indices
+    partls::DevBuf topWork, topRows;
     // called between the Gram build and the tableau preparation (partls_fit_opt_multi: the Gram products of the row blocks are summed)
     std::function<partls_status(partls_ctx *)> gram_hook;
     partls::PinnedDoubles amsHostIn, amsHostOut;   // ... of an iteration of partls_alt_multistart: the active list up, the records back

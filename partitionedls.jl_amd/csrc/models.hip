@@ -19,7 +19,8 @@ static constexpr int MD_THREADS = 64;
 __global__ __launch_bounds__(MD_THREADS) void models_cleanup_kernel(double *__restrict__ sol, const double *__restrict__ obj, int64_t g0,
                                                                     int64_t cnt, int M, int K, int kbits, BitOrder order, int order_identity,
                                                                     const int *__restrict__ perm, const double *__restrict__ scale,
-                                                                    const uint64_t *__restrict__ mask_aug, int want_raw, double *__restrict__ out)
+                                                                    const uint64_t *__restrict__ mask_aug, int want_raw, double *__restrict__ out,
+                                                                    const int64_t *__restrict__ glist)
 {
     extern __shared__ double md_smem[];
     const int n = M + 1, lane = threadIdx.x;
@@ -32,7 +33,7 @@ __global__ __launch_bounds__(MD_THREADS) void models_cleanup_kernel(double *__re
     double *oopt = out + cnt, *ot = out + 2 * cnt, *oal = out + 3 * cnt, *obe = oal + (size_t)cnt * M;
     __syncthreads();
     for (int64_t i = blockIdx.x; i < cnt; i += gridDim.x) {
-        const uint64_t g = (uint64_t)(g0 + i), q = g ^ (g >> 1);
+        const uint64_t g = (uint64_t)(glist ? glist[i] : g0 + i), q = g ^ (g >> 1);   // glist: partls_opt_top's compact rows
         uint64_t b = q;
         if (!order_identity) {
             b = 0;
@@ -80,13 +81,13 @@ __global__ __launch_bounds__(MD_THREADS) void models_cleanup_kernel(double *__re
 
 hipError_t launch_models_cleanup(double *sol, const double *obj, int64_t g0, int64_t cnt, int M, int K, int kbits, const BitOrder &order,
                                  bool order_identity, const int *perm, const double *scale, const uint64_t *mask_aug, bool want_raw,
-                                 double *out, hipStream_t s)
+                                 double *out, hipStream_t s, const int64_t *glist)
 {
     if (cnt <= 0) return hipSuccess;
     const size_t shmem = ((size_t)2 * (M + 1) + (size_t)M + (size_t)K) * sizeof(double);
     const int grid = (int)(cnt < 16384 ? cnt : 16384);
     hipLaunchKernelGGL(models_cleanup_kernel, dim3(grid), dim3(MD_THREADS), shmem, s, sol, obj, g0, cnt, M, K, kbits, order,
-                       order_identity ? 1 : 0, perm, scale, mask_aug, want_raw ? 1 : 0, out);
+                       order_identity ? 1 : 0, perm, scale, mask_aug, want_raw ? 1 : 0, out, glist);
     return hipGetLastError();
 }
 

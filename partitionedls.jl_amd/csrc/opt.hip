@@ -342,27 +342,64 @@ static void copy_rows(double *dst, int64_t ld_dst, const double *src, int64_t wi
     });
 }
 
-partls_status partls_opt_models(partls_ctx *c, int64_t g_begin, int64_t g_end, int64_t *pattern, double *optval, double *raw_alpha,
-                                int64_t ld_raw, double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t,
-                                int64_t *n_unconverged, int64_t *n_vetoes)
-try {
-    if (!c || !c->prepared) { set_error("partls_opt_models: context not prepared"); return PARTLS_ERR_STATE; }
-    if (!c->faithful) { set_error("partls_opt_models needs a context prepared with PARTLS_OPT_FAITHFUL_INTERCEPT"); return PARTLS_ERR_STATE; }
-    if (!opt_range_ok(c, "partls_opt_models")) return PARTLS_ERR_UNSUPPORTED;
+// What partls_opt_models and partls_opt_top share.  export_begin: the preconditions and range rules (who: the entry's name in the messages),
+// g_end = -1 resolved, the counters zeroed, the device selected and the visiting order fixed; *empty: an empty range, nothing to do.
+static partls_status export_begin(partls_ctx *c, const char *who, int64_t g_begin, int64_t *g_end_io, const int64_t *pattern,
+                                  const double *raw_alpha, int64_t ld_raw, const double *alpha, int64_t ld_alpha, const double *beta,
+                                  int64_t ld_beta, const double *t, int64_t *n_unconverged, int64_t *n_vetoes, bool *empty)
+{
+    if (!c || !c->prepared) { set_error("%s: context not prepared", who); return PARTLS_ERR_STATE; }
+    if (!c->faithful) { set_error("%s needs a context prepared with PARTLS_OPT_FAITHFUL_INTERCEPT", who); return PARTLS_ERR_STATE; }
+    if (!opt_range_ok(c, who)) return PARTLS_ERR_UNSUPPORTED;
     const int64_t npat = (int64_t)1 << c->kbits, M = c->M, K = c->K;
+    int64_t g_end = *g_end_io;
     if (g_end < 0) g_end = npat;
-    if (g_begin < 0 || g_begin > g_end || g_end > npat) { set_error("partls_opt_models: bad Gray-index range [%lld,%lld)", (long long)g_begin, (long long)g_end); return PARTLS_ERR_BAD_ARG; }
-    if (!pattern) { set_error("partls_opt_models: pattern is NULL"); return PARTLS_ERR_BAD_ARG; }
-    if ((alpha || beta || t) && !(alpha && beta && t)) { set_error("partls_opt_models: alpha, beta and t go together (all three or none)"); return PARTLS_ERR_BAD_ARG; }
-    if ((raw_alpha && ld_raw < M + 1) || (alpha && (ld_alpha < M || ld_beta < K))) { set_error("partls_opt_models: leading dimension too small"); return PARTLS_ERR_BAD_ARG; }
+    if (g_begin < 0 || g_begin > g_end || g_end > npat) { set_error("%s: bad Gray-index range [%lld,%lld)", who, (long long)g_begin, (long long)g_end); return PARTLS_ERR_BAD_ARG; }
+    if (!pattern) { set_error("%s: pattern is NULL", who); return PARTLS_ERR_BAD_ARG; }
+    if ((alpha || beta || t) && !(alpha && beta && t)) { set_error("%s: alpha, beta and t go together (all three or none)", who); return PARTLS_ERR_BAD_ARG; }
+    if ((raw_alpha && ld_raw < M + 1) || (alpha && (ld_alpha < M || ld_beta < K))) { set_error("%s: leading dimension too small", who); return PARTLS_ERR_BAD_ARG; }
     if (n_unconverged) *n_unconverged = 0;
     if (n_vetoes) *n_vetoes = 0;
     PARTLS_HIP_CHECK(hipSetDevice(c->device));
-    if (g_begin == g_end) return PARTLS_OK;
+    *g_end_io = g_end;
+    *empty = g_begin == g_end;
+    if (*empty) return PARTLS_OK;
     if (!c->order_ready) {
         partls_status st = calibrate_bit_order(c);
         if (st != PARTLS_OK) return st;
     }
+    return PARTLS_OK;
+}
+
+// export_piece: one piece [p0, p0 + cnt) of the range — one sweep with the export instantiation of the kernel on sweep_plan's plan for cnt
+// patterns; the scaled rows go to rows (ld n), the objectives to obj, the counters to the head of mdlCtr.  On the context's stream.
+static partls_status export_piece(partls_ctx *c, int64_t p0, int64_t cnt, double *rows, double *obj, const char *who)
+{
+    int64_t chain_len = 0;
+    int grid = 0;
+    if (!sweep_plan(c, cnt, &chain_len, &grid, who)) return PARTLS_ERR_UNSUPPORTED;
+    // the kernel's per-workgroup block (sweep_block without the runner-up columns): only its counters are read here
+    PARTLS_HIP_CHECK(c->mdlCtr.ensure(sizeof(double) * sweep_block_words(grid, false)));
+    PARTLS_HIP_CHECK(hipMemsetAsync(c->mdlCtr.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    const partls_status ss = ensure_sweep_scratch(c, grid);
+    if (ss != PARTLS_OK) return ss;
+    SweepParams p = sweep_params(c, /*internal_order=*/true);
+    p.g_begin = p0; p.g_end = p0 + cnt; p.chain_len = chain_len;
+    bind_sweep_block(p, c->mdlCtr.as<double>(), grid, false);
+    p.node_sol = rows; p.node_obj2 = obj; p.node_ld = c->n;
+    PARTLS_HIP_CHECK(launch_any_sweep(c, p, grid, /*models=*/true));
+    return PARTLS_OK;
+}
+
+partls_status partls_opt_models(partls_ctx *c, int64_t g_begin, int64_t g_end, int64_t *pattern, double *optval, double *raw_alpha,
+                                int64_t ld_raw, double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t,
+                                int64_t *n_unconverged, int64_t *n_vetoes)
+try {
+    bool empty = false;
+    const partls_status bs = export_begin(c, "partls_opt_models", g_begin, &g_end, pattern, raw_alpha, ld_raw, alpha, ld_alpha, beta, ld_beta, t,
+                                          n_unconverged, n_vetoes, &empty);
+    if (bs != PARTLS_OK || empty) return bs;
+    const int64_t M = c->M, K = c->K;
     const int n = c->n;
     const int64_t total = g_end - g_begin;
     const size_t out_w = 3 + (size_t)M + (size_t)K;                 // cleaned output per pattern: pattern, optval, t, alpha, beta
@@ -378,20 +415,9 @@ try {
     unsigned long long unconv = 0, vetoes = 0;
     for (int64_t p0 = g_begin; p0 < g_end; p0 += piece) {
         const int64_t cnt = std::min<int64_t>(piece, g_end - p0);
-        int64_t chain_len = 0;
-        int grid = 0;
-        if (!sweep_plan(c, cnt, &chain_len, &grid, "partls_opt_models")) return PARTLS_ERR_UNSUPPORTED;
-        // the kernel's per-workgroup block (sweep_block without the runner-up columns): only its counters are read here
-        PARTLS_HIP_CHECK(c->mdlCtr.ensure(sizeof(double) * sweep_block_words(grid, false)));
-        PARTLS_HIP_CHECK(hipMemsetAsync(c->mdlCtr.p, 0, 4 * sizeof(unsigned long long), c->stream));
-        const partls_status ss = ensure_sweep_scratch(c, grid);
-        if (ss != PARTLS_OK) return ss;
         double *rows = c->mdlRows.as<double>(), *obj = rows + (size_t)cnt * n, *out = c->mdlOut.as<double>();
-        SweepParams p = sweep_params(c, /*internal_order=*/true);
-        p.g_begin = p0; p.g_end = p0 + cnt; p.chain_len = chain_len;
-        bind_sweep_block(p, c->mdlCtr.as<double>(), grid, false);
-        p.node_sol = rows; p.node_obj2 = obj; p.node_ld = n;
-        PARTLS_HIP_CHECK(launch_any_sweep(c, p, grid, /*models=*/true));
+        const partls_status es = export_piece(c, p0, cnt, rows, obj, "partls_opt_models");
+        if (es != PARTLS_OK) return es;
         PARTLS_HIP_CHECK(launch_models_cleanup(rows, obj, p0, cnt, (int)M, (int)K, c->kbits, c->order, c->order_identity, c->permP,
                                                c->scale.as<double>(), c->maskAugD.as<uint64_t>(), raw_alpha != nullptr, out, c->stream));
         double *st = c->mdlStage.data();
@@ -416,6 +442,158 @@ try {
     }
     if (n_unconverged) *n_unconverged = (int64_t)unconv;
     if (n_vetoes) *n_vetoes = (int64_t)vetoes;
+    return PARTLS_OK;
+}
+PARTLS_ABI_GUARD
+
+// The k best patterns of a Gray-index range (include/partls.h).  Per piece, all on the context's stream: the export
+// sweep (export_piece), the selection, sort and gather of its k best rows (topk.hip), the cleanup of those rows (models.hip with the
+// list of their Gray indices), one copy back.  The host keeps the k best of the pieces' lists by the same order.
+static bool top_before(double oa, int64_t pa, double ob, int64_t pb) { return oa < ob || (oa == ob && pa < pb); }
+
+partls_status partls_opt_top(partls_ctx *c, int64_t g_begin, int64_t g_end, int64_t k, int64_t *pattern, double *optval, double *raw_alpha,
+                             int64_t ld_raw, double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t, int64_t *count,
+                             int64_t *n_unconverged, int64_t *n_vetoes)
+try {
+    bool empty = false;
+    const partls_status bs = export_begin(c, "partls_opt_top", g_begin, &g_end, pattern, raw_alpha, ld_raw, alpha, ld_alpha, beta, ld_beta, t,
+                                          n_unconverged, n_vetoes, &empty);
+    if (bs != PARTLS_OK) return bs;
+    if (!optval || !count) { set_error("partls_opt_top: optval or count is NULL"); return PARTLS_ERR_BAD_ARG; }
+    if (k < 1 || k > PARTLS_OPT_TOP_MAX_K) { set_error("partls_opt_top: k = %lld outside 1 .. %d", (long long)k, PARTLS_OPT_TOP_MAX_K); return PARTLS_ERR_BAD_ARG; }
+    *count = 0;
+    if (empty) return PARTLS_OK;
+    const int64_t M = c->M, K = c->K;
+    const int n = c->n;
+    const int64_t total = g_end - g_begin;
+    const size_t out_w = 3 + (size_t)M + (size_t)K;                 // cleaned output per selected pattern, as partls_opt_models lays it out
+    int64_t cap = std::max<int64_t>(1, (int64_t)(PARTLS_OPT_MODELS_PIECE_BYTES / (((size_t)n + 1) * sizeof(double))));
+    if (c->knobs.top_piece > 0) cap = (int64_t)c->knobs.top_piece;
+    cap = std::min<int64_t>(cap, (int64_t)1 << 30);                   // the selection counts in 32 bits
+    const int64_t npieces = (total + cap - 1) / cap;
+    const int64_t piece = (total + npieces - 1) / npieces;
+    const int64_t kmax = std::min<int64_t>(k, piece);                 // rows a piece can contribute
+    PARTLS_HIP_CHECK(c->mdlRows.ensure((size_t)piece * (n + 1) * sizeof(double)));
+    PARTLS_HIP_CHECK(c->mdlOut.ensure((size_t)kmax * out_w * sizeof(double)));
+    PARTLS_HIP_CHECK(c->topWork.ensure(topk_work_bytes(kmax)));
+    PARTLS_HIP_CHECK(c->topRows.ensure((size_t)kmax * (n + 2) * sizeof(double)));
+    const size_t stage_words = 8 + (size_t)kmax * (out_w + (raw_alpha ? (size_t)n : 0));
+    PARTLS_HIP_CHECK(c->mdlStage.resize(stage_words));
+    if (!c->use_reg) c->coop_state_valid = false;                    // the global-memory kernels overwrite the shared tableau scratch
+    unsigned long long unconv = 0, vetoes = 0;
+    // the best rows so far, in order: [optval | pattern | t | alpha (M) | beta (K) | raw (n)] per row
+    const size_t roww = 3 + (alpha ? (size_t)(M + K) : 0) + (raw_alpha ? (size_t)n : 0);
+    std::vector<double> best, next;
+    int64_t nbest = 0;
+    for (int64_t p0 = g_begin; p0 < g_end; p0 += piece) {
+        const int64_t cnt = std::min<int64_t>(piece, g_end - p0), kk = std::min<int64_t>(k, cnt);
+        double *rows = c->mdlRows.as<double>(), *obj = rows + (size_t)cnt * n, *out = c->mdlOut.as<double>();
+        double *crow = c->topRows.as<double>(), *cobj = crow + (size_t)kk * n;
+        int64_t *glist = reinterpret_cast<int64_t *>(cobj + kk);
+        const partls_status es = export_piece(c, p0, cnt, rows, obj, "partls_opt_top");
+        if (es != PARTLS_OK) return es;
+        PARTLS_HIP_CHECK(launch_topk_select(obj, cnt, p0, k, c->kbits, c->order, c->order_identity, c->topWork.p, c->stream));
+        PARTLS_HIP_CHECK(launch_topk_gather(rows, obj, n, p0, cnt, kk, c->topWork.p, crow, cobj, glist, c->stream));
+        PARTLS_HIP_CHECK(launch_models_cleanup(crow, cobj, p0, kk, (int)M, (int)K, c->kbits, c->order, c->order_identity, c->permP,
+                                               c->scale.as<double>(), c->maskAugD.as<uint64_t>(), raw_alpha != nullptr, out, c->stream, glist));
+        double *st = c->mdlStage.data();
+        PARTLS_HIP_CHECK(hipMemcpyAsync(st, c->mdlCtr.p, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(st + 4, c->topWork.p, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(st + 8, out, (size_t)kk * out_w * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (raw_alpha) PARTLS_HIP_CHECK(hipMemcpyAsync(st + 8 + (size_t)kk * out_w, crow, (size_t)kk * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        unsigned long long cn[8];
+        std::memcpy(cn, st, sizeof(cn));
+        unconv += cn[0];
+        vetoes += cn[2];
+        const int64_t got = (int64_t)cn[7];                          // TopState::count: min(k, converged patterns of the piece)
+        if (got < 0 || got > kk) { set_error("partls_opt_top: the selection reported %lld rows of at most %lld", (long long)got, (long long)kk); return PARTLS_ERR_HIP; }
+        // merge: both lists are in order; keep the first k
+        const double *o = st + 8;
+        const int64_t *opat = reinterpret_cast<const int64_t *>(o);
+        const double *oopt = o + kk, *ot = o + 2 * kk, *oal = o + 3 * kk, *obe = oal + (size_t)kk * M, *oraw = o + (size_t)kk * out_w;
+        const int64_t keep = std::min<int64_t>(k, nbest + got);
+        next.resize((size_t)keep * roww);
+        int64_t ia = 0, ib = 0;
+        for (int64_t r = 0; r < keep; ++r) {
+            double *d = next.data() + (size_t)r * roww;
+            const double *a = best.data() + (size_t)ia * roww;
+            int64_t apat = 0;
+            if (ia < nbest) std::memcpy(&apat, a + 1, sizeof(apat));
+            const bool take_a = ia < nbest && (ib >= got || top_before(a[0], apat, oopt[ib], opat[ib]));
+            if (take_a) { std::memcpy(d, a, roww * sizeof(double)); ++ia; continue; }
+            d[0] = oopt[ib];
+            std::memcpy(d + 1, &opat[ib], sizeof(int64_t));
+            d[2] = ot[ib];
+            double *e = d + 3;
+            if (alpha) {
+                std::memcpy(e, oal + (size_t)ib * M, (size_t)M * sizeof(double));
+                std::memcpy(e + M, obe + (size_t)ib * K, (size_t)K * sizeof(double));
+                e += M + K;
+            }
+            if (raw_alpha) std::memcpy(e, oraw + (size_t)ib * n, (size_t)n * sizeof(double));
+            ++ib;
+        }
+        best.swap(next);
+        nbest = keep;
+    }
+    for (int64_t r = 0; r < nbest; ++r) {
+        const double *d = best.data() + (size_t)r * roww, *e = d + 3;
+        optval[r] = d[0];
+        std::memcpy(&pattern[r], d + 1, sizeof(int64_t));
+        if (alpha) {
+            t[r] = d[2];
+            std::memcpy(alpha + (size_t)r * ld_alpha, e, (size_t)M * sizeof(double));
+            std::memcpy(beta + (size_t)r * ld_beta, e + M, (size_t)K * sizeof(double));
+            e += M + K;
+        }
+        if (raw_alpha) std::memcpy(raw_alpha + (size_t)r * ld_raw, e, (size_t)n * sizeof(double));
+    }
+    *count = nbest;
+    if (n_unconverged) *n_unconverged = (int64_t)unconv;
+    if (n_vetoes) *n_vetoes = (int64_t)vetoes;
+    return PARTLS_OK;
+}
+PARTLS_ABI_GUARD
+
+partls_status partls_opt_top_select(partls_ctx *c, const double *obj, int64_t cnt, int64_t g0, int64_t k, int64_t *index, int64_t *pattern,
+                                    double *optval, int64_t *count)
+try {
+    if (!c || !c->prepared) { set_error("partls_opt_top_select: context not prepared"); return PARTLS_ERR_STATE; }
+    if (!opt_range_ok(c, "partls_opt_top_select")) return PARTLS_ERR_UNSUPPORTED;
+    if (!obj || !index || !pattern || !optval || !count) { set_error("partls_opt_top_select: NULL argument"); return PARTLS_ERR_BAD_ARG; }
+    if (k < 1 || k > PARTLS_OPT_TOP_MAX_K) { set_error("partls_opt_top_select: k = %lld outside 1 .. %d", (long long)k, PARTLS_OPT_TOP_MAX_K); return PARTLS_ERR_BAD_ARG; }
+    const int64_t npat = (int64_t)1 << c->kbits;
+    if (cnt < 0 || cnt >= ((int64_t)1 << 31) || g0 < 0 || g0 > npat || cnt > npat - g0) { set_error("partls_opt_top_select: bad range g0 = %lld, cnt = %lld", (long long)g0, (long long)cnt); return PARTLS_ERR_BAD_ARG; }
+    *count = 0;
+    PARTLS_HIP_CHECK(hipSetDevice(c->device));
+    if (cnt == 0) return PARTLS_OK;
+    if (!c->order_ready) {
+        partls_status st = calibrate_bit_order(c);
+        if (st != PARTLS_OK) return st;
+    }
+    const int64_t kk = std::min<int64_t>(k, cnt);
+    PARTLS_HIP_CHECK(c->mdlRows.ensure((size_t)cnt * sizeof(double)));
+    PARTLS_HIP_CHECK(c->topWork.ensure(topk_work_bytes(kk)));
+    PARTLS_HIP_CHECK(c->mdlStage.resize(4 + 2 * (size_t)kk));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->mdlRows.p, obj, (size_t)cnt * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    PARTLS_HIP_CHECK(launch_topk_select(c->mdlRows.as<double>(), cnt, g0, k, c->kbits, c->order, c->order_identity, c->topWork.p, c->stream));
+    const TopkWork w = topk_work(c->topWork.p, kk);
+    double *st = c->mdlStage.data();
+    PARTLS_HIP_CHECK(hipMemcpyAsync(st, c->topWork.p, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(st + 4, w.out_idx, 2 * (size_t)kk * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));   // out_idx | out_pat
+    PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    unsigned long long hd[4];
+    std::memcpy(hd, st, sizeof(hd));
+    const int64_t got = (int64_t)hd[3];
+    if (got < 0 || got > kk) { set_error("partls_opt_top_select: the selection reported %lld rows of at most %lld", (long long)got, (long long)kk); return PARTLS_ERR_HIP; }
+    std::memcpy(index, st + 4, (size_t)got * sizeof(int64_t));
+    std::memcpy(pattern, st + 4 + kk, (size_t)got * sizeof(int64_t));
+    for (int64_t i = 0; i < got; ++i) {
+        if (index[i] < 0 || index[i] >= cnt) { set_error("partls_opt_top_select: selected position out of range"); return PARTLS_ERR_HIP; }
+        optval[i] = obj[index[i]];
+    }
+    *count = got;
     return PARTLS_OK;
 }
 PARTLS_ABI_GUARD

@@ -78,6 +78,28 @@ def reduce_winner(ctx, obj, pat, device=None, group=None, order_key=None):
     return gobj, gpat
 
 
+def merge_top(lists, k):
+    """The k best patterns of a sharded enumeration: lists = one Context.opt_top dict per shard (disjoint Gray ranges of the same prepared
+    problem), merged by opt_top's own order — (opt, pattern), -0.0 equal to +0.0 — into one dict of the same layout (raw_alpha when
+    every shard carries it; count, n_unconverged and n_vetoes summed).  Plain numpy, next to reduce_winner: every rank that holds all
+    lists gets the same result."""
+    import numpy as np
+    k = int(k)
+    if k < 1:
+        raise ValueError("merge_top: k must be >= 1")
+    lists = list(lists)
+    if not lists:
+        raise ValueError("merge_top: no lists")
+    keys = ["pattern", "opt", "alpha", "beta", "t"] + (["raw_alpha"] if all("raw_alpha" in r for r in lists) else [])
+    cat = {key: np.concatenate([np.asarray(r[key]) for r in lists]) for key in keys}
+    order = np.lexsort((cat["pattern"], cat["opt"] + 0.0))[:k]
+    out = {key: cat[key][order] for key in keys}
+    out["count"] = len(order)
+    out["n_unconverged"] = int(sum(r.get("n_unconverged", 0) for r in lists))
+    out["n_vetoes"] = int(sum(r.get("n_vetoes", 0) for r in lists))
+    return out
+
+
 def bnb_search(bound_fn, n_groups, rank=0, world=1, group=None, batch=512, device=None, max_nodes=None):
     """fit_BnB (BnB.jl:94-132) as a best-first search whose frontier batches are sharded across ranks.
 

@@ -10,7 +10,7 @@ A line is `symbol(arg, ...) -> status`: scalars by value, handles by the order o
 `name[count]=<first 8 hex digits of the sha1 of their bytes>` with the count taken from the call's own scalar arguments (from the handle's
 last prepare where the call carries none), device addresses by value, output pointers as `out`, null pointers as `NULL`.  The fake
 writes nothing to the outputs except the scalars control flow reads (handles, partls_opt_num_patterns, the sweep's best_pattern,
-n_unconverged = 0, partls_multi_size, the round size of partls_frontier_next) and returns FakeLib.status[symbol] (default 0).
+n_unconverged = 0, partls_multi_size, the round size of partls_frontier_next, partls_opt_top's patterns and counts) and returns FakeLib.status[symbol] (default 0).
 partls_destroy and its kin are not written down: most of them run from __del__, when the garbage collector pleases.
 tests/test_api_call_trace.py compares the trace with tests/golden/api_call_trace.txt."""
 import argparse
@@ -56,6 +56,8 @@ SPEC = {
     "partls_opt_merge_candidates": "h n objs:d:n pats:q:n out out",
     "partls_opt_pattern": "h pattern out out",
     "partls_opt_models": "h g_begin g_end out out out ld_raw out ld_alpha out ld_beta out out out",
+    "partls_opt_top": "h g_begin g_end k out out out ld_raw out ld_alpha out ld_beta out out out out",
+    "partls_opt_top_select": "h obj:d:cnt cnt g0 k out out out out",
     "partls_cv_opt": f"h {_XY} dev {_P} {_CV}",
     "partls_cv_opt_weighted": f"h {_XY} w:d:N dev {_P} {_CV}",
     "partls_opt_weightings": f"h {_XY} dev {_P} w:d:ldW*B ldW B eta flags out ld_alpha out ld_beta out out out out out out",
@@ -116,6 +118,7 @@ class FakeLib:
         self.lines = []
         self.status = {}               # symbol -> status it returns (default 0)
         self.best_pattern = 1          # what partls_opt_sweep reports
+        self.top_vetoes = 0            # what partls_opt_top reports in n_vetoes
         self.names = {}                # handle -> c1 / m1 / m1.r0 / f1
         self.state = {}                # handle -> the scalars later calls on it are sized by (M, K, npat; total of a frontier round)
         self.ranks = {}                # multi handle -> its rank handles
@@ -202,6 +205,12 @@ class FakeLib:
             return env.get("npat", 0)
         elif name == "partls_opt_sweep":
             args[4]._obj.value, args[6]._obj.value = self.best_pattern, 0
+        elif name == "partls_opt_top":                       # patterns 0, 1, ... of the range, as many as it holds up to k
+            g_end = env["g_end"] if env["g_end"] >= 0 else env.get("npat", 0)
+            got = max(0, min(env["k"], g_end - env["g_begin"]))
+            for i in range(got):
+                args[4][i] = i
+            args[13]._obj.value, args[14]._obj.value, args[15]._obj.value = got, 0, self.top_vetoes
         elif name == "partls_frontier_next":
             args[1]._obj.value = args[2]._obj.value = self.state[h]["total"] = ROUND
         elif name == "partls_last_error":
