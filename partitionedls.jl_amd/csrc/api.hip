@@ -108,6 +108,7 @@ try {
     if (const char *e = getenv("PARTLS_PAIR")) c->knobs.pair = atoi(e) != 0 ? 1 : 0;
     if (const char *e = getenv("PARTLS_BIT_ORDER")) c->knobs.bit_order = !strcmp(e, "identity") ? 1 : (!strcmp(e, "calibrate") ? 2 : 0);
     if (const char *e = getenv("PARTLS_ALT_MS_MAX_ROUNDS")) c->knobs.alt_ms_max_rounds = atoi(e);
+    if (const char *e = getenv("PARTLS_MAX_ROUNDS")) { const int v = atoi(e); if (v >= 1) c->knobs.max_rounds = v; }
     if (const char *e = getenv("PARTLS_ALT_MS_CHUNK")) c->knobs.alt_ms_chunk = atoll(e);
     if (const char *e = getenv("PARTLS_TOP_PIECE")) c->knobs.top_piece = atoll(e);
     if (const char *e = getenv("PARTLS_KKT_TOL")) c->knobs.kkt_tol = atof(e);

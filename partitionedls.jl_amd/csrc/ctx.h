@@ -129,6 +129,7 @@ struct partls_knobs {
     bool alt_always_check = false; // PARTLS_ALT_ALWAYS_CHECK: fit(Alt) verifies its last iteration against the data even when Gershgorin certifies the Gram form (tests)
     bool print_stamps = false;   // PARTLS_PRINT_STAMPS (diagnostic build only)
     int alt_ms_max_rounds = 0;   // PARTLS_ALT_MS_MAX_ROUNDS: pivot cap of the alpha-steps of partls_alt_multistart only (0: 20 (n + 1), as everywhere); tests
+    int max_rounds = 0;          // PARTLS_MAX_ROUNDS: pivot cap of every launch that takes the default one (sweep_params; values below 1: 20 (n + 1)); tests
     long long alt_ms_chunk = 0;  // PARTLS_ALT_MS_CHUNK: starts per chunk of partls_alt_multistart (0: what fits 256 MB of per-start scratch)
     double kkt_tol = 1e-12;      // PARTLS_KKT_TOL: data-space KKT violation of the winner (units of ||x_m|| ||y||) above which fit(Opt) / fit(BnB) report
                                  // PARTLS_ERR_ILL_CONDITIONED instead of PARTLS_OK (see kkt_says_ill_conditioned, refine.hip)
@@ -286,7 +287,7 @@ partls_status load_partition(partls_ctx *c, const int64_t *P, int64_t M, int64_t
 partls_status upload_matrix(partls_ctx *c, void *dst, const void *X, int64_t N, int64_t M, int64_t ldX, size_t esz = sizeof(double));
 // ---- the set-up of a sweep launch (sweep_setup.hip): every launch of a sweep kernel goes through these
 constexpr double SWEEP_PIV_EPS = 1e-11;                      // SweepParams::piv_eps of every launch
-inline int sweep_max_rounds(int n) { return 20 * (n + 1); }  // SweepParams::max_rounds unless the caller overrides it
+inline int sweep_max_rounds(int n) { return 20 * (n + 1); }  // SweepParams::max_rounds unless PARTLS_MAX_ROUNDS or the caller overrides it
 // The fields every launch shares: n, kbits, mask, scratch (ensure it first: ensure_sweep_scratch), tol, piv_eps, max_rounds, rbit.
 // internal_order (chain mode): patterns run in the calibrated bit order — mask = maskInt and rbit = the inverse of c->order unless that
 // order is the identity; otherwise mask = maskTabP and rbit = identity.  The caller sets what is its own: the range, the chain

@@ -19,6 +19,7 @@
 // A change to kkt_violates, ExchangeRule or rank_pattern is made here AND in those places (ten with the merged scan's two; the pair walk of
 // sweep_blk.hip adds kkt_violates twice more, under the twin's signs: the scan for its violators and the scan of its priced rhs column, and
 // the ranking once more: record_twin, the bookkeeping of a priced twin).
+// tests/test_gpu_exchange_rule.py runs every copy of ExchangeRule against tests/exchange_reference.py, decision for decision.
 #pragma once
 #include "common.h"
 

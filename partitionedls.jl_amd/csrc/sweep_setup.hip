@@ -17,7 +17,7 @@ SweepParams sweep_params(const partls_ctx *c, bool internal_order)
     p.n = c->n; p.kbits = c->kbits;
     p.mask = permuted ? c->maskInt.as<uint64_t>() : c->maskTabP;
     p.scratch = c->scratch.as<double>();
-    p.tol = c->tol; p.piv_eps = SWEEP_PIV_EPS; p.max_rounds = sweep_max_rounds(c->n);
+    p.tol = c->tol; p.piv_eps = SWEEP_PIV_EPS; p.max_rounds = c->knobs.max_rounds >= 1 ? c->knobs.max_rounds : sweep_max_rounds(c->n);
     for (int k = 0; k < 40; ++k) p.rbit.gbit[k] = (uint8_t)k;
     if (permuted) for (int k = 0; k < c->kbits; ++k) p.rbit.gbit[c->order.gbit[k]] = (uint8_t)k;   // exact ties: first REFERENCE index
     return p;
