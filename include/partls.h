@@ -32,7 +32,8 @@ typedef enum {
     PARTLS_ERR_NONFINITE = 3,      /* NaN/Inf in X or y, or a column whose sum of squares overflows fp64    */
     PARTLS_ERR_NO_DEVICE = 4,      /* no HIP device / device index out of range                           */
     PARTLS_ERR_HIP = 5,            /* a HIP runtime call failed (message has the hipError string)         */
-    PARTLS_ERR_NOT_CONVERGED = 6,  /* an active-set solve hit its pivot cap                               */
+    PARTLS_ERR_NOT_CONVERGED = 6,  /* an active-set solve hit its pivot cap (fit(Opt): and PARTLS_OPT_RESCUE_CAPPED was not set, or
+                                      the rescue ran out of main passes too; partls_get_rescue_stats)   */
     PARTLS_ERR_UNSUPPORTED = 7,    /* shape outside what the kernels are built for: M > 1022 features, ldX >= 2^30, K > 61 groups,
                                       K > 39 for the 2^K enumeration of fit(Opt)                                              */
     PARTLS_ERR_STATE = 8,          /* staged calls issued out of order                                    */
@@ -46,6 +47,19 @@ typedef enum {
                                             Without it the intercept is left free and 2^K subproblems are solved: the
                                             optimum (model and objective) is identical, min over the ± pair.             */
 #define PARTLS_OPT_GENERIC_KERNEL     2u /* force the global-memory tableau kernel (testing / cross-check)               */
+#define PARTLS_OPT_RESCUE_CAPPED      4u /* a pattern that hits the pivot cap of 20 (n + 1) exchange rounds (designs that are
+                                            correlated throughout) is solved again on the device by
+                                            Lawson-Hanson from the empty basis, at most 3 n main passes
+                                            (PARTLS_RESCUE_MAX_PASSES, read at partls_create: another bound; tests), instead of
+                                            being reported: partls_opt_sweep, partls_fit_opt, partls_opt_models, partls_opt_top,
+                                            partls_opt_finish and partls_opt_pattern (see each).  A rescued pattern meets the
+                                            sweeps' own KKT test under the context's tolerance; one that runs out of main
+                                            passes stays NaN / PARTLS_ERR_NOT_CONVERGED.  A sweep or single solve without a
+                                            capped pattern runs nothing extra (the export entries add two launches per piece
+                                            that find an empty list), and without the flag nothing changes.  partls_cv_opt(_weighted),
+                                            partls_opt_weightings and partls_fit_opt_multi answer the flag with
+                                            PARTLS_ERR_UNSUPPORTED; the Alt and BnB calls on a context prepared with it
+                                            ignore it (their solves are not rescued).                                      */
 
 typedef struct partls_ctx partls_ctx;
 
@@ -124,7 +138,11 @@ partls_status partls_multi_get_timing(const partls_multi *mc, int rank, int whic
  *           per prepared problem (partls_opt_bit_order; measured on the first sweep of long enumerations, deterministic in
  *           the data, so ranks that prepared the same problem agree).  Any disjoint ranges covering [0, 2^K') visit every
  *           pattern exactly once; every pattern index that crosses this boundary is the reference's (group k = bit k).
- * finish:   solves the given pattern once more on its own, computes opt from the data, normalises (cleanupResult). */
+ * finish:   solves the given pattern once more on its own, computes opt from the data, normalises (cleanupResult).
+ * With PARTLS_OPT_RESCUE_CAPPED: a sweep that reports capped patterns walks its range a second time through the export pieces of
+ * partls_opt_models, whose capped rows the rescue kernel solves; that pass is authoritative: winner, near ties and candidates
+ * (partls_opt_candidates), all_opt and *n_unconverged (what the rescue could not solve) are its results.  finish (and
+ * partls_opt_pattern): a single solve that hits the cap is solved by the rescue kernel instead of failing. */
 partls_status partls_opt_prepare(partls_ctx *ctx, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
                                  int x_on_device, const int64_t *P, int64_t K, int64_t ldP, double eta, uint32_t flags);
 /* ---- sample weights: the same prepare for the weighted problem (MLJ's supports_weights, scikit-learn's sample_weight) ---------------
@@ -181,6 +199,9 @@ partls_status partls_opt_pattern(partls_ctx *ctx, int64_t pattern, double *raw_a
  * Accuracy: these are the Gram-form solutions that rank all_opt, not refined in data space as partls_opt_finish's are ("Every pattern's model").
  * With *n_vetoes > 0 the data has (nearly) dependent columns and the Gram form carries no guarantee: use partls_opt_finish per pattern.
  * A pattern that hit the pivot cap gets NaN in its optval and model rows. The caller re-solves it with partls_opt_finish.
+ * With PARTLS_OPT_RESCUE_CAPPED the capped rows of every piece are solved on the device by the rescue kernel before the cleanup: they
+ * are ordinary rows then, *n_unconverged counts only what the rescue could not solve (those rows stay NaN) and *n_vetoes includes the
+ * rescue's refusals.
  * The range is processed in pieces whose device buffers stay below PARTLS_OPT_MODELS_PIECE_BYTES; a range whose buffers fit is one piece
  * on the chain plan of partls_opt_sweep for the same range.  To spread one export over several devices, give each device's context a
  * disjoint Gray range of the same prepared problem (equal visiting order: compare partls_opt_bit_order).
@@ -197,7 +218,8 @@ partls_status partls_opt_models(partls_ctx *ctx, int64_t g_begin, int64_t g_end,
  * three or none) is the i-th best pattern of [g_begin, g_end) in the total order
  *     a before b  iff  optval_a < optval_b, or optval_a == optval_b as doubles (-0.0 equals +0.0; +inf is an ordinary value) and
  *                      pattern_a < pattern_b   (pattern: the reference index b).
- * A pattern that hit the pivot cap (NaN objective) is never selected, only counted in *n_unconverged.
+ * A pattern that hit the pivot cap (NaN objective) is never selected, only counted in *n_unconverged.  With PARTLS_OPT_RESCUE_CAPPED
+ * the capped patterns of a piece are rescued before the selection (see partls_opt_models), so they are selectable.
  * *count = min(k, converged patterns of the range); rows at and beyond *count are not written.  Two calls with the same arguments
  * return the same bits.  The models are the Gram-form models of partls_opt_models, bit for bit the rows it returns for the same
  * patterns when both run the same piece; accuracy and the meaning of *n_vetoes are partls_opt_models'.
@@ -465,7 +487,8 @@ typedef enum {
     PARTLS_T_FINISH = 3,    /* winner re-solve + residual from data   */
     PARTLS_T_CALIB = 4,     /* bit-order calibration of the sweep (0 when it did not run) */
     PARTLS_T_OOB = 5,       /* out-of-bag pass of partls_opt_weightings (0 after every other call) */
-    PARTLS_T_COUNT = 6
+    PARTLS_T_RESCUE = 6,    /* PARTLS_OPT_RESCUE_CAPPED: the last launch of the rescue kernel (the last piece's; 0 when none ran) */
+    PARTLS_T_COUNT = 7
 } partls_timer;
 partls_status partls_get_timing(const partls_ctx *ctx, partls_timer which, double *ms);
 /* host -> device upload of X inside the last prepare / fit on this context: wall time (ms) and bytes (0 / 0 when the inputs were device
@@ -478,6 +501,11 @@ partls_status partls_get_pivots(const partls_ctx *ctx, int64_t *pivots);
 /* entering pivots the last partls_opt_sweep refused under the leave-one-out dependence rule (0 on well-conditioned data; a
  * large count says the data are rank deficient on the unit-diagonal scale — see DESIGN.md §4, numerical notes) */
 partls_status partls_get_vetoes(const partls_ctx *ctx, int64_t *vetoes);
+/* PARTLS_OPT_RESCUE_CAPPED: what the rescue kernel did in the last partls_opt_sweep, partls_opt_models or partls_opt_top of the context
+ * and in the partls_opt_finish / partls_opt_pattern calls since (a partls_fit_opt: its sweep and its finish; zeros when nothing capped,
+ * after a prepare, or without the flag): patterns it solved, the pivots it spent on all of them, patterns that ran out of main
+ * passes (each optional) */
+partls_status partls_get_rescue_stats(const partls_ctx *ctx, int64_t *rescued, int64_t *pivots, int64_t *failed);
 /* pivot blocks the cooperative kernel (one node on a global-memory tableau, n > 288) exchanged in the last single-node solve; 0 when
  * that solve ran on another kernel — including the one-workgroup retry after a grid-barrier timeout on a crowded device */
 partls_status partls_get_blocks(const partls_ctx *ctx, int64_t *blocks);

@@ -10,7 +10,8 @@ CSRC = os.path.join(_HERE, "csrc")
 OK, ERR_BAD_ARG, ERR_BAD_PARTITION, ERR_NONFINITE, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_CONVERGED, ERR_UNSUPPORTED, ERR_STATE, ERR_ILL_CONDITIONED = range(10)
 OPT_FAITHFUL_INTERCEPT = 1
 OPT_GENERIC_KERNEL = 2
-T_GRAM, T_PREP, T_SWEEP, T_FINISH, T_CALIB, T_OOB = range(6)
+OPT_RESCUE_CAPPED = 4   # capped patterns of fit(Opt) are solved again by Lawson-Hanson on the device (PARTLS_OPT_RESCUE_CAPPED, partls.h)
+T_GRAM, T_PREP, T_SWEEP, T_FINISH, T_CALIB, T_OOB, T_RESCUE = range(7)
 ROUTE_REG_256, ROUTE_REG_512, ROUTE_DEFERRED, ROUTE_EAGER = range(1, 5)
 # partls_predict_many: models per pass over X, most models / ranks of a call, bytes of a row chunk's N x B intermediate (partls.h)
 PREDICT_MANY_CHUNK, PREDICT_MANY_MAX_B, PREDICT_MANY_BYTES = 16, 4096, 64 << 20
@@ -97,6 +98,7 @@ SYMBOLS = [
     ("partls_get_gram", C.c_int, [C.c_void_p, _dp]),
     ("partls_get_pivots", C.c_int, [C.c_void_p, _ip]),
     ("partls_get_vetoes", C.c_int, [C.c_void_p, _ip]),
+    ("partls_get_rescue_stats", C.c_int, [C.c_void_p, _ip, _ip, _ip]),
     ("partls_get_blocks", C.c_int, [C.c_void_p, _ip]),
     ("partls_get_kkt_violation", C.c_int, [C.c_void_p, _dp, _dp]),
     ("partls_get_near_ties", C.c_int, [C.c_void_p, _ip]),

@@ -654,6 +654,13 @@ class Context:
     def vetoes(self):
         return self._count(L.lib().partls_get_vetoes)
 
+    def rescue_stats(self):
+        """lowlevel.OPT_RESCUE_CAPPED: Report(rescued, pivots, failed) of the rescue kernel in the last opt_sweep, opt_models or opt_top
+        and the opt_finish / opt_pattern calls since (include/partls.h: partls_get_rescue_stats)"""
+        r = C.c_int64(); p = C.c_int64(); f = C.c_int64()
+        _check(L.lib().partls_get_rescue_stats(self._h, C.byref(r), C.byref(p), C.byref(f)))
+        return Report(rescued=r.value, pivots=p.value, failed=f.value)
+
     def blocks(self):
         """pivot blocks of the cooperative kernel in the last single-node solve (0: the solve ran on another kernel)"""
         return self._count(L.lib().partls_get_blocks)
@@ -1077,7 +1084,7 @@ def _top_patterns(ctx, k, Pout):
 
 def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="nnls", returnAllSolutions=False, rng=None,
         alpha0=None, beta0=None, device=0, devices=None, faithful_intercept=False, generic_kernel=False, on_ill_conditioned="warn",
-        weights=None, restarts=None, top=None):
+        weights=None, restarts=None, top=None, rescue=False):
     """fit(::Type{Opt|Alt|BnB}, X, y, P; η, ...) -> (PartLSFitResult, None, Report)   [Opt.jl:73, Alt.jl:50, BnB.jl:30]
 
     η/eta: regularisation (default 0.0);  Alt: ϵ/eps (1e-6), T (100), rng (None | int seed | numpy Generator) or an
@@ -1107,9 +1114,17 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
     combines with it, with weights= and with a float32 X.  The ranking is the Gram-form one: report.best_index, re-ranked among near
     ties in data space, is among the first entries of top.pattern, not necessarily the first.  ValueError: top outside that range, or
     with Alt / BnB; NotImplementedError with devices= (merge per-shard Context.opt_top lists with dist.merge_top).
+    Opt, rescue=True: a sign pattern that hits the pivot cap of the sweep (designs that are correlated throughout; otherwise
+    PartlsError(ERR_NOT_CONVERGED)) is solved again on the device by Lawson-Hanson (lowlevel.OPT_RESCUE_CAPPED, DESIGN.md §4.14);
+    report.rescued counts them.  Nothing extra runs when no pattern caps.  ValueError with Alt / BnB; NotImplementedError with devices=.
     """
     if alg not in (Opt, Alt, BnB):
         raise TypeError("fit: first argument must be Opt, Alt or BnB")
+    if rescue:
+        if alg is not Opt:
+            raise ValueError("fit: rescue= is an option of Opt (the enumeration), not of %s" % alg.__name__)
+        if devices is not None:
+            raise NotImplementedError("fit: rescue= is not supported on several devices (devices=)")
     if top is not None:
         if isinstance(top, bool) or not isinstance(top, (int, np.integer)) or not 1 <= int(top) <= L.OPT_TOP_MAX_K:
             raise ValueError("fit: top must be an int in 1 .. %d, got %r" % (L.OPT_TOP_MAX_K, top))
@@ -1155,6 +1170,8 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
     with _tolerating(on_ill_conditioned, ctx, mc):
         if alg is Opt:
             flags = (faithful if (faithful_intercept or returnAllSolutions or top is not None) else 0) | (L.OPT_GENERIC_KERNEL if generic_kernel else 0)
+            if rescue:
+                flags |= L.OPT_RESCUE_CAPPED
             if mc is not None:
                 a, b, t, opt, bi, allopt = mc.fit_opt(Xf, yf, Pf, eta_v, flags, want_all=returnAllSolutions)
                 if returnAllSolutions:
@@ -1167,7 +1184,10 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
             if unconv:
                 raise PartlsError(L.ERR_NOT_CONVERGED, f"{unconv} subproblems hit the pivot cap")
             a, b, t, opt, bi = ctx.opt_finish(bpat)
+            rescued = ctx.rescue_stats().rescued if rescue else 0
             extra = {} if top is None else dict(top=_top_patterns(ctx, int(top), Pout))
+            if rescue:                                        # (after the sweep and the finish, before opt_top starts its own count)
+                extra.update(rescued=rescued)
             if returnAllSolutions:
                 return result(ctx, a, b, t, solutions=solutions(ctx, allopt, flags, device), **extra)
             return result(ctx, a, b, t, opt=opt, best_index=bi, **extra)

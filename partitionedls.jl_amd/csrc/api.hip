@@ -109,6 +109,7 @@ try {
     if (const char *e = getenv("PARTLS_BIT_ORDER")) c->knobs.bit_order = !strcmp(e, "identity") ? 1 : (!strcmp(e, "calibrate") ? 2 : 0);
     if (const char *e = getenv("PARTLS_ALT_MS_MAX_ROUNDS")) c->knobs.alt_ms_max_rounds = atoi(e);
     if (const char *e = getenv("PARTLS_MAX_ROUNDS")) { const int v = atoi(e); if (v >= 1) c->knobs.max_rounds = v; }
+    if (const char *e = getenv("PARTLS_RESCUE_MAX_PASSES")) { const int v = atoi(e); if (v >= 1) c->knobs.rescue_max_passes = v; }
     if (const char *e = getenv("PARTLS_ALT_MS_CHUNK")) c->knobs.alt_ms_chunk = atoll(e);
     if (const char *e = getenv("PARTLS_TOP_PIECE")) c->knobs.top_piece = atoll(e);
     if (const char *e = getenv("PARTLS_KKT_TOL")) c->knobs.kkt_tol = atof(e);
@@ -301,6 +302,16 @@ try {
     if (!c || !violation) { set_error("partls_get_kkt_violation: bad argument"); return PARTLS_ERR_BAD_ARG; }
     *violation = c->last_kkt;
     if (min_pivot) *min_pivot = c->last_min_loo;
+    return PARTLS_OK;
+}
+PARTLS_ABI_GUARD
+
+partls_status partls_get_rescue_stats(const partls_ctx *c, int64_t *rescued, int64_t *pivots, int64_t *failed)
+try {
+    if (!c) { set_error("partls_get_rescue_stats: bad argument"); return PARTLS_ERR_BAD_ARG; }
+    if (rescued) *rescued = (int64_t)c->rescue_rescued;
+    if (pivots) *pivots = (int64_t)c->rescue_pivots;
+    if (failed) *failed = (int64_t)c->rescue_failed;
     return PARTLS_OK;
 }
 PARTLS_ABI_GUARD

@@ -130,6 +130,7 @@ struct partls_knobs {
     bool print_stamps = false;   // PARTLS_PRINT_STAMPS (diagnostic build only)
     int alt_ms_max_rounds = 0;   // PARTLS_ALT_MS_MAX_ROUNDS: pivot cap of the alpha-steps of partls_alt_multistart only (0: 20 (n + 1), as everywhere); tests
     int max_rounds = 0;          // PARTLS_MAX_ROUNDS: pivot cap of every launch that takes the default one (sweep_params; values below 1: 20 (n + 1)); tests
+    int rescue_max_passes = 0;   // PARTLS_RESCUE_MAX_PASSES: main passes of the rescue kernel (rescue.hip; values below 1: 3 n); tests
     long long alt_ms_chunk = 0;  // PARTLS_ALT_MS_CHUNK: starts per chunk of partls_alt_multistart (0: what fits 256 MB of per-start scratch)
     double kkt_tol = 1e-12;      // PARTLS_KKT_TOL: data-space KKT violation of the winner (units of ||x_m|| ||y||) above which fit(Opt) / fit(BnB) report
                                  // PARTLS_ERR_ILL_CONDITIONED instead of PARTLS_OK (see kkt_says_ill_conditioned, refine.hip)
@@ -153,7 +154,7 @@ struct partls_ctx {
     double ms[PARTLS_T_COUNT] = {};
 
     // Reset by forget_problem (prepare.hip), the one reset of ctx_prepare, batch_reset and batch_calibrate — whatever below is derived
-    // from a prepared problem or its last sweep or solve: prepared, peers; near_for, near_pat, cand, export_wg; sweep_vetoes,
+    // from a prepared problem or its last sweep or solve: prepared, peers; near_for, near_pat, cand, export_wg; sweep_vetoes, rescue_*,
     // coop_state_valid, coop_fallback; tab_valid; order_ready, order_identity, flip_cost; dw, ds, x_f32; last_upload_*; ms[CALIB], ms[OOB].
     // (Not last_kkt / last_min_loo: partls_get_kkt_violation reports them, for the last model returned, without a prepared problem.)
     // problem
@@ -200,6 +201,13 @@ struct partls_ctx {
     // partls_opt_top (topk.hip) shares them (mdlRows: a piece's rows + objectives; mdlOut: the cleaned outputs of its k
     // rows) and adds: topWork, the selection's state and survivor lists; topRows, the k selected rows, objectives and Gray indices
     partls::DevBuf topWork, topRows;
+    // PARTLS_OPT_RESCUE_CAPPED (rescue.hip): rescueScratch, one tableau per workgroup of the rescue kernel; rescueList,
+    // [count | rescued | pivots | failed | vetoes | ...] and the list of a piece's capped rows (or one pattern, its row and objective);
+    // rescueStage, the host copy of that head (and of the single pattern's row).  rescue_*: the sums of the last call that can rescue
+    // (partls_get_rescue_stats), zeroed when such a call begins
+    partls::DevBuf rescueScratch, rescueList;
+    partls::PinnedDoubles rescueStage;
+    unsigned long long rescue_rescued = 0, rescue_pivots = 0, rescue_failed = 0;
     // called between the Gram build and the tableau preparation (partls_fit_opt_multi: the Gram products of the row blocks are summed)
     std::function<partls_status(partls_ctx *)> gram_hook;
     partls::PinnedDoubles amsHostIn, amsHostOut;   // ... of an iteration of partls_alt_multistart: the active list up, the records back
@@ -425,6 +433,20 @@ partls_status alt_finish(partls_ctx *c, const std::vector<double> &a, const std:
                          const std::vector<int8_t> &vcode_last, const std::vector<double> &hdiag, const std::vector<double> &gersh,
                          double optval, int64_t iters_done, unsigned long long unconv_total,
                          double *alpha, double *beta, double *t, double *opt, int64_t *iters);
+// ---- PARTLS_OPT_RESCUE_CAPPED (rescue.hip): capped patterns solved again by Lawson-Hanson, one workgroup each, on c->stream
+inline bool rescue_on(const partls_ctx *c) { return (c->flags & PARTLS_OPT_RESCUE_CAPPED) != 0; }
+// The piece [p0, p0 + cnt) of an export sweep (rows: cnt x n, obj: cnt, both on the device): the rows whose objective is NaN are listed
+// and solved, their rows and objectives written in place; a subproblem that runs out of main passes keeps its NaN.  Enqueues the copy
+// of the counters to rescueStage; after the stream has been synchronised, rescue_collect adds them to c->rescue_* and turns the
+// piece's *unconv (the export's count of capped patterns) into what is still unsolved; the rescue's vetoes are added to *vetoes.
+// rescue_begin_call: the counters and the timer of "the last call" start at 0.
+void rescue_begin_call(partls_ctx *c);
+partls_status rescue_piece(partls_ctx *c, int64_t p0, int64_t cnt, double *rows, double *obj);
+// obj[i], the objective of Gray index p0 + i -> all_opt[internal pattern of that index] (the second pass of a sweep)
+partls_status rescue_all_opt(partls_ctx *c, const double *obj, int64_t p0, int64_t cnt, double *all_opt);
+void rescue_collect(partls_ctx *c, unsigned long long *unconv, unsigned long long *vetoes);
+// one reference pattern, in the format of solve_nodes (sol: n scaled values, 0 for non-basic; obj2; *unconv = 1 when it failed)
+partls_status rescue_pattern(partls_ctx *c, uint64_t pattern, std::vector<double> &sol, double *obj2, unsigned long long *unconv);
 // node codes of one Opt sign pattern (Opt.jl:28-29): sign of the multiplier sum_k P[m,k] s_k of every tableau variable
 void opt_codes(const partls_ctx *c, uint64_t pattern, std::vector<int8_t> &codes);
 

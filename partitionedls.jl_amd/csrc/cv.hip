@@ -428,6 +428,7 @@ static partls_status cv_opt(partls_ctx *c, const double *X, int64_t N, int64_t M
     if (st != PARTLS_OK) return st;
     if (!alpha || !beta || !t || !opt || !best_index || !heldout_sse || !status) { set_error("partls_cv_opt: NULL output"); return PARTLS_ERR_BAD_ARG; }
     if (ld_alpha < M || ld_beta < K) { set_error("partls_cv_opt: leading dimension of alpha / beta too small"); return PARTLS_ERR_BAD_ARG; }
+    if (flags & PARTLS_OPT_RESCUE_CAPPED) { set_error("partls_cv_opt: PARTLS_OPT_RESCUE_CAPPED is not supported by the batched sweeps"); return PARTLS_ERR_UNSUPPORTED; }
     if ((flags & PARTLS_OPT_FAITHFUL_INTERCEPT ? K + 1 : K) > 40) {
         set_error("partls_cv_opt: K = %lld: the enumeration of fit(Opt) is out of range (K <= 39)", (long long)K);
         return PARTLS_ERR_UNSUPPORTED;

@@ -611,6 +611,7 @@ partls_status partls_fit_opt_multi(partls_multi *mc, const double *X, int64_t N,
 try {
     if (!mc) { set_error("partls_fit_opt_multi: handle is NULL"); return PARTLS_ERR_BAD_ARG; }
     if (!alpha || !beta || !t || !opt) { set_error("partls_fit_opt_multi: NULL output"); return PARTLS_ERR_BAD_ARG; }
+    if (flags & PARTLS_OPT_RESCUE_CAPPED) { set_error("partls_fit_opt_multi: PARTLS_OPT_RESCUE_CAPPED is not supported by the sharded sweep"); return PARTLS_ERR_UNSUPPORTED; }
     if (all_opt && (K < 1 || K > 39)) { set_error("partls_fit_opt_multi: all_opt needs 1 <= K <= 39"); return PARTLS_ERR_UNSUPPORTED; }
     if (all_opt) flags |= PARTLS_OPT_FAITHFUL_INTERCEPT;
     const FitArgs a{0, X, N, M, ldX, y, P, K, ldP, eta, flags, alpha, beta, t, opt, best_index, all_opt, nullptr};

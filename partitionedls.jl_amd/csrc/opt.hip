@@ -76,6 +76,9 @@ PARTLS_ABI_GUARD
 
 int64_t partls_opt_num_patterns(const partls_ctx *c) { return (c && c->prepared && c->kbits <= 40) ? ((int64_t)1 << c->kbits) : 0; }
 
+static partls_status sweep_second_pass(partls_ctx *c, int64_t g_begin, int64_t g_end, double *all_opt, double *bobj_io, int64_t *bpat_io,
+                                       unsigned long long *unconv_io);
+
 partls_status partls_opt_sweep(partls_ctx *c, int64_t g_begin, int64_t g_end, double *best_obj, int64_t *best_pattern,
                                double *all_opt, int64_t *n_unconverged)
 try {
@@ -162,6 +165,13 @@ try {
     double bobj = INFINITY;
     int64_t bpat = -1;
     install_sweep_result(c, sweep_out, grid, p.best_sol != nullptr, &bobj, &bpat);
+    if (rescue_on(c)) {
+        rescue_begin_call(c);
+        if (cnt[0]) {                                    // patterns capped: the second pass is authoritative
+            const partls_status rs = sweep_second_pass(c, g_begin, g_end, all_opt, &bobj, &bpat, &cnt[0]);
+            if (rs != PARTLS_OK) return rs;
+        }
+    }
     if (best_obj) *best_obj = bobj;
     if (best_pattern) *best_pattern = bpat;
     if (n_unconverged) *n_unconverged = (int64_t)cnt[0];
@@ -231,6 +241,11 @@ try {
             opt_codes(c, cands[ci], codes);
             st = solve_nodes(c, codes, 1, sols, obj2, &unconv, false, /*want_tab=*/true);
             if (st != PARTLS_OK) return st;
+            if (unconv && rescue_on(c)) {                    // the single solve capped: Lawson-Hanson instead; no final tableau then
+                st = rescue_pattern(c, cands[ci], sols, nullptr, &unconv);
+                if (st != PARTLS_OK) return st;
+                c->tab_valid = false;
+            }
         }
         unscale_solution(c, sols.data(), w);
         RefineOut ro;
@@ -293,6 +308,11 @@ try {
     opt_codes(c, (uint64_t)pattern, codes);
     partls_status st = solve_nodes(c, codes, 1, sols, obj2, &unconv, false, /*want_tab=*/true);
     if (st != PARTLS_OK) return st;
+    if (unconv && rescue_on(c)) {                            // the single solve capped: Lawson-Hanson instead; no final tableau then
+        st = rescue_pattern(c, (uint64_t)pattern, sols, nullptr, &unconv);
+        if (st != PARTLS_OK) return st;
+        c->tab_valid = false;
+    }
     unscale_solution(c, sols.data(), w);
     st = refine_solution(c, w, false);
     if (st != PARTLS_OK) return st;
@@ -391,6 +411,97 @@ static partls_status export_piece(partls_ctx *c, int64_t p0, int64_t cnt, double
     return PARTLS_OK;
 }
 
+// patterns per piece of partls_opt_models for a range of `total` (equal pieces: no short tail piece of cold chain starts)
+static int64_t models_piece(const partls_ctx *c, int64_t total)
+{
+    const size_t out_w = 3 + (size_t)c->M + (size_t)c->K;           // cleaned output per pattern: pattern, optval, t, alpha, beta
+    const size_t per_pat = (size_t)c->n + 1 + out_w;                  // + the scaled row (raw alpha in place) and its objective
+    const int64_t cap = std::max<int64_t>(1, (int64_t)(PARTLS_OPT_MODELS_PIECE_BYTES / (per_pat * sizeof(double))));
+    const int64_t npieces = (total + cap - 1) / cap;
+    return (total + npieces - 1) / npieces;
+}
+
+// PARTLS_OPT_RESCUE_CAPPED: the second pass of a partls_opt_sweep that reported capped patterns (the plain kernels do not say which).
+// The range is walked again through the export pieces of partls_opt_models, whose NaN rows the rescue kernel solves (rescue.hip); per
+// piece the four best (objective, pattern) pairs are selected on the device (topk.hip) and the host merges them.  The pass is
+// authoritative: its winner and near ties are installed the way partls_opt_merge_candidates installs a merged set (no exported
+// winner row: partls_opt_finish solves the winner again), all_opt holds its objectives, *unconv_io what the rescue could not solve.
+static partls_status sweep_second_pass(partls_ctx *c, int64_t g_begin, int64_t g_end, double *all_opt, double *bobj_io, int64_t *bpat_io,
+                                       unsigned long long *unconv_io)
+{
+    const auto w0 = std::chrono::steady_clock::now();
+    const int n = c->n;
+    const int64_t npat = (int64_t)1 << c->kbits, total = g_end - g_begin, piece = models_piece(c, total);
+    const int64_t K4 = 4, kmax = std::min<int64_t>(K4, piece);
+    PARTLS_HIP_CHECK(c->mdlRows.ensure((size_t)piece * (n + 1) * sizeof(double)));
+    PARTLS_HIP_CHECK(c->topWork.ensure(topk_work_bytes(kmax)));
+    PARTLS_HIP_CHECK(c->topRows.ensure((size_t)kmax * (n + 2) * sizeof(double)));
+    PARTLS_HIP_CHECK(c->mdlStage.resize(8 + 2 * (size_t)kmax));
+    if (!c->use_reg) c->coop_state_valid = false;                    // the global-memory kernels overwrite the shared tableau scratch
+    std::vector<std::pair<double, int64_t>> all;
+    unsigned long long unconv = 0, pivots = 0, vetoes = 0;
+    for (int64_t p0 = g_begin; p0 < g_end; p0 += piece) {
+        const int64_t cnt = std::min<int64_t>(piece, g_end - p0), kk = std::min<int64_t>(K4, cnt);
+        double *rows = c->mdlRows.as<double>(), *obj = rows + (size_t)cnt * n;
+        double *crow = c->topRows.as<double>(), *cobj = crow + (size_t)kk * n;
+        int64_t *glist = reinterpret_cast<int64_t *>(cobj + kk);
+        partls_status st = export_piece(c, p0, cnt, rows, obj, "partls_opt_sweep");
+        if (st == PARTLS_OK) st = rescue_piece(c, p0, cnt, rows, obj);
+        if (st == PARTLS_OK && all_opt) st = rescue_all_opt(c, obj, p0, cnt, c->allOpt.as<double>());
+        if (st != PARTLS_OK) return st;
+        PARTLS_HIP_CHECK(launch_topk_select(obj, cnt, p0, K4, c->kbits, c->order, c->order_identity, c->topWork.p, c->stream));
+        PARTLS_HIP_CHECK(launch_topk_gather(rows, obj, n, p0, cnt, kk, c->topWork.p, crow, cobj, glist, c->stream));
+        const TopkWork w = topk_work(c->topWork.p, kk);
+        double *hs = c->mdlStage.data();
+        PARTLS_HIP_CHECK(hipMemcpyAsync(hs, c->mdlCtr.p, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(hs + 4, c->topWork.p, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(hs + 8, cobj, (size_t)kk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(hs + 8 + kk, w.out_pat, (size_t)kk * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        unsigned long long cn[8];
+        std::memcpy(cn, hs, sizeof(cn));
+        unsigned long long left = cn[0], vet = cn[2];
+        rescue_collect(c, &left, &vet);
+        unconv += left; pivots += cn[1]; vetoes += vet;
+        const int64_t got = (int64_t)cn[7];
+        if (got < 0 || got > kk) { set_error("partls_opt_sweep: the selection reported %lld rows of at most %lld", (long long)got, (long long)kk); return PARTLS_ERR_HIP; }
+        for (int64_t i = 0; i < got; ++i) {
+            int64_t pat = 0;
+            std::memcpy(&pat, hs + 8 + kk + i, sizeof(pat));
+            all.emplace_back(hs[8 + i], pat);
+        }
+    }
+    if (all_opt) {                                           // as the first pass returned it, with this pass's entries
+        const void *src = c->allOpt.p;
+        if (!c->order_identity) {
+            PARTLS_HIP_CHECK(c->allOptRef.ensure((size_t)npat * sizeof(double)));
+            PARTLS_HIP_CHECK(launch_pattern_gather(c->allOpt.as<double>(), npat, c->kbits, c->order, c->allOptRef.as<double>(), c->stream));
+            src = c->allOptRef.p;
+        }
+        PARTLS_HIP_CHECK(hipMemcpyAsync(all_opt, src, (size_t)npat * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    }
+    c->last_pivots += pivots + c->rescue_pivots;
+    c->last_vetoes += vetoes;
+    c->sweep_vetoes += vetoes;
+    c->export_wg = -1;
+    c->near_pat.clear();
+    c->cand.clear();
+    c->near_for = -1;
+    double bobj = INFINITY;
+    int64_t bpat = -1;
+    if (!all.empty()) {
+        const std::pair<double, int64_t> win = *std::min_element(all.begin(), all.end());   // argmin's first-index rule
+        bobj = win.first; bpat = win.second;
+        const double yy = h_reg(c, (int)c->M + 1, (int)c->M + 1);
+        const double lim2 = bobj * bobj + c->knobs.near_tie_rel * (yy > 0.0 ? yy : 0.0);
+        install_near_ties(win, std::move(all), lim2, 3, c->cand, c->near_pat, c->near_for);
+    }
+    *bobj_io = bobj; *bpat_io = bpat; *unconv_io = unconv;
+    c->ms[PARTLS_T_SWEEP] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+    return PARTLS_OK;
+}
+
 partls_status partls_opt_models(partls_ctx *c, int64_t g_begin, int64_t g_end, int64_t *pattern, double *optval, double *raw_alpha,
                                 int64_t ld_raw, double *alpha, int64_t ld_alpha, double *beta, int64_t ld_beta, double *t,
                                 int64_t *n_unconverged, int64_t *n_vetoes)
@@ -403,20 +514,20 @@ try {
     const int n = c->n;
     const int64_t total = g_end - g_begin;
     const size_t out_w = 3 + (size_t)M + (size_t)K;                 // cleaned output per pattern: pattern, optval, t, alpha, beta
-    const size_t per_pat = (size_t)n + 1 + out_w;                     // + the scaled row (raw alpha in place) and its objective
-    const int64_t cap = std::max<int64_t>(1, (int64_t)(PARTLS_OPT_MODELS_PIECE_BYTES / (per_pat * sizeof(double))));
-    const int64_t npieces = (total + cap - 1) / cap;
-    const int64_t piece = (total + npieces - 1) / npieces;            // equal pieces: no short tail piece of cold chain starts
+    const int64_t piece = models_piece(c, total);
     PARTLS_HIP_CHECK(c->mdlRows.ensure((size_t)piece * (n + 1) * sizeof(double)));
     PARTLS_HIP_CHECK(c->mdlOut.ensure((size_t)piece * out_w * sizeof(double)));
     const size_t stage_words = 4 + (size_t)piece * (out_w + (raw_alpha ? (size_t)n : 0));
     PARTLS_HIP_CHECK(c->mdlStage.resize(stage_words));
     if (!c->use_reg) c->coop_state_valid = false;                    // the global-memory kernels overwrite the shared tableau scratch
+    const bool rescue = rescue_on(c);                                // capped rows are solved before the cleanup (rescue.hip)
+    if (rescue) rescue_begin_call(c);
     unsigned long long unconv = 0, vetoes = 0;
     for (int64_t p0 = g_begin; p0 < g_end; p0 += piece) {
         const int64_t cnt = std::min<int64_t>(piece, g_end - p0);
         double *rows = c->mdlRows.as<double>(), *obj = rows + (size_t)cnt * n, *out = c->mdlOut.as<double>();
-        const partls_status es = export_piece(c, p0, cnt, rows, obj, "partls_opt_models");
+        partls_status es = export_piece(c, p0, cnt, rows, obj, "partls_opt_models");
+        if (es == PARTLS_OK && rescue) es = rescue_piece(c, p0, cnt, rows, obj);
         if (es != PARTLS_OK) return es;
         PARTLS_HIP_CHECK(launch_models_cleanup(rows, obj, p0, cnt, (int)M, (int)K, c->kbits, c->order, c->order_identity, c->permP,
                                                c->scale.as<double>(), c->maskAugD.as<uint64_t>(), raw_alpha != nullptr, out, c->stream));
@@ -427,6 +538,7 @@ try {
         PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
         unsigned long long cn[3];
         std::memcpy(cn, st, sizeof(cn));
+        if (rescue) rescue_collect(c, &cn[0], &cn[2]);
         unconv += cn[0];
         vetoes += cn[2];
         const double *o = st + 4;
@@ -480,6 +592,8 @@ try {
     const size_t stage_words = 8 + (size_t)kmax * (out_w + (raw_alpha ? (size_t)n : 0));
     PARTLS_HIP_CHECK(c->mdlStage.resize(stage_words));
     if (!c->use_reg) c->coop_state_valid = false;                    // the global-memory kernels overwrite the shared tableau scratch
+    const bool rescue = rescue_on(c);                                // capped rows are solved before the selection (rescue.hip)
+    if (rescue) rescue_begin_call(c);
     unsigned long long unconv = 0, vetoes = 0;
     // the best rows so far, in order: [optval | pattern | t | alpha (M) | beta (K) | raw (n)] per row
     const size_t roww = 3 + (alpha ? (size_t)(M + K) : 0) + (raw_alpha ? (size_t)n : 0);
@@ -490,7 +604,8 @@ try {
         double *rows = c->mdlRows.as<double>(), *obj = rows + (size_t)cnt * n, *out = c->mdlOut.as<double>();
         double *crow = c->topRows.as<double>(), *cobj = crow + (size_t)kk * n;
         int64_t *glist = reinterpret_cast<int64_t *>(cobj + kk);
-        const partls_status es = export_piece(c, p0, cnt, rows, obj, "partls_opt_top");
+        partls_status es = export_piece(c, p0, cnt, rows, obj, "partls_opt_top");
+        if (es == PARTLS_OK && rescue) es = rescue_piece(c, p0, cnt, rows, obj);
         if (es != PARTLS_OK) return es;
         PARTLS_HIP_CHECK(launch_topk_select(obj, cnt, p0, k, c->kbits, c->order, c->order_identity, c->topWork.p, c->stream));
         PARTLS_HIP_CHECK(launch_topk_gather(rows, obj, n, p0, cnt, kk, c->topWork.p, crow, cobj, glist, c->stream));
@@ -504,6 +619,7 @@ try {
         PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
         unsigned long long cn[8];
         std::memcpy(cn, st, sizeof(cn));
+        if (rescue) rescue_collect(c, &cn[0], &cn[2]);
         unconv += cn[0];
         vetoes += cn[2];
         const int64_t got = (int64_t)cn[7];                          // TopState::count: min(k, converged patterns of the piece)

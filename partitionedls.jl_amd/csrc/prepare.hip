@@ -137,6 +137,7 @@ void forget_problem(partls_ctx *c)
     c->peers.clear();                              // a row-sharded fit sets them again after every rank has prepared its block
     c->near_for = -1; c->near_pat.clear(); c->cand.clear(); c->export_wg = -1;
     c->sweep_vetoes = 0;
+    c->rescue_rescued = c->rescue_pivots = c->rescue_failed = 0;
     c->coop_state_valid = false; c->coop_fallback = false;
     c->tab_valid = false;
     c->order_ready = false; c->order_identity = true; c->flip_cost.clear();

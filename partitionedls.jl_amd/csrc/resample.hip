@@ -176,6 +176,7 @@ try {
         set_error("partls_opt_weightings: a context of a partls_multi is not supported (multi-GPU fits are unweighted)");
         return PARTLS_ERR_UNSUPPORTED;
     }
+    if (flags & PARTLS_OPT_RESCUE_CAPPED) { set_error("partls_opt_weightings: PARTLS_OPT_RESCUE_CAPPED is not supported by the batched sweeps"); return PARTLS_ERR_UNSUPPORTED; }
     if ((flags & PARTLS_OPT_FAITHFUL_INTERCEPT ? K + 1 : K) > 40) {
         set_error("partls_opt_weightings: K = %lld: the enumeration of fit(Opt) is out of range (K <= 39)", (long long)K);
         return PARTLS_ERR_UNSUPPORTED;

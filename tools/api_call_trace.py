@@ -86,7 +86,7 @@ SPEC = {
     "partls_synth_device": "h seed N D wstar:d:D X:@ y:@",
     "partls_get_timing": "h which out", "partls_get_upload": "h out out", "partls_get_gram": "h out", "partls_get_pivots": "h out",
     "partls_get_vetoes": "h out", "partls_get_blocks": "h out", "partls_get_kkt_violation": "h out out", "partls_get_near_ties": "h out",
-    "partls_get_sweep_route": "h out out",
+    "partls_get_sweep_route": "h out out", "partls_get_rescue_stats": "h out out out",
 }
 _DTYPES = {"d": np.float64, "q": np.int64, "i": np.int32, "Q": np.uint64, "c": np.intc}
 _UNRECORDED = ("partls_destroy", "partls_multi_destroy", "partls_frontier_destroy")
