@@ -112,6 +112,7 @@ try {
     if (const char *e = getenv("PARTLS_RESCUE_MAX_PASSES")) { const int v = atoi(e); if (v >= 1) c->knobs.rescue_max_passes = v; }
     if (const char *e = getenv("PARTLS_ALT_MS_CHUNK")) c->knobs.alt_ms_chunk = atoll(e);
     if (const char *e = getenv("PARTLS_TOP_PIECE")) c->knobs.top_piece = atoll(e);
+    if (const char *e = getenv("PARTLS_BATCH_PIECE")) c->knobs.batch_piece = atoi(e);
     if (const char *e = getenv("PARTLS_KKT_TOL")) c->knobs.kkt_tol = atof(e);
     if (const char *e = getenv("PARTLS_NEAR_TIE_REL")) c->knobs.near_tie_rel = atof(e);
     if (const char *e = getenv("PARTLS_CAL_WB")) c->knobs.cal_wb = atof(e);

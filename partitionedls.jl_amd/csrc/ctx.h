@@ -3,6 +3,7 @@
 // solvers.hip, multi.hip and the host halves of cv.hip, alt_multi.hip and predict_many.hip.
 #pragma once
 #include "common.h"
+#include <chrono>
 #include <functional>
 #include <vector>
 
@@ -142,6 +143,8 @@ struct partls_knobs {
     long long top_piece = 0;     // PARTLS_TOP_PIECE: patterns per piece of partls_opt_top (0: what PARTLS_OPT_MODELS_PIECE_BYTES admits); tests
     int bit_order = 0;           // PARTLS_BIT_ORDER: 0 automatic (calibrate when the sweep is long enough to repay it), "identity" = 1
                                  // (group k on Gray bit k), "calibrate" = 2 (always measure; small problems in the tests)
+    int batch_piece = 0;         // PARTLS_BATCH_PIECE: problems per piece of the batched routes of partls_cv_opt, partls_opt_weightings and partls_cv_alt
+                                 // (0: batch_pieces_begin's byte rule; at most 65535); tests
 };
 
 struct partls_ctx {
@@ -153,7 +156,7 @@ struct partls_ctx {
     bool timed[PARTLS_T_COUNT] = {};
     double ms[PARTLS_T_COUNT] = {};
 
-    // Reset by forget_problem (prepare.hip), the one reset of ctx_prepare, batch_reset and batch_calibrate — whatever below is derived
+    // Reset by forget_problem (prepare.hip), the one reset of ctx_prepare, batch_reset and batch_work_prepare — whatever below is derived
     // from a prepared problem or its last sweep or solve: prepared, peers; near_for, near_pat, cand, export_wg; sweep_vetoes, rescue_*,
     // coop_state_valid, coop_fallback; tab_valid; order_ready, order_identity, flip_cost; dw, ds, x_f32; last_upload_*; ms[CALIB], ms[OOB].
     // (Not last_kkt / last_min_loo: partls_get_kkt_violation reports them, for the last model returned, without a prepared problem.)
@@ -252,7 +255,7 @@ struct partls_ctx {
     // partls_cv_opt (cv.hip): internal same-device contexts, created on first use and destroyed with this one.  cv_work holds one problem
     // at a time for the finish (its G, tableau, winner); cv_view[g] is a view of the rows of fold g (dX, dy, N, ldX into this context's
     // upload) — the peers of cv_work's data passes and the target of the held-out residual.  cvG: fold Grams, then the combined Grams;
-    // cvBatch: stacked per-problem state of a chunk (scale, Tfull, T0reg, tolerances, sweep results); cvHost: their host copies.
+    // cvBatch: stacked per-problem state of a piece (BatchPiece: scale, tolerances, Tfull, T0reg, the caller's tail); cvHost: host copies.
     partls_ctx *cv_work = nullptr;
     std::vector<partls_ctx *> cv_view;
     partls::DevBuf cvG, cvBatch, cvEta;
@@ -273,6 +276,8 @@ namespace partls {
 void t_begin(partls_ctx *c, int w);
 void t_end(partls_ctx *c, int w);
 void t_collect(partls_ctx *c);
+// host wall time since t0, in ms (the phases that events cannot time: finishes on the host, the iterations of partls_cv_alt)
+inline double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
 // Upload (or adopt) X, y; build the Gram products; lay the tableau out.  faithful = intercept is a regular variable.
 // w (optional): sample weights, a device pointer when x_on_device (see prepare_weights)
@@ -331,9 +336,13 @@ int64_t reference_pattern(const partls_ctx *c, int64_t q);
 // sweep_out: the host copy of a result block with runner-up columns (sweep_block)
 void install_sweep_result(partls_ctx *c, const double *sweep_out, int grid, bool has_sol, double *bobj_out, int64_t *bpat_out);
 
-// ---- many fit(Opt) problems over one (X, y, P) in one call (cv.hip): what partls_cv_opt and partls_opt_weightings (resample.hip) share.
-// The caller's context c keeps the upload and the Gram products (c->cvG) and holds no prepared problem afterwards; c->cv_work, an
-// internal context on the same device, holds one problem at a time for its finish.
+// ---- many problems over one (X, y, P) in one call (cv.hip): what partls_cv_opt, partls_opt_weightings (resample.hip) and partls_cv_alt
+// (cv_alt.hip) share.  The caller's context c keeps the upload and the Gram products (c->cvG) and holds no prepared problem
+// afterwards; c->cv_work, an internal context on the same device, holds one problem at a time for its finish.  The steps, each
+// defined once: batch_work_prepare (cv_work takes the batch's shape); then either batch_prepare_one per problem (the serial route)
+// or, after batch_pieces_begin (the piece rule), per piece batch_piece_prepare (all of them prepared on the device) and
+// batch_install per problem (its prepared state onto cv_work).  The Opt entries go through batch_calibrate and batch_sweep, which add
+// the calibration, the sweeps and the finish callback; partls_cv_alt runs its iterations between the steps itself.
 // what the caller gets per problem (host staging; nothing reaches the caller's arrays before the whole call has succeeded); sse: the
 // held-out SSE of a cross-validation problem, the out-of-bag SSE of a weighting
 struct CvOut {
@@ -346,7 +355,8 @@ struct CvOut {
                  double *opt_out, int64_t *best_out, double *sse_out, int32_t *status_out) const;
 };
 // B problems: problem q reads the Gram G + (q / E) * gs (device; hostG: the host copies at the same stride) with eta[q % E] (host).
-// finish(q, bpat, unconv): cv_work holds problem q prepared and swept (winner bpat, -1 when none; unconv patterns hit the pivot cap).
+// finish(q, bpat, unconv): cv_work holds problem q prepared and swept (winner bpat, -1 when none; unconv patterns hit the pivot cap);
+// batch_sweep alone calls it.
 struct ProblemBatch {
     int64_t B = 0, E = 1;
     const double *eta = nullptr;
@@ -367,14 +377,39 @@ partls_status cv_grams(partls_ctx *c, const double *X, int64_t N, int64_t M, int
                        int64_t K, const int64_t *fold_ptr, int64_t F, uint32_t flags, const char *who, int *ldg_out, int *chunks_out);
 // W's data passes cover the training rows of fold f (f == F: all rows): its own rows are the first training fold, the others its peers
 void cv_point_rows(partls_ctx *c, partls_ctx *W, const int64_t *fold_ptr, int64_t F, int64_t f);
+// o.sse[q] = the SSE of the model in column q of o (with cv_work's partition) on the rows of fold f, from the data
+partls_status cv_heldout_sse(partls_ctx *c, int64_t f, int64_t q, CvOut &o);
 // c forgets its prepared problem (forget_problem), zeroes every timer and takes the shape of the batch's
 void batch_reset(partls_ctx *c, int64_t N, int64_t M, int64_t K, uint32_t flags);
-// cv_work takes the batch's shape, partition and Gram layout, is prepared for Gram `cal_gram` at eta[0] with its rows set by
-// point_rows(cv_work), and the visiting order of the whole batch is calibrated there (the rule of a single fit decides whether that pays)
+// cv_work takes the batch's shape, partition and Gram layout and is prepared for Gram `cal_gram` at eta[0] with its rows set by
+// point_rows(cv_work); no enumeration is set up (partls_cv_alt has none, and so no limit on K)
+partls_status batch_work_prepare(partls_ctx *c, const int64_t *P, int64_t ldP, uint32_t flags, int ldg, int chunks, const ProblemBatch &pb,
+                                 int64_t cal_gram, const std::function<void(partls_ctx *)> &point_rows);
+// ... and the visiting order of the whole batch is calibrated there (the rule of a single fit decides whether that pays)
 partls_status batch_calibrate(partls_ctx *c, const int64_t *P, int64_t ldP, uint32_t flags, int ldg, int chunks, const ProblemBatch &pb,
                               int64_t cal_gram, const std::function<void(partls_ctx *)> &point_rows);
-// prepare and sweep every problem — batched on the register kernels (chunks bounded by PARTLS_OPT_MODELS_PIECE_BYTES and 65535
-// problems), or one after another (n > 288, PARTLS_OPT_GENERIC_KERNEL, pb.serial) — and call pb.finish on each; fills c->ms
+// the serial route's prepare of problem q on cv_work: its training Gram, its eta, ctx_prepare_tableau
+partls_status batch_prepare_one(partls_ctx *c, const ProblemBatch &pb, int64_t q);
+// The batched route begins: *per_piece = the problems of a piece — at most 65535 (gridDim.y), and no more than keep a piece's stacked
+// state below PARTLS_OPT_MODELS_PIECE_BYTES; extra: doubles per problem the caller stacks besides the common regions (partls_cv_alt: 1,
+// its y'y) — and the eta grid goes to c->cvEta, where the batched kernels read it.
+partls_status batch_pieces_begin(partls_ctx *c, const ProblemBatch &pb, size_t extra, int64_t *per_piece);
+// Problems [q0, q0 + bc) prepared together: regions of c->cvBatch (their order: batch_piece_prepare), problem q0 + j at row j of each.
+struct BatchPiece {
+    int64_t q0 = 0;
+    int bc = 0;
+    size_t tfd = 0, t0d = 0;                       // doubles of one problem's Tfull / T0reg
+    double *scale = nullptr, *tol = nullptr, *Tfull = nullptr, *T0reg = nullptr;   // bc x n, bc, bc x tfd, bc x t0d
+    double *tail = nullptr;                        // tail_words doubles of the caller's, uninitialised
+};
+// Ensures and carves c->cvBatch and queues launch_prep_batch and launch_layout_reg_batch on c->stream.  Queues only: the
+// caller copies back what it needs ([scale | tol] are contiguous: the piece's head, bc (n + 1) doubles) and waits once per piece.
+partls_status batch_piece_prepare(partls_ctx *c, const ProblemBatch &pb, int64_t q0, int bc, size_t tail_words, BatchPiece *pc);
+// Problem q0 + j's prepared state onto cv_work — what ctx_prepare_tableau would have left (the batched kernels compute the same
+// entries): eta, the host Gram, scale and tolerance from `head` (the host copy of the piece's head), G, scale, Tfull, T0reg, the flags.
+partls_status batch_install(partls_ctx *c, const ProblemBatch &pb, const BatchPiece &pc, int j, const double *head);
+// prepare and sweep every problem — batched on the register kernels, a piece at a time, or one after another (n > 288,
+// PARTLS_OPT_GENERIC_KERNEL, pb.serial) — and call pb.finish on each; fills c->ms
 partls_status batch_sweep(partls_ctx *c, const ProblemBatch &pb);
 // the tested single-fit finish of problem q on cv_work (its rows already set): partls_opt_finish into column q of o, o.status[q] =
 // 0 / PARTLS_ERR_ILL_CONDITIONED / PARTLS_ERR_NOT_CONVERGED (then NaN outputs, best -1); any other status fails the call

@@ -4,13 +4,13 @@
 // and swept in one launch of the BATCH instantiation of the register kernels (blockIdx.y = problem).  Each problem is then finished as
 // partls_opt_finish finishes a single fit (near-tie re-rank from the data, refinement, KKT check, cleanupResult), on an internal working
 // context whose data passes cover exactly its training rows (row-block views of the folds as its peers).  DESIGN.md §4.6.
-// The parts that do not know about folds — the reset, the calibration on the working context, the batched / serial sweep of B problems
-// over Grams at a fixed stride with the finish as a callback, the finish of one model — are the batch_* helpers of ctx.h, which
-// partls_opt_weightings (resample.hip) shares.  The steps a single prepare has too are the single prepare's (prepare.hip, prepare_rules.h):
+// The parts that do not know about folds — the reset, the working context's prepare and calibration, the piece rule, the prepare of a
+// piece and the install of one of its problems, the batched / serial sweep of B problems over Grams at a fixed stride with the finish
+// as a callback, the finish of one model — are the batch_* helpers of ctx.h, which partls_opt_weightings (resample.hip) and, up to the
+// sweep, partls_cv_alt (cv_alt.hip) share.  The steps a single prepare has too are the single prepare's (prepare.hip, prepare_rules.h):
 // forget_problem, adopt_or_upload, prepare_weights, gram_diag_finite, ctx_prepare_tableau and the preparation kernels.
 #include "ctx.h"
 #include "prepare_rules.h"
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <algorithm>
@@ -120,6 +120,17 @@ void model_weights(const partls_ctx *work, const CvOut &o, int64_t q, double *w)
     w[M] = o.t[(size_t)q];
 }
 
+partls_status cv_heldout_sse(partls_ctx *c, int64_t f, int64_t q, CvOut &o)
+{
+    // predict (PartitionedLS.jl:132): yhat = X (P .* alpha) beta .+ t on fold f's rows
+    std::vector<double> w((size_t)c->M + 1, 0.0);
+    model_weights(c->cv_work, o, q, w.data());
+    double s2 = 0.0;
+    const partls_status st = data_pass(c->cv_view[(size_t)f], w, true, false, &s2, nullptr, {});
+    if (st == PARTLS_OK) o.sse[(size_t)q] = s2;
+    return st;
+}
+
 // Finish problem q on W (prepared state already installed): the tested single-fit finish, then the held-out SSE on fold f's rows.
 static partls_status finish_one(partls_ctx *c, partls_ctx *W, const int64_t *fold_ptr, int64_t F, int64_t f, int64_t q, int64_t bpat,
                                 int64_t unconv, CvOut &o)
@@ -127,18 +138,8 @@ static partls_status finish_one(partls_ctx *c, partls_ctx *W, const int64_t *fol
     if (bpat >= 0) cv_point_rows(c, W, fold_ptr, F, f);
     const partls_status st = finish_model(c, q, bpat, unconv, o);
     W->peers.clear();
-    if (st != PARTLS_OK) return st;
-    if (o.status[(size_t)q] != PARTLS_ERR_NOT_CONVERGED && f < F) {
-        // predict (PartitionedLS.jl:132): yhat = X (P .* alpha) beta .+ t on fold f's rows
-        std::vector<double> w((size_t)c->M + 1, 0.0);
-        model_weights(W, o, q, w.data());
-        partls_ctx *v = c->cv_view[(size_t)f];
-        double s2 = 0.0;
-        const partls_status ds = data_pass(v, w, true, false, &s2, nullptr, {});
-        if (ds != PARTLS_OK) return ds;
-        o.sse[(size_t)q] = s2;
-    }
-    return PARTLS_OK;
+    if (st != PARTLS_OK || o.status[(size_t)q] == PARTLS_ERR_NOT_CONVERGED || f == F) return st;
+    return cv_heldout_sse(c, f, q, o);
 }
 
 void batch_reset(partls_ctx *c, int64_t N, int64_t M, int64_t K, uint32_t flags)
@@ -149,8 +150,16 @@ void batch_reset(partls_ctx *c, int64_t N, int64_t M, int64_t K, uint32_t flags)
     c->N = N; c->M = M; c->K = K; c->flags = flags; c->faithful = (flags & PARTLS_OPT_FAITHFUL_INTERCEPT) != 0;
 }
 
-partls_status batch_calibrate(partls_ctx *c, const int64_t *P, int64_t ldP, uint32_t flags, int ldg, int chunks, const ProblemBatch &pb,
-                              int64_t cal_gram, const std::function<void(partls_ctx *)> &point_rows)
+partls_status batch_prepare_one(partls_ctx *c, const ProblemBatch &pb, int64_t q)
+{
+    partls_ctx *W = c->cv_work;
+    PARTLS_HIP_CHECK(hipMemcpyAsync(W->G.p, pb.G + (size_t)(q / pb.E) * pb.gs, (size_t)pb.gs * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+    W->eta = pb.eta[q % pb.E];
+    return ctx_prepare_tableau(W);
+}
+
+partls_status batch_work_prepare(partls_ctx *c, const int64_t *P, int64_t ldP, uint32_t flags, int ldg, int chunks, const ProblemBatch &pb,
+                                 int64_t cal_gram, const std::function<void(partls_ctx *)> &point_rows)
 {
     partls_ctx *W = c->cv_work;
     const int64_t M = c->M, K = c->K;
@@ -162,12 +171,18 @@ partls_status batch_calibrate(partls_ctx *c, const int64_t *P, int64_t ldP, uint
     W->M = M; W->K = K; W->flags = flags; W->faithful = c->faithful;
     W->ldg = ldg; W->chunks = chunks;
     PARTLS_HIP_CHECK(W->G.ensure((size_t)pb.gs * sizeof(double)));
-    PARTLS_HIP_CHECK(hipMemcpyAsync(W->G.p, pb.G + (size_t)cal_gram * pb.gs, (size_t)pb.gs * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
-    W->eta = pb.eta[0];
     point_rows(W);
-    st = ctx_prepare_tableau(W);
-    if (st != PARTLS_OK) return st;
+    st = batch_prepare_one(c, pb, cal_gram * pb.E);          // Gram cal_gram at eta[0]
     W->peers.clear();
+    return st;
+}
+
+partls_status batch_calibrate(partls_ctx *c, const int64_t *P, int64_t ldP, uint32_t flags, int ldg, int chunks, const ProblemBatch &pb,
+                              int64_t cal_gram, const std::function<void(partls_ctx *)> &point_rows)
+{
+    partls_ctx *W = c->cv_work;
+    partls_status st = batch_work_prepare(c, P, ldP, flags, ldg, chunks, pb, cal_gram, point_rows);
+    if (st != PARTLS_OK) return st;
     if ((int64_t)W->kbits > 40) { set_error("%s: %d sign bits: the enumeration is out of range (K <= 39)", pb.who, W->kbits); return PARTLS_ERR_UNSUPPORTED; }
     st = calibrate_bit_order(W);
     if (st != PARTLS_OK) return st;
@@ -175,49 +190,88 @@ partls_status batch_calibrate(partls_ctx *c, const int64_t *P, int64_t ldP, uint
     return PARTLS_OK;
 }
 
+partls_status batch_pieces_begin(partls_ctx *c, const ProblemBatch &pb, size_t extra, int64_t *per_piece)
+{
+    // Per problem a piece stacks its full tableau ((n+1)^2), its tile-cyclic tableau, its scale (n), its tolerance (1) and the caller's
+    // `extra` doubles; what else a caller keeps in the tail is not counted.  PARTLS_BATCH_PIECE (tests) replaces the byte bound.
+    const partls_ctx *W = c->cv_work;
+    const size_t n = (size_t)W->n, per = ((n + 1) * (n + 1) + sweep_reg_t0_doubles(W->T) + n + 1 + extra) * sizeof(double);
+    *per_piece = std::max<int64_t>(1, std::min<int64_t>(65535, (int64_t)(PARTLS_OPT_MODELS_PIECE_BYTES / per)));
+    if (c->knobs.batch_piece > 0) *per_piece = std::min(65535, c->knobs.batch_piece);
+    PARTLS_HIP_CHECK(c->cvEta.ensure((size_t)pb.E * sizeof(double)));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->cvEta.p, pb.eta, (size_t)pb.E * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return PARTLS_OK;
+}
+
+partls_status batch_piece_prepare(partls_ctx *c, const ProblemBatch &pb, int64_t q0, int bc, size_t tail_words, BatchPiece *pc)
+{
+    const partls_ctx *W = c->cv_work;
+    const int n = W->n;
+    pc->q0 = q0; pc->bc = bc;
+    pc->tfd = (size_t)(n + 1) * (n + 1); pc->t0d = sweep_reg_t0_doubles(W->T);
+    PARTLS_HIP_CHECK(c->cvBatch.ensure(((size_t)bc * (n + 1 + pc->tfd + pc->t0d) + tail_words) * sizeof(double)));
+    // the one statement of the order: [scale (bc x n) | tol (bc) | Tfull (bc x tfd) | T0reg (bc x t0d) | tail (tail_words)]
+    pc->scale = c->cvBatch.as<double>(); pc->tol = pc->scale + (size_t)bc * n; pc->Tfull = pc->tol + bc;
+    pc->T0reg = pc->Tfull + (size_t)bc * pc->tfd; pc->tail = pc->T0reg + (size_t)bc * pc->t0d;
+    PARTLS_HIP_CHECK(launch_prep_batch(pb.G, pb.gs, (int)pb.E, q0, c->cvEta.as<double>(), W->ldg, (int)c->M, W->maskAugD.as<uint64_t>(),
+                                       W->faithful ? 0 : 1, W->permP, c->knobs.tol_rel, pc->scale, pc->Tfull, pc->tol, n, bc, c->stream));
+    PARTLS_HIP_CHECK(launch_layout_reg_batch(pc->Tfull, n, W->T, bc, pc->T0reg, c->stream));
+    return PARTLS_OK;
+}
+
+partls_status batch_install(partls_ctx *c, const ProblemBatch &pb, const BatchPiece &pc, int j, const double *head)
+{
+    partls_ctx *W = c->cv_work;
+    const int64_t q = pc.q0 + j, f = q / pb.E;
+    const size_t n = (size_t)W->n, gs = (size_t)pb.gs;
+    W->eta = pb.eta[q % pb.E];
+    std::memcpy(W->hG.data(), pb.hostG + (size_t)f * gs, gs * sizeof(double));
+    std::memcpy(W->hScale.data(), head + (size_t)j * n, n * sizeof(double));
+    W->tol = head[(size_t)pc.bc * n + (size_t)j];
+    PARTLS_HIP_CHECK(hipMemcpyAsync(W->G.p, pb.G + (size_t)f * gs, gs * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(W->scale.p, pc.scale + (size_t)j * n, n * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(W->Tfull.p, pc.Tfull + (size_t)j * pc.tfd, pc.tfd * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(W->T0reg.p, pc.T0reg + (size_t)j * pc.t0d, pc.t0d * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+    W->coop_state_valid = false;
+    W->tab_valid = false;
+    W->prepared = true;
+    return PARTLS_OK;
+}
+
 partls_status batch_sweep(partls_ctx *c, const ProblemBatch &pb)
 {
     partls_ctx *W = c->cv_work;
-    const int64_t B = pb.B, E = pb.E, gs = pb.gs, M = c->M;
-    const double *Gc = pb.G, *eta = pb.eta;
-    const bool faithful = c->faithful;
-    const int ldg = W->ldg;
+    const int64_t B = pb.B;
     const int n = W->n;
     const int64_t npat = (int64_t)1 << W->kbits;
     partls_status st = PARTLS_OK;
 
-    double ms_prep = 0.0, ms_sweep = 0.0, ms_finish = 0.0;
+    // c->ms[PREP / SWEEP / FINISH] (0 since batch_reset) sum over the problems or pieces
     // ---- every problem on its own through the existing launchers: n > 288, PARTLS_OPT_GENERIC_KERNEL, the entry's serial knob
     if (!W->use_reg || pb.serial) {
         for (int64_t q = 0; q < B; ++q) {
-            const int64_t f = q / E, e = q % E;
-            PARTLS_HIP_CHECK(hipMemcpyAsync(W->G.p, Gc + (size_t)f * gs, (size_t)gs * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
-            W->eta = eta[e];
-            st = ctx_prepare_tableau(W);
+            st = batch_prepare_one(c, pb, q);
             if (st != PARTLS_OK) return st;
-            ms_prep += W->ms[PARTLS_T_PREP];
+            c->ms[PARTLS_T_PREP] += W->ms[PARTLS_T_PREP];
             double bobj = 0.0;
             int64_t bpat = -1, unconv = 0;
             st = partls_opt_sweep(W, 0, -1, &bobj, &bpat, nullptr, &unconv);
             if (st != PARTLS_OK) return st;
-            ms_sweep += W->ms[PARTLS_T_SWEEP];
+            c->ms[PARTLS_T_SWEEP] += W->ms[PARTLS_T_SWEEP];
             const auto f0 = std::chrono::steady_clock::now();
             st = pb.finish(q, bpat, unconv);
             if (st != PARTLS_OK) return st;
-            ms_finish += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
+            c->ms[PARTLS_T_FINISH] += ms_since(f0);
         }
-        c->ms[PARTLS_T_PREP] = ms_prep; c->ms[PARTLS_T_SWEEP] = ms_sweep; c->ms[PARTLS_T_FINISH] = ms_finish;
         return PARTLS_OK;
     }
 
-    // ---- batched: chunks of problems whose stacked tableaux stay below PARTLS_OPT_MODELS_PIECE_BYTES and whose count fits gridDim.y
+    // ---- batched: a piece of problems at a time
     const int T = W->T;
-    const size_t t0d = sweep_reg_t0_doubles(T), tfd = (size_t)(n + 1) * (n + 1);
-    const size_t tab_bytes = (tfd + t0d + (size_t)n + 1) * sizeof(double);
-    const int64_t bc_max = std::max<int64_t>(1, std::min<int64_t>(65535, (int64_t)(PARTLS_OPT_MODELS_PIECE_BYTES / tab_bytes)));
+    int64_t bc_max = 0;
+    st = batch_pieces_begin(c, pb, 0, &bc_max);
+    if (st != PARTLS_OK) return st;
     const bool want_sol = (sweep_reg_small(T) || sweep_reg_exports(T)) && !c->knobs.no_export;
-    PARTLS_HIP_CHECK(c->cvEta.ensure((size_t)E * sizeof(double)));
-    PARTLS_HIP_CHECK(hipMemcpyAsync(c->cvEta.p, eta, (size_t)E * sizeof(double), hipMemcpyHostToDevice, c->stream));
     PARTLS_HIP_CHECK(c->scratch.ensure(64 * sizeof(double)));      // the register kernels' share (ensure_sweep_scratch goes by W, the prepared context)
     hipEvent_t ev[4];
     for (int i = 0; i < 4; ++i) PARTLS_HIP_CHECK(hipEventCreate(&ev[i]));
@@ -229,71 +283,55 @@ partls_status batch_sweep(partls_ctx *c, const ProblemBatch &pb)
         if (!sweep_plan(W, npat * bc, &chain_len, &grid_all, pb.who)) return PARTLS_ERR_UNSUPPORTED;
         const int64_t nch = (npat + chain_len - 1) / chain_len;
         const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(nch, (grid_all + bc - 1) / bc));
-        const size_t out_w = sweep_block_words(gx, true);
-        // [scale (bc x n) | Tfull (bc x (n+1)^2) | T0reg (bc x t0d) | tol (bc) | sweep blocks (bc x out_w) | best_sol (bc x gx x n)]
-        const size_t o_scale = 0, o_tf = o_scale + (size_t)bc * n, o_t0 = o_tf + (size_t)bc * tfd, o_tol = o_t0 + (size_t)bc * t0d,
-                     o_out = o_tol + (size_t)bc, o_sol = o_out + (size_t)bc * out_w, words = o_sol + (want_sol ? (size_t)bc * gx * n : 0);
-        PARTLS_HIP_CHECK(c->cvBatch.ensure(words * sizeof(double)));
-        double *base = c->cvBatch.as<double>();
+        // the piece's tail: [sweep blocks (bc x out_w) | best_sol (bc x gx x n), when exported]
+        const size_t out_w = sweep_block_words(gx, true), sol_w = want_sol ? (size_t)gx * n : 0, head_w = (size_t)bc * (n + 1);
+        BatchPiece pc;
         PARTLS_HIP_CHECK(hipEventRecord(ev[0], c->stream));
-        PARTLS_HIP_CHECK(launch_prep_batch(Gc, gs, (int)E, q0, c->cvEta.as<double>(), ldg, (int)M, W->maskAugD.as<uint64_t>(), faithful ? 0 : 1,
-                                           W->permP, c->knobs.tol_rel, base + o_scale, base + o_tf, base + o_tol, n, bc, c->stream));
-        PARTLS_HIP_CHECK(launch_layout_reg_batch(base + o_tf, n, T, bc, base + o_t0, c->stream));
-        PARTLS_HIP_CHECK(hipMemsetAsync(base + o_out, 0, (size_t)bc * out_w * sizeof(double), c->stream));
+        st = batch_piece_prepare(c, pb, q0, bc, (size_t)bc * (out_w + sol_w), &pc);
+        if (st != PARTLS_OK) return st;
+        double *d_out = pc.tail, *d_sol = pc.tail + (size_t)bc * out_w;
+        PARTLS_HIP_CHECK(hipMemsetAsync(d_out, 0, (size_t)bc * out_w * sizeof(double), c->stream));
         PARTLS_HIP_CHECK(hipEventRecord(ev[1], c->stream));
         SweepParams p = sweep_params(W, /*internal_order=*/true);
-        p.T0 = base + o_t0;
+        p.T0 = pc.T0reg;
         p.scratch = c->scratch.as<double>();
         p.g_begin = 0; p.g_end = npat; p.chain_len = chain_len;
         p.tol = 0.0;                                             // every problem has its own: batch_tol
-        bind_sweep_block(p, base + o_out, gx, true);             // problem 0's block; problem q's lies q * batch_out words further
-        if (want_sol) { p.best_sol = base + o_sol; p.node_ld = n; }
-        p.batch_t0 = (int64_t)t0d; p.batch_out = (int64_t)out_w; p.batch_tol = base + o_tol;
+        bind_sweep_block(p, d_out, gx, true);                    // problem 0's block; problem q's lies q * batch_out words further
+        if (want_sol) { p.best_sol = d_sol; p.node_ld = n; }
+        p.batch_t0 = (int64_t)pc.t0d; p.batch_out = (int64_t)out_w; p.batch_tol = pc.tol;
         PARTLS_HIP_CHECK(launch_sweep_blk_batch(p, T, gx, bc, c->stream));
         PARTLS_HIP_CHECK(hipEventRecord(ev[2], c->stream));
-        // host copies: scale, tolerances, sweep blocks
-        const size_t hw = (size_t)bc * n + (size_t)bc + (size_t)bc * out_w;
-        PARTLS_HIP_CHECK(c->cvHost.resize(hw));
-        double *h = c->cvHost.data();
-        PARTLS_HIP_CHECK(hipMemcpyAsync(h, base + o_scale, (size_t)bc * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        PARTLS_HIP_CHECK(hipMemcpyAsync(h + (size_t)bc * n, base + o_tol, ((size_t)bc + (size_t)bc * out_w) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        // host copies: [scale | tol] (the piece's head), then the sweep blocks
+        PARTLS_HIP_CHECK(c->cvHost.resize(head_w + (size_t)bc * out_w));
+        double *h = c->cvHost.data(), *hout = h + head_w;
+        PARTLS_HIP_CHECK(hipMemcpyAsync(h, pc.scale, head_w * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(hout, d_out, (size_t)bc * out_w * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
         float f01 = 0.f, f12 = 0.f;
-        if (hipEventElapsedTime(&f01, ev[0], ev[1]) == hipSuccess) ms_prep += f01;
-        if (hipEventElapsedTime(&f12, ev[1], ev[2]) == hipSuccess) ms_sweep += f12;
-        const double *hscale = h, *htol = h + (size_t)bc * n, *hout = htol + bc;
+        if (hipEventElapsedTime(&f01, ev[0], ev[1]) == hipSuccess) c->ms[PARTLS_T_PREP] += f01;
+        if (hipEventElapsedTime(&f12, ev[1], ev[2]) == hipSuccess) c->ms[PARTLS_T_SWEEP] += f12;
         const auto f0 = std::chrono::steady_clock::now();
         for (int j = 0; j < bc; ++j) {
-            const int64_t q = q0 + j, f = q / E, e = q % E;
-            // install problem q's prepared state on the working context: what ctx_prepare_tableau would have left (the batched kernels
-            // compute the same entries) and what partls_opt_sweep would have left (winner, near ties, the winner's exported solution)
-            W->eta = eta[e];
-            std::memcpy(W->hG.data(), pb.hostG + (size_t)f * gs, (size_t)gs * sizeof(double));
-            std::memcpy(W->hScale.data(), hscale + (size_t)j * n, (size_t)n * sizeof(double));
-            W->tol = htol[j];
-            PARTLS_HIP_CHECK(hipMemcpyAsync(W->G.p, Gc + (size_t)f * gs, (size_t)gs * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
-            PARTLS_HIP_CHECK(hipMemcpyAsync(W->scale.p, base + o_scale + (size_t)j * n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
-            PARTLS_HIP_CHECK(hipMemcpyAsync(W->Tfull.p, base + o_tf + (size_t)j * tfd, tfd * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
-            PARTLS_HIP_CHECK(hipMemcpyAsync(W->T0reg.p, base + o_t0 + (size_t)j * t0d, t0d * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+            // what ctx_prepare_tableau would have left (batch_install), then what partls_opt_sweep would have left: the winner's exported
+            // solution, the winner and the near ties
+            st = batch_install(c, pb, pc, j, h);
+            if (st != PARTLS_OK) return st;
             if (want_sol) {
-                PARTLS_HIP_CHECK(W->bestSol.ensure((size_t)gx * n * sizeof(double)));
-                PARTLS_HIP_CHECK(hipMemcpyAsync(W->bestSol.p, base + o_sol + (size_t)j * gx * n, (size_t)gx * n * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
+                PARTLS_HIP_CHECK(W->bestSol.ensure(sol_w * sizeof(double)));
+                PARTLS_HIP_CHECK(hipMemcpyAsync(W->bestSol.p, d_sol + (size_t)j * sol_w, sol_w * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
             }
-            W->coop_state_valid = false;
-            W->tab_valid = false;
-            W->prepared = true;
             double bobj = 0.0;
             int64_t bpat = -1;
             const double *blk = hout + (size_t)j * out_w;
             install_sweep_result(W, blk, gx, want_sol, &bobj, &bpat);
             unsigned long long unconv = 0;
             std::memcpy(&unconv, blk, sizeof(unconv));
-            st = pb.finish(q, bpat, (int64_t)unconv);
+            st = pb.finish(q0 + j, bpat, (int64_t)unconv);
             if (st != PARTLS_OK) return st;
         }
-        ms_finish += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
+        c->ms[PARTLS_T_FINISH] += ms_since(f0);
     }
-    c->ms[PARTLS_T_PREP] = ms_prep; c->ms[PARTLS_T_SWEEP] = ms_sweep; c->ms[PARTLS_T_FINISH] = ms_finish;
     return PARTLS_OK;
 }
 

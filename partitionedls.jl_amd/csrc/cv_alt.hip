@@ -1,17 +1,16 @@
 // cv_alt.hip — partls_cv_alt (include/partls.h): K-fold cross-validation of the multistart fit(Alt) over an η grid, and the full-data
 // path, in one call.  The upload, the fold Grams and the combined training Grams are partls_cv_opt's (cv_grams,
-// cv.hip); the (F+1) x E problems are prepared in one batched launch (launch_prep_batch, launch_layout_reg_batch) and the R
-// trajectories of every problem advance together (alt_multistart_core with AltProblems, alt_multi.hip): one block of records per
-// iteration for the whole batch, one node-mode launch per problem that still has active starts.  Every problem's winner then goes
-// through the ending of a single fit(Alt) (alt_finish) on the working context, whose data passes cover exactly its training rows, and
-// one more pass over fold f gives the held-out SSE.  n > 288, PARTLS_OPT_GENERIC_KERNEL and PARTLS_CV_SERIAL=1 take one problem after
-// another through ctx_prepare_tableau and the multistart of a single problem instead; both routes end in the same finish.
+// cv.hip), and so are the steps of a batch (ctx.h: batch_work_prepare, batch_prepare_one, batch_pieces_begin, batch_piece_prepare,
+// batch_install): the (F+1) x E problems are prepared a piece at a time and the R trajectories of every problem of a piece advance
+// together (alt_multistart_core with AltProblems, alt_multi.hip): one block of records per iteration for the whole piece, one
+// node-mode launch per problem that still has active starts.  Every problem's winner then goes through the ending of a single
+// fit(Alt) (alt_finish) on the working context, whose data passes cover exactly its training rows, and one more pass over fold f
+// gives the held-out SSE.  n > 288, PARTLS_OPT_GENERIC_KERNEL and PARTLS_CV_SERIAL=1 take one problem after another through
+// batch_prepare_one and the multistart of a single problem instead; both routes end in the same finish.
 #include "ctx.h"
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
-#include <limits>
 
 using namespace partls;
 
@@ -31,11 +30,6 @@ struct CvAltOut {
     std::vector<int64_t> iters_all;
     std::vector<int32_t> status_all;
 };
-
-double ms_since(const std::chrono::steady_clock::time_point &t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 
 // Problem q is prepared on W (tableau, host Gram and scale copies, eta): its winner through alt_finish on the training rows of its
 // fold, then the held-out SSE from the data.  Status 0 / 9 per problem, 6 when no start finished; anything else fails the call.
@@ -64,16 +58,7 @@ partls_status finish_problem(partls_ctx *c, partls_ctx *W, const CvAltArgs &a, i
     if (st != PARTLS_OK && st != PARTLS_ERR_ILL_CONDITIONED) return st;
     o.status[(size_t)q] = (int32_t)st;
     o.best[(size_t)q] = win.start;
-    if (f < a.F) {
-        // predict (PartitionedLS.jl:132): yhat = X (P .* alpha) beta .+ t on fold f's rows
-        std::vector<double> w((size_t)M + 1, 0.0);
-        model_weights(W, o, q, w.data());
-        double s2 = 0.0;
-        const partls_status ds = data_pass(c->cv_view[(size_t)f], w, true, false, &s2, nullptr, {});
-        if (ds != PARTLS_OK) return ds;
-        o.sse[(size_t)q] = s2;
-    }
-    return PARTLS_OK;
+    return f < a.F ? cv_heldout_sse(c, f, q, o) : PARTLS_OK;
 }
 
 partls_status cv_alt_run(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *w, int x_on_device,
@@ -84,29 +69,13 @@ partls_status cv_alt_run(partls_ctx *c, const double *X, int64_t N, int64_t M, i
     partls_status st = cv_grams(c, X, N, M, ldX, y, w, x_on_device, K, a.fold_ptr, F, flags, "partls_cv_alt", &ldg, &chunks);
     if (st != PARTLS_OK) return st;
     partls_ctx *W = c->cv_work;
-    const int64_t gs = (int64_t)ldg * ldg;
-    const double *Gc = c->cvG.as<double>() + (size_t)(F > 0 ? F : 1) * gs, *hostG = c->cvHostG.data();
+    ProblemBatch pb;
+    pb.B = B; pb.E = E; pb.eta = a.eta; pb.gs = (int64_t)ldg * ldg;
+    pb.G = c->cvG.as<double>() + (size_t)(F > 0 ? F : 1) * pb.gs; pb.hostG = c->cvHostG.data();
+    pb.serial = c->knobs.cv_serial; pb.who = "partls_cv_alt";
 
-    // ---- the working context takes the batch's shape and partition and is prepared for the full-data problem at eta[0]
-    forget_problem(W);
-    W->knobs = c->knobs;
-    W->gram_hook = nullptr;
-    st = load_partition(W, P, M, K, ldP);
-    if (st != PARTLS_OK) return st;
-    W->M = M; W->K = K; W->flags = flags; W->faithful = true;
-    W->ldg = ldg; W->chunks = chunks;
-    PARTLS_HIP_CHECK(W->G.ensure((size_t)gs * sizeof(double)));
-    auto prepare_on_W = [&](int64_t q) {
-        if (hipMemcpyAsync(W->G.p, Gc + (size_t)(q / E) * gs, (size_t)gs * sizeof(double), hipMemcpyDeviceToDevice, W->stream) != hipSuccess) {
-            set_error("partls_cv_alt: copying a training Gram failed");
-            return PARTLS_ERR_HIP;
-        }
-        W->eta = a.eta[q % E];
-        return ctx_prepare_tableau(W);
-    };
-    cv_point_rows(c, W, a.fold_ptr, F, F);
-    st = prepare_on_W(F * E);
-    W->peers.clear();
+    // ---- the working context: prepared for the full-data problem at eta[0]; nothing is enumerated, so nothing is calibrated
+    st = batch_work_prepare(c, P, ldP, flags, ldg, chunks, pb, F, [&](partls_ctx *Wc) { cv_point_rows(c, Wc, a.fold_ptr, F, F); });
     if (st != PARTLS_OK) return st;
 
     if (want_tables) {
@@ -117,89 +86,68 @@ partls_status cv_alt_run(partls_ctx *c, const double *X, int64_t N, int64_t M, i
         if (want_tables) { tb.opt_all = out.opt_all.data() + q * R; tb.iters_all = out.iters_all.data() + q * R; tb.status_all = out.status_all.data() + q * R; }
         return tb;
     };
-    double ms_prep = 0.0, ms_iter = 0.0, ms_finish = 0.0;
+    // c->ms[PREP / SWEEP = the iterations / FINISH] (0 since batch_reset) sum wall times over the problems or pieces
     const int n = W->n;
 
     // ---- one problem after another: the single problem's prepare, the single problem's multistart
-    if (!W->use_reg || c->knobs.cv_serial) {
+    if (!W->use_reg || pb.serial) {
         AltWinner win;
         for (int64_t q = 0; q < B; ++q) {
             auto t0 = std::chrono::steady_clock::now();
-            st = prepare_on_W(q);
+            st = batch_prepare_one(c, pb, q);
             if (st != PARTLS_OK) return st;
             PARTLS_HIP_CHECK(hipStreamSynchronize(W->stream));
-            ms_prep += ms_since(t0);
+            c->ms[PARTLS_T_PREP] += ms_since(t0);
             t0 = std::chrono::steady_clock::now();
             st = alt_multistart_core(W, nullptr, a.eps, a.T, R, a.alpha0, a.ld_alpha0, a.beta0, a.ld_beta0, tables_at(q), &win);
             if (st != PARTLS_OK) return st;
-            ms_iter += ms_since(t0);
+            c->ms[PARTLS_T_SWEEP] += ms_since(t0);
             t0 = std::chrono::steady_clock::now();
             st = finish_problem(c, W, a, q, win, out);
             if (st != PARTLS_OK) return st;
-            ms_finish += ms_since(t0);
+            c->ms[PARTLS_T_FINISH] += ms_since(t0);
         }
-        c->ms[PARTLS_T_PREP] = ms_prep; c->ms[PARTLS_T_SWEEP] = ms_iter; c->ms[PARTLS_T_FINISH] = ms_finish;
         return PARTLS_OK;
     }
 
-    // ---- batched: pieces of problems whose stacked tableaux stay below PARTLS_OPT_MODELS_PIECE_BYTES and whose count fits gridDim.y
-    const int T = W->T;
-    const size_t t0d = sweep_reg_t0_doubles(T), tfd = (size_t)(n + 1) * (n + 1);
-    const size_t tab_bytes = (tfd + t0d + (size_t)n + 2) * sizeof(double);
-    const int64_t bc_max = std::max<int64_t>(1, std::min<int64_t>(65535, (int64_t)(PARTLS_OPT_MODELS_PIECE_BYTES / tab_bytes)));
-    PARTLS_HIP_CHECK(c->cvEta.ensure((size_t)E * sizeof(double)));
-    PARTLS_HIP_CHECK(hipMemcpyAsync(c->cvEta.p, a.eta, (size_t)E * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    // ---- batched: a piece of problems at a time, each with one double more than the common regions, its y'y
+    int64_t bc_max = 0;
+    st = batch_pieces_begin(c, pb, 1, &bc_max);
+    if (st != PARTLS_OK) return st;
     std::vector<AltWinner> win;
     for (int64_t q0 = 0; q0 < B; q0 += bc_max) {
         const int bc = (int)std::min<int64_t>(bc_max, B - q0);
         auto t0 = std::chrono::steady_clock::now();
-        // [scale (bc x n) | tol (bc) | y'y (bc) | Tfull (bc x (n+1)^2) | T0reg (bc x t0d)]; host: [scale | tol | y'y]
-        const size_t o_scale = 0, o_tol = o_scale + (size_t)bc * n, o_yy = o_tol + (size_t)bc, o_tf = o_yy + (size_t)bc,
-                     o_t0 = o_tf + (size_t)bc * tfd, words = o_t0 + (size_t)bc * t0d;
-        PARTLS_HIP_CHECK(c->cvBatch.ensure(words * sizeof(double)));
-        double *base = c->cvBatch.as<double>();
-        PARTLS_HIP_CHECK(c->cvHost.resize(o_tf));
-        double *h = c->cvHost.data();
+        BatchPiece pc;
+        st = batch_piece_prepare(c, pb, q0, bc, (size_t)bc, &pc);
+        if (st != PARTLS_OK) return st;
+        // host: [scale | tol] (the piece's head) | y'y
+        const size_t head_w = (size_t)bc * (n + 1);
+        PARTLS_HIP_CHECK(c->cvHost.resize(head_w + (size_t)bc));
+        double *h = c->cvHost.data(), *hyy = h + head_w;
         // y'y of a problem's regularised Gram (the eta rows leave y alone): the entry h_reg reads for a single problem
-        for (int j = 0; j < bc; ++j) h[o_yy + (size_t)j] = hostG[(size_t)((q0 + j) / E) * gs + (size_t)(M + 1) * ldg + (size_t)(M + 1)];
-        PARTLS_HIP_CHECK(hipMemcpyAsync(base + o_yy, h + o_yy, (size_t)bc * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        PARTLS_HIP_CHECK(launch_prep_batch(Gc, gs, (int)E, q0, c->cvEta.as<double>(), ldg, (int)M, W->maskAugD.as<uint64_t>(), /*free_intercept=*/0,
-                                           W->permP, c->knobs.tol_rel, base + o_scale, base + o_tf, base + o_tol, n, bc, c->stream));
-        PARTLS_HIP_CHECK(launch_layout_reg_batch(base + o_tf, n, T, bc, base + o_t0, c->stream));
+        for (int j = 0; j < bc; ++j) hyy[j] = pb.hostG[(size_t)((q0 + j) / E) * pb.gs + (size_t)(M + 1) * ldg + (size_t)(M + 1)];
+        PARTLS_HIP_CHECK(hipMemcpyAsync(pc.tail, hyy, (size_t)bc * sizeof(double), hipMemcpyHostToDevice, c->stream));
         // the B tolerances (and the scales, for the finish) come back once per piece, not per iteration
-        PARTLS_HIP_CHECK(hipMemcpyAsync(h, base, o_yy * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(h, pc.scale, head_w * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
-        ms_prep += ms_since(t0);
+        c->ms[PARTLS_T_PREP] += ms_since(t0);
         t0 = std::chrono::steady_clock::now();
         AltProblems pp;
-        pp.B = bc; pp.E = E; pp.q0 = q0; pp.G = Gc; pp.gs = gs; pp.eta = c->cvEta.as<double>();
-        pp.scale = base + o_scale; pp.T0reg = base + o_t0; pp.t0d = t0d; pp.tol = h + o_tol; pp.yy = base + o_yy;
+        pp.B = bc; pp.E = E; pp.q0 = q0; pp.G = pb.G; pp.gs = pb.gs; pp.eta = c->cvEta.as<double>();
+        pp.scale = pc.scale; pp.T0reg = pc.T0reg; pp.t0d = pc.t0d; pp.tol = h + (size_t)bc * n; pp.yy = pc.tail;
         win.assign((size_t)bc, AltWinner());
         st = alt_multistart_core(W, &pp, a.eps, a.T, R, a.alpha0, a.ld_alpha0, a.beta0, a.ld_beta0, tables_at(q0), win.data());
         if (st != PARTLS_OK) return st;
-        ms_iter += ms_since(t0);
+        c->ms[PARTLS_T_SWEEP] += ms_since(t0);
         t0 = std::chrono::steady_clock::now();
         for (int j = 0; j < bc; ++j) {
-            const int64_t q = q0 + j;
-            // install problem q's prepared state on the working context: what ctx_prepare_tableau would have left (the batched kernels
-            // compute the same entries)
-            W->eta = a.eta[q % E];
-            std::memcpy(W->hG.data(), hostG + (size_t)(q / E) * gs, (size_t)gs * sizeof(double));
-            std::memcpy(W->hScale.data(), h + o_scale + (size_t)j * n, (size_t)n * sizeof(double));
-            W->tol = h[o_tol + (size_t)j];
-            PARTLS_HIP_CHECK(hipMemcpyAsync(W->G.p, Gc + (size_t)(q / E) * gs, (size_t)gs * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
-            PARTLS_HIP_CHECK(hipMemcpyAsync(W->scale.p, base + o_scale + (size_t)j * n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
-            PARTLS_HIP_CHECK(hipMemcpyAsync(W->Tfull.p, base + o_tf + (size_t)j * tfd, tfd * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
-            PARTLS_HIP_CHECK(hipMemcpyAsync(W->T0reg.p, base + o_t0 + (size_t)j * t0d, t0d * sizeof(double), hipMemcpyDeviceToDevice, W->stream));
-            W->coop_state_valid = false;
-            W->tab_valid = false;
-            W->prepared = true;
-            st = finish_problem(c, W, a, q, win[(size_t)j], out);
+            st = batch_install(c, pb, pc, j, h);
+            if (st == PARTLS_OK) st = finish_problem(c, W, a, q0 + j, win[(size_t)j], out);
             if (st != PARTLS_OK) return st;
         }
-        ms_finish += ms_since(t0);
+        c->ms[PARTLS_T_FINISH] += ms_since(t0);
     }
-    c->ms[PARTLS_T_PREP] = ms_prep; c->ms[PARTLS_T_SWEEP] = ms_iter; c->ms[PARTLS_T_FINISH] = ms_finish;
     return PARTLS_OK;
 }
 

@@ -34,6 +34,18 @@ def test_julia_dropin_has_a_stock_fallback():
     assert "function cv_opt" in text and "_cv_opt_julia" in text
 
 
+def test_batch_piece_knob_is_read_once_at_create():
+    """PARTLS_BATCH_PIECE (problems per piece of the batched routes; the GPU tests of the pieces rest on it) is parsed in partls_create
+    with the other knobs and nowhere else: the compute entries never call getenv"""
+    csrc = os.path.join(ROOT, "partitionedls.jl_amd", "csrc")
+    hits = {n: open(os.path.join(csrc, n)).read().count('getenv("PARTLS_BATCH_PIECE")') for n in sorted(os.listdir(csrc))
+            if n.endswith((".hip", ".h"))}
+    assert {n: k for n, k in hits.items() if k} == {"api.hip": 1}
+    api = open(os.path.join(csrc, "api.hip")).read()
+    create = api[api.index("partls_status partls_create("):api.index("void partls_destroy(")]
+    assert 'getenv("PARTLS_BATCH_PIECE")) c->knobs.batch_piece = atoi(e);' in create
+
+
 def test_cv_folds_uneven_sizes(partls):
     fp, perm = partls.cv_folds(11, 3)
     assert list(fp) == [0, 4, 8, 11]

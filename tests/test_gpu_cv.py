@@ -220,6 +220,71 @@ def test_batched_matches_serial_and_repeats_bitwise(partls, ctx, ctx_serial, D, 
     assert np.allclose(a["heldout_sse"][ok], s["heldout_sse"][ok], rtol=1e-9, atol=0)
 
 
+def _agree(a, s):
+    """two routes of one call: the same statuses and winners, models and objectives within the tolerances of batched against serial"""
+    assert np.array_equal(a["status"], s["status"])
+    assert np.array_equal(a["best_index"], s["best_index"])
+    for q in range(len(a["t"])):
+        sc = max(1.0, np.abs(s["alpha"][:, q]).max(), np.abs(s["beta"][:, q]).max())
+        assert np.allclose(a["alpha"][:, q], s["alpha"][:, q], rtol=0, atol=1e-9 * sc), q
+        assert np.allclose(a["beta"][:, q], s["beta"][:, q], rtol=1e-9, atol=1e-9 * sc), q
+        assert abs(a["opt"][q] - s["opt"][q]) <= 1e-10 * s["opt"][q], q
+    ok = ~np.isnan(s["heldout_sse"])
+    assert np.array_equal(ok, ~np.isnan(a["heldout_sse"]))
+    assert np.allclose(a["heldout_sse"][ok], s["heldout_sse"][ok], rtol=1e-9, atol=0)
+
+
+@pytest.fixture(scope="module")
+def ctx_pieces(partls):
+    """contexts whose batched route takes PARTLS_BATCH_PIECE problems per piece (read at partls_create)"""
+    made = {}
+    old = os.environ.get("PARTLS_BATCH_PIECE")
+    try:
+        for piece in (3, 1):
+            os.environ["PARTLS_BATCH_PIECE"] = str(piece)
+            made[piece] = partls.Context(0)
+    finally:
+        if old is None:
+            del os.environ["PARTLS_BATCH_PIECE"]
+        else:
+            os.environ["PARTLS_BATCH_PIECE"] = old
+    return made
+
+
+# 256-thread kernel; 512-thread kernel with winner export; T = 18 without export.  B = 8 problems, E = 2: pieces of 3 begin at q0 = 3 (not
+# a multiple of E) and 6, and the fold changes inside each.  The gap between the best and the second-best pattern of every problem
+# (oracle, in units of y'y on obj^2) is at least 7.0e-4, 4.0e-4 and 1.5e-6, far from the near-tie window: the winners must be equal.
+PIECE_SHAPES = {"n24": (99 + 24, 700, 24, 5, None), "n200": (99 + 200, 700, 200, 3, None), "n280": (1234 + 280, 600, 280, 3, [0, 101, 333, 600])}
+PIECE_ETAS = [0.0, 0.5]
+
+
+@pytest.fixture(scope="module")
+def piece_refs(partls, ctx, ctx_serial):
+    """per shape, computed once: the problem and its unpieced and serial results"""
+    refs = {}
+
+    def get(name):
+        if name not in refs:
+            seed, N, D, K, fp = PIECE_SHAPES[name]
+            X, y, P = _shape(seed, N, D, K)
+            fp = _fold_ptr(N, 3) if fp is None else np.asarray(fp, dtype=np.int64)
+            refs[name] = (X, y, P, fp, _run(partls, ctx, X, y, P, fp, PIECE_ETAS), _run(partls, ctx_serial, X, y, P, fp, PIECE_ETAS))
+        return refs[name]
+    return get
+
+
+@pytest.mark.parametrize("piece", [3, 1])
+@pytest.mark.parametrize("name", list(PIECE_SHAPES))
+def test_pieces_of_the_batch(partls, oracle, ctx_pieces, piece_refs, name, piece):
+    X, y, P, fp, whole, serial = piece_refs(name)
+    assert len(whole["t"]) == 8
+    a = _run(partls, ctx_pieces[piece], X, y, P, fp, PIECE_ETAS)
+    _same(a, _run(partls, ctx_pieces[piece], X, y, P, fp, PIECE_ETAS))
+    assert _check(partls, oracle, X, y, P, fp, PIECE_ETAS, 0, a, f"{name} pieces of {piece}") == 0
+    _agree(a, whole)
+    _agree(a, serial)
+
+
 def test_host_and_device_inputs_agree_bitwise(partls, ctx):
     import torch
     X, y, P = _shape(5, 800, 30, 4)

@@ -288,6 +288,19 @@ def test_a_column_does_not_depend_on_the_grid_the_chunking_or_the_start_order(pa
     assert np.array_equal(rev["best_start"], f["R"] - 1 - full["best_start"])                # A5 has no exact ties between starts
 
 
+@pytest.mark.parametrize("name,env", [("A5", dict(PARTLS_BATCH_PIECE=3)), ("A5", dict(PARTLS_BATCH_PIECE=1)),
+                                      ("B", dict(PARTLS_BATCH_PIECE=3)), ("B", dict(PARTLS_BATCH_PIECE=1)),
+                                      ("A5", dict(PARTLS_BATCH_PIECE=3, PARTLS_ALT_MS_CHUNK=5))])
+def test_pieces_of_the_batch(partls, name, env):
+    """the problems prepared and iterated a piece at a time (pieces of 3 cut through a fold's eta grid: E = 5 and 2), alone and with
+    the trajectories of a piece chunked as well: a problem's trajectories do not depend on its neighbours, so everything is bitwise"""
+    f = FIXTURES[name]
+    X, y, P, a0, b0, fold_ptr = problem(name)
+    pieced = _cv_alt(partls, X, y, P, fold_ptr, f["etas"], a0, b0, f["T"], **env)
+    _same(pieced, device(name))
+    _same(pieced, device(name, serial=True))
+
+
 def test_more_slots_than_one_grid_dimension(partls, oracle):
     N, D, K, F, R = 40, 3, 2, 5, 1400
     etas = [0.0, 0.1, 0.3, 1.0, 3.0, 10.0, 30.0, 100.0]

@@ -171,6 +171,56 @@ def test_position_in_the_batch(partls, ctx, ctx_serial, small, shape):
             _close_models(*_col(other, j), *_col(r, b), yy, f"{shape} column {b} {name}")
 
 
+# ---- 3b. pieces of the batch ----------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def ctx_pieces(partls):
+    """contexts whose batched route takes PARTLS_BATCH_PIECE problems per piece (read at partls_create)"""
+    made = {}
+    old = os.environ.get("PARTLS_BATCH_PIECE")
+    try:
+        for piece in (3, 1):
+            os.environ["PARTLS_BATCH_PIECE"] = str(piece)
+            made[piece] = partls.Context(0)
+    finally:
+        if old is None:
+            del os.environ["PARTLS_BATCH_PIECE"]
+        else:
+            os.environ["PARTLS_BATCH_PIECE"] = old
+    return made
+
+
+@pytest.fixture(scope="module")
+def piece_refs(partls, ctx, ctx_serial):
+    """per shape, computed once: the problem, its seven bootstrap weightings and the unpieced and serial results"""
+    refs = {}
+
+    def get(D, K):
+        if D not in refs:
+            X, y, P = _shape(99 + D, 700, D, K)
+            W = np.asfortranarray(np.random.default_rng(5).multinomial(700, np.full(700, 1 / 700), size=7).T.astype(np.float64))
+            refs[D] = (X, y, P, W, ctx.opt_weightings(X, y, P, W, 0.5), ctx_serial.opt_weightings(X, y, P, W, 0.5))
+        return refs[D]
+    return get
+
+
+# the 256-thread kernel and the 512-thread kernel with winner export; B = 7 in pieces of 3, 3, 1 and of 1.  The best and the
+# second-best pattern of every column are at least 6.8e-4 and 1.9e-4 y'Wy apart on obj^2 (oracle on the row-replicated data), far
+# from the near-tie window: the winners must be equal.
+@pytest.mark.parametrize("piece", [3, 1])
+@pytest.mark.parametrize("D,K", [(24, 5), (200, 3)])
+def test_pieces_of_the_batch(partls, ctx_pieces, piece_refs, D, K, piece):
+    X, y, P, W, whole, serial = piece_refs(D, K)
+    assert W.shape == (700, 7) and np.all((W > 0).sum(0) >= 430)
+    r = ctx_pieces[piece].opt_weightings(X, y, P, W, 0.5)
+    _same(r, ctx_pieces[piece].opt_weightings(X, y, P, W, 0.5))
+    for other, name in ((whole, "unpieced"), (serial, "serial")):
+        assert np.array_equal(r["status"], other["status"]) and np.array_equal(r["oob_rows"], other["oob_rows"])
+        assert np.array_equal(r["best_index"], other["best_index"]), name
+        for b in range(7):
+            yy = float(np.sum(W[:, b] * y * y))
+            assert _close_models(*_col(r, b), *_col(other, b), yy, f"D={D} pieces of {piece} column {b} {name}") == 0
+
+
 # ---- 4. every sweep route -----------------------------------------------------------------------------------------------------------
 # the shapes of test_gpu_cv.py::test_every_sweep_route: 512-thread kernel with winner export (T = 13), T = 18 without export, beyond the
 # register kernel (serial on the deferred-update kernel), the generic kernel by flag, several chains per problem (K = 12)
