@@ -158,7 +158,7 @@ struct partls_ctx {
 
     // Reset by forget_problem (prepare.hip), the one reset of ctx_prepare, batch_reset and batch_work_prepare — whatever below is derived
     // from a prepared problem or its last sweep or solve: prepared, peers; near_for, near_pat, cand, export_wg; sweep_vetoes, rescue_*,
-    // coop_state_valid, coop_fallback; tab_valid; order_ready, order_identity, flip_cost; dw, ds, x_f32; last_upload_*; ms[CALIB], ms[OOB].
+    // coop_state_valid, coop_fallback; tab_valid; order_ready, order_identity, flip_cost, pair_laid; dw, ds, x_f32; last_upload_*; ms[CALIB], ms[OOB].
     // (Not last_kkt / last_min_loo: partls_get_kkt_violation reports them, for the last model returned, without a prepared problem.)
     // problem
     bool prepared = false;
@@ -225,6 +225,12 @@ struct partls_ctx {
     std::vector<int> perm;
     std::vector<uint64_t> mask_tab;
     bool use_reg = false;
+    // pair walk: the live variables of the group on Gray bit 0 have been moved into one tile column (pair_relayout, sweep_setup.hip; perm and
+    // everything laid out by it rebuilt), once per prepare behind the calibration (prepare_sweep_order).  Cleared by ctx_prepare_tableau;
+    // sweep_pairs holds only on such a context, so the problems partls_cv_opt prepares one after another on cv_work under one calibration
+    // keep the prepare's layout and the plain walk.
+    bool pair_laid = false;
+    std::vector<uint64_t> mask_int_host;           // staging of maskInt's upload after a relayout (lives as long as the copy may)
     // Opt sweep: which group sits on which bit of the Gray index (calibrate_bit_order, once per prepare, on the first sweep).
     // The boundary speaks the reference's pattern index (group k = bit k, Opt.jl:4-12) everywhere; only the sweep kernel and the
     // Gray-index ranges of partls_opt_sweep live in the internal order.
@@ -295,6 +301,9 @@ partls_status prepare_weights(partls_ctx *c, const double *w, int64_t N, int on_
 // The second half of ctx_prepare: from the Gram products in c->G (c->M, K, eta, flags, faithful and the partition already set) to the
 // tableau, the host copies and the tolerance.  partls_cv_opt calls it on a context whose G it filled itself.
 partls_status ctx_prepare_tableau(partls_ctx *c);
+// The part of it that follows from c->perm: mask_tab, the packed upload, scale, Tfull, T0reg.  Queues on c->stream, no sync; timed: under
+// the PARTLS_T_PREP events
+partls_status ctx_layout_tableau(partls_ctx *c, bool timed);
 partls_status load_partition(partls_ctx *c, const int64_t *P, int64_t M, int64_t K, int64_t ldP);
 // host X (N x M, ldX, elements of `esz` bytes) -> packed device image (ld N) on c->stream, staged through page-locked buffers when large
 partls_status upload_matrix(partls_ctx *c, void *dst, const void *X, int64_t N, int64_t M, int64_t ldX, size_t esz = sizeof(double));
@@ -330,6 +339,12 @@ void bind_sweep_block(SweepParams &p, double *base, int grid, bool runner_up);  
 hipError_t launch_any_sweep(partls_ctx *c, SweepParams &p, int grid, bool models = false);
 // the Opt sweep's pieces that partls_cv_opt shares
 partls_status calibrate_bit_order(partls_ctx *c);
+// What every entry that sweeps in chain mode does once per prepare (c->order_ready): calibrate_bit_order, then pair_relayout
+partls_status prepare_sweep_order(partls_ctx *c);
+// Pair walk: where the rule of sweep_pairs holds for the whole enumeration, the live variables of the group on Gray bit 0 move into tile
+// column T - 2 (sweep_blk.hip prices twins from that column's fixed tile slots); every other variable keeps its relative order.  c->perm
+// stays the one map from tableau index to feature.  No host sync.  Nothing changes where the rule does not hold.
+partls_status pair_relayout(partls_ctx *c);
 bool sweep_plan(partls_ctx *c, int64_t total, int64_t *chain_len_out, int *grid_out, const char *who);
 bool sweep_pairs(const partls_ctx *c, int64_t total);   // does partls_opt_sweep walk a range of `total` Gray indices in pairs on this context?
 int64_t reference_pattern(const partls_ctx *c, int64_t q);

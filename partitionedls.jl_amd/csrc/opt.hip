@@ -96,7 +96,7 @@ try {
         return PARTLS_OK;
     }
     if (!c->order_ready) {
-        partls_status st = calibrate_bit_order(c);
+        partls_status st = prepare_sweep_order(c);
         if (st != PARTLS_OK) return st;
     }
     const int n = c->n;
@@ -385,7 +385,7 @@ static partls_status export_begin(partls_ctx *c, const char *who, int64_t g_begi
     *empty = g_begin == g_end;
     if (*empty) return PARTLS_OK;
     if (!c->order_ready) {
-        partls_status st = calibrate_bit_order(c);
+        partls_status st = prepare_sweep_order(c);
         if (st != PARTLS_OK) return st;
     }
     return PARTLS_OK;
@@ -685,7 +685,7 @@ try {
     PARTLS_HIP_CHECK(hipSetDevice(c->device));
     if (cnt == 0) return PARTLS_OK;
     if (!c->order_ready) {
-        partls_status st = calibrate_bit_order(c);
+        partls_status st = prepare_sweep_order(c);
         if (st != PARTLS_OK) return st;
     }
     const int64_t kk = std::min<int64_t>(k, cnt);
@@ -739,7 +739,7 @@ try {
     if (!opt_range_ok(c, "partls_opt_bit_order")) return PARTLS_ERR_UNSUPPORTED;
     PARTLS_HIP_CHECK(hipSetDevice(c->device));
     if (!c->order_ready) {
-        partls_status st = calibrate_bit_order(c);
+        partls_status st = prepare_sweep_order(c);
         if (st != PARTLS_OK) return st;
     }
     for (int k = 0; k < c->kbits; ++k) {

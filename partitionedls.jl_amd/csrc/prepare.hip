@@ -141,6 +141,7 @@ void forget_problem(partls_ctx *c)
     c->coop_state_valid = false; c->coop_fallback = false;
     c->tab_valid = false;
     c->order_ready = false; c->order_identity = true; c->flip_cost.clear();
+    c->pair_laid = false;
     c->dw = nullptr; c->ds = nullptr;
     c->x_f32 = false;
     c->last_upload_ms = 0.0; c->last_upload_bytes = 0.0;
@@ -201,20 +202,15 @@ partls_status ctx_prepare(partls_ctx *c, const void *X, int64_t N, int64_t M, in
     return ctx_prepare_tableau(c);
 }
 
-partls_status ctx_prepare_tableau(partls_ctx *c)
+// c->perm -> everything that is laid out by it: the group masks in tableau order, the one upload of masks and permutation, the scale, the
+// tableau and the register kernels' image of it.  Queues on c->stream only (no sync); ctx_prepare_tableau and pair_relayout
+// (sweep_setup.hip) call it.
+partls_status ctx_layout_tableau(partls_ctx *c, bool timed)
 {
-    const int64_t M = c->M, K = c->K;
+    const int64_t M = c->M;
     const double eta = c->eta;
     const bool faithful = c->faithful;
     const uint32_t flags = c->flags;
-    // tableau variables, grouped by partition (stable sort on the lowest group a variable belongs to) so that the
-    // variables one Gray-code flip touches sit in as few 16-wide tile columns as possible
-    c->n = faithful ? (int)M + 1 : (int)M;
-    c->kbits = faithful ? (int)K + 1 : (int)K;
-    c->perm.resize((size_t)c->n);
-    std::iota(c->perm.begin(), c->perm.end(), 0);
-    auto key = [&](int v) { const uint64_t m = c->mask_aug[(size_t)v]; return m ? __builtin_ctzll(m) : 64; };
-    std::stable_sort(c->perm.begin(), c->perm.end(), [&](int a, int b) { return key(a) < key(b); });
     c->mask_tab.resize((size_t)c->n);
     for (int i = 0; i < c->n; ++i) c->mask_tab[(size_t)i] = c->mask_aug[(size_t)c->perm[(size_t)i]];
 
@@ -232,7 +228,7 @@ partls_status ctx_prepare_tableau(partls_ctx *c)
     }
     PARTLS_HIP_CHECK(c->scale.ensure((size_t)c->n * sizeof(double)));
     PARTLS_HIP_CHECK(c->Tfull.ensure((size_t)(c->n + 1) * (c->n + 1) * sizeof(double)));
-    t_begin(c, PARTLS_T_PREP);
+    if (timed) t_begin(c, PARTLS_T_PREP);
     PARTLS_HIP_CHECK(launch_prep(c->G.as<double>(), c->ldg, (int)M, eta, c->maskAugD.as<uint64_t>(), faithful ? 0 : 1,
                                  c->permP, c->scale.as<double>(), c->Tfull.as<double>(), c->n, c->stream));
     c->use_reg = sweep_reg_supported(c->n) && c->n <= 16 * c->knobs.reg_maxt && !(flags & PARTLS_OPT_GENERIC_KERNEL);
@@ -241,7 +237,25 @@ partls_status ctx_prepare_tableau(partls_ctx *c)
         PARTLS_HIP_CHECK(c->T0reg.ensure(sweep_reg_t0_doubles(c->T) * sizeof(double)));
         PARTLS_HIP_CHECK(launch_layout_reg(c->Tfull.as<double>(), c->n, c->T, c->T0reg.as<double>(), c->stream));
     }
-    t_end(c, PARTLS_T_PREP);
+    if (timed) t_end(c, PARTLS_T_PREP);
+    return PARTLS_OK;
+}
+
+partls_status ctx_prepare_tableau(partls_ctx *c)
+{
+    const int64_t M = c->M, K = c->K;
+    const bool faithful = c->faithful;
+    // tableau variables, grouped by partition (stable sort on the lowest group a variable belongs to) so that the
+    // variables one Gray-code flip touches sit in as few 16-wide tile columns as possible
+    c->n = faithful ? (int)M + 1 : (int)M;
+    c->kbits = faithful ? (int)K + 1 : (int)K;
+    c->perm.resize((size_t)c->n);
+    std::iota(c->perm.begin(), c->perm.end(), 0);
+    auto key = [&](int v) { const uint64_t m = c->mask_aug[(size_t)v]; return m ? __builtin_ctzll(m) : 64; };
+    std::stable_sort(c->perm.begin(), c->perm.end(), [&](int a, int b) { return key(a) < key(b); });
+    c->pair_laid = false;
+    partls_status st = ctx_layout_tableau(c, /*timed=*/true);
+    if (st != PARTLS_OK) return st;
     PARTLS_HIP_CHECK(c->hG.resize((size_t)c->ldg * c->ldg));
     PARTLS_HIP_CHECK(c->hScale.resize((size_t)c->n));
     PARTLS_HIP_CHECK(hipMemcpyAsync(c->hG.data(), c->G.p, c->hG.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));

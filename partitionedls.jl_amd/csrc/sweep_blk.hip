@@ -298,7 +298,7 @@ __device__ __forceinline__ int panel_block(double *P, double *Z, double *U, doub
 }
 
 // ---- pair walk: the twin's |C| x |C| solve on ONE wave, no workgroup barrier inside ------------------------------------------
-// The m gathered columns of C (panel columns 0..m-1, ascending variable index) are eliminated by the m sequential pivots of
+// The m columns of C (ascending variable index; where they lie in the panel: below) are eliminated by the m sequential pivots of
 // panel_block, restricted to what decides: the m pivot rows and, as a column of its own, their rhs entries q_C (the panel's rhs row,
 // by symmetry).  The rhs column ends as the twin's rhs entries q'_C of the pivot rows (what scatter takes from the final panel), and
 // these ARE the coefficients of the rank-m update of every other row: with T_ik / |d|, T_kk = -1/d a single pivot gives
@@ -310,21 +310,25 @@ __device__ __forceinline__ int panel_block(double *P, double *Z, double *U, doub
 // indices.  8 VGPRs of matrix per lane: with a whole row per lane (32) the chain kernel of T = 16 spilled.
 // out: [0..16) a_j, [16..32) q'_C, [33] != 0: an entering pivot at or below the guard, or a pivot that is not finite (nothing else of `out` is
 // then meaningful)
-template <int CW>
+// The panel holds ALL 16 columns of the pair column KC (sweep_body: the static gather), panel column k = variable 16 KC + k; cpos[j] = k of
+// the j-th violator (~k: the variable is basic), whose row position is k RS + KC.
+template <int CW, int RS, int KC>
 __device__ __forceinline__ void pair_solve(const double *P, const int *cpos, int m, int lane, int rhspos, double *out)
 {
     const int r = lane & 15, h = lane >> 4;
     const int code = cpos[r < m ? r : 0];
     const unsigned basm = (unsigned)__ballot(code < 0 && lane < m);
-    const int pos = code < 0 ? ~code : code;
+    const int kr = code < 0 ? ~code : code;
+    const int pos = kr * RS + KC;
     double pv[4];
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
         const int c = 4 * h + jj;
-        const double v = P[c * CW + pos];
+        const int cc = cpos[c < m ? c : 0];
+        const double v = P[(cc < 0 ? ~cc : cc) * CW + pos];
         pv[jj] = (r < m && c < m) ? v : 0.0;
     }
-    double qc = P[r * CW + rhspos];
+    double qc = P[kr * CW + rhspos];
     if (r >= m) qc = 0.0;
     bool hard = false;
 #pragma unroll 1
@@ -396,12 +400,14 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
     double *const s_best = lds_image.s_best;
     // pair walk: U and Dinv are idle while a twin is priced (the panel steps rewrite what they read) and lie in the first 64 KB — fields of
     // their own behind the panel each cost an address register that lives through the whole kernel.  s_pair: the solve's results (pair_solve's
-    // `out`); s_cpos[j]: panel row position of the twin's j-th violator (~position: the variable is basic); s_tw[w]: wave w still sees a violator
+    // `out`); s_cpos[j]: local index in the pair column of the twin's j-th violator (~index: the variable is basic); s_tw[w]: wave w still sees a
+    // violator; s_cm: the twin's violators, one bit per variable of the pair column
     [[maybe_unused]] double *const s_pair = U;
     [[maybe_unused]] int *const s_cpos = reinterpret_cast<int *>(Dinv);
     [[maybe_unused]] int *const s_tw = s_cpos + PAIR_MAXC;
+    [[maybe_unused]] int *const s_cm = s_tw + 8;
     static_assert(2 * (MB + 64) >= 2 * PAIR_MAXC + 2, "pair_solve's `out` (doubles) fits U");
-    static_assert(2 * (MB + 64) >= PAIR_MAXC + 8, "s_cpos and s_tw (PAIR_MAXC + 8 ints) fit Dinv (MB + 64 doubles)");
+    static_assert(2 * (MB + 64) >= PAIR_MAXC + 9, "s_cpos, s_tw and s_cm (PAIR_MAXC + 9 ints) fit Dinv (MB + 64 doubles)");
     for (int i = tid; i < 2 * MB * CW; i += THREADS) Pbase[i] = 0.0;                   // padding rows are never gathered
     for (int i = tid; i < MB * CW; i += THREADS) Z[i] = 0.0;
     if (tid < 2 * (MB + 64)) U[tid] = 0.0;
@@ -554,11 +560,11 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
         // Patterns g and g ^ 1 (Gray indices) differ in internal bit 0 only: a PAIR when both lie in the chain.  The tableau visits ONE
         // member per pair — the one whose bit 0 is the committed state's, so a step from pair to pair flips one group on a bit >= 1 — and
         // once that member is confirmed its twin is PRICED from the columns of its violators C: nothing of the tableau is written.  A twin
-        // that pricing cannot finish (more than PAIR_MAXC violators, a small entering pivot, violators left after the block pivot on C) is
+        // that pricing cannot finish (a small entering pivot, violators left after the block pivot on C; more than PAIR_MAXC violators do not
+        // occur: C lies in the one tile column the host gave the group on bit 0, and with a wider group the walk is off) is
         // solved by the ordinary rounds from the current tableau instead; a pattern without its partner in the chain (odd chain ends) is
         // an ordinary pattern.  All of this state is wave-uniform and the same in both halves (the barrier invariant below).
         [[maybe_unused]] bool tw_pending = false;                         // the pattern being solved has a twin that is still to come
-        [[maybe_unused]] int pr_ncol = -1;                                // >= 0: the exchange loop is gathering a twin's columns; columns so far
         // index of the partner of chain pattern i, -1 if it has none
         [[maybe_unused]] auto pair_partner = [&](int i) -> int {
             const int j = (((unsigned)g0 + (unsigned)i) & 1u) ? i - 1 : i + 1;
@@ -690,46 +696,82 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                     if constexpr (!MERGED) break;                         // the turn of the outer loop ends
                     finish_pattern(gi, count != 0);
                     if constexpr (PAIR) {
-                        // 0: no twin to come (second member of a pair, a pattern without partner, or a twin with empty C: done)
-                        // 2: the twin goes to the ordinary rounds  3: its columns are gathered, pricing goes on inside the exchange loop
+                        // 0: no twin to come (second member of a pair, a pattern without partner), or the twin is priced and recorded
+                        // 2: the twin goes to the ordinary rounds
                         int tw = 0;
                         if (tw_pending) {
                             tw = 2;                                   // (a capped pattern's pair is finished by the ordinary path)
                             if (count == 0) {
-                                // ---- violators C of the twin's signs on the current rhs column and basis: a scan of its own ----
-                                const int part = sc & 1;
-                                ++sc;
-                                const uint64_t vmask = s_vmask[tid < 16 * T ? tid : 0] & (has_var ? ~0ULL : 0ULL);
+                                // ---- pricing the twin of pattern gi: a routine of its own, outside the exchange loop --------------------------
+                                // The host has laid every live variable of the group on bit 0 into tile column KC (pair_relayout, sweep_setup.hip),
+                                // so the twin's violators C — variables whose sign bit 0 changes — are among the 16 variables of that column: the
+                                // tile slots to gather are the same in every pattern (static register indices, immediate LDS offsets) and the
+                                // twin's scan is 16 lanes' worth of rhs entries.  ALL 16 columns go to the two panel buffers (both idle at a
+                                // confirmed pattern), the rhs row with them, under the barrier that publishes the violator mask; the solve, the
+                                // rows and the confirming scan then restrict themselves to C.  Nothing of the tableau is written.
+                                constexpr int KC = T - 2, WQ = (16 * KC) >> 6, SHQ = (16 * KC) & 63;
+                                static_assert(KC >= L::G, "the pair column's tile slots all lie in half 1");
+                                // the thread's coordinates once more, opaque: everything derived from `tid` itself is hoisted out of the chain loop
+                                // and held in registers through the whole kernel (lane masks, row positions: 8 spilled VGPRs at T = 16)
+                                int tidp = tid;
+                                asm volatile("" : "+v"(tidp));
+                                const int lanep = tidp & 63, wavep = __builtin_amdgcn_readfirstlane(tidp >> 6), kp = tidp & 15;
+                                const bool mine = (tidp >> 4) == KC;      // this thread holds the rhs entry of variable 16 KC + kp
+                                const uint64_t vmask = s_vmask[tidp < 16 * T ? tidp : 0] & (has_var ? ~0ULL : 0ULL);
                                 const uint64_t gt = (uint64_t)g0 + (unsigned)pair_partner(gi);
                                 const int ft = sign_of_var(vmask, gt ^ (gt >> 1));
-                                const double fqt = q * (double)(ft > 1 ? 1 : (ft < -1 ? -1 : ft));
-                                const bool badt = has_var && (basic ? ((ft == 0) || (fqt < -p.tol)) : (fqt > p.tol));   // kkt_violates (sweep_rules.h), written out
-                                const unsigned long long bt = __ballot(badt);
-                                unsigned summt = (unsigned)__popcll(bt);
-#pragma unroll
-                                for (int sub = 0; sub < 4; ++sub)
-                                    if ((bt >> (16 * sub)) & 0xFFFFull) summt |= 0x100u << sub;
-                                if (lane == 0 && wave < nwords) { s_inf[part * 8 + wave] = bt; s_sum[part * 8 + wave] = summt; }
+                                gather_tile<T, H, W, KC>(S, Pbase, a, b, 0xFFFFu);
+                                if (mine) Pbase[kp * CW + RHSPOS] = q;
+                                if (H == 0 && wavep == WQ) {              // the one wave that holds the pair column's rhs entries
+                                    const double fqt = q * (double)(ft > 1 ? 1 : (ft < -1 ? -1 : ft));
+                                    const bool badt = mine && has_var && (basic ? ((ft == 0) || (fqt < -p.tol)) : (fqt > p.tol));   // kkt_violates (sweep_rules.h), written out
+                                    const unsigned cmw = (unsigned)(__ballot(badt) >> SHQ) & 0xFFFFu;
+                                    if (badt) s_cpos[__builtin_popcount(cmw & ((1u << kp) - 1u))] = basic ? ~kp : kp;
+                                    if (lanep == 0) s_cm[0] = (int)cmw;
+                                }
                                 __syncthreads();
                                 STAMP(15);
-                                int countt = 0;
-                                unsigned tilest = 0;
-#pragma unroll
-                                for (int w = 0; w < NW; ++w) {
-                                    const unsigned sw = (unsigned)__builtin_amdgcn_readfirstlane((int)s_sum[part * 8 + w]);
-                                    countt += (int)(sw & 0xFFu);
-                                    tilest |= (sw >> 8) << (4 * w);
-                                }
-                                if (countt == 0) {                    // C is empty: the twin's optimum is the current corner
+                                const unsigned cm = (unsigned)__builtin_amdgcn_readfirstlane(s_cm[0]);
+                                if (cm == 0) {                        // C is empty: the twin's optimum is the current corner
                                     record_twin(pair_partner(gi), corner, q, basic);
-                                    tw = 0;                           // ... and the confirming scan's look-ahead still holds
-                                } else if (countt <= PAIR_MAXC) {     // gather C through the exchange loop's own gather
-                                    tw = 3;
-                                    pr_ncol = 0;
-                                    all = true;
-                                    tiles = tilest;
-                                    soff = part * 8;
+                                    tw = 0;
+                                } else {
+                                    // One wave solves while the other seven wait at the barrier: nothing else of the pricing can start before the
+                                    // coefficients exist (every row's FMAs need all of them).  Wave 3, of half 0 rather than the blocks' idle wave of
+                                    // half 1: half 0 holds fewer tile slots (66 against 70 at T = 16), so the solve's live registers land where the
+                                    // allocation has room.
+                                    if (H == 0 && wavep == 3) pair_solve<CW, RS, KC>(Pbase, s_cpos, __builtin_popcount(cm), lanep, RHSPOS, s_pair);
+                                    __syncthreads();
+                                    const bool guard = __builtin_amdgcn_readfirstlane(__double2hiint(s_pair[2 * PAIR_MAXC + 1])) != 0;
+                                    // every thread forms its twin rhs entry: the pivot rows take the solve's, the others |C| FMAs on their own panel row
+                                    const bool in_c = mine && ((cm >> kp) & 1u);
+                                    double qt = q, cornert = corner;
+                                    {
+                                        const int rp = tidp < 16 * T ? kp * RS + (tidp >> 4) : RHSPOS;
+                                        int j = 0;
+                                        for (unsigned mm = cm; mm; mm &= mm - 1u, ++j) {
+                                            const int k = __builtin_ctz(mm);
+                                            const double aj = s_pair[j];
+                                            qt = fma(-Pbase[k * CW + rp], aj, qt);
+                                            cornert = fma(-Pbase[k * CW + RHSPOS], aj, cornert);   // the rhs row's own entry: the objective
+                                        }
+                                    }
+                                    if (in_c) qt = s_pair[PAIR_MAXC + __builtin_popcount(cm & ((1u << kp) - 1u))];
+                                    const bool bt = basic != in_c;
+                                    const double fqt = qt * (double)(ft > 1 ? 1 : (ft < -1 ? -1 : ft));
+                                    const bool bad2 = has_var && (bt ? ((ft == 0) || (fqt < -p.tol)) : (fqt > p.tol));   // kkt_violates (sweep_rules.h), written out
+                                    const unsigned long long b2 = __ballot(bad2);
+                                    if (lanep == 0) s_tw[wavep] = b2 != 0ull;
+                                    __syncthreads();
+                                    int left = guard ? 1 : 0;
+#pragma unroll
+                                    for (int w = 0; w < 8; ++w) left |= s_tw[w];
+                                    left = __builtin_amdgcn_readfirstlane(left);
+                                    // easy: the block pivot on C is the whole story — recorded as finish_pattern records; else nothing of the pricing
+                                    // is kept.  Either way the confirming scan's look-ahead still holds: the next pattern starts from it below
+                                    if (!left) { record_twin(pair_partner(gi), cornert, qt, bt); tw = 0; }
                                 }
+                                STAMP(14);
                             }
                         }
                         if (tw == 2) {                                // a fresh scan starts the twin
@@ -739,7 +781,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                             continue;
                         }
                     }
-                    if (!(PAIR && pr_ncol >= 0)) {
+                    {
                     // ---- ... and the next one starts: from this very scan where it can ---------------------------------------------
                     if constexpr (PAIR) { if (!pair_next(false, f, fn)) break; }       // (f and fn: the next visited pattern's and its successor's)
                     else if (++gi >= glen) break;
@@ -782,7 +824,6 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                     tmask = (unsigned)((s_inf[soff + wl] >> shl) & 0xFFFFull) | ((unsigned)((s_bas[par * 8 + wl] >> shl) & 0xFFFFull) << 16);
                 }
 
-                [[maybe_unused]] bool chain_end = false;                  // PAIR: the chain's last pattern was a priced twin
                 while (tiles) {
                     const int kappa = __builtin_ctz(tiles);
                     unsigned pmall, basm;
@@ -801,7 +842,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                     while (pmall) {
                         // ---- block: the lowest <= MB violators of tile column kappa -------------------------------------
                         unsigned rest = 0;
-                        if (__builtin_expect(__builtin_popcount(pmall) > MB && !(PAIR && pr_ncol >= 0), 0)) {       // (pricing gathers a tile column's violators at once)
+                        if (__builtin_expect(__builtin_popcount(pmall) > MB, 0)) {
                             rest = pmall;
 #pragma unroll
                             for (int i = 0; i < MB; ++i) rest &= rest - 1;
@@ -811,12 +852,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                         const int m = __builtin_popcount(pm);
                         const int bpar = bc & 1;
                         double *P = Pbase + bpar * MB * CW;
-                        if constexpr (PAIR) {
-                            // pricing: no block — only its gather, into the next free columns of the two panel buffers (both idle at a confirmed
-                            // pattern; bc, bpar and s_veto stay as they are for the block that follows)
-                            if (pr_ncol >= 0) P = Pbase + pr_ncol * CW;
-                            else ++bc;
-                        } else ++bc;
+                        ++bc;
                         // the tile index is invariant in this loop: left alone, the compiler hoists all 17 `kappa == i` tests out of it
                         // as 64-bit lane masks (34 SGPRs, spilled to VGPR lanes and reloaded per block); the opaque copy keeps each
                         // test a plain s_cmp at its use (C3 sweep 93.0 -> 85.3 ms)
@@ -830,10 +866,6 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                         STAMP(13);
                         if (tid < 16 * T && (tid >> 4) == kappa && ((pm >> (tid & 15)) & 1u))
                             P[__builtin_popcount(pm & ((1u << (tid & 15)) - 1u)) * CW + RHSPOS] = q;
-                        if constexpr (PAIR) {
-                            if (pr_ncol >= 0 && tid < 16 * T && (tid >> 4) == kappa && ((pm >> (tid & 15)) & 1u))
-                                s_cpos[pr_ncol + __builtin_popcount(pm & ((1u << (tid & 15)) - 1u))] = basic ? ~mypos : mypos;
-                        }
                         // is this thread's panel row a pivot row?  row position t <-> variable 16*rowrho + rowc
                         int myj = -1;
                         bool my_basic = false;
@@ -846,9 +878,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                         STAMP(1);
                         if (tid == 0) s_veto[bpar ^ 1] = NO_VETO;              // the other slot: last read before this barrier
                         // ---- 2. panel elimination -----------------------------------------------------------------------
-                        // (pricing: the gathered columns stay as they are — no panel, and below no pivot: the block body runs empty, as after a veto;
-                        // a `continue` behind the gather instead makes the allocator spill 770 VGPRs of the tableau)
-                        if (!(PAIR && pr_ncol >= 0)) {
+                        {
                             int veto;
                             switch (m) {
 #define PARTLS_PB(i) case i: if constexpr (i <= MB) veto = panel_block<(i <= MB ? i : 1), CW, MB>(P, Z, U, Dinv, myj, my_basic, p.piv_eps, tid, tid, idle_wave); else veto = 0; break;
@@ -877,12 +907,6 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                             pmx = 0;
                             mx = 0;
                             ++nveto;
-                        }
-                        if constexpr (PAIR) {
-                            const bool pr = pr_ncol >= 0;
-                            pmx = pr ? 0u : pmx;
-                            mx = pr ? 0 : mx;
-                            pr_ncol += pr ? m : 0;
                         }
                         // ---- 3. fused rank-m update of the register tableau ------------------------------------------------
                         bool blk_ok = false;
@@ -921,80 +945,6 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                         STAMP(4);
                     }
                     tiles &= tiles - 1;
-                if constexpr (PAIR) {
-                    // (inside the loop over the tile columns, behind the last one: an easy twin hands the loop the NEXT pattern's tile columns,
-                    // those of the confirming scan's look-ahead, and its exchange starts without a scan, as it does behind an ordinary pattern)
-                    if (pr_ncol >= 0 && tiles == 0) {
-                        // ---- pricing the twin of pattern gi: its m violators' columns are panel columns 0..m-1 (after this barrier) ----------
-                        const int m = pr_ncol;
-                        pr_ncol = -1;
-                        const int part = (sc - 1) & 1;                    // the twin's scan was the last one
-                        // the thread's coordinates once more, opaque: everything derived from `tid` itself is hoisted out of the chain loop and
-                        // held in registers through the whole kernel (lane masks, row positions: 8 spilled VGPRs at T = 16)
-                        int tidp = tid;
-                        asm volatile("" : "+v"(tidp));
-                        const int lanep = tidp & 63, wavep = __builtin_amdgcn_readfirstlane(tidp >> 6);
-                        __syncthreads();
-                        // One wave solves while the other seven wait at the barrier: nothing else of the pricing can start before the coefficients
-                        // exist (every row's FMAs need all of them).  The panel is not in use, so no wave owns a panel row here and any wave will
-                        // do — wave 3, of half 0 rather than the blocks' idle wave of half 1: half 0 holds fewer tile slots (66 against 70 at
-                        // T = 16), so the solve's ten live registers land where the allocation has room.
-                        if (H == 0 && wavep == 3) pair_solve<CW>(Pbase, s_cpos, m, lanep, RHSPOS, s_pair);
-                        __syncthreads();
-                        const bool guard = __builtin_amdgcn_readfirstlane(__double2hiint(s_pair[2 * PAIR_MAXC + 1])) != 0;
-                        // every thread forms its twin rhs entry: the pivot rows take the solve's, the others m FMAs on their own panel row
-                        const unsigned long long cw = s_inf[part * 8 + wavep];
-                        const bool in_c = has_var && ((cw >> lanep) & 1ull);
-                        double qt = q, cornert = corner;
-                        {
-                            const int rp = tidp < 16 * T ? (tidp & 15) * RS + (tidp >> 4) : RHSPOS;
-                            for (int j = 0; j < m; ++j) {
-                                const double aj = s_pair[j];
-                                qt = fma(-Pbase[j * CW + rp], aj, qt);
-                                cornert = fma(-Pbase[j * CW + RHSPOS], aj, cornert);       // the rhs row's own entry: the objective
-                            }
-                        }
-                        if (in_c) {
-                            int rank = __popcll(cw & ((1ull << lanep) - 1ull));
-#pragma unroll
-                            for (int w = 0; w < NW; ++w)
-                                if (w < wavep) rank += __popcll(s_inf[part * 8 + w]);
-                            qt = s_pair[PAIR_MAXC + rank];
-                        }
-                        const bool bt = basic != in_c;
-                        const uint64_t vmask = s_vmask[tidp < 16 * T ? tidp : 0] & (has_var ? ~0ULL : 0ULL);
-                        const uint64_t gt = (uint64_t)g0 + (unsigned)pair_partner(gi);
-                        const int ft = sign_of_var(vmask, gt ^ (gt >> 1));
-                        const double fqt = qt * (double)(ft > 1 ? 1 : (ft < -1 ? -1 : ft));
-                        const bool bad2 = has_var && (bt ? ((ft == 0) || (fqt < -p.tol)) : (fqt > p.tol));   // kkt_violates (sweep_rules.h), written out
-                        const unsigned long long b2 = __ballot(bad2);
-                        if (lanep == 0) s_tw[wavep] = b2 != 0ull;
-                        __syncthreads();
-                        int left = guard ? 1 : 0;
-#pragma unroll
-                        for (int w = 0; w < 8; ++w) left |= s_tw[w];
-                        left = __builtin_amdgcn_readfirstlane(left);
-                        // easy: the block pivot on C is the whole story — recorded as finish_pattern records; else nothing of the pricing is kept
-                        if (!left) record_twin(pair_partner(gi), cornert, qt, bt);
-                        STAMP(14);
-                        if (!pair_next(left != 0, f, fn)) chain_end = true;
-                        else {
-                            blocked = false;
-                            ninf_best = n + 1; patience = 3; rounds = 0;
-                            if (!left && count2 != 0 && p.max_rounds >= 1) {          // as behind finish_pattern above
-                                ninf_best = count2; rounds = 1;
-                                all = true;
-                                tiles = (unsigned)__builtin_amdgcn_readfirstlane((int)tiles2);
-                                soff = par * 8 + 16;
-                                const int tl = lanep < T ? lanep : 0, wl = tl >> 2, shl = 16 * (tl & 3);
-                                tmask = (unsigned)((s_inf[soff + wl] >> shl) & 0xFFFFull) | ((unsigned)((s_bas[par * 8 + wl] >> shl) & 0xFFFFull) << 16);
-                            }
-                        }
-                    }
-                }
-                }
-                if constexpr (PAIR) {
-                    if (chain_end) break;
                 }
             }
             if constexpr (!MERGED) {

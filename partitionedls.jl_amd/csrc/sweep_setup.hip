@@ -337,18 +337,79 @@ int64_t partls::reference_pattern(const partls_ctx *c, int64_t q)
 //     (C3, K = 20) the walk gains 4.1 % (sweep 47.61 -> 45.65 ms), with 10 (C5, K = 24) it LOSES 3.3 % (669.2 -> 691.6 ms with the walk
 //     forced) — pricing a twin (a scan, a gather pass through the block body, the solve on one wave, the rows, a scan: ~16k cycles in
 //     the stamp build) costs about what 10 pivots in two block pivots cost (profiles/pair_ab_c3.txt).  Nothing between 10 and 12 was
-//     measured; the rule stays on the side that was seen to win.  Beyond 16 every twin goes to the rounds and only its scan is added.
-bool partls::sweep_pairs(const partls_ctx *c, int64_t total)
+//     measured; the rule stays on the side that was seen to win.  (With the static pricing column the forced walk wins on C5 as well,
+//     586.9 against 679.4 ms — profiles/pair_static_ab_c3.txt §4; the bound is still 12 because tests/test_gpu_pair_routes.py pins it.)
+//   * the kernel prices a twin from ONE tile column, so even the forced walk needs that group's live variables to fit one: with more
+//     than 16 the walk is off whatever PARTLS_PAIR says (every twin went to the rounds there anyway).
+// pair_rule is the rule; sweep_pairs also asks that the group has been laid into the pair column (pair_relayout).
+// is tableau variable i a live variable of the group on Gray bit 0?
+static bool on_bit0(const partls_ctx *c, int i)
+{
+    if (c->hScale[(size_t)i] == 0.0) return false;
+    for (int k = 0; k < c->kbits; ++k)
+        if (c->order.gbit[k] == 0 && ((c->mask_tab[(size_t)i] >> k) & 1ULL)) return true;
+    return false;
+}
+
+static bool pair_rule(const partls_ctx *c, int64_t total)
 {
     if (!c->use_reg || sweep_reg_small(c->T) || c->T > 16 || c->knobs.pair == 0) return false;
+    int live = 0;
+    for (int i = 0; i < c->n; ++i) live += on_bit0(c, i);
+    if (live > 16) return false;
     if (c->knobs.pair == 1) return true;
     const int kb = c->kbits, seg_len = (kb + (kb >= 8 ? 2 : 1) - 1) / (kb >= 8 ? 2 : 1);
     if (kb < 2 || ((int64_t)1 << kb) < (int64_t)c->ncu * 32 * (8 + seg_len) || total < (int64_t)c->ncu * 32) return false;
-    int live = 0;
-    for (int k = 0; k < kb; ++k)
-        if (c->order.gbit[k] == 0)
-            for (int i = 0; i < c->n; ++i) live += ((c->mask_tab[(size_t)i] >> k) & 1ULL) != 0 && c->hScale[(size_t)i] != 0.0;
-    return live >= 12 && live <= 16;
+    return live >= 12;
+}
+
+bool partls::sweep_pairs(const partls_ctx *c, int64_t total) { return c->pair_laid && pair_rule(c, total); }
+
+// The pair column is tile column T - 2, not the last one: the last column holds n - 16 (T - 1) variables, as few as one, while T - 2 is
+// full at every n of its tile count.  The new order: the other variables in their present order up to the pair column, then the group's
+// live variables, then the other variables that fill the column, then the rest — the relative order of everything outside the group is
+// kept (tools/layout_probe.py: the order of the other groups moves the sweep by +- 3 %).  scale and the tableau are functions of
+// (perm[i], perm[j]) alone, so the kernels that rebuild them give a permutation of the former entries bit for bit and the host copy of the
+// scale is permuted here instead of read back: no sync.  The calibrated order, the flip costs and dist.order_key's key were derived
+// from the data before this and do not change.
+partls_status partls::pair_relayout(partls_ctx *c)
+{
+    if (c->pair_laid || !pair_rule(c, (int64_t)1 << c->kbits)) return PARTLS_OK;
+    const int n = c->n, base = 16 * (c->T - 2);
+    std::vector<int> grp, oth, idx;
+    for (int i = 0; i < n; ++i) (on_bit0(c, i) ? grp : oth).push_back(i);
+    idx.assign(oth.begin(), oth.begin() + base);            // n >= 16 (T - 1) + 1 and at most 16 in the group: the others reach the column
+    idx.insert(idx.end(), grp.begin(), grp.end());
+    idx.insert(idx.end(), oth.begin() + base, oth.end());
+    c->pair_laid = true;
+    bool same = true;
+    for (int i = 0; i < n; ++i) same = same && idx[(size_t)i] == i;
+    if (same) return PARTLS_OK;
+    std::vector<int> perm((size_t)n);
+    std::vector<double> sc((size_t)n);
+    for (int i = 0; i < n; ++i) { perm[(size_t)i] = c->perm[(size_t)idx[(size_t)i]]; sc[(size_t)i] = c->hScale[(size_t)idx[(size_t)i]]; }
+    c->perm = perm;
+    std::memcpy(c->hScale.data(), sc.data(), (size_t)n * sizeof(double));
+    const partls_status st = ctx_layout_tableau(c, /*timed=*/false);
+    if (st != PARTLS_OK) return st;
+    if (!c->order_identity) {                               // the group masks in the internal bit order, as calibrate_bit_order builds them
+        c->mask_int_host.resize((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            uint64_t m = c->mask_tab[(size_t)i], q = 0;
+            for (; m; m &= m - 1) q |= 1ULL << c->order.gbit[__builtin_ctzll(m)];
+            c->mask_int_host[(size_t)i] = q;
+        }
+        PARTLS_HIP_CHECK(hipMemcpyAsync(c->maskInt.p, c->mask_int_host.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    }
+    c->coop_state_valid = false;
+    c->tab_valid = false;
+    return PARTLS_OK;
+}
+
+partls_status partls::prepare_sweep_order(partls_ctx *c)
+{
+    const partls_status st = calibrate_bit_order(c);
+    return st != PARTLS_OK ? st : pair_relayout(c);
 }
 
 // Chain length and grid of a sweep over `total` Gray indices (partls_opt_sweep; partls_opt_models per piece: the same plan for the same

@@ -16,6 +16,12 @@ rejects a column for them — that count must be 0.
 
   python tools/pair_emul.py tests            the problems of tests/test_gpu_pair.py and tests/test_gpu_pair_routes.py
   python tools/pair_emul.py fuzz [count]     problems drawn by tests/test_gpu_fuzz.py's _random_problem (default 200)
+  python tools/pair_emul.py static [count]   the same fuzz problems after the host's relayout (pair_relayout, sweep_setup.hip): the live
+                                             variables of the group on bit 0 in ONE tile column, the twin priced from that column alone
+                                             (price_static: all its columns gathered, the violator mask taken from its rhs entries only).
+                                             Fails if a twin has a violator outside the column, if the relayout moves another variable out
+                                             of order, or on any priced-but-rejected twin.  The fuzz problems are small, so the tile width
+                                             is 16 where two full columns exist and 8 or 4 below that; the tests' problems run at 16.
 """
 import os
 import sys
@@ -119,12 +125,49 @@ def price(T, n, basic, C):
     return False, qt, T[n, n] - T[C, n] @ a, dmin
 
 
+def relayout(pr, width=16):
+    """pair_relayout: the problem with the live variables of the group on bit 0 in tile column T - 2 (tiles of `width`), every other
+    variable in its present relative order; None where the kernel would keep the parent's layout (the group does not fit, T < 2)"""
+    n, mask, scale = pr["n"], pr["mask"], pr["scale"]
+    T = (n + width - 1) // width
+    on0 = np.array([bool(int(mask[i]) & 1) and scale[i] != 0.0 for i in range(n)])
+    if T < 2 or on0.sum() > width:
+        return None
+    base = width * (T - 2)
+    grp, oth = [i for i in range(n) if on0[i]], [i for i in range(n) if not on0[i]]
+    idx = oth[:base] + grp + oth[base:]
+    assert sorted(idx) == list(range(n)) and [i for i in idx if not on0[i]] == oth and idx[base:base + len(grp)] == grp
+    full = idx + [n]
+    out = dict(pr, T0=pr["T0"][np.ix_(full, full)].copy(), mask=mask[idx], perm=[pr["perm"][i] for i in idx], scale=scale[idx])
+    out["pair_col"] = (base, width)
+    return out
+
+
+def price_static(T, n, basic, ft, tol, col):
+    """the kernel's pricing from the fixed column: violator mask from the column's rhs entries alone, all `width` columns gathered, the
+    solve and the rows restricted to the mask's variables.  (C, price(...)); C is None when a violator lies outside the column"""
+    base, width = col
+    viol = violators(T, n, basic, ft, tol)
+    if viol[:base].any() or viol[base + width:].any():
+        return None, None
+    panel = T[:, base:base + width].copy()                  # the gather: every column of the tile column, rhs row included
+    cm = [k for k in range(width) if viol[base + k]]
+    C = np.array([base + k for k in cm], dtype=int)
+    Tp = np.zeros_like(T)                                   # only what the panel holds may be read
+    Tp[:, C] = panel[:, cm]
+    Tp[C, n] = panel[n, cm]                                 # the rhs entries of C: the panel's rhs row, by symmetry
+    Tp[:n, n] = np.where(np.isin(np.arange(n), C), Tp[:n, n], T[:n, n])
+    Tp[n, n] = T[n, n]
+    return C, price(Tp, n, basic, C)
+
+
 def pair_sweep(pr, chain_len, g_begin=0, g_end=None, pairing=True):
     n, T0, mask, kbits, tol = pr["n"], pr["T0"], pr["mask"], pr["kbits"], pr["tol"]
+    pcol = pr.get("pair_col")
     g_end = (1 << kbits) if g_end is None else g_end
     out = np.full(1 << kbits, np.nan)
     st = dict(pivots=0, easy=0, empty=0, hard_wide=0, hard_guard=0, hard_left=0, capped=0, rejections=0, csize=[], ctiles=[],
-              dmin=np.inf, formula_err=0.0, priced_but_rejected=0)
+              dmin=np.inf, formula_err=0.0, priced_but_rejected=0, outside=0)
     gray = lambda g: g ^ (g >> 1)
     for g0 in range(g_begin, g_end, chain_len):
         glen = min(chain_len, g_end - g0)
@@ -153,6 +196,13 @@ def pair_sweep(pr, chain_len, g_begin=0, g_end=None, pairing=True):
                 ft = signs(mask, n, gray(g0 + partner(gi)))
                 C = np.nonzero(violators(T, n, basic, ft, tol))[0]
                 to_twin = True
+                static = None
+                if pcol is not None:
+                    Cs, static = price_static(T, n, basic, ft, tol, pcol)
+                    if Cs is None:
+                        st["outside"] += 1
+                    else:
+                        assert np.array_equal(Cs, C)
                 if len(C) == 0:
                     st["empty"] += 1
                     out[gray(g0 + partner(gi))] = np.sqrt(max(T[n, n], 0.0))
@@ -160,7 +210,7 @@ def pair_sweep(pr, chain_len, g_begin=0, g_end=None, pairing=True):
                 elif len(C) > PAIR_MAXC:
                     st["hard_wide"] += 1
                 else:
-                    guard, qt, ct, dmin = price(T, n, basic, C)
+                    guard, qt, ct, dmin = price(T, n, basic, C) if static is None else static
                     st["dmin"] = min(st["dmin"], dmin)
                     if guard:
                         st["hard_guard"] += 1
@@ -302,12 +352,36 @@ def main():
         from test_gpu_fuzz import _random_problem
         cnt = int(sys.argv[2]) if len(sys.argv) > 2 else 200
         rng = np.random.default_rng(9000)
+        laid = 0
         for i in range(cnt):
             X, y, P, eta = _random_problem(rng)
             ref = O.fit_opt(X, y, P, eta=eta, return_all=True)["all_opt"]
             pr = prepare(X, y, P, eta)
-            st, err = report("fuzz %d %s K=%d" % (i, X.shape, P.shape[1]), pr, ref, 16)
-            bad += st["priced_but_rejected"]
+            tag = "fuzz %d %s K=%d" % (i, X.shape, P.shape[1])
+            if what == "static":
+                width = 16 if pr["n"] > 32 else (8 if pr["n"] > 16 else 4)
+                pl = relayout(pr, width)
+                if pl is None:
+                    print("%-28s keeps its layout (group on bit 0 wider than a tile column of %d, or one column only)" % (tag, width))
+                    continue
+                laid += 1
+                pr, tag = pl, tag + " w=%d" % width
+            st, err = report(tag, pr, ref, 16)
+            # (the oracle error is reported, not checked: the fuzz draws dependent columns, whose objectives the plain walk misses as well)
+            bad += st["priced_but_rejected"] + st["outside"] + (what == "static" and st["formula_err"] > 1e-9)
+        if what == "static":
+            print("relaid out: %d of %d problems" % (laid, cnt))
+            # the tests' problems at the kernel's own tile width
+            import test_gpu_pair as tp
+            for kind, n, flags in tp.CASES:
+                X, y, P = tp.problem(kind, n, flags)
+                faithful = bool(flags & tp.FAITHFUL)
+                pl = relayout(prepare(np.asarray(X), y, np.asarray(P), 0.0, faithful=faithful))
+                assert (pl is None) == (kind == "wide"), kind
+                if pl is None:
+                    continue
+                st, err = report("%s n=%d flags=%d w=16" % (kind, n, flags), pl, None, 16)
+                bad += st["priced_but_rejected"] + st["outside"] + (st["formula_err"] > 1e-9)
     print("priced-but-rejected / failed checks in total: %d" % bad)
     return 1 if bad else 0
 
