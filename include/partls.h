@@ -538,6 +538,8 @@ partls_status partls_get_gram(const partls_ctx *ctx, double *G_aug);
  * entry points added since (partls_predict_many_f32). */
 #include "partls_f32.h"
 #include "partls_f32_more.h"
+/* ---- sparse design matrices: the prepare and the predict for an X stored in CSR (never densified). */
+#include "partls_csr.h"
 
 #ifdef __cplusplus
 }

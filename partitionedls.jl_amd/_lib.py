@@ -120,6 +120,14 @@ SYMBOLS_F32_MORE = [
                                           C.c_void_p, _i64, _i64, _ip, C.c_void_p, C.c_void_p]),
 ]
 
+# ... and every symbol include/partls_csr.h declares (a design matrix in CSR: int64 row pointers, int32 column indices, float64 values)
+SYMBOLS_CSR = [
+    ("partls_opt_prepare_csr", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_void_p, _i64, _i64, C.c_double, C.c_uint32]),
+    ("partls_predict_csr", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i64, _i64, C.c_int, C.c_void_p, _i64, _i64, _dp, _dp,
+                                     C.c_double, C.c_void_p]),
+]
+
 _lib = None
 
 
@@ -166,7 +174,7 @@ def lib():
                               f"(make -C '{CSRC}'); partitionedls.jl_amd has no CPU fallback")
         _preload_torch_hip_runtime()
         l = C.CDLL(SO_PATH)
-        for name, res, args in SYMBOLS + SYMBOLS_F32 + SYMBOLS_F32_MORE:
+        for name, res, args in SYMBOLS + SYMBOLS_F32 + SYMBOLS_F32_MORE + SYMBOLS_CSR:
             if os.environ.get("PARTLS_LIB") and not hasattr(l, name):
                 continue                   # diagnostic A/B builds of older sources may lack the newest entry points
             f = getattr(l, name)           # AttributeError here = header/library mismatch

@@ -94,10 +94,61 @@ def _u64p(a):
 def _inputs(X, y, P, f32=True):
     """host X, y (or None), P as the library takes them — the ONE place that decides dtype and layout.  X: a float32 array stays float32
     where the entry has a float32 form (f32), every other dtype becomes float64; F-contiguous either way (a C-ordered or
-    strided input is copied, never widened; an array already in that form is returned as it is).  y: float64.  P: F-contiguous int64."""
+    strided input is copied, never widened; an array already in that form is returned as it is).  y: float64.  P: F-contiguous int64.
+    A sparse X never gets here on a supported path (_csr marshals it): an entry that takes a dense X only refuses it."""
+    _no_sparse("this entry point takes a dense X", X, "use fit / predict / Context.opt_prepare_csr / Context.predict_csr, or densify X yourself")
     xt = np.float32 if f32 and getattr(X, "dtype", None) == np.float32 else np.float64
     return (np.asfortranarray(X, dtype=xt), None if y is None else np.ascontiguousarray(y, dtype=np.float64),
             np.asfortranarray(P, dtype=np.int64))
+
+
+class CSR(NamedTuple):
+    """A sparse design matrix in CSR, for callers without scipy: row i holds data[indptr[i]:indptr[i+1]] in the columns
+    indices[indptr[i]:indptr[i+1]], which strictly increase within a row (0-based, no duplicates); shape = (N, M).  Any object with
+    .tocsr() (every scipy.sparse matrix and array) is accepted wherever this is.  DESIGN.md §4.15."""
+    indptr: np.ndarray
+    indices: np.ndarray
+    data: np.ndarray
+    shape: tuple
+
+
+def _is_sparse(X):
+    return isinstance(X, CSR) or hasattr(X, "tocsr")
+
+
+def _no_sparse(who, X, instead):
+    """the entry points that read a dense X only: a sparse X is refused, never densified behind the caller's back"""
+    if _is_sparse(X):
+        raise NotImplementedError("%s: a sparse X is not supported here; %s (the library never densifies a sparse matrix itself)"
+                                  % (who, instead))
+
+
+def _csr(X, who="fit"):
+    """A sparse X as the library takes it — the ONE place that marshals one: canonical CSR (indices sorted within a row, duplicates
+    summed: scipy's sum_duplicates; the arrays of a CSR tuple must be canonical already, the library's validation says so otherwise),
+    indptr int64, indices int32, data float64, all contiguous.  float32 values are widened here: nnz numbers, never N x M.  TypeError /
+    ValueError as the dense path's for a matrix that is not 2-D or not floating point."""
+    if not isinstance(X, CSR):
+        A = X.tocsr()
+        if A is X:
+            A = A.copy()                                     # the caller's matrix is not reordered in place
+        A.sum_duplicates()
+        X = CSR(A.indptr, A.indices, A.data, tuple(A.shape))
+    if len(X.shape) != 2:
+        raise TypeError("%s: X must be a matrix and y a vector (MethodError in the reference)" % who)
+    N, M = int(X.shape[0]), int(X.shape[1])
+    data = np.asarray(X.data)
+    if not np.issubdtype(data.dtype, np.floating):
+        raise TypeError("%s: X and y must be floating point (X::Array{<:AbstractFloat,2}, Opt.jl:73)" % who)
+    indptr = np.ascontiguousarray(X.indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(X.indices, dtype=np.int32)
+    data = np.ascontiguousarray(data, dtype=np.float64)
+    if indptr.shape != (N + 1,) or indices.ndim != 1 or indices.shape != data.shape:
+        raise ValueError("%s: a CSR matrix of shape %s needs indptr of length %d and indices / data of one length, got %s, %s, %s"
+                         % (who, (N, M), N + 1, indptr.shape, indices.shape, data.shape))
+    if int(indptr[-1]) != len(data):                         # the library reads indptr[N] entries of indices and data
+        raise ValueError("%s: indptr[N] = %d, but indices / data hold %d entries" % (who, int(indptr[-1]), len(data)))
+    return CSR(indptr, indices, data, (N, M))
 
 
 def _weights(weights, N, who=None):
@@ -236,7 +287,10 @@ class Context:
         """X, y: host arrays (any layout; copied F-contiguous).  weights: optional per-row sample weights (host, length N):
         partls_opt_prepare_weighted, after which every staged call on the problem is weighted.
         A float32 X stays float32 — uploaded and read as such through partls_opt_prepare_f32, with or without weights; the results are
-        those of X.astype(float64) bit for bit.  Every other dtype is converted to float64; y always is."""
+        those of X.astype(float64) bit for bit.  Every other dtype is converted to float64; y always is.
+        A sparse X (CSR tuple, or anything with .tocsr()) goes through opt_prepare_csr."""
+        if _is_sparse(X):
+            return self.opt_prepare_csr(X, y, P, eta, flags, weights=weights)
         X, y, P = _inputs(X, y, P)
         N, M = X.shape
         w = _weights(weights, N)
@@ -265,6 +319,50 @@ class Context:
             _check(lib.partls_opt_prepare(*head, *tail))
         else:
             _check(lib.partls_opt_prepare_weighted(*head, wp, *tail))
+
+    def opt_prepare_csr(self, csr, y, P, eta=0.0, flags=0, weights=None):
+        """opt_prepare for a sparse X (a CSR tuple or anything with .tocsr(); host arrays): partls_opt_prepare_csr — X goes up as
+        8 (N + 1) + 12 nnz bytes and is never densified; every staged call then works as after a dense prepare."""
+        A = _csr(csr, "opt_prepare_csr")
+        N, M = A.shape
+        y, P = np.ascontiguousarray(y, dtype=np.float64), np.asfortranarray(P, dtype=np.int64)
+        if y.shape != (N,) or P.ndim != 2 or P.shape[0] != M:
+            raise ValueError("DimensionMismatch: X is %s, y is %s, P is %s" % ((N, M), y.shape, P.shape))
+        w = _weights(weights, N)
+        self._prepare_csr(A.indptr.ctypes.data, A.indices.ctypes.data, A.data.ctypes.data, y.ctypes.data,
+                          None if w is None else w.ctypes.data, 0, N, M, P, eta, flags)
+
+    def opt_prepare_csr_device(self, indptr_ptr, indices_ptr, data_ptr, dy_ptr, N, M, P, eta=0.0, flags=0, dw_ptr=None):
+        """the same with the CSR arrays (int64 indptr[N + 1], int32 indices, float64 data), y and the optional weights in HBM: raw device
+        addresses that stay owned by the caller and must stay valid while the context holds the problem"""
+        self._prepare_csr(C.c_void_p(indptr_ptr), C.c_void_p(indices_ptr), C.c_void_p(data_ptr), C.c_void_p(dy_ptr),
+                          None if dw_ptr is None else C.c_void_p(dw_ptr), 1, int(N), int(M), np.asfortranarray(P, dtype=np.int64), eta, flags)
+
+    def _prepare_csr(self, pp, ip, vp, yp, wp, on_device, N, M, P, eta, flags):
+        self._shape = (N, M, P.shape[1])
+        self.generation += 1
+        _check(L.lib().partls_opt_prepare_csr(self._h, pp, ip, vp, N, M, yp, wp, on_device, P.ctypes.data, P.shape[1], P.shape[0],
+                                              float(eta), int(flags)))
+
+    def predict_csr(self, csr, P, alpha, beta, t):
+        """predict for a sparse X (a CSR tuple or anything with .tocsr(); host arrays): partls_predict_csr.  An empty row gives t."""
+        A = _csr(csr, "predict_csr")
+        N, M = A.shape
+        yh = np.zeros(N)
+        self._predict_csr(A.indptr.ctypes.data, A.indices.ctypes.data, A.data.ctypes.data, 0, N, M, np.asfortranarray(P, dtype=np.int64),
+                          alpha, beta, t, yh.ctypes.data)
+        return yh
+
+    def predict_csr_device(self, indptr_ptr, indices_ptr, data_ptr, N, M, P, alpha, beta, t, dyhat_ptr):
+        """the same with the CSR arrays and yhat (N doubles) in HBM: raw device addresses"""
+        self._predict_csr(C.c_void_p(indptr_ptr), C.c_void_p(indices_ptr), C.c_void_p(data_ptr), 1, int(N), int(M),
+                          np.asfortranarray(P, dtype=np.int64), alpha, beta, t, C.c_void_p(dyhat_ptr))
+
+    def _predict_csr(self, pp, ip, vp, on_device, N, M, P, alpha, beta, t, yhat):
+        a = np.ascontiguousarray(alpha, dtype=np.float64)
+        b = np.ascontiguousarray(beta, dtype=np.float64)
+        _check(L.lib().partls_predict_csr(self._h, pp, ip, vp, N, M, on_device, P.ctypes.data, P.shape[1], P.shape[0], _dp(a), _dp(b),
+                                          float(t), yhat))
 
     def num_patterns(self):
         return int(L.lib().partls_opt_num_patterns(self._h))
@@ -569,7 +667,9 @@ class Context:
     def predict(self, X, P, alpha, beta, t):
         """yhat = X (P .* alpha) beta .+ t for a host X of any layout (partls_predict).  A float32 X stays float32 — copied F-contiguous
         when it is C-ordered or strided, never widened — and is uploaded and read as such (partls_predict_f32); every
-        other dtype is converted to float64."""
+        other dtype is converted to float64.  A sparse X goes through predict_csr."""
+        if _is_sparse(X):
+            return self.predict_csr(X, P, alpha, beta, t)
         X, _, P = _inputs(X, None, P)
         N, M = X.shape
         yh = np.zeros(N)
@@ -876,18 +976,21 @@ def regularizeProblem(X, y, P, η):
 def _fit_inputs(X, y, P, f32=False):
     """fit's and cross_validate's argument checks (the reference's method signatures), then _inputs.  Float32 inputs
     (test/runtests.jl:123-146): y is widened (N numbers), X only where the device path has no float32 form (f32 False); result fields
-    are abstract floats in the reference."""
-    X = np.asarray(X)
+    are abstract floats in the reference.  A sparse X (fit only) comes back as the marshalled CSR tuple (_csr), under the same checks."""
     y = np.asarray(y)
     P = np.asarray(P)
-    if X.ndim != 2 or y.ndim != 1:
+    sparse = _is_sparse(X)
+    X = _csr(X, "fit") if sparse else np.asarray(X)          # (_csr: 2-D and floating, the same two errors)
+    if (not sparse and X.ndim != 2) or y.ndim != 1:
         raise TypeError("fit: X must be a matrix and y a vector (MethodError in the reference)")
-    if not (np.issubdtype(X.dtype, np.floating) and np.issubdtype(y.dtype, np.floating)):
+    if not ((sparse or np.issubdtype(X.dtype, np.floating)) and np.issubdtype(y.dtype, np.floating)):
         raise TypeError("fit: X and y must be floating point (X::Array{<:AbstractFloat,2}, Opt.jl:73)")
     if not np.issubdtype(P.dtype, np.integer) or P.ndim != 2:
         raise TypeError("fit: P must be an integer matrix (P::Array{Int,2})")
     if X.shape[0] != y.shape[0] or P.shape[0] != X.shape[1]:
-        raise ValueError("DimensionMismatch: X is %s, y is %s, P is %s" % (X.shape, y.shape, P.shape))
+        raise ValueError("DimensionMismatch: X is %s, y is %s, P is %s" % (tuple(X.shape), y.shape, P.shape))
+    if sparse:
+        return X, np.ascontiguousarray(y, dtype=np.float64), np.asfortranarray(P, dtype=np.int64)
     return _inputs(X, y, P, f32)
 
 
@@ -1102,6 +1205,10 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
     (NotImplementedError with devices=).  DESIGN.md §4.7.
     A float32 X is uploaded and read as float32 (half the transfer and half the device memory of float64); all arithmetic stays fp64
     and every result equals the fit of X.astype(float64) bit for bit.  With devices= it is widened on the host.  DESIGN.md §4.8.
+    A sparse X — any object with .tocsr() (every scipy.sparse matrix or array) or a CSR(indptr, indices, data, shape) tuple — is
+    uploaded as CSR and never densified: every option of Opt (returnAllSolutions, top=, rescue=, faithful_intercept, generic_kernel),
+    Alt (restarts= too), BnB, weights=, η and on_ill_conditioned works as for a dense X; NotImplementedError with devices=.
+    DESIGN.md §4.15.
     Alt, restarts=R (int >= 1): Alt is a local method — R starting points run in one batched device call on one Gram matrix
     (partls_alt_multistart) and the best one is returned.  The starts are R successive single draws from rng (start 0
     is the start of fit(Alt, rng=seed)), or explicit: alpha0 of shape (R, M+1) with beta0 of shape (R, K+1) (restarts then None or R).
@@ -1139,11 +1246,14 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
         raise ValueError("nnlsalg must be one of :nnls, :pivot, :fnnls")
     if on_ill_conditioned not in ("warn", "raise"):
         raise ValueError('on_ill_conditioned must be "warn" or "raise"')
+    if devices is not None:
+        _no_sparse("fit(devices=)", X, "fit on one device, or densify X yourself")
     Xf, yf, Pf = _fit_inputs(X, y, P, f32=devices is None)
     N, M = Xf.shape
     K = Pf.shape[1]
     wf = _weights(weights, N, "fit")
-    staged = wf is not None or Xf.dtype == np.float32     # fits that exist as prepare + a staged call only
+    # fits that exist as prepare + a staged call only (a sparse Xf is the marshalled CSR tuple: Context.opt_prepare takes it as it is)
+    staged = wf is not None or isinstance(Xf, CSR) or Xf.dtype == np.float32
     starts = _alt_starts(alg, M, K, restarts, alpha0, beta0, rng)     # None: a single fit, today's path
     if wf is not None and devices is not None:
         raise NotImplementedError("fit: sample weights are not supported on several devices (devices=)")
@@ -1293,6 +1403,7 @@ def cross_validate(alg, X, y, P, *, η=None, eta=None, nfolds=5, shuffle=False, 
         raise ValueError("cross_validate: restarts, alpha0 and beta0 are options of Alt")
     if on_ill_conditioned not in ("warn", "raise"):
         raise ValueError('on_ill_conditioned must be "warn" or "raise"')
+    _no_sparse("cross_validate", X, "densify X yourself, or call fit per fold and η")
     grid = [0.0] if (η is None and eta is None) else (η if η is not None else eta)
     etas = np.ascontiguousarray(np.atleast_1d(np.asarray(grid, dtype=np.float64)))
     Xf, yf, Pf = _fit_inputs(X, y, P)
@@ -1449,6 +1560,7 @@ class BootstrapResult:
             raise ValueError("predict: no successful replicate")
         if self.P is None:
             raise ValueError("predict: this result does not carry its partition P")
+        _no_sparse("BootstrapResult.predict", X, "densify X yourself, or call predict per model")
         X = np.asarray(X)
         if not np.issubdtype(X.dtype, np.floating) or X.ndim != 2:
             raise TypeError("predict: X must be a floating-point matrix")
@@ -1491,6 +1603,7 @@ def _resample(who, alg, X, y, P, make_W, eta, faithful_intercept, generic_kernel
         raise TypeError("%s: only Opt is supported" % who)
     if on_ill_conditioned not in ("warn", "raise"):
         raise ValueError('on_ill_conditioned must be "warn" or "raise"')
+    _no_sparse(who, X, "densify X yourself, or call fit(weights=...) per weighting")
     Xf, yf, Pf = _fit_inputs(X, y, P)
     N, M = Xf.shape
     counts, W = make_W(N)
@@ -1566,7 +1679,8 @@ def resample(alg, X, y, P, W, *, η=None, eta=None, faithful_intercept=False, ge
 
 
 def predict(*args, device=0):
-    """predict(model, X) or predict(α, β, t, P, X)  ->  X * (P .* α) * β .+ t     [PartitionedLS.jl:132-134,152-155]"""
+    """predict(model, X) or predict(α, β, t, P, X)  ->  X * (P .* α) * β .+ t     [PartitionedLS.jl:132-134,152-155]
+    X: a floating-point matrix, or sparse (anything with .tocsr(), or a CSR tuple): predicted from CSR, never densified."""
     if len(args) == 2:
         model, X = args
         α, β, t, P = model.α, model.β, model.t, model.P
@@ -1574,10 +1688,13 @@ def predict(*args, device=0):
         α, β, t, P, X = args
     else:
         raise TypeError("predict(model, X) or predict(α, β, t, P, X)")
-    X = np.asarray(X)
-    if not np.issubdtype(X.dtype, np.floating) or X.ndim != 2:
-        raise TypeError("predict: X must be a floating-point matrix")
-    Xf, _, Pf = _inputs(X, None, P)                     # what the context is handed is what goes up (Context.predict takes it as it is)
+    if _is_sparse(X):                                   # marshalled here once (TypeError as below); Context.predict takes the tuple as it is
+        Xf, Pf = _csr(X, "predict"), np.asfortranarray(P, dtype=np.int64)
+    else:
+        X = np.asarray(X)
+        if not np.issubdtype(X.dtype, np.floating) or X.ndim != 2:
+            raise TypeError("predict: X must be a floating-point matrix")
+        Xf, _, Pf = _inputs(X, None, P)                 # what the context is handed is what goes up (Context.predict takes it as it is)
     a = np.ascontiguousarray(α, dtype=np.float64)
     b = np.ascontiguousarray(β, dtype=np.float64)
     M = Xf.shape[1]
@@ -1605,6 +1722,7 @@ def predict_many(models, X, *, device=0):
         if len({np.shape(m.α) for m in ms}) != 1 or len({np.shape(m.β) for m in ms}) != 1:
             raise ValueError("predict_many: the models differ in shape")
         a, b, t = np.stack([m.α for m in ms]), np.stack([m.β for m in ms]), np.array([m.t for m in ms], dtype=np.float64)
+    _no_sparse("predict_many", X, "densify X yourself, or call predict per model")
     X = np.asarray(X)
     if not np.issubdtype(X.dtype, np.floating) or X.ndim != 2:
         raise TypeError("predict_many: X must be a floating-point matrix")

@@ -74,7 +74,7 @@ using namespace partls;
 
 extern "C" {
 
-int partls_version(void) { return 106; }
+int partls_version(void) { return 107; }
 const char *partls_last_error(void) { return g_err; }
 
 int partls_device_count(void)
@@ -177,9 +177,12 @@ void partls_destroy(partls_ctx *c)
 }
 
 // predict: w_m = sum_k P[m,k] alpha_m beta_k on the host (predict_weights: M*K flops), yhat = X w + t on the device (one pass over X)
+// pass(wdev, dyh): the one step that knows how X is stored — a host X goes up into the context's pred* buffers, then the prediction
+// pass is queued on c->stream: dyh = X wdev + t (dense_predict_pass below; csr_predict_pass for a sparse X)
+using PredictPass = std::function<partls_status(const double *wdev, double *dyh)>;
 static partls_status predict_common(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, int x_on_device,
-                                    const int64_t *P, int64_t K, int64_t ldP, const double *alpha, const double *beta, double t,
-                                    double *yhat, bool x_f32 = false)
+                                    const int64_t *P, int64_t K, int64_t ldP, const double *alpha, const double *beta,
+                                    double *yhat, const PredictPass &pass)
 {
     partls_status st = check_common(c, X, N, M, ldX, P, K, ldP);
     if (st != PARTLS_OK) return st;
@@ -190,50 +193,89 @@ static partls_status predict_common(partls_ctx *c, const void *X, int64_t N, int
     if (st != PARTLS_OK) return st;
     PARTLS_HIP_CHECK(c->wdev.ensure((size_t)(M + 1) * sizeof(double)));
     PARTLS_HIP_CHECK(hipMemcpyAsync(c->wdev.p, w.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const void *dX = X;
-    int64_t ld = ldX;
-    double *dyh = yhat;
-    if (!x_on_device) {
-        const size_t esz = x_f32 ? sizeof(float) : sizeof(double);
-        PARTLS_HIP_CHECK(c->predX.ensure((size_t)N * M * esz));
-        PARTLS_HIP_CHECK(c->predY.ensure((size_t)N * sizeof(double)));
-        const partls_status us = upload_matrix(c, c->predX.p, X, N, M, ldX, esz);
-        if (us != PARTLS_OK) return us;
-        dX = c->predX.p; ld = N; dyh = c->predY.as<double>();
-    }
-    PARTLS_HIP_CHECK(launch_residual(dX, N, M, ld, nullptr, c->wdev.as<double>(), t, nullptr, 1024, dyh, c->stream, nullptr, x_f32));
-    if (!x_on_device)
-        PARTLS_HIP_CHECK(hipMemcpyAsync(yhat, c->predY.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (!x_on_device) { c->predX.release(); c->predY.release(); }    // a prediction set is not retained
-    return PARTLS_OK;
+    auto run = [&]() -> partls_status {
+        double *dyh = yhat;
+        if (!x_on_device) {
+            PARTLS_HIP_CHECK(c->predY.ensure((size_t)N * sizeof(double)));
+            dyh = c->predY.as<double>();
+        }
+        const partls_status ps = pass(c->wdev.as<double>(), dyh);
+        if (ps != PARTLS_OK) return ps;
+        if (!x_on_device)
+            PARTLS_HIP_CHECK(hipMemcpyAsync(yhat, c->predY.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        return PARTLS_OK;
+    };
+    st = run();
+    if (!x_on_device) { c->predX.release(); c->predY.release(); c->predPtr.release(); c->predIdx.release(); }    // a prediction set is not retained
+    return st;
 }
+
+static partls_status predict_dense(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, int x_on_device,
+                                   const int64_t *P, int64_t K, int64_t ldP, const double *alpha, const double *beta, double t,
+                                   double *yhat, bool x_f32 = false)
+{
+    return predict_common(c, X, N, M, ldX, x_on_device, P, K, ldP, alpha, beta, yhat, [&](const double *wdev, double *dyh) -> partls_status {
+        const void *dX = X;
+        int64_t ld = ldX;
+        if (!x_on_device) {
+            const size_t esz = x_f32 ? sizeof(float) : sizeof(double);
+            PARTLS_HIP_CHECK(c->predX.ensure((size_t)N * M * esz));
+            const partls_status us = upload_matrix(c, c->predX.p, X, N, M, ldX, esz);
+            if (us != PARTLS_OK) return us;
+            dX = c->predX.p; ld = N;
+        }
+        PARTLS_HIP_CHECK(launch_residual(dX, N, M, ld, nullptr, wdev, t, nullptr, 1024, dyh, c->stream, nullptr, x_f32));
+        return PARTLS_OK;
+    });
+}
+
+partls_status partls_predict_csr(partls_ctx *c, const int64_t *indptr, const int32_t *indices, const double *values, int64_t N, int64_t M,
+                                 int x_on_device, const int64_t *P, int64_t K, int64_t ldP, const double *alpha, const double *beta,
+                                 double t, double *yhat)
+try {
+    const char *who = "partls_predict_csr";
+    return predict_common(c, indptr, N, M, N, x_on_device, P, K, ldP, alpha, beta, yhat, [&](const double *wdev, double *dyh) -> partls_status {
+        CsrView A;
+        int64_t nnz = 0;
+        double bytes = 0.0, ms = 0.0;
+        partls_status st = csr_adopt(c, who, indptr, indices, values, N, M, x_on_device, c->predPtr, c->predIdx, c->predX, &A, &nnz, &bytes, &ms);
+        if (st != PARTLS_OK) return st;
+        DevBuf err;                                          // the validation's three words (a prepared problem's buffers stay untouched)
+        PARTLS_HIP_CHECK(err.ensure(3 * sizeof(unsigned long long)));
+        st = csr_check(c, who, A, nnz, err.as<unsigned long long>(), nullptr, {});
+        if (st != PARTLS_OK) return st;
+        PARTLS_HIP_CHECK(launch_csr_residual(A, nullptr, wdev, t, nullptr, 1024, dyh, c->stream));
+        return PARTLS_OK;
+    });
+}
+PARTLS_ABI_GUARD
 
 partls_status partls_predict(partls_ctx *c, const double *X, int64_t N, int64_t M, int64_t ldX, const int64_t *P, int64_t K,
                              int64_t ldP, const double *alpha, const double *beta, double t, double *yhat)
 try {
-    return predict_common(c, X, N, M, ldX, 0, P, K, ldP, alpha, beta, t, yhat);
+    return predict_dense(c, X, N, M, ldX, 0, P, K, ldP, alpha, beta, t, yhat);
 }
 PARTLS_ABI_GUARD
 
 partls_status partls_predict_device(partls_ctx *c, const double *dX, int64_t N, int64_t M, int64_t ldX, const int64_t *P,
                                     int64_t K, int64_t ldP, const double *alpha, const double *beta, double t, double *dyhat)
 try {
-    return predict_common(c, dX, N, M, ldX, 1, P, K, ldP, alpha, beta, t, dyhat);
+    return predict_dense(c, dX, N, M, ldX, 1, P, K, ldP, alpha, beta, t, dyhat);
 }
 PARTLS_ABI_GUARD
 
 partls_status partls_predict_f32(partls_ctx *c, const float *X, int64_t N, int64_t M, int64_t ldX, const int64_t *P, int64_t K,
                                  int64_t ldP, const double *alpha, const double *beta, double t, double *yhat)
 try {
-    return predict_common(c, X, N, M, ldX, 0, P, K, ldP, alpha, beta, t, yhat, /*x_f32=*/true);
+    return predict_dense(c, X, N, M, ldX, 0, P, K, ldP, alpha, beta, t, yhat, /*x_f32=*/true);
 }
 PARTLS_ABI_GUARD
 
 partls_status partls_predict_device_f32(partls_ctx *c, const float *dX, int64_t N, int64_t M, int64_t ldX, const int64_t *P,
                                         int64_t K, int64_t ldP, const double *alpha, const double *beta, double t, double *dyhat)
 try {
-    return predict_common(c, dX, N, M, ldX, 1, P, K, ldP, alpha, beta, t, dyhat, /*x_f32=*/true);
+    return predict_dense(c, dX, N, M, ldX, 1, P, K, ldP, alpha, beta, t, dyhat, /*x_f32=*/true);
 }
 PARTLS_ABI_GUARD
 

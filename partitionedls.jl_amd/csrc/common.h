@@ -234,6 +234,36 @@ hipError_t launch_residual(const void *X, int64_t N, int64_t M, int64_t ldX, con
 int        xtr_slices(int64_t N);
 hipError_t launch_xtr(const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, const double *yhat, double *gpart,
                       hipStream_t s, const double *wt = nullptr, bool x_f32 = false);
+
+// ---- a design matrix stored in CSR (csr.hip): device views of the matrix and of its column-ordered (CSC) copy
+struct CsrView { const int64_t *indptr = nullptr; const int32_t *indices = nullptr; const double *values = nullptr; int64_t N = 0, M = 0; };
+struct CscView { const int64_t *colptr = nullptr; const int32_t *rows = nullptr; const double *values = nullptr; };
+constexpr int CSR_MAX_WAVES = 4096;                          // the rows are dealt to at most this many waves, in contiguous ranges
+constexpr unsigned long long CSR_NO_ROW = ~0ULL;
+int64_t    csr_rows_per_wave(int64_t N);
+int        csr_row_waves(int64_t N);
+// Validation: err[0..2] (device) = the first row with a bad indptr entry / an index outside [0, M) or not above its predecessor / a
+// NaN or Inf value, CSR_NO_ROW where there is none.  nnz = indptr[N] as read by the host (indptr[0] == 0 is the host's check too);
+// nothing outside [0, nnz) is read.  wcnt (optional, csr_row_waves(N) x M): the per-wave column counts launch_csr_transpose starts from.
+hipError_t launch_csr_check(const CsrView &A, int64_t nnz, unsigned long long *err, unsigned *wcnt, hipStream_t s);
+// The CSC copy of a VALID matrix from those counts: launch_csr_colptr (wcnt -> per-wave offsets in place, cnt: M column totals,
+// colptr[M + 1]; safe on an invalid matrix too, so it can run before the host has seen err) and launch_csr_place (rows ascending within
+// every column, by construction: no sort, no atomics).
+hipError_t launch_csr_colptr(const CsrView &A, unsigned *wcnt, unsigned long long *cnt, int64_t *colptr, hipStream_t s);
+hipError_t launch_csr_place(const CsrView &A, const unsigned *wcnt, const int64_t *colptr, int32_t *crow, double *cval, hipStream_t s);
+// The image launch_gram leaves in G (ldg x ldg, [features, ones, y], full symmetric), from the nonzeros alone; wt (optional): the
+// sample weights w (not their roots), entry = sum_i w_i x_ip x_iq.  longest: nonzeros of the longest column; seg / S: nonzeros per wave
+// of a column and the most ranges a column has; part: csr_gram_part_doubles(M, S) doubles; corner: 3 doubles.
+void       csr_gram_plan(int64_t M, int64_t longest, int64_t *seg_out, int *S_out);
+size_t     csr_gram_part_doubles(int64_t M, int S);
+hipError_t launch_csr_gram(const CsrView &A, const CscView &T, const double *y, const double *wt, int64_t seg, int S, double *part,
+                           double *corner, int ldg, double *G, hipStream_t s);
+// launch_residual / launch_xtr for a CSR matrix (X'r reads the CSC copy): the same outputs and fold rules
+hipError_t launch_csr_residual(const CsrView &A, const double *y, const double *w, double t, double *partial, int nblocks, double *yhat,
+                               hipStream_t s, const double *wt = nullptr);
+hipError_t launch_csr_xtr(const CscView &T, int64_t N, int64_t M, const double *y, const double *yhat, double *gpart, hipStream_t s,
+                          const double *wt = nullptr);
+
 hipError_t launch_synth(uint64_t seed, int64_t N, int64_t D, const double *wstar_dev, double *X, double *y, hipStream_t s);
 
 // host-side mirror of the device generator (synth.hip); also used by partls_synth_truth

@@ -13,6 +13,7 @@ namespace partls {
 // destructor, so `delete c` frees whatever partls_ctx declares and no list has to be kept in step with it.  runtime_gone() (api.hip)
 // is true while partls_destroy drops a context whose HIP runtime no longer answers: release() then only forgets the handle.
 bool runtime_gone();
+enum class XStorage { dense64, dense32, csr };      // how the prepared problem's X is stored (partls_ctx::storage)
 struct NoCopy {
     NoCopy() = default;
     NoCopy(const NoCopy &) = delete;
@@ -158,7 +159,7 @@ struct partls_ctx {
 
     // Reset by forget_problem (prepare.hip), the one reset of ctx_prepare, batch_reset and batch_work_prepare — whatever below is derived
     // from a prepared problem or its last sweep or solve: prepared, peers; near_for, near_pat, cand, export_wg; sweep_vetoes, rescue_*,
-    // coop_state_valid, coop_fallback; tab_valid; order_ready, order_identity, flip_cost, pair_laid; dw, ds, x_f32; last_upload_*; ms[CALIB], ms[OOB].
+    // coop_state_valid, coop_fallback; tab_valid; order_ready, order_identity, flip_cost, pair_laid; dw, ds, x_f32, storage; last_upload_*; ms[CALIB], ms[OOB].
     // (Not last_kkt / last_min_loo: partls_get_kkt_violation reports them, for the last model returned, without a prepared problem.)
     // problem
     bool prepared = false;
@@ -168,6 +169,15 @@ struct partls_ctx {
     bool faithful = false;                         // intercept is a sign-constrained tableau variable (2^(K+1) patterns)
     const void *dX = nullptr;                      // device views (owned copies below, or the caller's): X, elements of type ...
     bool x_f32 = false;                            // ... float (partls_opt_prepare_f32) or double; set by every prepare
+    // ... or X is sparse (partls_opt_prepare_csr): dX is nullptr and the data passes read csr (the caller's device arrays, or
+    // the uploads ownPtr / ownIdx / ownVal) and csc, the column-ordered copy the prepare builds into cscPtr / cscRow / cscVal.  csrWork: the
+    // transposition's per-wave column counts, column totals and error words; csrPart: the Gram's partial columns and corner.  storage says
+    // which of the three kinds the prepared problem is; every prepare sets it, forget_problem resets it.
+    partls::XStorage storage = partls::XStorage::dense64;
+    partls::CsrView csr;
+    partls::CscView csc;
+    partls::DevBuf ownPtr, ownIdx, ownVal, cscPtr, cscRow, cscVal, csrWork, csrPart;
+    partls::DevBuf predPtr, predIdx;               // partls_predict_csr: indptr / indices of a host prediction set (values: predX), released after the call
     const double *dy = nullptr;
     partls::DevBuf ownX, ownY;
     // sample weights of the prepared problem (partls_opt_prepare_weighted / partls_cv_opt_weighted; nullptr: unweighted): dw = w (the
@@ -291,6 +301,22 @@ inline double ms_since(std::chrono::steady_clock::time_point t0) { return std::c
 partls_status ctx_prepare(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
                           const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags, const double *w = nullptr,
                           bool x_f32 = false);
+// The same for an X stored in CSR (prepare.hip): everything of ctx_prepare except adopt / upload, the validation and
+// the Gram launch.  Host arrays when !x_on_device (the upload is timed and counted: 8 (N + 1) + 12 nnz bytes)
+partls_status ctx_prepare_csr(partls_ctx *c, const int64_t *indptr, const int32_t *indices, const double *values, int64_t N, int64_t M,
+                              const double *y, const double *w, int x_on_device, const int64_t *P, int64_t K, int64_t ldP, double eta,
+                              bool faithful, uint32_t flags);
+// What it shares with partls_predict_csr (api.hip); who: the entry's name in the messages.
+// csr_adopt: indptr[0] == 0 and indptr[N] >= 0 checked and read (*nnz), N < 2^31; then device arrays are adopted, host arrays go up into
+// up_ptr / up_idx / up_val on c->stream (*bytes = 8 (N + 1) + 12 nnz, *ms: the wall time of the copies) -> *A.
+partls_status csr_adopt(partls_ctx *c, const char *who, const int64_t *indptr, const int32_t *indices, const double *values, int64_t N,
+                        int64_t M, int x_on_device, DevBuf &up_ptr, DevBuf &up_idx, DevBuf &up_val, CsrView *A, int64_t *nnz,
+                        double *bytes, double *ms);
+// csr_check: launch_csr_check into err (3 device words) and wcnt (optional), `queue` (optional: more work for the stream, results
+// the caller wants after the same wait), one wait, and the status and message of the first failed check: a bad indptr or index ->
+// PARTLS_ERR_BAD_ARG naming the first offending row, else NaN / Inf -> PARTLS_ERR_NONFINITE.
+partls_status csr_check(partls_ctx *c, const char *who, const CsrView &A, int64_t nnz, unsigned long long *err, unsigned *wcnt,
+                        const std::function<partls_status()> &queue);
 // c forgets its prepared problem and what its last sweep or solve left behind (the list: partls_ctx); buffers and the upload of X stay
 void forget_problem(partls_ctx *c);
 // X (elements of esz bytes: 8 or 4) and y: device arrays are adopted, host arrays go up into ownX (ld N) / ownY and the upload is timed

@@ -74,6 +74,14 @@ try {
 }
 PARTLS_ABI_GUARD
 
+partls_status partls_opt_prepare_csr(partls_ctx *c, const int64_t *indptr, const int32_t *indices, const double *values, int64_t N, int64_t M,
+                                     const double *y, const double *w, int x_on_device, const int64_t *P, int64_t K, int64_t ldP, double eta,
+                                     uint32_t flags)
+try {
+    return ctx_prepare_csr(c, indptr, indices, values, N, M, y, w, x_on_device, P, K, ldP, eta, (flags & PARTLS_OPT_FAITHFUL_INTERCEPT) != 0, flags);
+}
+PARTLS_ABI_GUARD
+
 int64_t partls_opt_num_patterns(const partls_ctx *c) { return (c && c->prepared && c->kbits <= 40) ? ((int64_t)1 << c->kbits) : 0; }
 
 static partls_status sweep_second_pass(partls_ctx *c, int64_t g_begin, int64_t g_end, double *all_opt, double *bobj_io, int64_t *bpat_io,

@@ -143,7 +143,7 @@ void forget_problem(partls_ctx *c)
     c->order_ready = false; c->order_identity = true; c->flip_cost.clear();
     c->pair_laid = false;
     c->dw = nullptr; c->ds = nullptr;
-    c->x_f32 = false;
+    c->x_f32 = false; c->storage = XStorage::dense64;
     c->last_upload_ms = 0.0; c->last_upload_bytes = 0.0;
     c->ms[PARTLS_T_CALIB] = 0.0; c->ms[PARTLS_T_OOB] = 0.0;
 }
@@ -166,15 +166,19 @@ partls_status adopt_or_upload(partls_ctx *c, const void *X, int64_t N, int64_t M
     return PARTLS_OK;
 }
 
-partls_status ctx_prepare(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
-                          const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags, const double *w, bool x_f32)
+// The two ends of a single problem's prepare, whatever the storage of X (ctx_prepare, ctx_prepare_csr).  prepare_begin: the checks,
+// the reset, the weights, the partition and the shape — everything before X is touched (X: any non-NULL pointer of the matrix; no_multi:
+// the refusal of a context of a partls_multi, NULL where such a context is fine).  prepare_end: from the Gram products in c->G on.
+static partls_status prepare_begin(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
+                                   const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags, const double *w,
+                                   const char *no_multi)
 {
     partls_status st = check_common(c, X, N, M, ldX, P, K, ldP);
     if (st != PARTLS_OK) return st;
     if (!y) { set_error("y is NULL"); return PARTLS_ERR_BAD_ARG; }
     if (!(eta >= 0.0)) { set_error("eta must be >= 0"); return PARTLS_ERR_BAD_ARG; }
     forget_problem(c);
-    if (x_f32 && c->multi_rank) { set_error("float X: a context of a partls_multi is not supported (row-sharded multi-GPU fits are fp64)"); return PARTLS_ERR_UNSUPPORTED; }
+    if (no_multi && c->multi_rank) { set_error("%s", no_multi); return PARTLS_ERR_UNSUPPORTED; }
     PARTLS_HIP_CHECK(hipSetDevice(c->device));
     if (w) {
         if (c->multi_rank) { set_error("sample weights: a context of a partls_multi is not supported (multi-GPU fits are unweighted)"); return PARTLS_ERR_UNSUPPORTED; }
@@ -184,10 +188,25 @@ partls_status ctx_prepare(partls_ctx *c, const void *X, int64_t N, int64_t M, in
     st = load_partition(c, P, M, K, ldP);
     if (st != PARTLS_OK) return st;
     c->N = N; c->M = M; c->K = K; c->eta = eta; c->flags = flags; c->faithful = faithful;
+    return PARTLS_OK;
+}
 
+static partls_status prepare_end(partls_ctx *c)
+{
+    // rows of X sharded over several devices: the Gram products of the blocks are summed here (partls_fit_opt_multi, multi.hip)
+    if (c->gram_hook) { const partls_status st = c->gram_hook(c); if (st != PARTLS_OK) return st; }
+    return ctx_prepare_tableau(c);
+}
+
+partls_status ctx_prepare(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
+                          const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags, const double *w, bool x_f32)
+{
+    partls_status st = prepare_begin(c, X, N, M, ldX, y, x_on_device, P, K, ldP, eta, faithful, flags, w,
+                                     x_f32 ? "float X: a context of a partls_multi is not supported (row-sharded multi-GPU fits are fp64)" : nullptr);
+    if (st != PARTLS_OK) return st;
     st = adopt_or_upload(c, X, N, M, ldX, y, x_on_device, x_f32 ? sizeof(float) : sizeof(double));
     if (st != PARTLS_OK) return st;
-    c->x_f32 = x_f32;
+    c->x_f32 = x_f32; c->storage = x_f32 ? XStorage::dense32 : XStorage::dense64;
 
     // Gram products (fp64 MFMA)
     const size_t slabd = gram_slab_doubles(N, M, c->knobs.gram_S, c->knobs.gram_cr, &c->chunks, &c->ldg);
@@ -197,9 +216,129 @@ partls_status ctx_prepare(partls_ctx *c, const void *X, int64_t N, int64_t M, in
     PARTLS_HIP_CHECK(launch_gram(c->dX, N, M, c->ldX, c->dy, c->slab.as<double>(), c->chunks, c->ldg, c->knobs.gram_S, c->knobs.gram_cr,
                                  c->G.as<double>(), c->stream, c->ds, c->x_f32));
     t_end(c, PARTLS_T_GRAM);
-    // rows of X sharded over several devices: the Gram products of the blocks are summed here (partls_fit_opt_multi, multi.hip)
-    if (c->gram_hook) { st = c->gram_hook(c); if (st != PARTLS_OK) return st; }
-    return ctx_prepare_tableau(c);
+    return prepare_end(c);
+}
+
+// ---- X stored in CSR
+// a host array -> dst on c->stream: as four columns through upload_matrix (its copier threads and page-locked staging), the tail behind
+static partls_status upload_array(partls_ctx *c, void *dst, const void *src, size_t bytes)
+{
+    const size_t col = (bytes / 4) & ~(size_t)7;
+    if (col) { const partls_status st = upload_matrix(c, dst, src, (int64_t)col, 4, (int64_t)col, 1); if (st != PARTLS_OK) return st; }
+    if (bytes > 4 * col)
+        PARTLS_HIP_CHECK(hipMemcpyAsync(static_cast<char *>(dst) + 4 * col, static_cast<const char *>(src) + 4 * col, bytes - 4 * col,
+                                        hipMemcpyHostToDevice, c->stream));
+    return PARTLS_OK;
+}
+
+partls_status csr_adopt(partls_ctx *c, const char *who, const int64_t *indptr, const int32_t *indices, const double *values, int64_t N,
+                        int64_t M, int x_on_device, DevBuf &up_ptr, DevBuf &up_idx, DevBuf &up_val, CsrView *A, int64_t *nnz,
+                        double *bytes, double *ms)
+{
+    if (N >= ((int64_t)1 << 31)) { set_error("%s: N = %lld rows: this build supports N < 2^31 for a sparse X", who, (long long)N); return PARTLS_ERR_UNSUPPORTED; }
+    int64_t ends[2] = {0, 0};
+    if (x_on_device) {
+        PARTLS_HIP_CHECK(hipMemcpyAsync(&ends[0], indptr, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(&ends[1], indptr + N, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    } else { ends[0] = indptr[0]; ends[1] = indptr[N]; }
+    if (ends[0] != 0) { set_error("%s: indptr[0] = %lld, not 0 (row 0)", who, (long long)ends[0]); return PARTLS_ERR_BAD_ARG; }
+    if (ends[1] < 0) { set_error("%s: indptr[N] = %lld is negative (row %lld)", who, (long long)ends[1], (long long)(N - 1)); return PARTLS_ERR_BAD_ARG; }
+    *nnz = ends[1];
+    if (*nnz > 0 && (!indices || !values)) { set_error("%s: indices or values is NULL", who); return PARTLS_ERR_BAD_ARG; }
+    *bytes = 0.0; *ms = 0.0;
+    A->N = N; A->M = M;
+    if (x_on_device) { A->indptr = indptr; A->indices = indices; A->values = values; return PARTLS_OK; }
+    const size_t bp = (size_t)(N + 1) * sizeof(int64_t), bi = (size_t)*nnz * sizeof(int32_t), bv = (size_t)*nnz * sizeof(double);
+    PARTLS_HIP_CHECK(up_ptr.ensure(bp));
+    PARTLS_HIP_CHECK(up_idx.ensure(bi));
+    PARTLS_HIP_CHECK(up_val.ensure(bv));
+    const auto u0 = std::chrono::steady_clock::now();
+    partls_status st = upload_array(c, up_ptr.p, indptr, bp);
+    if (st == PARTLS_OK && bi) st = upload_array(c, up_idx.p, indices, bi);
+    if (st == PARTLS_OK && bv) st = upload_array(c, up_val.p, values, bv);
+    if (st != PARTLS_OK) return st;
+    PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    *ms = ms_since(u0);
+    *bytes = (double)bp + (double)bi + (double)bv;
+    A->indptr = up_ptr.as<int64_t>(); A->indices = up_idx.as<int32_t>(); A->values = up_val.as<double>();
+    return PARTLS_OK;
+}
+
+partls_status csr_check(partls_ctx *c, const char *who, const CsrView &A, int64_t nnz, unsigned long long *err, unsigned *wcnt,
+                        const std::function<partls_status()> &queue)
+{
+    unsigned long long h[3] = {CSR_NO_ROW, CSR_NO_ROW, CSR_NO_ROW};
+    PARTLS_HIP_CHECK(launch_csr_check(A, nnz, err, wcnt, c->stream));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(h, err, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    if (queue) { const partls_status st = queue(); if (st != PARTLS_OK) return st; }
+    PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (h[0] != CSR_NO_ROW && h[0] <= h[1]) {
+        set_error("%s: indptr decreases, is negative or exceeds indptr[N] at row %llu", who, h[0]);
+        return PARTLS_ERR_BAD_ARG;
+    }
+    if (h[1] != CSR_NO_ROW) {
+        set_error("%s: row %llu has a column index outside [0, %lld) or indices that do not strictly increase", who, h[1], (long long)A.M);
+        return PARTLS_ERR_BAD_ARG;
+    }
+    if (h[2] != CSR_NO_ROW) { set_error("%s: values contains NaN/Inf (row %llu)", who, h[2]); return PARTLS_ERR_NONFINITE; }
+    return PARTLS_OK;
+}
+
+partls_status ctx_prepare_csr(partls_ctx *c, const int64_t *indptr, const int32_t *indices, const double *values, int64_t N, int64_t M,
+                              const double *y, const double *w, int x_on_device, const int64_t *P, int64_t K, int64_t ldP, double eta,
+                              bool faithful, uint32_t flags)
+{
+    const char *who = "partls_opt_prepare_csr";
+    partls_status st = prepare_begin(c, indptr, N, M, N, y, x_on_device, P, K, ldP, eta, faithful, flags, w,
+                                     "sparse X: a context of a partls_multi is not supported (row-sharded multi-GPU fits are dense)");
+    if (st != PARTLS_OK) return st;
+    int64_t nnz = 0;
+    double up_bytes = 0.0, up_ms = 0.0;
+    CsrView A;
+    st = csr_adopt(c, who, indptr, indices, values, N, M, x_on_device, c->ownPtr, c->ownIdx, c->ownVal, &A, &nnz, &up_bytes, &up_ms);
+    if (st != PARTLS_OK) return st;
+    if (x_on_device) c->dy = y;
+    else {
+        PARTLS_HIP_CHECK(c->ownY.ensure((size_t)N * sizeof(double)));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(c->ownY.p, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        c->dy = c->ownY.as<double>();
+    }
+    c->last_upload_ms = up_ms; c->last_upload_bytes = up_bytes;
+
+    // csrWork: [error words (3) | column totals (M) | per-wave column counts (waves x M, 32-bit)]
+    const int W = csr_row_waves(N);
+    PARTLS_HIP_CHECK(c->csrWork.ensure((size_t)(3 + M) * 8 + (size_t)W * M * sizeof(unsigned)));
+    unsigned long long *err = c->csrWork.as<unsigned long long>(), *cnt = err + 3;
+    unsigned *wcnt = reinterpret_cast<unsigned *>(cnt + M);
+    PARTLS_HIP_CHECK(c->cscPtr.ensure((size_t)(M + 1) * sizeof(int64_t)));
+    PARTLS_HIP_CHECK(c->cscRow.ensure((size_t)nnz * sizeof(int32_t)));
+    PARTLS_HIP_CHECK(c->cscVal.ensure((size_t)nnz * sizeof(double)));
+    (void)gram_slab_doubles(N, M, c->knobs.gram_S, c->knobs.gram_cr, &c->chunks, &c->ldg);       // the dense image's leading dimension
+    PARTLS_HIP_CHECK(c->G.ensure((size_t)c->ldg * c->ldg * sizeof(double)));
+    std::vector<int64_t> colptr((size_t)M + 1, 0);
+    t_begin(c, PARTLS_T_GRAM);                            // validation, transposition and Gram
+    // the column pointers are safe to form from the counts of an invalid matrix too: they ride on the validation's one wait
+    st = csr_check(c, who, A, nnz, err, wcnt, [&]() -> partls_status {
+        PARTLS_HIP_CHECK(launch_csr_colptr(A, wcnt, cnt, c->cscPtr.as<int64_t>(), c->stream));
+        PARTLS_HIP_CHECK(hipMemcpyAsync(colptr.data(), c->cscPtr.p, colptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        return PARTLS_OK;
+    });
+    if (st != PARTLS_OK) return st;
+    c->csr = A;
+    c->csc = CscView{c->cscPtr.as<int64_t>(), c->cscRow.as<int32_t>(), c->cscVal.as<double>()};
+    c->dX = nullptr; c->ldX = N; c->x_f32 = false; c->storage = XStorage::csr;
+    PARTLS_HIP_CHECK(launch_csr_place(A, wcnt, c->csc.colptr, c->cscRow.as<int32_t>(), c->cscVal.as<double>(), c->stream));
+    int64_t longest = 0, seg = 0;
+    int S = 1;
+    for (int64_t m = 0; m < M; ++m) longest = std::max(longest, colptr[(size_t)m + 1] - colptr[(size_t)m]);
+    csr_gram_plan(M, longest, &seg, &S);
+    const size_t partd = csr_gram_part_doubles(M, S);
+    PARTLS_HIP_CHECK(c->csrPart.ensure((partd + 3) * sizeof(double)));
+    PARTLS_HIP_CHECK(launch_csr_gram(A, c->csc, c->dy, c->dw, seg, S, c->csrPart.as<double>(), c->csrPart.as<double>() + partd, c->ldg,
+                                     c->G.as<double>(), c->stream));
+    t_end(c, PARTLS_T_GRAM);
+    return prepare_end(c);
 }
 
 // c->perm -> everything that is laid out by it: the group masks in tableau order, the one upload of masks and permutation, the scale, the

@@ -49,10 +49,17 @@ partls_status data_pass(partls_ctx *c, const std::vector<double> &w, bool want_o
             yhat = q->yhatD.as<double>();
             PARTLS_HIP_CHECK(q->hGpart.resize((size_t)xr * (M + 1)));
         }
-        PARTLS_HIP_CHECK(launch_residual(q->dX, N, M, q->ldX, want_obj ? q->dy : nullptr, q->wdev.as<double>(), w[(size_t)M],
-                                         want_obj ? q->partial.as<double>() : nullptr, nb, yhat, q->stream, q->dw, q->x_f32));
+        // the two kernels by the storage of X (a sparse X: csr.hip, the same outputs and fold rules)
+        const bool sparse = q->storage == XStorage::csr;
+        if (sparse)
+            PARTLS_HIP_CHECK(launch_csr_residual(q->csr, want_obj ? q->dy : nullptr, q->wdev.as<double>(), w[(size_t)M],
+                                                 want_obj ? q->partial.as<double>() : nullptr, nb, yhat, q->stream, q->dw));
+        else
+            PARTLS_HIP_CHECK(launch_residual(q->dX, N, M, q->ldX, want_obj ? q->dy : nullptr, q->wdev.as<double>(), w[(size_t)M],
+                                             want_obj ? q->partial.as<double>() : nullptr, nb, yhat, q->stream, q->dw, q->x_f32));
         if (want_grad) {
-            PARTLS_HIP_CHECK(launch_xtr(q->dX, N, M, q->ldX, q->dy, yhat, q->gD.as<double>(), q->stream, q->dw, q->x_f32));
+            if (sparse) PARTLS_HIP_CHECK(launch_csr_xtr(q->csc, N, M, q->dy, yhat, q->gD.as<double>(), q->stream, q->dw));
+            else PARTLS_HIP_CHECK(launch_xtr(q->dX, N, M, q->ldX, q->dy, yhat, q->gD.as<double>(), q->stream, q->dw, q->x_f32));
             PARTLS_HIP_CHECK(hipMemcpyAsync(q->hGpart.data(), q->gD.p, q->hGpart.size() * sizeof(double), hipMemcpyDeviceToHost, q->stream));
         }
         if (want_obj) PARTLS_HIP_CHECK(hipMemcpyAsync(q->hPart.data(), q->partial.p, nb * sizeof(double), hipMemcpyDeviceToHost, q->stream));
