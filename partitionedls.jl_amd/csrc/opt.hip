@@ -166,9 +166,11 @@ try {
         if (hipMemcpy(st, c->scratch.p, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess)
             fprintf(stderr, "[partls stamps] scan: pre %.0f barrier %.0f post %.0f | gather: work %.0f barrier %.0f | panel: work %.0f barrier %.0f | "
                             "update %.0f | scatter %.0f | chain-load %.0f/%.0f | pivots %llu || gather split: block setup %.0f chain %.0f rhs/myj %.0f"
-                            " || workgroup 0: %.0f blocks, %.0f scans, %.0f pivots || pair walk: twin scan %.0f, solve + rows + scan %.0f\n",
+                            " || workgroup 0: %.0f blocks, %.0f scans, %.0f pivots || pair walk: twin scan %.0f, solve + rows + scan %.0f"
+                            " = solve prologue %.0f steps %.0f (both on the solving wave only: PARTLS_STAMP_TID=192) barrier behind the solve %.0f"
+                            " rows %.0f verdict %.0f\n",
                     st[9], st[10], st[0], st[12] + st[13] + st[8], st[1], st[11], st[2], st[3], st[4], st[5], st[6], cnt[1], st[12], st[13], st[8],
-                    st[24], st[25], st[26], st[15], st[14]);
+                    st[24], st[25], st[26], st[15], st[16] + st[17] + st[18] + st[19] + st[20], st[16], st[17], st[18], st[19], st[20]);
     }
     double bobj = INFINITY;
     int64_t bpat = -1;

@@ -109,10 +109,14 @@ template <class PT> __device__ __forceinline__ PT *uniform_ptr(PT *p)     // a w
 #endif
 #define STAMP_FLUSH do { if (tid == PARTLS_STAMP_TID && blockIdx.x == 0 && p.scratch) { for (int _i = 0; _i < 24; ++_i) p.scratch[_i] = (double)st_acc[_i]; \
                                 p.scratch[24] = (double)bc; p.scratch[25] = (double)sc; p.scratch[26] = (double)npiv; } } while (0)   /* + blocks, scans, pivots of workgroup 0 */
+#define STAMP_PARAMS , unsigned long long (&st_acc)[24], unsigned long long &st_t       /* a helper that stamps: the caller's accumulators */
+#define STAMP_ARGS , st_acc, st_t
 #else
 #define STAMP_DECL
 #define STAMP(ph) do { } while (0)
 #define STAMP_FLUSH do { } while (0)
+#define STAMP_PARAMS
+#define STAMP_ARGS
 #endif
 
 // LDS image, statically allocated at namespace scope (one copy per kernel, shared by the two half instantiations): every
@@ -305,55 +309,57 @@ __device__ __forceinline__ int panel_block(double *P, double *Z, double *U, doub
 // q_i - T_ik q_k / d and q'_k = q_k / |d|, i.e. q_i - T_ik a_k with a_k = +q'_k for an entering and -q'_k for a leaving variable, and
 // so for the block (the sweeps of distinct variables commute); the rhs row itself is such a row: corner' = corner - sum_k q_k a_k.
 // Checked against sequential pivots in tools/pair_emul.py.
-// Layout: lane = r + 16 h holds row r of the four columns 4 h .. 4 h + 3, as ROTATED: at step s register jj of quarter h is column
-// (s + 4 h + jj) mod 16, so the pivot column is always register 0 of quarter 0 and the step loop stays rolled with static register
-// indices.  8 VGPRs of matrix per lane: with a whole row per lane (32) the chain kernel of T = 16 spilled.
-// out: [0..16) a_j, [16..32) q'_C, [33] != 0: an entering pivot at or below the guard, or a pivot that is not finite (nothing else of `out` is
-// then meaningful)
-// The panel holds ALL 16 columns of the pair column KC (sweep_body: the static gather), panel column k = variable 16 KC + k; cpos[j] = k of
-// the j-th violator (~k: the variable is basic), whose row position is k RS + KC.
+// Layout, DENSE: the panel holds ALL 16 columns of the pair column KC (sweep_body: the static gather), panel column k = variable 16 KC + k,
+// whose row position is k RS + KC.  Lane = r + 16 h holds row r of the four columns 4 h .. 4 h + 3 of that 16 x 16 block, loaded from
+// fixed addresses.  The steps run over k = 0 .. 15 in ascending order and a wave-uniform bit test of the violator mask `cm` skips every
+// column outside C: exactly |C| steps execute, in the order of the compacted solve.  The pivot column of step k is register k & 3 of
+// quarter k >> 2: four steps written out inside a rolled loop over the quarters keep the register indices static, only the source lane
+// of the shuffles moves.  Rows and columns outside C carry whatever the tableau holds there and are updated along with the rest; an
+// entry (r, c) with r and c in C only ever takes its factors from rows r and c of a pivot column of C, so none of that reaches C, and the
+// guard tests the steps of C only.  8 VGPRs of matrix per lane: with a whole row per lane (32) the chain kernel of T = 16 spilled.
+// basm: the basis flags of the 16 variables (bit k: variable 16 KC + k is basic).
+// out, indexed by k: [0..16) a_k (0 outside C), [16..32) q'_k (meaningful on C), [33] != 0: an entering pivot at or below the guard, or a
+// pivot that is not finite (nothing else of `out` is then meaningful)
 template <int CW, int RS, int KC>
-__device__ __forceinline__ void pair_solve(const double *P, const int *cpos, int m, int lane, int rhspos, double *out)
+__device__ __forceinline__ void pair_solve(const double *P, unsigned cm, unsigned basm, int lane, int rhspos, double *out STAMP_PARAMS)
 {
     const int r = lane & 15, h = lane >> 4;
-    const int code = cpos[r < m ? r : 0];
-    const unsigned basm = (unsigned)__ballot(code < 0 && lane < m);
-    const int kr = code < 0 ? ~code : code;
-    const int pos = kr * RS + KC;
+    const int pos = r * RS + KC;
     double pv[4];
 #pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-        const int c = 4 * h + jj;
-        const int cc = cpos[c < m ? c : 0];
-        const double v = P[(cc < 0 ? ~cc : cc) * CW + pos];
-        pv[jj] = (r < m && c < m) ? v : 0.0;
-    }
-    double qc = P[kr * CW + rhspos];
-    if (r >= m) qc = 0.0;
+    for (int jj = 0; jj < 4; ++jj) pv[jj] = P[(4 * h + jj) * CW + pos];
+    double qc = P[r * CW + rhspos];
     bool hard = false;
+    STAMP(16);
 #pragma unroll 1
-    for (int s = 0; s < m; ++s) {
-        const double d = readlane_f64(pv[0], s);
-        const int dh = __double2hiint(d);                       // (wave-uniform: scalar compares)
-        if ((!((basm >> s) & 1u) && !(dh > PAIR_PIV_MIN_HI)) || (dh & F64_EXP_HI) == F64_EXP_HI) { hard = true; break; }
-        const double inv = rcp_newton(d), ainv = fabs(inv);
-        const double pvs = __shfl(pv[0], r);                    // this row's entry of the pivot column
-        const double fz = -pvs * inv;
-        const double qs = readlane_f64(qc, s);
-        double val[4];
+    for (int hq = 0; hq < 4 && !hard; ++hq) {
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
-            const double u = __shfl(pv[0], (s + 4 * h + jj) & 15);     // the pivot row's entry, from the pivot COLUMN (panel_block's NUMERICS)
-            val[jj] = (r == s) ? u * ainv : fma(fz, u, pv[jj]);
+            const int s = 4 * hq + jj;
+            if (hard || !((cm >> s) & 1u)) continue;            // (wave-uniform: a scalar branch)
+            const double d = readlane_f64(pv[jj], 16 * hq + s);
+            const int dh = __double2hiint(d);                   // (wave-uniform: scalar compares)
+            if ((!((basm >> s) & 1u) && !(dh > PAIR_PIV_MIN_HI)) || (dh & F64_EXP_HI) == F64_EXP_HI) { hard = true; continue; }
+            const double inv = rcp_newton(d), ainv = fabs(inv);
+            const double pvs = __shfl(pv[jj], 16 * hq + r);     // this row's entry of the pivot column
+            const double fz = -pvs * inv;
+            const double qs = readlane_f64(qc, s);
+            double u[4];
+#pragma unroll
+            for (int j2 = 0; j2 < 4; ++j2) u[j2] = __shfl(pv[jj], 16 * hq + 4 * h + j2);     // the pivot row's entry, from the pivot COLUMN (panel_block's NUMERICS)
+#pragma unroll
+            for (int j2 = 0; j2 < 4; ++j2) {
+                const double v = (r == s) ? u[j2] * ainv : fma(fz, u[j2], pv[j2]);
+                pv[j2] = (j2 == jj && h == hq) ? ((r == s) ? -inv : pvs * ainv) : v;     // (... : the pivot column itself)
+            }
+            qc = (r == s) ? qs * ainv : fma(fz, qs, qc);
         }
-        if (h == 0) val[0] = (r == s) ? -inv : pvs * ainv;      // the pivot column itself
-        qc = (r == s) ? qs * ainv : fma(fz, qs, qc);
-        const double nx = __shfl(val[0], (lane + 16) & 63);
-        pv[0] = val[1]; pv[1] = val[2]; pv[2] = val[3]; pv[3] = nx;
     }
+    STAMP(17);
     if (lane < PAIR_MAXC) {
+        const bool in_c = (cm >> lane) & 1u;
         out[PAIR_MAXC + lane] = qc;
-        out[lane] = ((basm >> lane) & 1u) ? -qc : qc;
+        out[lane] = in_c ? (((basm >> lane) & 1u) ? -qc : qc) : 0.0;
     }
     if (lane == 0) out[2 * PAIR_MAXC + 1] = hard ? 1.0 : 0.0;
 }
@@ -400,14 +406,14 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
     double *const s_best = lds_image.s_best;
     // pair walk: U and Dinv are idle while a twin is priced (the panel steps rewrite what they read) and lie in the first 64 KB — fields of
     // their own behind the panel each cost an address register that lives through the whole kernel.  s_pair: the solve's results (pair_solve's
-    // `out`); s_cpos[j]: local index in the pair column of the twin's j-th violator (~index: the variable is basic); s_tw[w]: wave w still sees a
-    // violator; s_cm: the twin's violators, one bit per variable of the pair column
+    // `out`); s_tw[w]: wave w still sees a violator; s_cm: the twin's violators, one bit per variable of the pair column, in the low half and
+    // the basis flags of the column's variables in the high half
     [[maybe_unused]] double *const s_pair = U;
-    [[maybe_unused]] int *const s_cpos = reinterpret_cast<int *>(Dinv);
-    [[maybe_unused]] int *const s_tw = s_cpos + PAIR_MAXC;
+    [[maybe_unused]] int *const s_tw = reinterpret_cast<int *>(Dinv);
     [[maybe_unused]] int *const s_cm = s_tw + 8;
+    static_assert(PAIR_MAXC == 16, "the pair column is one tile column: 16 variables, one mask bit each");
     static_assert(2 * (MB + 64) >= 2 * PAIR_MAXC + 2, "pair_solve's `out` (doubles) fits U");
-    static_assert(2 * (MB + 64) >= PAIR_MAXC + 9, "s_cpos, s_tw and s_cm (PAIR_MAXC + 9 ints) fit Dinv (MB + 64 doubles)");
+    static_assert(2 * (MB + 64) >= 9, "s_tw and s_cm (9 ints) fit Dinv (MB + 64 doubles)");
     for (int i = tid; i < 2 * MB * CW; i += THREADS) Pbase[i] = 0.0;                   // padding rows are never gathered
     for (int i = tid; i < MB * CW; i += THREADS) Z[i] = 0.0;
     if (tid < 2 * (MB + 64)) U[tid] = 0.0;
@@ -726,12 +732,13 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                                     const double fqt = q * (double)(ft > 1 ? 1 : (ft < -1 ? -1 : ft));
                                     const bool badt = mine && has_var && (basic ? ((ft == 0) || (fqt < -p.tol)) : (fqt > p.tol));   // kkt_violates (sweep_rules.h), written out
                                     const unsigned cmw = (unsigned)(__ballot(badt) >> SHQ) & 0xFFFFu;
-                                    if (badt) s_cpos[__builtin_popcount(cmw & ((1u << kp) - 1u))] = basic ? ~kp : kp;
-                                    if (lanep == 0) s_cm[0] = (int)cmw;
+                                    const unsigned basw = (unsigned)(__ballot(basic) >> SHQ) & 0xFFFFu;     // this wave's word of s_bas, at the column
+                                    if (lanep == 0) s_cm[0] = (int)(cmw | (basw << 16));
                                 }
                                 __syncthreads();
                                 STAMP(15);
-                                const unsigned cm = (unsigned)__builtin_amdgcn_readfirstlane(s_cm[0]);
+                                const unsigned cmb = (unsigned)__builtin_amdgcn_readfirstlane(s_cm[0]);
+                                const unsigned cm = cmb & 0xFFFFu;
                                 if (cm == 0) {                        // C is empty: the twin's optimum is the current corner
                                     record_twin(pair_partner(gi), corner, q, basic);
                                     tw = 0;
@@ -740,23 +747,42 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                                     // coefficients exist (every row's FMAs need all of them).  Wave 3, of half 0 rather than the blocks' idle wave of
                                     // half 1: half 0 holds fewer tile slots (66 against 70 at T = 16), so the solve's live registers land where the
                                     // allocation has room.
-                                    if (H == 0 && wavep == 3) pair_solve<CW, RS, KC>(Pbase, s_cpos, __builtin_popcount(cm), lanep, RHSPOS, s_pair);
+                                    if (H == 0 && wavep == 3) pair_solve<CW, RS, KC>(Pbase, cm, cmb >> 16, lanep, RHSPOS, s_pair STAMP_ARGS);
+                                    else STAMP(16);               // (the other waves' stamps: all of the solve is their wait, 18)
                                     __syncthreads();
+                                    STAMP(18);
                                     const bool guard = __builtin_amdgcn_readfirstlane(__double2hiint(s_pair[2 * PAIR_MAXC + 1])) != 0;
-                                    // every thread forms its twin rhs entry: the pivot rows take the solve's, the others |C| FMAs on their own panel row
+                                    // Every thread forms its twin rhs entry: the pivot rows take the solve's, the others 16 FMAs on their own panel row, in
+                                    // ascending k — a term outside C has a_k = 0 and leaves the sum as it is, bit for bit.  The objective (the rhs row's
+                                    // own entry) is a second chain of the same form.  The coefficients are wave-uniform: lane k of every row of 16
+                                    // lanes reads -a_k and the rhs row's q_k ONCE, and the FMAs take them as DPP row broadcasts (sweep_lazy.hip's
+                                    // lz_fmac_bcast); each thread's own 16 panel entries are reads at immediate offsets of one address.
                                     const bool in_c = mine && ((cm >> kp) & 1u);
                                     double qt = q, cornert = corner;
                                     {
-                                        const int rp = tidp < 16 * T ? kp * RS + (tidp >> 4) : RHSPOS;
-                                        int j = 0;
-                                        for (unsigned mm = cm; mm; mm &= mm - 1u, ++j) {
-                                            const int k = __builtin_ctz(mm);
-                                            const double aj = s_pair[j];
-                                            qt = fma(-Pbase[k * CW + rp], aj, qt);
-                                            cornert = fma(-Pbase[k * CW + RHSPOS], aj, cornert);   // the rhs row's own entry: the objective
-                                        }
+                                        const double *prow = Pbase + (tidp < 16 * T ? kp * RS + (tidp >> 4) : RHSPOS);
+                                        const double na = -s_pair[kp], qk = Pbase[kp * CW + RHSPOS];
+                                        double tq;
+                                        // (inline asm: the compiler pads no hazard of a DPP operand — a VGPR written by the VALU needs two wait states
+                                        // before a DPP instruction reads it, an EXEC written by the VALU five)
+#define PARTLS_ROW(K, PAD) asm volatile("s_nop " #PAD "\n\t" \
+                                          "v_mov_b64_dpp %2, %4 row_newbcast:" #K " row_mask:0xf bank_mask:0xf\n\t" \
+                                          "v_fmac_f64_dpp %0, %3, %5 row_newbcast:" #K " row_mask:0xf bank_mask:0xf\n\t" \
+                                          "s_nop 0\n\t" \
+                                          "v_fmac_f64_dpp %1, %3, %2 row_newbcast:" #K " row_mask:0xf bank_mask:0xf" \
+                                          : "+v"(qt), "+v"(cornert), "=&v"(tq) : "v"(na), "v"(qk), "v"(pk[K]));
+                                        // (an asm statement is a barrier to the scheduler: all 16 reads are issued ahead of the FMAs, one round trip; the
+                                        // allocation takes the 32 registers — they are dead again before the tableau is touched)
+                                        double pk[PAIR_MAXC];
+#pragma unroll
+                                        for (int k = 0; k < PAIR_MAXC; ++k) pk[k] = prow[k * CW];
+                                        PARTLS_ROW(0, 4) PARTLS_ROW(1, 1) PARTLS_ROW(2, 1) PARTLS_ROW(3, 1) PARTLS_ROW(4, 1) PARTLS_ROW(5, 1)
+                                        PARTLS_ROW(6, 1) PARTLS_ROW(7, 1) PARTLS_ROW(8, 1) PARTLS_ROW(9, 1) PARTLS_ROW(10, 1) PARTLS_ROW(11, 1)
+                                        PARTLS_ROW(12, 1) PARTLS_ROW(13, 1) PARTLS_ROW(14, 1) PARTLS_ROW(15, 1)
+#undef PARTLS_ROW
                                     }
-                                    if (in_c) qt = s_pair[PAIR_MAXC + __builtin_popcount(cm & ((1u << kp) - 1u))];
+                                    if (in_c) qt = s_pair[PAIR_MAXC + kp];
+                                    STAMP(19);
                                     const bool bt = basic != in_c;
                                     const double fqt = qt * (double)(ft > 1 ? 1 : (ft < -1 ? -1 : ft));
                                     const bool bad2 = has_var && (bt ? ((ft == 0) || (fqt < -p.tol)) : (fqt > p.tol));   // kkt_violates (sweep_rules.h), written out
@@ -771,7 +797,7 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
                                     // is kept.  Either way the confirming scan's look-ahead still holds: the next pattern starts from it below
                                     if (!left) { record_twin(pair_partner(gi), cornert, qt, bt); tw = 0; }
                                 }
-                                STAMP(14);
+                                STAMP(20);                            // (16 .. 20: the pricing behind the scan, STAMP 14 of the earlier records)
                             }
                         }
                         if (tw == 2) {                                // a fresh scan starts the twin

@@ -1,11 +1,21 @@
 #!/bin/bash
-# build_ab.sh — libpartls_hip.so from the working tree + libpartls_hip_lz.so with HEAD's sweep_lazy.hip (same-box A/B: tools/ab_lazy.sh)
-set -e
-cd /root/repo/partitionedls.jl_amd/csrc
-make 2>&1 | grep -E "rror" || true
-mkdir -p _build_lz
-git show HEAD:partitionedls.jl_amd/csrc/sweep_lazy.hip > sweep_lazy_head.hip
-/opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -Wno-unused-function -ffp-contract=off -c sweep_lazy_head.hip -o _build_lz/sweep_lazy_head.o 2>&1 | grep -E "rror" || true
-rm -f sweep_lazy_head.hip
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../libpartls_hip_lz.so _build/api.o _build/gram.o _build/misc.o _build/sweep_generic.o _build/sweep_blk.o _build/sweep_coop.o _build/solvers.o _build/multi.o _build_lz/sweep_lazy_head.o -ldl
-ls -la ../*.so
+# (round 4 used an earlier form of this script for an A/B of sweep_lazy.hip alone: the history has it)
+# build_ab.sh [commit] — the three libraries of a same-box A/B of the sweep (select each with PARTLS_LIB):
+#   libpartls_hip.so             the working tree
+#   libpartls_hip_parent.so      <commit> (default HEAD), built from an export of it in a temporary directory
+#   libpartls_hip_parent_t16.so  the placement control: <commit>'s sources with sweep_blk.hip compiled for T = 16 alone (-DPARTLS_ONLY_T=16)
+set -e -o pipefail
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+REV=${1:-HEAD}
+HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
+FLAGS="-O3 -fPIC -std=c++17 --offload-arch=gfx950 -Wall -Wno-unused-function -ffp-contract=off"
+make -s -C "$ROOT/partitionedls.jl_amd/csrc" -j8
+TMP=$(mktemp -d)
+trap 'rm -rf "$TMP"' EXIT
+git -C "$ROOT" archive "$REV" | tar -x -C "$TMP"
+make -s -C "$TMP/partitionedls.jl_amd/csrc" -j8
+cp "$TMP/partitionedls.jl_amd/libpartls_hip.so" "$ROOT/partitionedls.jl_amd/libpartls_hip_parent.so"
+cd "$TMP/partitionedls.jl_amd/csrc"
+$HIPCC $FLAGS -DPARTLS_ONLY_T=16 -c sweep_blk.hip -o "$TMP/sweep_blk_t16.o"
+$HIPCC -shared -fPIC --offload-arch=gfx950 -o "$ROOT/partitionedls.jl_amd/libpartls_hip_parent_t16.so" $(ls _build/*.o | grep -v /sweep_blk.o) "$TMP/sweep_blk_t16.o" -ldl
+ls -la "$ROOT"/partitionedls.jl_amd/*.so

@@ -22,6 +22,10 @@ rejects a column for them — that count must be 0.
                                              Fails if a twin has a violator outside the column, if the relayout moves another variable out
                                              of order, or on any priced-but-rejected twin.  The fuzz problems are small, so the tile width
                                              is 16 where two full columns exist and 8 or 4 below that; the tests' problems run at 16.
+  python tools/pair_emul.py dense [count]    the kernel's DENSE pricing (price_dense: the whole 16 x 16 block of the column as it stands, the
+                                             steps masked, every row 16 terms with a_k = 0 outside C) against price_static, bit for bit, on the
+                                             same fuzz problems, the problems of tests/test_gpu_pair.py and those of
+                                             tests/test_gpu_pair_dense.py (whose expected pivot counts come from here).  Exit status 0 or 1.
 """
 import os
 import sys
@@ -120,9 +124,12 @@ def price(T, n, basic, C):
         A[:, s] = col * ainv
         A[s, s] = -inv
     a = np.where(basic[C], -qc, qc)
-    qt = T[:n, n] - T[:n][:, C] @ a
+    qt, ct = T[:n, n].copy(), T[n, n]
+    for j in range(m):                            # the rows: one term per violator, ascending (the kernel's chain of FMAs)
+        qt = qt + (-T[:n, C[j]]) * a[j]
+        ct = ct + (-T[C[j], n]) * a[j]
     qt[C] = qc
-    return False, qt, T[n, n] - T[C, n] @ a, dmin
+    return False, qt, ct, dmin
 
 
 def relayout(pr, width=16):
@@ -161,13 +168,68 @@ def price_static(T, n, basic, ft, tol, col):
     return C, price(Tp, n, basic, C)
 
 
+def price_dense(T, n, basic, ft, tol, col):
+    """the kernel's DENSE pricing from the fixed column: the whole width x width block of the column is loaded as it stands (rows and
+    columns outside C carry the tableau's entries, never zeros), the steps run over k = 0 .. width - 1 and skip the columns outside C,
+    every step updates every row and column of the block, a_k = 0 outside C and every row adds all `width` terms in ascending k.
+    (C, (guard, q', corner', smallest entering pivot), mask of C) as price_static; C is None when a violator lies outside the column"""
+    base, width = col
+    viol = violators(T, n, basic, ft, tol)
+    if viol[:base].any() or viol[base + width:].any():
+        return None, None, 0
+    panel = T[:, base:base + width].copy()                  # the gather: rows 0 .. n - 1 and the rhs row n
+    cm = sum(1 << k for k in range(width) if viol[base + k])
+    C = np.array([base + k for k in range(width) if (cm >> k) & 1], dtype=int)
+    A = panel[base:base + width, :].copy()
+    qc = panel[n, :].copy()
+    bas = basic[base:base + width]
+    dmin = np.inf
+    for s in range(width):
+        if not (cm >> s) & 1:
+            continue
+        d = A[s, s]
+        if not bas[s]:
+            dmin = min(dmin, d)
+            if not d >= PIV_MIN:
+                return C, (True, None, None, dmin), cm
+        inv = 1.0 / d
+        ainv = abs(inv)
+        colv = A[:, s].copy()
+        qs = qc[s]
+        for r in range(width):
+            fz = -colv[r] * inv
+            if r == s:
+                A[r, :] = colv * ainv
+                qc[r] = qs * ainv
+            else:
+                A[r, :] += fz * colv
+                qc[r] += fz * qs
+        A[:, s] = colv * ainv
+        A[s, s] = -inv
+    a = np.array([(-qc[k] if bas[k] else qc[k]) if (cm >> k) & 1 else 0.0 for k in range(width)])
+    qt, ct = T[:n, n].copy(), T[n, n]
+    for k in range(width):
+        qt = qt + (-panel[:n, k]) * a[k]
+        ct = ct + (-panel[n, k]) * a[k]
+    qt[C] = qc[C - base]
+    return C, (False, qt, ct, dmin), cm
+
+
+def same_price(x, y):
+    """two pricings of one twin, bit for bit: guard, q', corner', smallest entering pivot"""
+    if x[0] != y[0] or x[3] != y[3]:
+        return False
+    return x[0] or (np.array_equal(x[1], y[1]) and x[2] == y[2])
+
+
 def pair_sweep(pr, chain_len, g_begin=0, g_end=None, pairing=True):
     n, T0, mask, kbits, tol = pr["n"], pr["T0"], pr["mask"], pr["kbits"], pr["tol"]
     pcol = pr.get("pair_col")
     g_end = (1 << kbits) if g_end is None else g_end
     out = np.full(1 << kbits, np.nan)
     st = dict(pivots=0, easy=0, empty=0, hard_wide=0, hard_guard=0, hard_left=0, capped=0, rejections=0, csize=[], ctiles=[],
-              dmin=np.inf, formula_err=0.0, priced_but_rejected=0, outside=0)
+              dmin=np.inf, formula_err=0.0, priced_but_rejected=0, outside=0, dense=0, dense_diff=0, gap_easy=0)
+    dense = pr.get("dense", False)
     gray = lambda g: g ^ (g >> 1)
     for g0 in range(g_begin, g_end, chain_len):
         glen = min(chain_len, g_end - g0)
@@ -203,6 +265,11 @@ def pair_sweep(pr, chain_len, g_begin=0, g_end=None, pairing=True):
                         st["outside"] += 1
                     else:
                         assert np.array_equal(Cs, C)
+                        if dense and 0 < len(C) <= PAIR_MAXC:           # the dense form prices the walk; the compacted one is its check
+                            Cd, dns, cmask = price_dense(T, n, basic, ft, tol, pcol)
+                            st["dense"] += 1
+                            st["dense_diff"] += not (np.array_equal(Cd, C) and same_price(static, dns))
+                            static = dns
                 if len(C) == 0:
                     st["empty"] += 1
                     out[gray(g0 + partner(gi))] = np.sqrt(max(T[n, n], 0.0))
@@ -224,6 +291,8 @@ def pair_sweep(pr, chain_len, g_begin=0, g_end=None, pairing=True):
                         else:
                             st["easy"] += 1
                             st["csize"].append(len(C))
+                            if pcol is not None:                        # a column between the lowest and the highest of C is not in C
+                                st["gap_easy"] += int(C[-1] - C[0] + 1 > len(C))
                             st["ctiles"].append(len(set(int(k) // 16 for k in C)))
                             out[gray(g0 + partner(gi))] = np.sqrt(max(ct, 0.0))
                             to_twin = False
@@ -386,5 +455,69 @@ def main():
     return 1 if bad else 0
 
 
+def dense_against_static(tag, pl, chain_len):
+    """one problem (laid out) walked twice, priced by price_static and by price_dense: every twin's two pricings, all objectives,
+    verdicts and pivot counts bit for bit; returns (failures, stats and objectives of the dense walk)"""
+    out_s, st_s = pair_sweep(pl, chain_len)
+    out_d, st_d = pair_sweep(dict(pl, dense=True), chain_len)
+    keys = ("pivots", "easy", "empty", "hard_wide", "hard_guard", "hard_left", "capped", "rejections", "outside")
+    bad = st_d["dense_diff"] + (not np.array_equal(out_s, out_d, equal_nan=True)) + any(st_s[k] != st_d[k] for k in keys)
+    bad += st_d["priced_but_rejected"] + st_d["outside"] + (st_d["formula_err"] > 1e-9)
+    print("%-34s chain %2d: pivots %6d  twins: dense-priced %4d easy %4d (with a gap in C %4d) empty %4d guard %3d left %3d  |C| %s  "
+          "differences from the compacted pricing %d%s" % (
+              tag, chain_len, st_d["pivots"], st_d["dense"], st_d["easy"], st_d["gap_easy"], st_d["empty"], st_d["hard_guard"], st_d["hard_left"],
+              ("%d..%d" % (min(st_d["csize"]), max(st_d["csize"]))) if st_d["csize"] else "-", st_d["dense_diff"], "   FAILED" if bad else ""))
+    return int(bad), st_d, out_d
+
+
+def main_dense():
+    """python tools/pair_emul.py dense [count]: the fuzz problems of `static`, the 24 problems of tests/test_gpu_pair.py and the problems
+    of tests/test_gpu_pair_dense.py, each walked with the compacted and with the dense pricing (dense_against_static).  For the last
+    group also what each is there for, the oracle's objectives, and the pivot counts the GPU test expects (EMUL_PIVOTS there)."""
+    from oracle import oracle as O
+    O.build()
+    from test_gpu_fuzz import _random_problem
+    import test_gpu_pair as tp
+    import test_gpu_pair_dense as td
+    cnt = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+    rng = np.random.default_rng(9000)
+    bad = laid = 0
+    for i in range(cnt):
+        X, y, P, eta = _random_problem(rng)
+        pr = prepare(X, y, P, eta)
+        width = 16 if pr["n"] > 32 else (8 if pr["n"] > 16 else 4)
+        pl = relayout(pr, width)
+        if pl is None:
+            continue
+        laid += 1
+        bad += dense_against_static("fuzz %d %s K=%d w=%d" % (i, X.shape, P.shape[1], width), pl, 16)[0]
+    print("relaid out: %d of %d fuzz problems" % (laid, cnt))
+    for kind, n, flags in tp.CASES:
+        X, y, P = tp.problem(kind, n, flags)
+        pl = relayout(prepare(np.asarray(X), y, np.asarray(P), 0.0, faithful=bool(flags & tp.FAITHFUL)))
+        assert (pl is None) == (kind == "wide"), kind
+        if pl is not None:
+            bad += dense_against_static("%s n=%d flags=%d" % (kind, n, flags), pl, 16)[0]
+    for kind, n in td.CASES:
+        X, y, P = td.make(kind, n)
+        ref = O.fit_opt(X, y, P, return_all=True)["all_opt"]
+        pl = relayout(prepare(np.asarray(X), y, np.asarray(P), 0.0, faithful=True))
+        assert pl is not None and pl["pair_col"][1] == 16
+        for cl in (16, 7):
+            b, st, got = dense_against_static("dense test: %s n=%d seed %d" % (kind, n, td.SEED[kind, n]), pl, cl)
+            err = float(np.max(np.abs(got - ref) / np.maximum(1.0, ref)))
+            plain = pair_sweep(pl, cl, pairing=False)[1]["pivots"]
+            want = {"gaps": st["gap_easy"] >= 1, "full": max(st["csize"], default=0) == 16, "one": st["easy"] >= 1 and max(st["csize"], default=0) == 1,
+                    "nine": st["easy"] >= 1, "collinear": st["hard_guard"] >= 1 and st["easy"] >= 1}[kind]
+            exp = td.EMUL_PIVOTS.get((kind, n, cl))
+            print("    oracle err %.2g, plain walk %d pivots, tests/test_gpu_pair_dense.py expects %s" % (err, plain, exp))
+            if not (want and err <= 1e-9 and st["pivots"] < plain and exp == st["pivots"]):
+                print("    ^ lacks the twins it is there for, misses the oracle, saves no pivots or the test's count is another")
+                b += 1
+            bad += b
+    print("failed checks in total: %d" % bad)
+    return 1 if bad else 0
+
+
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(main_dense() if len(sys.argv) > 1 and sys.argv[1] == "dense" else main())
