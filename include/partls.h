@@ -540,6 +540,9 @@ partls_status partls_get_gram(const partls_ctx *ctx, double *G_aug);
 #include "partls_f32_more.h"
 /* ---- sparse design matrices: the prepare and the predict for an X stored in CSR (never densified). */
 #include "partls_csr.h"
+/* ---- group contributions: the N x K breakdown of the predictions of one or many models, per-row order statistics and mean over the
+ * models, per-group sums over the rows. */
+#include "partls_contrib.h"
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,7 @@ T_GRAM, T_PREP, T_SWEEP, T_FINISH, T_CALIB, T_OOB, T_RESCUE = range(7)
 ROUTE_REG_256, ROUTE_REG_512, ROUTE_DEFERRED, ROUTE_EAGER = range(1, 5)
 # partls_predict_many: models per pass over X, most models / ranks of a call, bytes of a row chunk's N x B intermediate (partls.h)
 PREDICT_MANY_CHUNK, PREDICT_MANY_MAX_B, PREDICT_MANY_BYTES = 16, 4096, 64 << 20
+CONTRIB_CHUNK = 16      # partls_contributions: models per pass over X (PARTLS_CONTRIB_CHUNK, partls_contrib.h)
 OPT_TOP_MAX_K = 4096    # partls_opt_top: most patterns of a call (PARTLS_OPT_TOP_MAX_K, partls.h)
 
 _dp = C.POINTER(C.c_double)
@@ -128,6 +129,14 @@ SYMBOLS_CSR = [
                                      C.c_double, C.c_void_p]),
 ]
 
+# ... and every symbol include/partls_contrib.h declares (group contributions; X is a double or a float pointer, passed as an address)
+_CONTRIB_ARGS = [C.c_void_p, C.c_void_p, _i64, _i64, _i64, C.c_int, C.c_void_p, _i64, _i64, _i64, _dp, _i64, _dp, _i64, C.c_void_p, _i64, _i64, _ip,
+                 C.c_void_p, C.c_void_p, _dp]
+SYMBOLS_CONTRIB = [
+    ("partls_contributions", C.c_int, _CONTRIB_ARGS),
+    ("partls_contributions_f32", C.c_int, _CONTRIB_ARGS),
+]
+
 _lib = None
 
 
@@ -174,7 +183,7 @@ def lib():
                               f"(make -C '{CSRC}'); partitionedls.jl_amd has no CPU fallback")
         _preload_torch_hip_runtime()
         l = C.CDLL(SO_PATH)
-        for name, res, args in SYMBOLS + SYMBOLS_F32 + SYMBOLS_F32_MORE + SYMBOLS_CSR:
+        for name, res, args in SYMBOLS + SYMBOLS_F32 + SYMBOLS_F32_MORE + SYMBOLS_CSR + SYMBOLS_CONTRIB:
             if os.environ.get("PARTLS_LIB") and not hasattr(l, name):
                 continue                   # diagnostic A/B builds of older sources may lack the newest entry points
             f = getattr(l, name)           # AttributeError here = header/library mismatch

@@ -179,20 +179,21 @@ def _f32(dtype, who):
     return dtype == np.float32
 
 
-def _many_models(alpha, beta, t, M, K, ranks):
+def _many_models(alpha, beta, t, M, K, ranks, who="predict_many"):
     """B models as partls_predict_many takes them: alpha[B, M], beta[B, K], t[B] C-contiguous float64 (row b = model b) and the ranks as
-    an int64 vector (None: no order statistics).  ValueError for shapes that do not fit each other, M and K; a rank outside [0, B)."""
+    an int64 vector (None: no order statistics).  ValueError for shapes that do not fit each other, M and K; a rank outside [0, B).
+    partls_contributions takes the same models without t (its callers pass zeros); who: the caller's name in the messages."""
     a = np.ascontiguousarray(alpha, dtype=np.float64)
     b = np.ascontiguousarray(beta, dtype=np.float64)
     tv = np.ascontiguousarray(t, dtype=np.float64)
     if a.ndim != 2 or b.ndim != 2 or tv.ndim != 1 or a.shape[0] < 1 or a.shape != (tv.shape[0], M) or b.shape != (tv.shape[0], K):
-        raise ValueError("predict_many: expected alpha (B, %d), beta (B, %d) and t (B,) with B >= 1, got %s, %s and %s"
-                         % (M, K, a.shape, b.shape, tv.shape))
+        raise ValueError("%s: expected alpha (B, %d), beta (B, %d) and t (B,) with B >= 1, got %s, %s and %s"
+                         % (who, M, K, a.shape, b.shape, tv.shape))
     if ranks is None:
         return a, b, tv, None
     r = np.ascontiguousarray(ranks, dtype=np.int64)
     if r.ndim != 1 or len(r) < 1 or r.min() < 0 or r.max() >= a.shape[0]:
-        raise ValueError("predict_many: ranks must be a non-empty vector of positions in [0, %d)" % a.shape[0])
+        raise ValueError("%s: ranks must be a non-empty vector of positions in [0, %d)" % (who, a.shape[0]))
     return a, b, tv, r
 
 
@@ -731,6 +732,56 @@ class Context:
         fn = lib.partls_predict_many_f32 if f32 else lib.partls_predict_many
         _check(fn(self._h, xp, N, M, ldX, on_device, P.ctypes.data, P.shape[1], M, a.shape[0], _dp(a), _dp(b), _dp(tv), yhat, ldY,
                   0 if ranks is None else len(ranks), None if ranks is None else _ip(ranks), stats, mean))
+
+    def contributions(self, X, P, alpha, beta, *, ranks=None, want_contrib=True, want_mean=False, want_sums=False):
+        """The group contributions c[i, k, b] = beta[b, k] sum over the features m of group k of alpha[b, m] X[i, m] of B models over one
+        partition P, in one upload of a host X (partls_contributions): one fma chain per (row, group, model) over
+        the group's features in ascending m; the intercept is part of no contribution.  alpha[B, M], beta[B, K]: row b = model b.
+        Returns dict(contrib, stats, mean, sums), all F-ordered: contrib[N, K, B] (None unless want_contrib), slab b = the call with
+        model b alone bit for bit; stats[N, K, len(ranks)] (None without ranks), [i, k, q] = the value at 0-based position ranks[q] of
+        the ascending sort of c[i, k, :]; mean[N, K] (None unless want_mean), summed over b in index order; sums[3, K, B] (None unless
+        want_sums): over the rows, the sums of c, |c| and c^2, in an order that depends on N alone.  Without want_contrib no N x K x B
+        array exists on the host.  X as in predict: float32 stays float32; a sparse X is refused (NotImplementedError)."""
+        _no_sparse("Context.contributions", X, "densify X yourself")
+        X, _, P = _inputs(X, None, P)
+        N, M = X.shape
+        K = P.shape[1]
+        a, b, _, r = _many_models(alpha, beta, np.zeros(np.shape(alpha)[:1]), M, K, ranks, "contributions")
+        B = a.shape[0]
+        ct = np.zeros((N, K, B), order="F") if want_contrib else None
+        st = None if r is None else np.zeros((N, K, len(r)), order="F")
+        mu = np.zeros((N, K), order="F") if want_mean else None
+        sm = np.zeros((3, K, B), order="F") if want_sums else None
+        self._contributions(X.ctypes.data, 0, X.dtype == np.float32, N, M, N, P, a, b, None if ct is None else ct.ctypes.data, N, r,
+                            None if st is None else st.ctypes.data, None if mu is None else mu.ctypes.data, sm)
+        return dict(contrib=ct, stats=st, mean=mu, sums=sm)
+
+    def contributions_device(self, dX_ptr, N, M, ldX, P, alpha, beta, *, dcontrib_ptr=None, ldC=0, ranks=None, dstats_ptr=None,
+                             dmean_ptr=None, want_sums=False, dtype=np.float64):
+        """the same with X (N x M, ldX, elements of `dtype`: float64 or float32) and every wanted array output in HBM, as raw device
+        addresses: dcontrib_ptr (N x K x B doubles, element (i, k, b) at i + ldC (k + K b), ldC >= N; rows N .. ldC are not
+        written), dstats_ptr (N x K x len(ranks), leading dimension N; wanted exactly when ranks is given), dmean_ptr (N x K).
+        Returns sums[3, K, B] on the host when want_sums, else None."""
+        f32 = _f32(dtype, "contributions_device")
+        P = np.asfortranarray(P, dtype=np.int64)
+        a, b, _, r = _many_models(alpha, beta, np.zeros(np.shape(alpha)[:1]), int(M), P.shape[1], ranks, "contributions_device")
+        if (r is None) != (dstats_ptr is None):
+            raise ValueError("contributions_device: dstats_ptr goes with ranks")
+        sm = np.zeros((3, P.shape[1], a.shape[0]), order="F") if want_sums else None
+        self._contributions(C.c_void_p(dX_ptr), 1, f32, int(N), int(M), int(ldX), P, a, b,
+                            None if dcontrib_ptr is None else C.c_void_p(dcontrib_ptr), int(ldC), r,
+                            None if dstats_ptr is None else C.c_void_p(dstats_ptr), None if dmean_ptr is None else C.c_void_p(dmean_ptr), sm)
+        return sm
+
+    def _contributions(self, xp, on_device, f32, N, M, ldX, P, a, b, contrib, ldC, ranks, stats, mean, sums):
+        """The one call behind contributions and contributions_device: xp, contrib, stats and mean (or None) are addresses on the host
+        or (on_device) in HBM; a[B, M], b[B, K] C-contiguous float64 (the M x B / K x B column-major layouts of the ABI, leading
+        dimensions M and K); ranks: int64 vector or None; sums: a host float64 array of 3 K B elements or None"""
+        lib = L.lib()
+        fn = lib.partls_contributions_f32 if f32 else lib.partls_contributions
+        K = P.shape[1]
+        _check(fn(self._h, xp, N, M, ldX, on_device, P.ctypes.data, K, M, a.shape[0], _dp(a), M, _dp(b), K, contrib, ldC,
+                  0 if ranks is None else len(ranks), None if ranks is None else _ip(ranks), stats, mean, None if sums is None else _dp(sums)))
 
     def _count(self, getter):
         n = C.c_int64()
@@ -1552,28 +1603,57 @@ class BootstrapResult:
         happens here, by np.percentile's own formula.  return_all=True adds yhat[N, B_ok], column j = predict with the j-th successful
         replicate; without it no N x B array exists on the host.  X as in predict.  ValueError: level outside (0, 1), no
         successful replicate, a result without its partition (P)."""
-        level = float(level)
-        if not 0.0 < level < 1.0:
-            raise ValueError("predict: level must lie in (0, 1), got %r" % level)
-        ok = self.ok
-        if not ok.any():
-            raise ValueError("predict: no successful replicate")
-        if self.P is None:
-            raise ValueError("predict: this result does not carry its partition P")
-        _no_sparse("BootstrapResult.predict", X, "densify X yourself, or call predict per model")
-        X = np.asarray(X)
-        if not np.issubdtype(X.dtype, np.floating) or X.ndim != 2:
-            raise TypeError("predict: X must be a floating-point matrix")
-        a, b, t = np.asarray(self.alpha)[ok], np.asarray(self.beta)[ok], np.asarray(self.t)[ok]
-        if X.shape[1] != a.shape[1]:
-            raise ValueError("DimensionMismatch in predict")
-        ranks, parts = _percentile_ranks(len(t), [50.0 - 50.0 * level, 50.0 + 50.0 * level])
-        r = default_context(device).predict_many(X, self.P, a, b, t, ranks=ranks, want_yhat=return_all, want_mean=True)
-        lo, hi = (_lerp(r["stats"][:, i], r["stats"][:, j], g) for i, j, g in parts)
+        X, a, b, t = self._band_inputs("predict", X, level)
+        r, lo, hi = _percentile_band(level, len(t), lambda ranks: default_context(device).predict_many(
+            X, self.P, a, b, t, ranks=ranks, want_yhat=return_all, want_mean=True))
         out = dict(mean=r["mean"], lo=lo, hi=hi)
         if return_all:
             out["yhat"] = r["yhat"]
         return out
+
+    def contributions(self, X, level=0.95, return_all=False, *, device=0):
+        """Percentile band of the successful replicates' group contributions for the rows of X, in one pass over X
+        (partls_contributions): dict(mean, lo, hi), each [N, K] — per (row, group) the mean over the replicates and
+        the percentiles 50 - 50 level and 50 + 50 level of its B_ok contributions, np.percentile(all, q, axis=2) to the last bit (the
+        device returns the order statistics either side of each percentile and the mean, the interpolation happens here, as in
+        predict).  return_all=True adds all[N, K, B_ok], slab j = contributions of the j-th successful replicate; without it no
+        N x K x B array exists on the host.  X and the errors as in predict; a sparse X raises NotImplementedError."""
+        X, a, b, t = self._band_inputs("contributions", X, level)
+        r, lo, hi = _percentile_band(level, len(t), lambda ranks: default_context(device).contributions(
+            X, self.P, a, b, ranks=ranks, want_contrib=return_all, want_mean=True))
+        out = dict(mean=r["mean"], lo=lo, hi=hi)
+        if return_all:
+            out["all"] = r["contrib"]
+        return out
+
+    def _band_inputs(self, who, X, level):
+        """the checks predict and contributions share, before any device work -> X as an array and the successful replicates' alpha, beta, t"""
+        level = float(level)
+        if not 0.0 < level < 1.0:
+            raise ValueError("%s: level must lie in (0, 1), got %r" % (who, level))
+        ok = self.ok
+        if not ok.any():
+            raise ValueError("%s: no successful replicate" % who)
+        if self.P is None:
+            raise ValueError("%s: this result does not carry its partition P" % who)
+        _no_sparse("BootstrapResult.%s" % who, X, "densify X yourself, or call %s per model" % who)
+        X = np.asarray(X)
+        if not np.issubdtype(X.dtype, np.floating) or X.ndim != 2:
+            raise TypeError("%s: X must be a floating-point matrix" % who)
+        a, b, t = np.asarray(self.alpha)[ok], np.asarray(self.beta)[ok], np.asarray(self.t)[ok]
+        if X.shape[1] != a.shape[1]:
+            raise ValueError("DimensionMismatch in %s" % who)
+        return X, a, b, t
+
+
+def _percentile_band(level, n, call):
+    """The band of BootstrapResult.predict and .contributions over n values per cell: the ranks either side of the percentiles
+    50 - 50 level and 50 + 50 level (_percentile_ranks: at most four), call(ranks) -> a result dict whose "stats" holds those order
+    statistics along its last axis, and numpy's interpolation between the neighbours (_lerp) -> (the result dict, lo, hi)"""
+    ranks, parts = _percentile_ranks(n, [50.0 - 50.0 * float(level), 50.0 + 50.0 * float(level)])
+    r = call(ranks)
+    lo, hi = (_lerp(r["stats"][..., i], r["stats"][..., j], g) for i, j, g in parts)
+    return r, lo, hi
 
 
 def _percentile_ranks(n, q):
@@ -1703,6 +1783,24 @@ def predict(*args, device=0):
     return default_context(device).predict(Xf, Pf, a, b, t)
 
 
+def _model_arrays(who, models):
+    """models as predict_many, contributions_many and group_importance accept them -> (alpha[B, M], beta[B, K], t[B], P): a sequence of
+    PartLSFitResult over one common partition, or a tuple (alpha, beta, t, P) of arrays, passed on as it is"""
+    if isinstance(models, tuple) and len(models) == 4 and not isinstance(models[0], PartLSFitResult):
+        a, b, t, P = models
+    else:
+        ms = list(models)
+        if not ms or not all(isinstance(m, PartLSFitResult) for m in ms):
+            raise ValueError("%s: models must be a non-empty sequence of PartLSFitResult or a tuple (alpha, beta, t, P)" % who)
+        P = np.asarray(ms[0].P)
+        if not all(m.P is ms[0].P or np.array_equal(np.asarray(m.P), P) for m in ms[1:]):
+            raise ValueError("%s: the models must share one partition P" % who)
+        if len({np.shape(m.α) for m in ms}) != 1 or len({np.shape(m.β) for m in ms}) != 1:
+            raise ValueError("%s: the models differ in shape" % who)
+        a, b, t = np.stack([m.α for m in ms]), np.stack([m.β for m in ms]), np.array([m.t for m in ms], dtype=np.float64)
+    return a, b, t, P
+
+
 def predict_many(models, X, *, device=0):
     """The predictions of many models for the rows of X in one upload of X (partls_predict_many)  ->  [N, B] float64,
     column b = predict(models[b], X) bit for bit.  models: a sequence of PartLSFitResult over one common partition (bootstrap's
@@ -1710,18 +1808,7 @@ def predict_many(models, X, *, device=0):
     (BootstrapResult's alpha, beta, t, P; solutions.arrays()).  X as in predict: float32 goes up as float32.  More than
     lowlevel.PREDICT_MANY_MAX_B models are predicted in slices of that many columns (one upload of X per slice).
     ValueError: an empty sequence, models over different partitions, shapes that do not fit; TypeError: X not a floating matrix."""
-    if isinstance(models, tuple) and len(models) == 4 and not isinstance(models[0], PartLSFitResult):
-        a, b, t, P = models
-    else:
-        ms = list(models)
-        if not ms or not all(isinstance(m, PartLSFitResult) for m in ms):
-            raise ValueError("predict_many: models must be a non-empty sequence of PartLSFitResult or a tuple (alpha, beta, t, P)")
-        P = np.asarray(ms[0].P)
-        if not all(m.P is ms[0].P or np.array_equal(np.asarray(m.P), P) for m in ms[1:]):
-            raise ValueError("predict_many: the models must share one partition P")
-        if len({np.shape(m.α) for m in ms}) != 1 or len({np.shape(m.β) for m in ms}) != 1:
-            raise ValueError("predict_many: the models differ in shape")
-        a, b, t = np.stack([m.α for m in ms]), np.stack([m.β for m in ms]), np.array([m.t for m in ms], dtype=np.float64)
+    a, b, t, P = _model_arrays("predict_many", models)
     _no_sparse("predict_many", X, "densify X yourself, or call predict per model")
     X = np.asarray(X)
     if not np.issubdtype(X.dtype, np.floating) or X.ndim != 2:
@@ -1733,6 +1820,70 @@ def predict_many(models, X, *, device=0):
     ctx, cap = default_context(device), L.PREDICT_MANY_MAX_B
     parts = [ctx.predict_many(Xf, Pf, a[s:s + cap], b[s:s + cap], t[s:s + cap])["yhat"] for s in range(0, len(t), cap)]
     return parts[0] if len(parts) == 1 else np.concatenate(parts, axis=1)
+
+
+def _contrib_inputs(who, models, X):
+    """what contributions_many and group_importance share, before any device work: the models (t is ignored), X and P as the library
+    takes them"""
+    a, b, t, P = _model_arrays(who, models)
+    _no_sparse(who, X, "densify X yourself (contributions from CSR are not implemented)")
+    X = np.asarray(X)
+    if not np.issubdtype(X.dtype, np.floating) or X.ndim != 2:
+        raise TypeError("%s: X must be a floating-point matrix" % who)
+    Xf, _, Pf = _inputs(X, None, P)
+    if Pf.ndim != 2 or Pf.shape[0] != Xf.shape[1]:
+        raise ValueError("DimensionMismatch in %s" % who)
+    a, b, _, _ = _many_models(a, b, np.zeros(np.shape(a)[:1]) if t is None else t, Xf.shape[1], Pf.shape[1], None, who)
+    return a, b, Xf, Pf
+
+
+def contributions_many(models, X, *, device=0):
+    """The group contributions of many models for the rows of X in one upload of X (partls_contributions)  ->
+    [N, K, B] float64: [i, k, b] = β_k Σ_{m in group k} α_m X[i, m] of model b, one fma chain over the group's features in ascending m.
+    For a partition, contributions.sum(1) + t is predict up to summation order.  models as in predict_many (t is ignored); slab b equals
+    contributions(models[b], X) bit for bit.  More than lowlevel.PREDICT_MANY_MAX_B models go in slices of that many (one upload of X
+    per slice).  ValueError / TypeError as predict_many; NotImplementedError for a sparse X (the library never densifies)."""
+    a, b, Xf, Pf = _contrib_inputs("contributions_many", models, X)
+    ctx, cap = default_context(device), L.PREDICT_MANY_MAX_B
+    parts = [ctx.contributions(Xf, Pf, a[s:s + cap], b[s:s + cap])["contrib"] for s in range(0, len(a), cap)]
+    return parts[0] if len(parts) == 1 else np.concatenate(parts, axis=2)
+
+
+def contributions(model, X, *, device=0):
+    """How much each group contributes to each prediction  ->  [N, K] float64: [i, k] = β_k Σ_{m in group k} α_m X[i, m]; for a partition
+    the row sums plus t are predict(model, X) up to summation order.  See contributions_many."""
+    if not isinstance(model, PartLSFitResult):
+        raise TypeError("contributions: model must be a PartLSFitResult (many models: contributions_many)")
+    return np.ascontiguousarray(contributions_many([model], X, device=device)[:, :, 0])
+
+
+def group_importance(model_or_models, X, *, device=0):
+    """Per-group summaries of the contributions over the rows of X  ->  Report(mean, mean_abs, rms, share), each [K] for one
+    PartLSFitResult and [B, K] for many models (as predict_many accepts them, or a BootstrapResult: its successful replicates):
+    the mean of c, of |c|, the root mean square of c, and share[k] = mean_abs[k] / Σ_k mean_abs (NaN where that sum is 0).  All four
+    are derived here from the 3 K B sums the device returns (partls_contributions' sums): no N x K array crosses PCIe."""
+    who = "group_importance"
+    one = isinstance(model_or_models, PartLSFitResult)
+    if isinstance(model_or_models, BootstrapResult):
+        res = model_or_models
+        if not res.ok.any():
+            raise ValueError("%s: no successful replicate" % who)
+        if res.P is None:
+            raise ValueError("%s: this result does not carry its partition P" % who)
+        ok = res.ok
+        models = (np.asarray(res.alpha)[ok], np.asarray(res.beta)[ok], np.asarray(res.t)[ok], res.P)
+    else:
+        models = [model_or_models] if one else model_or_models
+    a, b, Xf, Pf = _contrib_inputs(who, models, X)
+    ctx, cap, N = default_context(device), L.PREDICT_MANY_MAX_B, Xf.shape[0]
+    parts = [ctx.contributions(Xf, Pf, a[s:s + cap], b[s:s + cap], want_contrib=False, want_sums=True)["sums"] for s in range(0, len(a), cap)]
+    sums = parts[0] if len(parts) == 1 else np.concatenate(parts, axis=2)
+    mean, mean_abs, rms = sums[0].T / N, sums[1].T / N, np.sqrt(sums[2].T / N)           # [B, K]
+    total = mean_abs.sum(axis=1, keepdims=True)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        share = np.where(total > 0, mean_abs / total, np.nan)
+    pick = (lambda v: np.ascontiguousarray(v[0])) if one else np.ascontiguousarray
+    return Report(mean=pick(mean), mean_abs=pick(mean_abs), rms=pick(rms), share=pick(share))
 
 
 def predict_device(model, dX_ptr, N, ldX, dyhat_ptr, device=0, dtype=np.float64):

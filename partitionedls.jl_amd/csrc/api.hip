@@ -74,7 +74,7 @@ using namespace partls;
 
 extern "C" {
 
-int partls_version(void) { return 107; }
+int partls_version(void) { return 108; }
 const char *partls_last_error(void) { return g_err; }
 
 int partls_device_count(void)
@@ -113,6 +113,7 @@ try {
     if (const char *e = getenv("PARTLS_ALT_MS_CHUNK")) c->knobs.alt_ms_chunk = atoll(e);
     if (const char *e = getenv("PARTLS_TOP_PIECE")) c->knobs.top_piece = atoll(e);
     if (const char *e = getenv("PARTLS_BATCH_PIECE")) c->knobs.batch_piece = atoi(e);
+    if (const char *e = getenv("PARTLS_CONTRIB_BYTES")) c->knobs.contrib_bytes = atoll(e);
     if (const char *e = getenv("PARTLS_KKT_TOL")) c->knobs.kkt_tol = atof(e);
     if (const char *e = getenv("PARTLS_NEAR_TIE_REL")) c->knobs.near_tie_rel = atof(e);
     if (const char *e = getenv("PARTLS_CAL_WB")) c->knobs.cal_wb = atof(e);

@@ -27,6 +27,18 @@ void set_error(const char *fmt, ...);
     catch (const std::bad_alloc &) { ::partls::set_error("out of host memory"); return PARTLS_ERR_BAD_ARG; }                      \
     catch (...) { ::partls::set_error("internal error: an exception reached the C ABI"); return PARTLS_ERR_BAD_ARG; }
 
+// The block sum of the 256-thread kernels (misc.hip, contrib.hip): a fixed-order tree over red[256] (LDS).  Every thread calls it; all get the sum.
+__device__ __forceinline__ double block_sum_256(double *red, double v)
+{
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+    }
+    return red[0];
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // sweep parameters (shared by the register-resident and the global-memory tableau kernels)
 // ---------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 // ctx.h — the context behind the opaque partls_ctx handle, the owning buffer types it is made of, and the host helpers the host
 // translation units share: api.hip (create / destroy / predict / getters), prepare.hip, sweep_setup.hip, opt.hip, refine.hip,
-// solvers.hip, multi.hip and the host halves of cv.hip, alt_multi.hip and predict_many.hip.
+// solvers.hip, multi.hip and the host halves of cv.hip, alt_multi.hip, predict_many.hip and contrib.hip.
 #pragma once
 #include "common.h"
 #include <chrono>
@@ -144,6 +144,8 @@ struct partls_knobs {
     long long top_piece = 0;     // PARTLS_TOP_PIECE: patterns per piece of partls_opt_top (0: what PARTLS_OPT_MODELS_PIECE_BYTES admits); tests
     int bit_order = 0;           // PARTLS_BIT_ORDER: 0 automatic (calibrate when the sweep is long enough to repay it), "identity" = 1
                                  // (group k on Gray bit k), "calibrate" = 2 (always measure; small problems in the tests)
+    long long contrib_bytes = 0; // PARTLS_CONTRIB_BYTES: byte budget of a row chunk's intermediate in partls_contributions (0: PARTLS_PREDICT_MANY_BYTES);
+                                 // tests, which reach a chunk boundary with N ~ 2000 through it
     int batch_piece = 0;         // PARTLS_BATCH_PIECE: problems per piece of the batched routes of partls_cv_opt, partls_opt_weightings and partls_cv_alt
                                  // (0: batch_pieces_begin's byte rule; at most 65535); tests
 };
@@ -285,6 +287,11 @@ struct partls_ctx {
     // intercepts; pmRanks, the ranks wanted; pmY, the N x B intermediate of a row chunk (at most PARTLS_PREDICT_MANY_BYTES); pmStats /
     // pmMean, the device images of a host caller's stats (one row chunk) and mean
     partls::DevBuf pmW, pmRanks, pmY, pmStats, pmMean;
+    // partls_contributions (contrib.hip) shares pmRanks and adds: ctW, the models of a call as chunk-blocked weights of
+    // the group lists, followed by the lists themselves (gptr[K + 1], feature indices; int32); ctC, the rows x K x B intermediate of a
+    // row chunk; ctStats / ctMean, the device images of a host caller's stats and mean for one row chunk; ctSums, the 3 K B running
+    // sums carried across the row chunks, followed by the per-block partial sums of one chunk
+    partls::DevBuf ctW, ctC, ctStats, ctMean, ctSums;
 };
 
 namespace partls {
@@ -551,5 +558,11 @@ partls_status check_common(partls_ctx *c, const void *X, int64_t N, int64_t M, i
 // behind partls_predict* and partls_predict_many*, whose columns equal the single predictions bit for bit.  Checks P on the way:
 // PARTLS_ERR_BAD_PARTITION for an entry outside {0,1}.
 partls_status predict_weights(const int64_t *P, int64_t M, int64_t K, int64_t ldP, const double *alpha, const double *beta, double *w);
+// The per-row statistics of predict_many.hip for any column-major rows x B matrix Y on the device (partls_contributions hands them its
+// (row, group) pairs as rows), queued on `stream`.  launch_row_select: S[i + q ldS] = the value at position ranks[q] (device array, nr
+// of them) of the ascending sort of Y[i, 0 .. B); B <= PARTLS_PREDICT_MANY_MAX_B.  launch_row_mean: mean[i] = the index-ordered sum / B.
+hipError_t launch_row_select(const double *Y, int64_t rows, int64_t ldY, int64_t B, const int64_t *ranks, int64_t nr, double *S, int64_t ldS,
+                             hipStream_t stream);
+hipError_t launch_row_mean(const double *Y, int64_t rows, int64_t ldY, int64_t B, double *mean, hipStream_t stream);
 
 }  // namespace partls

@@ -4,17 +4,7 @@
 
 namespace partls {
 
-// The block sum of the 256-thread kernels below: a fixed-order tree over red[256] (LDS).  Every thread calls it; all get the sum.
-__device__ __forceinline__ double block_sum_256(double *red, double v)
-{
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-        __syncthreads();
-    }
-    return red[0];
-}
+// (block_sum_256, the fixed-order block sum of the 256-thread kernels below: common.h)
 
 // Prediction of row i of column-major X (widened as it is loaded) under the weights sw[0..M) and intercept t: four chains over m mod 4,
 // ((a0 + a1) + (a2 + a3)) + t — the one order in which a row is predicted, so that a model's residual and its out-of-bag error agree

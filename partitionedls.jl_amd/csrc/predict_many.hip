@@ -101,6 +101,23 @@ __global__ __launch_bounds__(256) void row_mean_kernel(const double *__restrict_
     mean[i] = s / (double)B;
 }
 
+hipError_t launch_row_select(const double *Y, int64_t rows, int64_t ldY, int64_t B, const int64_t *ranks, int64_t nr, double *S, int64_t ldS,
+                             hipStream_t stream)
+{
+    int n = 1;
+    while (n < B) n <<= 1;
+    const int R = rows_per_group(n);
+    hipLaunchKernelGGL(row_select_kernel, dim3((unsigned)((rows + R - 1) / R)), dim3(256), (size_t)R * n * sizeof(double), stream, Y, rows, ldY, (int)B, n,
+                       ranks, (int)nr, S, ldS);
+    return hipGetLastError();
+}
+
+hipError_t launch_row_mean(const double *Y, int64_t rows, int64_t ldY, int64_t B, double *mean, hipStream_t stream)
+{
+    hipLaunchKernelGGL(row_mean_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, Y, rows, ldY, B, mean);
+    return hipGetLastError();
+}
+
 // rows of a chunk: the N x B intermediate (and a host caller's device image of stats) within PARTLS_PREDICT_MANY_BYTES
 static int64_t rows_per_chunk(int64_t N, int64_t B, int64_t nr)
 {
@@ -170,8 +187,6 @@ static partls_status predict_many_common(partls_ctx *c, const void *X, int64_t N
     if (!direct) PARTLS_HIP_CHECK(c->pmY.ensure((size_t)rmax * B * sizeof(double)));
     if (!x_on_device && nr > 0) PARTLS_HIP_CHECK(c->pmStats.ensure((size_t)rmax * nr * sizeof(double)));
     if (!x_on_device && mean) PARTLS_HIP_CHECK(c->pmMean.ensure((size_t)N * sizeof(double)));
-    int n = 1;
-    while (n < B) n <<= 1;
     for (int64_t r0 = 0; r0 < N; r0 += rmax) {
         const int64_t rows = N - r0 < rmax ? N - r0 : rmax;
         double *Y = direct ? yhat + r0 : c->pmY.as<double>();
@@ -186,18 +201,14 @@ static partls_status predict_many_common(partls_ctx *c, const void *X, int64_t N
         if (nr > 0) {
             double *S = x_on_device ? stats + r0 : c->pmStats.as<double>();
             const int64_t lds = x_on_device ? N : rows;
-            const int R = rows_per_group(n);
-            hipLaunchKernelGGL(row_select_kernel, dim3((unsigned)((rows + R - 1) / R)), dim3(256), (size_t)R * n * sizeof(double), c->stream, Y, rows, ldy, (int)B, n,
-                               c->pmRanks.as<int64_t>(), (int)nr, S, lds);
-            PARTLS_HIP_CHECK(hipGetLastError());
+            PARTLS_HIP_CHECK(launch_row_select(Y, rows, ldy, B, c->pmRanks.as<int64_t>(), nr, S, lds, c->stream));
             if (!x_on_device)
                 PARTLS_HIP_CHECK(hipMemcpy2DAsync(stats + r0, (size_t)N * sizeof(double), S, (size_t)rows * sizeof(double), (size_t)rows * sizeof(double),
                                                   (size_t)nr, hipMemcpyDeviceToHost, c->stream));
         }
         if (mean) {
             double *mu = (x_on_device ? mean : c->pmMean.as<double>()) + r0;
-            hipLaunchKernelGGL(row_mean_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, Y, rows, ldy, B, mu);
-            PARTLS_HIP_CHECK(hipGetLastError());
+            PARTLS_HIP_CHECK(launch_row_mean(Y, rows, ldy, B, mu, c->stream));
         }
     }
     if (!x_on_device && mean)

@@ -38,6 +38,7 @@ _OUT5 = "out out out out out"
 _CV = "fold_ptr:q:F+1 F etas:d:E E flags out ld_alpha out ld_beta out out out out out"
 _PREDICT = "h X:%s N M ldX " + _P + " alpha:d:M beta:d:K t %s"
 _PREDICT_MANY = "h X:x:ldX*M N M ldX dev " + _P + " B alpha:d:M*B beta:d:K*B t:d:B yhat:@ ldY nr ranks:q:nr stats:@ mean:@"
+_CONTRIB = "h X:x:ldX*M N M ldX dev " + _P + " B alpha:d:lda*B lda beta:d:ldb*B ldb contrib:@ ldC nr ranks:q:nr stats:@ mean:@ out"
 SPEC = {
     "partls_version": "", "partls_last_error": "", "partls_device_count": "",
     "partls_create": "device out", "partls_destroy": "h",
@@ -82,6 +83,7 @@ SPEC = {
     "partls_predict": _PREDICT % ("x:ldX*M", "out"), "partls_predict_f32": _PREDICT % ("x:ldX*M", "out"),
     "partls_predict_device": _PREDICT % ("@", "yhat:@"), "partls_predict_device_f32": _PREDICT % ("@", "yhat:@"),
     "partls_predict_many": _PREDICT_MANY, "partls_predict_many_f32": _PREDICT_MANY,
+    "partls_contributions": _CONTRIB, "partls_contributions_f32": _CONTRIB,
     "partls_synth_truth": "seed D K out out",
     "partls_synth_device": "h seed N D wstar:d:D X:@ y:@",
     "partls_get_timing": "h which out", "partls_get_upload": "h out out", "partls_get_gram": "h out", "partls_get_pivots": "h out",
@@ -122,7 +124,7 @@ class FakeLib:
         self.names = {}                # handle -> c1 / m1 / m1.r0 / f1
         self.state = {}                # handle -> the scalars later calls on it are sized by (M, K, npat; total of a frontier round)
         self.ranks = {}                # multi handle -> its rank handles
-        symbols = lowlevel.SYMBOLS + lowlevel.SYMBOLS_F32 + lowlevel.SYMBOLS_F32_MORE
+        symbols = lowlevel.SYMBOLS + lowlevel.SYMBOLS_F32 + lowlevel.SYMBOLS_F32_MORE + lowlevel.SYMBOLS_CONTRIB
         assert {s[0] for s in symbols} == set(SPEC), "SPEC and the symbol tables disagree"
         for name, res, argtypes in symbols:
             assert len(SPEC[name].split()) == len(argtypes), name
