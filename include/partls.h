@@ -543,6 +543,9 @@ partls_status partls_get_gram(const partls_ctx *ctx, double *G_aug);
 /* ---- group contributions: the N x K breakdown of the predictions of one or many models, per-row order statistics and mean over the
  * models, per-group sums over the rows. */
 #include "partls_contrib.h"
+/* ---- regression diagnostics of one model on the prepared problem: leverage, leave-one-out residuals, studentized residuals, Cook's
+ * distances, degrees of freedom, standard errors. */
+#include "partls_diag.h"
 
 #ifdef __cplusplus
 }

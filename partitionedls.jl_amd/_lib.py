@@ -137,6 +137,15 @@ SYMBOLS_CONTRIB = [
     ("partls_contributions_f32", C.c_int, _CONTRIB_ARGS),
 ]
 
+# ... and every symbol include/partls_diag.h declares (regression diagnostics on the prepared problem; the per-row outputs are host
+# arrays or device addresses, passed as addresses)
+DIAG_NPLUS, DIAG_P, DIAG_DOF, DIAG_RSS, DIAG_PRESS, DIAG_SIGMA2, DIAG_TSS, DIAG_R2, DIAG_R2_LOO, DIAG_STATIONARITY, DIAG_NSUM = range(11)
+SYMBOLS_DIAG = [
+    ("partls_diagnostics", C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _dp, _dp,
+                                     C.POINTER(C.c_int32), _dp]),
+    ("partls_get_diagnostics_timing", C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+]
+
 _lib = None
 
 
@@ -183,7 +192,7 @@ def lib():
                               f"(make -C '{CSRC}'); partitionedls.jl_amd has no CPU fallback")
         _preload_torch_hip_runtime()
         l = C.CDLL(SO_PATH)
-        for name, res, args in SYMBOLS + SYMBOLS_F32 + SYMBOLS_F32_MORE + SYMBOLS_CSR + SYMBOLS_CONTRIB:
+        for name, res, args in SYMBOLS + SYMBOLS_F32 + SYMBOLS_F32_MORE + SYMBOLS_CSR + SYMBOLS_CONTRIB + SYMBOLS_DIAG:
             if os.environ.get("PARTLS_LIB") and not hasattr(l, name):
                 continue                   # diagnostic A/B builds of older sources may lack the newest entry points
             f = getattr(l, name)           # AttributeError here = header/library mismatch

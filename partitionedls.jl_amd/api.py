@@ -6,6 +6,7 @@ fit(Opt|Alt|BnB, X, y, P; η, ...) / predict keep the reference's names, argumen
 """
 import atexit
 import ctypes as C
+import os
 import warnings
 import weakref
 from contextlib import contextmanager
@@ -313,6 +314,7 @@ class Context:
         head = (self._h, xp, N, M, ldX, yp)
         tail = (on_device, P.ctypes.data, P.shape[1], P.shape[0], float(eta), int(flags))
         self._shape = (N, M, P.shape[1])
+        self._on_device = bool(on_device)                    # where the per-row outputs of diagnostics live
         self.generation += 1
         if f32:
             _check(lib.partls_opt_prepare_f32(*head, wp, *tail))
@@ -341,6 +343,7 @@ class Context:
 
     def _prepare_csr(self, pp, ip, vp, yp, wp, on_device, N, M, P, eta, flags):
         self._shape = (N, M, P.shape[1])
+        self._on_device = bool(on_device)
         self.generation += 1
         _check(L.lib().partls_opt_prepare_csr(self._h, pp, ip, vp, N, M, yp, wp, on_device, P.ctypes.data, P.shape[1], P.shape[0],
                                               float(eta), int(flags)))
@@ -782,6 +785,64 @@ class Context:
         K = P.shape[1]
         _check(fn(self._h, xp, N, M, ldX, on_device, P.ctypes.data, K, M, a.shape[0], _dp(a), M, _dp(b), K, contrib, ldC,
                   0 if ranks is None else len(ranks), None if ranks is None else _ip(ranks), stats, mean, None if sums is None else _dp(sums)))
+
+    _DIAG_ROWS = ("leverage", "loo", "studentized", "cooks", "residual")
+
+    def diagnostics(self, alpha, beta, t, *, rows=_DIAG_ROWS, want_se=True):
+        """Regression diagnostics of the model (alpha[M], beta[K], t) on the problem this context is prepared for, from HOST arrays
+        (opt_prepare): partls_diagnostics, DESIGN.md §4.17.  Returns a dict: the per-row arrays named in `rows` (of leverage, loo,
+        studentized, cooks, residual; N doubles each), se_w[M + 1] and se_beta[K] (unless want_se is False), active[M + 1] (bool) and
+        summary[lowlevel.DIAG_NSUM] (indices lowlevel.DIAG_*).  The prepared problem is untouched."""
+        if getattr(self, "_on_device", False):
+            raise ValueError("Context.diagnostics: the problem was prepared from device pointers; its per-row outputs are device "
+                             "arrays (diagnostics_device)")
+        bad = [r for r in rows if r not in self._DIAG_ROWS]
+        if bad:
+            raise ValueError("Context.diagnostics: unknown per-row output %r (known: %s)" % (bad[0], ", ".join(self._DIAG_ROWS)))
+        N = self._diag_shape("Context.diagnostics")[0]
+        out = {r: np.zeros(N) for r in rows}
+        out.update(self._diagnostics(alpha, beta, t, {r: a.ctypes.data for r, a in out.items()}, want_se))
+        return out
+
+    def diagnostics_device(self, alpha, beta, t, *, dleverage_ptr=None, dloo_ptr=None, dstudentized_ptr=None, dcooks_ptr=None,
+                           dresidual_ptr=None, want_se=True):
+        """the same on a problem prepared from DEVICE pointers (opt_prepare_device): the per-row outputs that are wanted are raw device
+        addresses of N doubles each; returns dict(se_w, se_beta, active, summary) on the host"""
+        if not getattr(self, "_on_device", True):
+            raise ValueError("Context.diagnostics_device: the problem was prepared from host arrays; its per-row outputs are host "
+                             "arrays (diagnostics)")
+        self._diag_shape("Context.diagnostics_device")
+        ptrs = dict(zip(self._DIAG_ROWS, (dleverage_ptr, dloo_ptr, dstudentized_ptr, dcooks_ptr, dresidual_ptr)))
+        return self._diagnostics(alpha, beta, t, {r: int(a) for r, a in ptrs.items() if a is not None}, want_se)
+
+    def _diag_shape(self, who):
+        shape = getattr(self, "_shape", None)
+        if shape is None:
+            raise ValueError("%s: no prepared problem on this context" % who)
+        return shape
+
+    def _diagnostics(self, alpha, beta, t, rows, want_se):
+        """The one call behind diagnostics and diagnostics_device: rows maps the names of the wanted per-row outputs to addresses, on the
+        host or in HBM as the prepare was"""
+        _, M, K = self._shape
+        a = np.ascontiguousarray(alpha, dtype=np.float64)
+        b = np.ascontiguousarray(beta, dtype=np.float64)
+        if a.shape != (M,) or b.shape != (K,):
+            raise ValueError("diagnostics: expected alpha (%d,) and beta (%d,), got %s and %s" % (M, K, a.shape, b.shape))
+        if not (np.all(np.isfinite(a)) and np.all(np.isfinite(b)) and np.isfinite(t)):
+            raise ValueError("diagnostics: the model has a NaN / Inf in alpha, beta or t")
+        se_w, se_b = (np.zeros(M + 1), np.zeros(K)) if want_se else (None, None)
+        active, summary = np.zeros(M + 1, dtype=np.int32), np.zeros(L.DIAG_NSUM)
+        _check(L.lib().partls_diagnostics(self._h, _dp(a), _dp(b), float(t), *(rows.get(r) for r in self._DIAG_ROWS),
+                                          None if se_w is None else _dp(se_w), None if se_b is None else _dp(se_b), _i32p(active),
+                                          _dp(summary)))
+        return dict(se_w=se_w, se_beta=se_b, active=active.astype(bool), summary=summary)
+
+    def diagnostics_timing(self):
+        """(leverage kernel, host factorisation, whole call) of the last diagnostics call on this context, in ms"""
+        ms = [C.c_double() for _ in range(3)]
+        _check(L.lib().partls_get_diagnostics_timing(self._h, *(C.byref(m) for m in ms)))
+        return tuple(m.value for m in ms)
 
     def _count(self, getter):
         n = C.c_int64()
@@ -1884,6 +1945,92 @@ def group_importance(model_or_models, X, *, device=0):
         share = np.where(total > 0, mean_abs / total, np.nan)
     pick = (lambda v: np.ascontiguousarray(v[0])) if one else np.ascontiguousarray
     return Report(mean=pick(mean), mean_abs=pick(mean_abs), rms=pick(rms), share=pick(share))
+
+
+@dataclass
+class Diagnostics:
+    """Row-by-row diagnostics of one model on (X, y, weights, η) — see diagnostics().  Per row [N]: leverage, loo, studentized, cooks,
+    residual.  Per weight / group: se_w[M + 1] (0 outside the support; the intercept's last), se_beta[K], se_t, active[M + 1].
+    Scalars: n_pos (rows of positive weight), p (size of the support), dof, rss, press, sigma2, tss, r2, r2_loo, stationarity and
+    loo_mse = press / Σw."""
+    leverage: np.ndarray
+    loo: np.ndarray
+    studentized: np.ndarray
+    cooks: np.ndarray
+    residual: np.ndarray
+    se_w: np.ndarray
+    se_beta: np.ndarray
+    se_t: float
+    active: np.ndarray
+    n_pos: int
+    p: int
+    dof: float
+    rss: float
+    press: float
+    sigma2: float
+    tss: float
+    r2: float
+    r2_loo: float
+    stationarity: float
+    loo_mse: float
+
+
+def _kkt_tol():
+    """the data-space KKT tolerance a context is created with (PARTLS_KKT_TOL, read at partls_create; 1e-12)"""
+    try:
+        return float(os.environ.get("PARTLS_KKT_TOL", "1e-12"))
+    except ValueError:
+        return 1e-12
+
+
+def diagnostics(model, X, y, *, η=None, eta=None, weights=None, device=0):
+    """Judge one fit row by row  ->  Diagnostics.  model: a PartLSFitResult fitted to (X, y) with the same η and weights.
+
+    Conditional on the model's sign pattern and support A (the weights v_m = α_m Σ_k P[m,k] β_k that are not 0, and the intercept) the
+    fit is a linear smoother with H = Xo_A' W Xo_A + η Q_A, and the device returns: leverage h_i = w_i x_iA' H^-1 x_iA; residual
+    e_i = y_i − predict(model, X)_i, bit for bit; loo_i = e_i / (1 − h_i), by Sherman–Morrison the residual of row i had it been left out
+    (what resample with a jackknife weighting gives whenever the refit keeps pattern and support — without N Grams and N sweeps);
+    studentized and Cook's distances; dof = Σ h, rss, press = Σ w loo², sigma2 = rss / (n_pos − dof), r2, r2_loo; and the standard
+    errors of the weights, of β and of t from Cov = sigma2 H^-1 B H^-1 (partls_diagnostics).  One prepare (upload of X
+    and Gram products) and one call; a float32 X stays float32.
+
+    Caveats.  Everything is conditional on the selected pattern and support: there is no selection adjustment, so the standard errors
+    are those of the least-squares problem the selection ended on.  Weights are precision weights (w_i ∝ 1 / variance_i), not
+    frequencies: n_pos counts rows, not Σw.  stationarity tells whether the model really is the penalised least-squares solution on its
+    support (it is for fit(Opt) / fit(BnB)); where it exceeds the context's KKT tolerance an IllConditionedWarning is given, and loo,
+    sigma2 and the standard errors do not mean what their names say.  A sparse X is refused (NotImplementedError)."""
+    who = "diagnostics"
+    if not isinstance(model, PartLSFitResult):
+        raise TypeError("%s: model must be a PartLSFitResult" % who)
+    _no_sparse(who, X, "densify X yourself (diagnostics from CSR are not implemented)")
+    X, y = np.asarray(X), np.asarray(y)
+    if X.ndim != 2 or y.ndim != 1 or not np.issubdtype(X.dtype, np.floating) or not np.issubdtype(y.dtype, np.floating):
+        raise TypeError("%s: X must be a floating-point matrix and y a floating-point vector" % who)
+    Xf, yf, Pf = _inputs(X, y, model.P)
+    N, M = Xf.shape
+    a, b = np.ascontiguousarray(model.α, dtype=np.float64), np.ascontiguousarray(model.β, dtype=np.float64)
+    if yf.shape != (N,) or Pf.ndim != 2 or Pf.shape[0] != M or a.shape != (M,) or b.shape != (Pf.shape[1],):
+        raise ValueError("DimensionMismatch in %s" % who)
+    if not (np.all(np.isfinite(a)) and np.all(np.isfinite(b)) and np.isfinite(model.t)):
+        raise ValueError("%s: the model has a NaN / Inf in α, β or t" % who)
+    η = _eta(η, eta)
+    if not (η >= 0 and np.isfinite(η)):
+        raise ValueError("%s: η must be finite and >= 0" % who)
+    w = _weights(weights, N, who)
+    ctx = default_context(device)
+    ctx.opt_prepare(Xf, yf, Pf, η, 0, weights=w)
+    out = ctx.diagnostics(a, b, float(model.t))
+    s = out["summary"]
+    if s[L.DIAG_STATIONARITY] > _kkt_tol():
+        warnings.warn("diagnostics: the model is not the least-squares solution on its support for this (X, y, η, weights) "
+                      "(stationarity %.3g): loo, sigma2 and the standard errors are not those of a refit" % s[L.DIAG_STATIONARITY],
+                      IllConditionedWarning, stacklevel=2)
+    return Diagnostics(leverage=out["leverage"], loo=out["loo"], studentized=out["studentized"], cooks=out["cooks"],
+                       residual=out["residual"], se_w=out["se_w"], se_beta=out["se_beta"], se_t=float(out["se_w"][M]),
+                       active=out["active"], n_pos=int(s[L.DIAG_NPLUS]), p=int(s[L.DIAG_P]), dof=float(s[L.DIAG_DOF]),
+                       rss=float(s[L.DIAG_RSS]), press=float(s[L.DIAG_PRESS]), sigma2=float(s[L.DIAG_SIGMA2]), tss=float(s[L.DIAG_TSS]),
+                       r2=float(s[L.DIAG_R2]), r2_loo=float(s[L.DIAG_R2_LOO]), stationarity=float(s[L.DIAG_STATIONARITY]),
+                       loo_mse=float(s[L.DIAG_PRESS] / (N if w is None else w.sum())))
 
 
 def predict_device(model, dX_ptr, N, ldX, dyhat_ptr, device=0, dtype=np.float64):

@@ -1,6 +1,6 @@
 // ctx.h — the context behind the opaque partls_ctx handle, the owning buffer types it is made of, and the host helpers the host
 // translation units share: api.hip (create / destroy / predict / getters), prepare.hip, sweep_setup.hip, opt.hip, refine.hip,
-// solvers.hip, multi.hip and the host halves of cv.hip, alt_multi.hip, predict_many.hip and contrib.hip.
+// solvers.hip, multi.hip and the host halves of cv.hip, alt_multi.hip, predict_many.hip, contrib.hip and diag.hip.
 #pragma once
 #include "common.h"
 #include <chrono>
@@ -292,6 +292,12 @@ struct partls_ctx {
     // row chunk; ctStats / ctMean, the device images of a host caller's stats and mean for one row chunk; ctSums, the 3 K B running
     // sums carried across the row chunks, followed by the per-block partial sums of one chunk
     partls::DevBuf ctW, ctC, ctStats, ctMean, ctSums;
+    // partls_diagnostics (diag.hip): dgT, the packed tiles of T = L^-1, the index list of the active columns and the
+    // prediction weights of the model; dgRow, yhat and the squared norms ||T x_iA||^2 of the rows, followed by the device images of a host
+    // caller's per-row outputs; dgSums, the four running sums and sigma2, followed by the per-block partial sums.  dg_ms: kernel /
+    // factorisation / whole call of the last call (partls_get_diagnostics_timing)
+    partls::DevBuf dgT, dgRow, dgSums;
+    double dg_ms[3] = {0.0, 0.0, 0.0};
 };
 
 namespace partls {
@@ -553,6 +559,9 @@ struct RefineOut { bool have = false; double obj = 0.0; std::vector<double> g; }
 partls_status refine_solution(partls_ctx *c, std::vector<double> &w, bool free_intercept, int steps = 2, RefineOut *out = nullptr);
 // regularised augmented Gram entry on the host copy
 double h_reg(const partls_ctx *c, int a, int b);
+// Row-oriented Cholesky of a dense SPD matrix, in place (refine.hip): lower triangle, row-major, leading dimension p; false when a pivot
+// is not positive.  The finish's refinement and partls_diagnostics factor the regularised Gram block of a support with it.
+bool chol_rows(double *L, int p);
 partls_status check_common(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, const void *P, int64_t K, int64_t ldP);
 // The weights a prediction applies (api.hip), w[m] = sum over k = 0 .. K-1, in that order, of P[m,k] alpha[m] beta[k]: the ONE definition
 // behind partls_predict* and partls_predict_many*, whose columns equal the single predictions bit for bit.  Checks P on the way:

@@ -234,7 +234,7 @@ static bool chol_rows_plain(double *L, int p)
     }
     return true;
 }
-static bool chol_rows(double *L, int p)
+bool chol_rows(double *L, int p)
 {
 #if defined(__x86_64__)
     static const bool fast = __builtin_cpu_supports("avx2") && __builtin_cpu_supports("fma");

@@ -84,6 +84,7 @@ SPEC = {
     "partls_predict_device": _PREDICT % ("@", "yhat:@"), "partls_predict_device_f32": _PREDICT % ("@", "yhat:@"),
     "partls_predict_many": _PREDICT_MANY, "partls_predict_many_f32": _PREDICT_MANY,
     "partls_contributions": _CONTRIB, "partls_contributions_f32": _CONTRIB,
+    "partls_diagnostics": "h alpha:d:M beta:d:K t out out out out out out out out out", "partls_get_diagnostics_timing": "h out out out",
     "partls_synth_truth": "seed D K out out",
     "partls_synth_device": "h seed N D wstar:d:D X:@ y:@",
     "partls_get_timing": "h which out", "partls_get_upload": "h out out", "partls_get_gram": "h out", "partls_get_pivots": "h out",
@@ -124,7 +125,7 @@ class FakeLib:
         self.names = {}                # handle -> c1 / m1 / m1.r0 / f1
         self.state = {}                # handle -> the scalars later calls on it are sized by (M, K, npat; total of a frontier round)
         self.ranks = {}                # multi handle -> its rank handles
-        symbols = lowlevel.SYMBOLS + lowlevel.SYMBOLS_F32 + lowlevel.SYMBOLS_F32_MORE + lowlevel.SYMBOLS_CONTRIB
+        symbols = lowlevel.SYMBOLS + lowlevel.SYMBOLS_F32 + lowlevel.SYMBOLS_F32_MORE + lowlevel.SYMBOLS_CONTRIB + lowlevel.SYMBOLS_DIAG
         assert {s[0] for s in symbols} == set(SPEC), "SPEC and the symbol tables disagree"
         for name, res, argtypes in symbols:
             assert len(SPEC[name].split()) == len(argtypes), name
