@@ -142,7 +142,12 @@ partls_status partls_multi_get_timing(const partls_multi *mc, int rank, int whic
  * With PARTLS_OPT_RESCUE_CAPPED: a sweep that reports capped patterns walks its range a second time through the export pieces of
  * partls_opt_models, whose capped rows the rescue kernel solves; that pass is authoritative: winner, near ties and candidates
  * (partls_opt_candidates), all_opt and *n_unconverged (what the rescue could not solve) are its results.  finish (and
- * partls_opt_pattern): a single solve that hits the cap is solved by the rescue kernel instead of failing. */
+ * partls_opt_pattern): a single solve that hits the cap is solved by the rescue kernel instead of failing.
+ * A refused prepare (this one, _weighted, _f32, _csr).  The argument checks come first and leave the context as it was, so a problem
+ * prepared before still sweeps and finishes to the same bits: a NULL X, y or P, N, M or K < 1, ldX < N, ldP < M, a size beyond the
+ * build's limits, eta < 0 or NaN.  Every failure found later leaves the context unprepared (the next staged call returns
+ * PARTLS_ERR_STATE until a prepare succeeds): the weights, the structure or values of a CSR matrix, an entry of P outside {0,1},
+ * NaN / Inf in X or y (found in the Gram products), a HIP error.  tests/test_gpu_context_reuse.py holds both to it. */
 partls_status partls_opt_prepare(partls_ctx *ctx, const double *X, int64_t N, int64_t M, int64_t ldX, const double *y,
                                  int x_on_device, const int64_t *P, int64_t K, int64_t ldP, double eta, uint32_t flags);
 /* ---- sample weights: the same prepare for the weighted problem (MLJ's supports_weights, scikit-learn's sample_weight) ---------------

@@ -313,8 +313,6 @@ class Context:
         lib = L.lib()
         head = (self._h, xp, N, M, ldX, yp)
         tail = (on_device, P.ctypes.data, P.shape[1], P.shape[0], float(eta), int(flags))
-        self._shape = (N, M, P.shape[1])
-        self._on_device = bool(on_device)                    # where the per-row outputs of diagnostics live
         self.generation += 1
         if f32:
             _check(lib.partls_opt_prepare_f32(*head, wp, *tail))
@@ -322,6 +320,13 @@ class Context:
             _check(lib.partls_opt_prepare(*head, *tail))
         else:
             _check(lib.partls_opt_prepare_weighted(*head, wp, *tail))
+        self._prepared_as(N, M, P.shape[1], on_device)
+
+    def _prepared_as(self, N, M, K, on_device):
+        """What the staged calls size their outputs by, recorded once a prepare has SUCCEEDED: a prepare refused by the argument checks
+        leaves the library's problem untouched (csrc/prepare.hip: prepare_begin), so it must leave the shape of that problem here too."""
+        self._shape = (N, M, K)
+        self._on_device = bool(on_device)                    # where the per-row outputs of diagnostics live
 
     def opt_prepare_csr(self, csr, y, P, eta=0.0, flags=0, weights=None):
         """opt_prepare for a sparse X (a CSR tuple or anything with .tocsr(); host arrays): partls_opt_prepare_csr — X goes up as
@@ -342,11 +347,10 @@ class Context:
                           None if dw_ptr is None else C.c_void_p(dw_ptr), 1, int(N), int(M), np.asfortranarray(P, dtype=np.int64), eta, flags)
 
     def _prepare_csr(self, pp, ip, vp, yp, wp, on_device, N, M, P, eta, flags):
-        self._shape = (N, M, P.shape[1])
-        self._on_device = bool(on_device)
         self.generation += 1
         _check(L.lib().partls_opt_prepare_csr(self._h, pp, ip, vp, N, M, yp, wp, on_device, P.ctypes.data, P.shape[1], P.shape[0],
                                               float(eta), int(flags)))
+        self._prepared_as(N, M, P.shape[1], on_device)
 
     def predict_csr(self, csr, P, alpha, beta, t):
         """predict for a sparse X (a CSR tuple or anything with .tocsr(); host arrays): partls_predict_csr.  An empty row gives t."""
