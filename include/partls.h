@@ -551,6 +551,9 @@ partls_status partls_get_gram(const partls_ctx *ctx, double *G_aug);
 /* ---- regression diagnostics of one model on the prepared problem: leverage, leave-one-out residuals, studentized residuals, Cook's
  * distances, degrees of freedom, standard errors. */
 #include "partls_diag.h"
+/* ---- robust fits: the Huber / bisquare row weights of a model on the prepared problem, formed on the device, and the re-prepare that
+ * swaps the sample weights of a prepared problem without touching X. */
+#include "partls_robust.h"
 
 #ifdef __cplusplus
 }

@@ -146,6 +146,16 @@ SYMBOLS_DIAG = [
     ("partls_get_diagnostics_timing", C.c_int, [C.c_void_p, _dp, _dp, _dp]),
 ]
 
+# ... and every symbol include/partls_robust.h declares (robust fits: the row weights of a Huber / bisquare loss on the prepared problem
+# and the re-prepare that swaps its sample weights; w_out and w are host arrays or device addresses, passed as addresses)
+ROBUST_HUBER, ROBUST_BISQUARE = range(2)
+SYMBOLS_ROBUST = [
+    ("partls_robust_weights", C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_int, C.c_double, C.c_double, _dp, _dp, _dp, _ip, _ip,
+                                        C.c_void_p]),
+    ("partls_opt_reweight", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("partls_get_robust_timing", C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+]
+
 _lib = None
 
 
@@ -192,7 +202,7 @@ def lib():
                               f"(make -C '{CSRC}'); partitionedls.jl_amd has no CPU fallback")
         _preload_torch_hip_runtime()
         l = C.CDLL(SO_PATH)
-        for name, res, args in SYMBOLS + SYMBOLS_F32 + SYMBOLS_F32_MORE + SYMBOLS_CSR + SYMBOLS_CONTRIB + SYMBOLS_DIAG:
+        for name, res, args in SYMBOLS + SYMBOLS_F32 + SYMBOLS_F32_MORE + SYMBOLS_CSR + SYMBOLS_CONTRIB + SYMBOLS_DIAG + SYMBOLS_ROBUST:
             if os.environ.get("PARTLS_LIB") and not hasattr(l, name):
                 continue                   # diagnostic A/B builds of older sources may lack the newest entry points
             f = getattr(l, name)           # AttributeError here = header/library mismatch

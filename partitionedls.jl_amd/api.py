@@ -848,6 +848,70 @@ class Context:
         _check(L.lib().partls_get_diagnostics_timing(self._h, *(C.byref(m) for m in ms)))
         return tuple(m.value for m in ms)
 
+    # ---- robust fits ----------------------------------------------------------------------------------
+    def robust_weights(self, alpha, beta, t, *, loss="huber", c=None, scale=None, want_weights=True):
+        """The row weights of a Huber or bisquare loss at the model (alpha[M], beta[K], t) on the problem this context is prepared for,
+        from HOST arrays (opt_prepare): partls_robust_weights, DESIGN.md §4.18.  c: the tuning constant (None: 1.345 / 4.685);
+        scale: a positive float holds the residual scale fixed, None (or "mad") estimates it as median |residual| / 0.6745.
+        Returns a dict: weights[N] (None unless want_weights, or when scale is 0), scale, rho_sum, max_dw (against the previous
+        call's weights since the last prepare; all ones when there was none), n_down, n_zero.  scale == 0 (at least half of the rows
+        are fitted exactly): no weights were formed.  The prepared problem is untouched."""
+        if getattr(self, "_on_device", False):
+            raise ValueError("Context.robust_weights: the problem was prepared from device pointers; its weights are a device "
+                             "array (robust_weights_device)")
+        N = self._diag_shape("Context.robust_weights")[0]
+        w = np.zeros(N) if want_weights else None
+        out = self._robust_weights(alpha, beta, t, loss, c, scale, None if w is None else w.ctypes.data)
+        out["weights"] = w if out["scale"] != 0.0 else None
+        return out
+
+    def robust_weights_device(self, alpha, beta, t, *, loss="huber", c=None, scale=None, dw_ptr=None):
+        """the same on a problem prepared from DEVICE pointers (opt_prepare_device): dw_ptr (optional) is the raw device address of N
+        doubles that receive the weights; returns the dict without weights"""
+        if not getattr(self, "_on_device", True):
+            raise ValueError("Context.robust_weights_device: the problem was prepared from host arrays; its weights are a host "
+                             "array (robust_weights)")
+        self._diag_shape("Context.robust_weights_device")
+        return self._robust_weights(alpha, beta, t, loss, c, scale, None if dw_ptr is None else C.c_void_p(dw_ptr))
+
+    def _robust_weights(self, alpha, beta, t, loss, c, scale, w_out):
+        """The one call behind robust_weights and robust_weights_device: w_out (or None) is an address on the host or in HBM, as the
+        prepare was"""
+        _, M, K = self._shape
+        code, cv, sv = _robust_options(loss, c, scale, "robust_weights")
+        a = np.ascontiguousarray(alpha, dtype=np.float64)
+        b = np.ascontiguousarray(beta, dtype=np.float64)
+        if a.shape != (M,) or b.shape != (K,):
+            raise ValueError("robust_weights: expected alpha (%d,) and beta (%d,), got %s and %s" % (M, K, a.shape, b.shape))
+        s, rho, dw = C.c_double(), C.c_double(), C.c_double()
+        nd, nz = C.c_int64(), C.c_int64()
+        _check(L.lib().partls_robust_weights(self._h, _dp(a), _dp(b), float(t), code, cv, sv, C.byref(s), C.byref(rho), C.byref(dw),
+                                             C.byref(nd), C.byref(nz), w_out))
+        return dict(scale=s.value, rho_sum=rho.value, max_dw=dw.value, n_down=nd.value, n_zero=nz.value)
+
+    def opt_reweight(self, weights=None):
+        """New sample weights for the prepared problem, X untouched (partls_opt_reweight): weights[N] (host; the rules
+        of opt_prepare's weights), or None for the weights of the last robust_weights call on this context.  Afterwards the context
+        is in the state opt_prepare(..., weights=weights) would leave it in, bit for bit; nothing but a host weights vector is
+        uploaded.  A refusal leaves the context unprepared."""
+        N = self._diag_shape("Context.opt_reweight")[0]
+        w = _weights(weights, N)
+        self.generation += 1
+        _check(L.lib().partls_opt_reweight(self._h, None if w is None else w.ctypes.data, 0))
+
+    def opt_reweight_device(self, dw_ptr):
+        """the same with the weights in HBM: the raw device address of N doubles, which stay owned by the caller and must stay valid
+        while the context holds the problem"""
+        self._diag_shape("Context.opt_reweight_device")
+        self.generation += 1
+        _check(L.lib().partls_opt_reweight(self._h, C.c_void_p(dw_ptr), 1))
+
+    def robust_timing(self):
+        """(residual pass, selection of the median, weight kernel) of the last robust_weights call on this context, in ms of device time"""
+        ms = [C.c_double() for _ in range(3)]
+        _check(L.lib().partls_get_robust_timing(self._h, *(C.byref(m) for m in ms)))
+        return tuple(m.value for m in ms)
+
     def _count(self, getter):
         n = C.c_int64()
         _check(getter(self._h, C.byref(n)))
@@ -1443,6 +1507,138 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
         else:
             a, b, t, o, no = _host_fit(ctx, L.lib().partls_fit_bnb, Xf, yf, Pf, eta_v)
         return result(ctx, a, b, t, opt=o, nopen=no)
+
+
+class RobustConvergenceWarning(UserWarning):
+    """fit_robust ran out of iterations (max_iter) before the row weights settled within tol"""
+
+
+ROBUST_C = {"huber": 1.345, "bisquare": 4.685}     # the usual 95 %-efficiency tuning constants
+
+
+def _robust_options(loss, c, scale, who):
+    """(loss code, c, scale_in) as partls_robust_weights takes them; ValueError for anything else.  scale: None or "mad" (0.0: the
+    library estimates it) or a positive finite float"""
+    if loss not in ROBUST_C:
+        raise ValueError('%s: loss must be "huber" or "bisquare", got %r' % (who, loss))
+    if c is None:
+        c = ROBUST_C[loss]
+    if isinstance(c, (bool, str)) or not isinstance(c, (int, float, np.integer, np.floating)) or not np.isfinite(c) or not c > 0:
+        raise ValueError("%s: c must be a finite number > 0, got %r" % (who, c))
+    if scale is None or (isinstance(scale, str) and scale == "mad"):
+        s = 0.0
+    elif isinstance(scale, (bool, str)) or not isinstance(scale, (int, float, np.integer, np.floating)) or not np.isfinite(scale) or not scale > 0:
+        raise ValueError('%s: scale must be "mad" or a finite number > 0, got %r' % (who, scale))
+    else:
+        s = float(scale)
+    return (L.ROBUST_HUBER if loss == "huber" else L.ROBUST_BISQUARE), float(c), s
+
+
+def fit_robust(alg, X, y, P, *, loss="huber", c=None, scale="mad", max_iter=50, tol=1e-6, η=None, eta=None, ϵ=None, eps=None, T=100,
+               rng=None, alpha0=None, beta0=None, faithful_intercept=False, generic_kernel=False, rescue=False, device=0,
+               on_ill_conditioned="warn", weights=None, restarts=None, top=None, returnAllSolutions=False, devices=None):
+    """fit_robust(Opt|Alt|BnB, X, y, P; loss, c, scale, ...) -> (PartLSFitResult, None, Report): an M-estimator of the partitioned
+    model by iteratively reweighted least squares.  X is uploaded once; every iteration forms the row weights of the
+    loss at the current model on the device (Context.robust_weights), swaps them into the prepared problem (Context.opt_reweight)
+    and runs the staged fit of alg again.  The loop, exactly:
+      1. prepare as fit does for a staged fit, unweighted (float32 stays float32, sparse stays CSR) and fit model_0 (Opt: sweep +
+         finish, PartlsError(ERR_NOT_CONVERGED) on capped patterns as in fit; Alt: alt_prepared; BnB: bnb_prepared);
+      2. for j = 1 .. max_iter: info = robust_weights(model_{j-1}); info.scale == 0 (at least half of the rows fitted exactly): stop,
+         exact and converged; info.max_dw <= tol: stop, converged; else opt_reweight() and the staged fit again -> model_j.
+    Alt starts every iteration from the one starting point fit(Alt, rng=, alpha0=, beta0=) would use.
+    loss: "huber" or "bisquare"; c: its tuning constant (None: 1.345 / 4.685); scale: "mad" (median |residual| / 0.6745 of every
+    iteration's residuals) or a positive float that holds it fixed — then, with Opt, each step minimises a majoriser of the loss
+    exactly and report.robust.rho_sum does not increase (up to rounding).  The other options are fit's.
+    Returns the last model; the report carries the last fit's fields (opt, best_index / iters / nopen, ill_conditioned ...) and
+    report.robust = Report(loss, c, scale, iterations (re-weighted fits run), converged, exact, weights[N] (the last ones formed; all
+    ones when none were), rho_sum, max_dw, scales (lists, one entry per robust_weights call), n_down, n_zero).  Out of iterations:
+    converged = False and a RobustConvergenceWarning.
+    ValueError before any device work: weights=, restarts=, top=, returnAllSolutions= (not combined with a robust loss), a bad loss,
+    c, scale, max_iter or tol; NotImplementedError: devices=."""
+    if alg not in (Opt, Alt, BnB):
+        raise TypeError("fit_robust: first argument must be Opt, Alt or BnB")
+    for name, given in (("weights", weights is not None), ("restarts", restarts is not None), ("top", top is not None),
+                        ("returnAllSolutions", bool(returnAllSolutions))):
+        if given:
+            raise ValueError("fit_robust: %s= is not supported together with a robust loss" % name)
+    if devices is not None:
+        raise NotImplementedError("fit_robust: several devices (devices=) are not supported")
+    code, cv, sv = _robust_options(loss, c, scale, "fit_robust")
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or int(max_iter) < 1:
+        raise ValueError("fit_robust: max_iter must be an integer >= 1, got %r" % (max_iter,))
+    if isinstance(tol, (bool, str)) or not isinstance(tol, (int, float, np.integer, np.floating)) or not np.isfinite(tol) or tol < 0:
+        raise ValueError("fit_robust: tol must be a finite number >= 0, got %r" % (tol,))
+    if rescue and alg is not Opt:
+        raise ValueError("fit_robust: rescue= is an option of Opt (the enumeration), not of %s" % alg.__name__)
+    if on_ill_conditioned not in ("warn", "raise"):
+        raise ValueError('on_ill_conditioned must be "warn" or "raise"')
+    eta_v = _eta(η, eta)
+    eps_v = 1e-6 if (ϵ is None and eps is None) else float(ϵ if ϵ is not None else eps)
+    Xf, yf, Pf = _fit_inputs(X, y, P, f32=True)
+    N, M = Xf.shape
+    K = Pf.shape[1]
+    flags = L.OPT_FAITHFUL_INTERCEPT
+    if alg is Opt:
+        flags = (L.OPT_FAITHFUL_INTERCEPT if faithful_intercept else 0) | (L.OPT_GENERIC_KERNEL if generic_kernel else 0) | (L.OPT_RESCUE_CAPPED if rescue else 0)
+    if alg is Alt:
+        if np.ndim(alpha0) == 2 or np.ndim(beta0) == 2:
+            raise ValueError("fit_robust: several starting points (restarts) are not supported together with a robust loss")
+        if alpha0 is None or beta0 is None:
+            alpha0, beta0 = _draw_start(_generator(rng), M, K)
+        a0 = np.ascontiguousarray(alpha0, dtype=np.float64)
+        b0 = np.ascontiguousarray(beta0, dtype=np.float64)
+        if a0.shape != (M + 1,) or b0.shape != (K + 1,):
+            raise ValueError("alpha0 must have M+1 and beta0 K+1 entries")
+    ctx = default_context(device)
+    ctx.last_ill = False
+    Pout = np.array(Pf, dtype=np.int64, order="C")
+
+    def staged():
+        """the staged call of alg on the prepared problem -> (alpha, beta, t, the Report fields of this fit)"""
+        if alg is Opt:
+            _, bpat, _, unconv = ctx.opt_sweep(0, -1)
+            if unconv:
+                raise PartlsError(L.ERR_NOT_CONVERGED, f"{unconv} subproblems hit the pivot cap")
+            a, b, t, opt, bi = ctx.opt_finish(bpat)
+            kw = dict(opt=opt, best_index=bi)
+            if rescue:
+                kw.update(rescued=ctx.rescue_stats().rescued)
+            return a, b, t, kw
+        if alg is Alt:
+            a, b, t, o, it = ctx.alt_prepared(a0, b0, eps_v, int(T))
+            return a, b, t, dict(opt=o, iters=it)
+        a, b, t, o, no = ctx.bnb_prepared()
+        return a, b, t, dict(opt=o, nopen=no)
+
+    rho_sums, max_dws, scales = [], [], []
+    w_last = np.ones(N)                                       # the library writes the weights of every call that forms some into it
+    iterations, converged, exact = 0, False, False
+    with _tolerating(on_ill_conditioned, ctx):
+        ctx.opt_prepare(Xf, yf, Pf, eta_v, flags)
+        a, b, t, kw = staged()
+        for _ in range(int(max_iter)):
+            info = ctx._robust_weights(a, b, t, loss, cv, sv if sv > 0 else None, w_last.ctypes.data)
+            rho_sums.append(info["rho_sum"]); max_dws.append(info["max_dw"]); scales.append(info["scale"])
+            if info["scale"] == 0.0:
+                converged = exact = True
+                break
+            if info["max_dw"] <= tol:
+                converged = True
+                break
+            ctx.opt_reweight()
+            a, b, t, kw = staged()
+            iterations += 1
+        if ctx.last_ill:
+            warnings.warn("partitionedls: the model's KKT conditions do not hold in data space (X is too ill-conditioned for the fp64 "
+                          "Gram form); the returned model is the best Gram-form one — " + L.lib().partls_last_error().decode(),
+                          IllConditionedWarning, stacklevel=2)
+            kw.update(ill_conditioned=True, kkt_violation=ctx.kkt_violation())
+    if not converged:
+        warnings.warn("partitionedls: fit_robust stopped after max_iter = %d re-weighted fits with the weights still moving "
+                      "(max |dw| = %.3g > tol = %.3g)" % (int(max_iter), max_dws[-1], tol), RobustConvergenceWarning, stacklevel=2)
+    kw["robust"] = Report(loss=loss, c=cv, scale=info["scale"], iterations=iterations, converged=converged, exact=exact, weights=w_last,
+                          rho_sum=rho_sums, max_dw=max_dws, scales=scales, n_down=info["n_down"], n_zero=info["n_zero"])
+    return PartLSFitResult(a, b, t, Pout), None, Report(**kw)
 
 
 def cv_folds(N, nfolds=5, shuffle=False, rng=None):

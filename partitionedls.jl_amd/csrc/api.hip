@@ -74,7 +74,7 @@ using namespace partls;
 
 extern "C" {
 
-int partls_version(void) { return 109; }
+int partls_version(void) { return 110; }
 const char *partls_last_error(void) { return g_err; }
 
 int partls_device_count(void)

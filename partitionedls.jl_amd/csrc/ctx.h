@@ -1,6 +1,6 @@
 // ctx.h — the context behind the opaque partls_ctx handle, the owning buffer types it is made of, and the host helpers the host
 // translation units share: api.hip (create / destroy / predict / getters), prepare.hip, sweep_setup.hip, opt.hip, refine.hip,
-// solvers.hip, multi.hip and the host halves of cv.hip, alt_multi.hip, predict_many.hip, contrib.hip and diag.hip.
+// solvers.hip, multi.hip and the host halves of cv.hip, alt_multi.hip, predict_many.hip, contrib.hip, diag.hip and robust.hip.
 #pragma once
 #include "common.h"
 #include <chrono>
@@ -161,7 +161,7 @@ struct partls_ctx {
 
     // Reset by forget_problem (prepare.hip), the one reset of ctx_prepare, batch_reset and batch_work_prepare — whatever below is derived
     // from a prepared problem or its last sweep or solve: prepared, peers; near_for, near_pat, cand, export_wg; sweep_vetoes, rescue_*,
-    // coop_state_valid, coop_fallback; tab_valid; order_ready, order_identity, flip_cost, pair_laid; dw, ds, x_f32, storage; last_upload_*; ms[CALIB], ms[OOB].
+    // coop_state_valid, coop_fallback; tab_valid; order_ready, order_identity, flip_cost, pair_laid; dw, ds, x_f32, storage; last_upload_*; ms[CALIB], ms[OOB]; rb_have.
     // (Not last_kkt / last_min_loo: partls_get_kkt_violation reports them, for the last model returned, without a prepared problem.)
     // problem
     bool prepared = false;
@@ -298,6 +298,18 @@ struct partls_ctx {
     // factorisation / whole call of the last call (partls_get_diagnostics_timing)
     partls::DevBuf dgT, dgRow, dgSums;
     double dg_ms[3] = {0.0, 0.0, 0.0};
+    // partls_robust_weights / partls_opt_reweight (robust.hip): rbA, the absolute residuals of the model; rbW, the
+    // weights of the last call (read as the previous weights by the next one, which updates them in place); rbState, the selection's
+    // state followed by the prediction weights of the model; rbPart / rbHost, the per-block partials of the weight kernel and their host
+    // copy.  rb_have: rbW holds the weights of a call since the last prepare (forget_problem clears it; partls_opt_reweight keeps it).
+    // csr_seg / csr_S: the Gram plan of a problem prepared from CSR (csr_gram_plan), kept for partls_opt_reweight.  rb_ms: residual
+    // pass / selection / weight kernel of the last partls_robust_weights call (partls_get_robust_timing)
+    partls::DevBuf rbA, rbW, rbState, rbPart;
+    partls::PinnedDoubles rbHost;
+    bool rb_have = false;
+    int64_t csr_seg = 0;
+    int csr_S = 1;
+    double rb_ms[3] = {0.0, 0.0, 0.0};
 };
 
 namespace partls {
@@ -337,6 +349,10 @@ partls_status adopt_or_upload(partls_ctx *c, const void *X, int64_t N, int64_t M
 // Sample weights w[N] (host, or device when on_device) -> c->dw, c->ds after one weight_prep_kernel pass, or the status of the first
 // failed check: NaN / Inf -> PARTLS_ERR_NONFINITE; a negative weight or a sum that is not > 0 -> PARTLS_ERR_BAD_ARG.
 partls_status prepare_weights(partls_ctx *c, const double *w, int64_t N, int on_device);
+// partls_opt_reweight: the prepared problem of c takes the sample weights w (prepare_weights' rules; never NULL) and
+// its Gram products and tableau are built again — forget_problem, prepare_weights, the storage kind's Gram launch and the ending of
+// every prepare, from the X, y, partition, eta and flags the context holds.  A refusal leaves the context unprepared.
+partls_status ctx_reweight(partls_ctx *c, const double *w, int on_device);
 // The second half of ctx_prepare: from the Gram products in c->G (c->M, K, eta, flags, faithful and the partition already set) to the
 // tableau, the host copies and the tolerance.  partls_cv_opt calls it on a context whose G it filled itself.
 partls_status ctx_prepare_tableau(partls_ctx *c);

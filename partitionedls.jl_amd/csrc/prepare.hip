@@ -146,6 +146,7 @@ void forget_problem(partls_ctx *c)
     c->x_f32 = false; c->storage = XStorage::dense64;
     c->last_upload_ms = 0.0; c->last_upload_bytes = 0.0;
     c->ms[PARTLS_T_CALIB] = 0.0; c->ms[PARTLS_T_OOB] = 0.0;
+    c->rb_have = false;
 }
 
 partls_status adopt_or_upload(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device, size_t esz)
@@ -198,6 +199,31 @@ static partls_status prepare_end(partls_ctx *c)
     return ctx_prepare_tableau(c);
 }
 
+// The Gram launch of the problem c holds, queued on c->stream (no sync) — one definition per storage kind, shared by the prepare and by
+// ctx_reweight, so that a re-prepare builds exactly what a fresh prepare builds.  Dense (fp64 MFMA): X, y, ds = sqrt(w) -> c->G, timed
+// as PARTLS_T_GRAM (the launch alone, not the allocations in front of it).
+static partls_status queue_dense_gram(partls_ctx *c)
+{
+    const size_t slabd = gram_slab_doubles(c->N, c->M, c->knobs.gram_S, c->knobs.gram_cr, &c->chunks, &c->ldg);
+    PARTLS_HIP_CHECK(c->slab.ensure(slabd * sizeof(double)));
+    PARTLS_HIP_CHECK(c->G.ensure((size_t)c->ldg * c->ldg * sizeof(double)));
+    t_begin(c, PARTLS_T_GRAM);
+    PARTLS_HIP_CHECK(launch_gram(c->dX, c->N, c->M, c->ldX, c->dy, c->slab.as<double>(), c->chunks, c->ldg, c->knobs.gram_S, c->knobs.gram_cr,
+                                 c->G.as<double>(), c->stream, c->ds, c->x_f32));
+    t_end(c, PARTLS_T_GRAM);
+    return PARTLS_OK;
+}
+// CSR: the matrix, its CSC copy, y, dw = w and the plan (csr_seg, csr_S) the prepare made from the column lengths -> c->G (c->ldg set).
+// Not timed here: the prepare's PARTLS_T_GRAM spans the validation and the transposition in front of it as well.
+static partls_status queue_csr_gram(partls_ctx *c)
+{
+    const size_t partd = csr_gram_part_doubles(c->M, c->csr_S);
+    PARTLS_HIP_CHECK(c->csrPart.ensure((partd + 3) * sizeof(double)));
+    PARTLS_HIP_CHECK(launch_csr_gram(c->csr, c->csc, c->dy, c->dw, c->csr_seg, c->csr_S, c->csrPart.as<double>(),
+                                     c->csrPart.as<double>() + partd, c->ldg, c->G.as<double>(), c->stream));
+    return PARTLS_OK;
+}
+
 partls_status ctx_prepare(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device,
                           const int64_t *P, int64_t K, int64_t ldP, double eta, bool faithful, uint32_t flags, const double *w, bool x_f32)
 {
@@ -208,14 +234,8 @@ partls_status ctx_prepare(partls_ctx *c, const void *X, int64_t N, int64_t M, in
     if (st != PARTLS_OK) return st;
     c->x_f32 = x_f32; c->storage = x_f32 ? XStorage::dense32 : XStorage::dense64;
 
-    // Gram products (fp64 MFMA)
-    const size_t slabd = gram_slab_doubles(N, M, c->knobs.gram_S, c->knobs.gram_cr, &c->chunks, &c->ldg);
-    PARTLS_HIP_CHECK(c->slab.ensure(slabd * sizeof(double)));
-    PARTLS_HIP_CHECK(c->G.ensure((size_t)c->ldg * c->ldg * sizeof(double)));
-    t_begin(c, PARTLS_T_GRAM);
-    PARTLS_HIP_CHECK(launch_gram(c->dX, N, M, c->ldX, c->dy, c->slab.as<double>(), c->chunks, c->ldg, c->knobs.gram_S, c->knobs.gram_cr,
-                                 c->G.as<double>(), c->stream, c->ds, c->x_f32));
-    t_end(c, PARTLS_T_GRAM);
+    st = queue_dense_gram(c);
+    if (st != PARTLS_OK) return st;
     return prepare_end(c);
 }
 
@@ -333,12 +353,33 @@ partls_status ctx_prepare_csr(partls_ctx *c, const int64_t *indptr, const int32_
     int S = 1;
     for (int64_t m = 0; m < M; ++m) longest = std::max(longest, colptr[(size_t)m + 1] - colptr[(size_t)m]);
     csr_gram_plan(M, longest, &seg, &S);
-    const size_t partd = csr_gram_part_doubles(M, S);
-    PARTLS_HIP_CHECK(c->csrPart.ensure((partd + 3) * sizeof(double)));
-    PARTLS_HIP_CHECK(launch_csr_gram(A, c->csc, c->dy, c->dw, seg, S, c->csrPart.as<double>(), c->csrPart.as<double>() + partd, c->ldg,
-                                     c->G.as<double>(), c->stream));
+    c->csr_seg = seg; c->csr_S = S;                       // kept: partls_opt_reweight builds the Gram again by the same plan
+    st = queue_csr_gram(c);
+    if (st != PARTLS_OK) return st;
     t_end(c, PARTLS_T_GRAM);
     return prepare_end(c);
+}
+
+// ---- partls_opt_reweight: new sample weights for the prepared problem, X untouched
+partls_status ctx_reweight(partls_ctx *c, const double *w, int on_device)
+{
+    const XStorage storage = c->storage;
+    const bool x_f32 = c->x_f32, had = c->rb_have;
+    const int64_t N = c->N;
+    forget_problem(c);
+    c->storage = storage; c->x_f32 = x_f32;               // the kind of the X the context keeps holding
+    PARTLS_HIP_CHECK(hipSetDevice(c->device));
+    partls_status st = prepare_weights(c, w, N, on_device);
+    if (st != PARTLS_OK) return st;
+    if (storage == XStorage::csr) {
+        t_begin(c, PARTLS_T_GRAM);
+        st = queue_csr_gram(c);
+        if (st == PARTLS_OK) t_end(c, PARTLS_T_GRAM);
+    } else st = queue_dense_gram(c);
+    if (st != PARTLS_OK) return st;
+    st = prepare_end(c);
+    if (st == PARTLS_OK) c->rb_have = had;                // the record of the previous robust weights survives a re-prepare
+    return st;
 }
 
 // c->perm -> everything that is laid out by it: the group masks in tableau order, the one upload of masks and permutation, the scale, the
