@@ -3,6 +3,7 @@
 // data passes and refinement; solvers.hip: fit(Alt), fit(BnB).)  No CPU fallback: every compute entry needs a HIP device and fails
 // with PARTLS_ERR_NO_DEVICE / PARTLS_ERR_HIP otherwise.
 #include "ctx.h"
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -65,6 +66,42 @@ partls_status predict_weights(const int64_t *P, int64_t M, int64_t K, int64_t ld
         }
         w[m] = s;
     }
+    return PARTLS_OK;
+}
+
+partls_status check_prepared_single(const partls_ctx *c, const char *who, partls_status unprepared)
+{
+    if (!c) { set_error("context is NULL"); return PARTLS_ERR_BAD_ARG; }
+    if (c->multi_rank || !c->peers.empty()) { set_error("%s: a context of a partls_multi is not supported", who); return PARTLS_ERR_UNSUPPORTED; }
+    if (!c->prepared) { set_error("%s: context not prepared", who); return unprepared; }
+    return PARTLS_OK;
+}
+
+partls_status check_models(const char *who, const double *alpha, int64_t ld_alpha, const double *beta, int64_t ld_beta, const double *t,
+                           int64_t M, int64_t K, int64_t B, bool many)
+{
+    for (int64_t b = 0; b < B; ++b) {
+        bool fin = !t || std::isfinite(t[b]);
+        for (int64_t m = 0; m < M && fin; ++m) fin = std::isfinite(alpha[m + b * ld_alpha]);
+        for (int64_t k = 0; k < K && fin; ++k) fin = std::isfinite(beta[k + b * ld_beta]);
+        if (fin) continue;
+        if (many) set_error("%s: model %lld has a NaN / Inf in %s", who, (long long)b, t ? "alpha, beta or t" : "alpha or beta");
+        else set_error("%s: the model has a NaN / Inf in %s", who, t ? "alpha, beta or t" : "alpha or beta");
+        return PARTLS_ERR_BAD_ARG;
+    }
+    return PARTLS_OK;
+}
+
+partls_status stage_dense_x(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, int x_on_device, bool x_f32, const void **dX,
+                            int64_t *ld)
+{
+    *dX = X; *ld = ldX;
+    if (x_on_device) return PARTLS_OK;
+    const size_t esz = x_f32 ? sizeof(float) : sizeof(double);
+    PARTLS_HIP_CHECK(c->predX.ensure((size_t)N * M * esz));
+    const partls_status us = upload_matrix(c, c->predX.p, X, N, M, ldX, esz);
+    if (us != PARTLS_OK) return us;
+    *dX = c->predX.p; *ld = N;
     return PARTLS_OK;
 }
 
@@ -217,15 +254,9 @@ static partls_status predict_dense(partls_ctx *c, const void *X, int64_t N, int6
                                    double *yhat, bool x_f32 = false)
 {
     return predict_common(c, X, N, M, ldX, x_on_device, P, K, ldP, alpha, beta, yhat, [&](const double *wdev, double *dyh) -> partls_status {
-        const void *dX = X;
-        int64_t ld = ldX;
-        if (!x_on_device) {
-            const size_t esz = x_f32 ? sizeof(float) : sizeof(double);
-            PARTLS_HIP_CHECK(c->predX.ensure((size_t)N * M * esz));
-            const partls_status us = upload_matrix(c, c->predX.p, X, N, M, ldX, esz);
-            if (us != PARTLS_OK) return us;
-            dX = c->predX.p; ld = N;
-        }
+        const void *dX = nullptr; int64_t ld = 0;
+        const partls_status us = stage_dense_x(c, X, N, M, ldX, x_on_device, x_f32, &dX, &ld);
+        if (us != PARTLS_OK) return us;
         PARTLS_HIP_CHECK(launch_residual(dX, N, M, ld, nullptr, wdev, t, nullptr, 1024, dyh, c->stream, nullptr, x_f32));
         return PARTLS_OK;
     });

@@ -39,6 +39,28 @@ __device__ __forceinline__ double block_sum_256(double *red, double v)
     return red[0];
 }
 
+// NV values at once: one pass of the same tree over NV rows of LDS, slot j by fmax when bit j of MAXMASK is set, else by + (operands
+// and order are block_sum_256's: a sum keeps its bits).  All threads get all results; a barrier goes in front of a second call.
+template <int NV, unsigned MAXMASK = 0>
+__device__ __forceinline__ void block_tree_256(double (*red)[256], double (&v)[NV])
+{
+#pragma unroll
+    for (int j = 0; j < NV; ++j) red[j][threadIdx.x] = v[j];
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                if ((MAXMASK >> j) & 1u) red[j][threadIdx.x] = fmax(red[j][threadIdx.x], red[j][threadIdx.x + h]);
+                else red[j][threadIdx.x] += red[j][threadIdx.x + h];
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] = red[j][0];
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // sweep parameters (shared by the register-resident and the global-memory tableau kernels)
 // ---------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // contrib.hip — partls_contributions(_f32): the N x K group contributions of B models in one pass over X per PARTLS_CONTRIB_CHUNK
 // models, their per-(row, group) order statistics and mean over the models (the kernels of predict_many.hip) and their per-(group,
-// model) sums over the rows.  Kernels first, then the host driver and the two entries.
+// model) sums over the rows.  Kernels first, then the entry's share of the host side (the row-chunk driver is
+// many_model_pass, predict_many.hip) and the two entries.
 #include "ctx.h"
 #include <cmath>
 #include <cstring>
@@ -66,38 +67,25 @@ __global__ __launch_bounds__(256) void contrib_kernel(const XT *__restrict__ X, 
 // ---------------------------------------------------------------------------------------------------------------------
 // (b) the sums over the rows, in an order that is a function of N alone.  The rows of a chunk (which begins at a multiple of 256 of the
 // global row index) are cut into blocks of 256; workgroup (blockIdx.x, blockIdx.y) sums block blockIdx.x of the columns (k, b) =
-// blockIdx.y, blockIdx.y + gridDim.y, ... by block_sum_256 (a fixed tree; a lane past the last row adds +0.0): part[(blk cols + col) 3
-// + s] for s = 0: c, 1: |c|, 2: c^2.  Column col = k + K b of the chunk is C[. + ldC col].
+// blockIdx.y, blockIdx.y + gridDim.y, ... by block_tree_256 (a fixed tree; a lane past the last row adds +0.0): part[(blk cols + col) 3
+// + s] for s = 0: c, 1: |c|, 2: c^2.  Column col = k + K b of the chunk is C[. + ldC col].  launch_fold_partials then adds a chunk's
+// block sums to the 3 cols running sums, zeroed before the first chunk: ((0.0 + block 0) + block 1) + ... over the blocks of all chunks.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void contrib_sums_kernel(const double *__restrict__ C, int64_t rows, int64_t ldC, int64_t cols,
                                                            double *__restrict__ part)
 {
-    __shared__ double red[256];
+    __shared__ double red[3][256];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     for (int64_t col = blockIdx.y; col < cols; col += gridDim.y) {
         const double v = i < rows ? C[i + ldC * col] : 0.0;
-        const double s0 = block_sum_256(red, v);
-        __syncthreads();                                     // every thread has read red[0] before the next sum overwrites it
-        const double s1 = block_sum_256(red, fabs(v));
-        __syncthreads();
-        const double s2 = block_sum_256(red, v * v);
-        __syncthreads();
+        double s[3] = {v, fabs(v), v * v};
+        block_tree_256<3>(red, s);
+        __syncthreads();                                     // every thread has read its results before the next column overwrites them
         if (threadIdx.x == 0) {
             double *p = part + ((int64_t)blockIdx.x * cols + col) * 3;
-            p[0] = s0; p[1] = s1; p[2] = s2;
+            p[0] = s[0]; p[1] = s[1]; p[2] = s[2];
         }
     }
-}
-
-// ... and the block sums of a chunk added to the running sums in ascending block order: one thread per (column, s).  run: 3 cols
-// doubles, zeroed before the first chunk, so that every sum is ((0.0 + block 0) + block 1) + ... over the blocks of all chunks.
-__global__ __launch_bounds__(256) void contrib_sums_fold_kernel(const double *__restrict__ part, int64_t blocks, int64_t cols, double *__restrict__ run)
-{
-    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (q >= 3 * cols) return;
-    double s = run[q];
-    for (int64_t blk = 0; blk < blocks; ++blk) s += part[blk * 3 * cols + q];
-    run[q] = s;
 }
 
 // rows of a chunk: the rows x K x max(B, nr) intermediate within `budget` bytes, a multiple of 256 rows and at least 256 (so that the
@@ -134,24 +122,11 @@ static partls_status contrib_common(partls_ctx *c, const void *X, int64_t N, int
         return PARTLS_ERR_BAD_ARG;
     }
     if (!contrib && !stats && !mean && !sums) { set_error("%s: no output wanted (contrib, stats, mean and sums are all NULL)", who); return PARTLS_ERR_BAD_ARG; }
-    if (nr < 0 || (nr == 0) != (stats == nullptr) || (nr > 0 && !ranks)) {
-        set_error("%s: stats must be NULL exactly when nr == 0, and ranks given when it is not (nr = %lld)", who, (long long)nr);
-        return PARTLS_ERR_BAD_ARG;
-    }
-    if (contrib && ldC < N) { set_error("%s: ldC = %lld is smaller than N = %lld", who, (long long)ldC, (long long)N); return PARTLS_ERR_BAD_ARG; }
-    if (B > PARTLS_PREDICT_MANY_MAX_B || nr > PARTLS_PREDICT_MANY_MAX_B) {
-        set_error("%s: B = %lld models, nr = %lld ranks: this build supports at most %d of either in one call (call in slices of models)", who,
-                  (long long)B, (long long)nr, PARTLS_PREDICT_MANY_MAX_B);
-        return PARTLS_ERR_UNSUPPORTED;
-    }
-    for (int64_t q = 0; q < nr; ++q)
-        if (ranks[q] < 0 || ranks[q] >= B) { set_error("%s: ranks[%lld] = %lld lies outside [0, B = %lld)", who, (long long)q, (long long)ranks[q], (long long)B); return PARTLS_ERR_BAD_ARG; }
-    for (int64_t b = 0; b < B; ++b) {
-        bool fin = true;
-        for (int64_t m = 0; m < M && fin; ++m) fin = std::isfinite(alpha[m + b * ld_alpha]);
-        for (int64_t k = 0; k < K && fin; ++k) fin = std::isfinite(beta[k + b * ld_beta]);
-        if (!fin) { set_error("%s: model %lld has a NaN / Inf in alpha or beta", who, (long long)b); return PARTLS_ERR_BAD_ARG; }
-    }
+    ManyModelPass mp;
+    mp.who = who; mp.ld_name = "ldC"; mp.slices = "call in slices of models";
+    mp.K = K; mp.B = B; mp.x_f32 = x_f32; mp.out = contrib; mp.ld_out = ldC; mp.nr = nr; mp.ranks = ranks; mp.stats = stats; mp.mean = mean;
+    if ((st = many_model_check(mp, N)) != PARTLS_OK) return st;
+    if ((st = check_models(who, alpha, ld_alpha, beta, ld_beta, nullptr, M, K, B, /*many=*/true)) != PARTLS_OK) return st;
     // the group lists of P, and the models as predict_weights forms its terms, blocked by chunk: hw = [chunk][list entry][j], zero where
     // a chunk runs past B
     std::vector<int> lists((size_t)K + 1, 0);
@@ -177,85 +152,35 @@ static partls_status contrib_common(partls_ctx *c, const void *X, int64_t N, int
     }
 
     PARTLS_HIP_CHECK(hipSetDevice(c->device));
-    PARTLS_HIP_CHECK(c->ctW.ensure(hw.size() * sizeof(double)));
-    PARTLS_HIP_CHECK(hipMemcpyAsync(c->ctW.p, hw.data(), hw.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const double *dW = c->ctW.as<double>();
+    PARTLS_HIP_CHECK(c->mmW.ensure(hw.size() * sizeof(double)));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->mmW.p, hw.data(), hw.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const double *dW = c->mmW.as<double>();
     const int *dPtr = reinterpret_cast<const int *>(dW + wcount), *dIdx = dPtr + K + 1;
-    if (nr > 0) {
-        PARTLS_HIP_CHECK(c->pmRanks.ensure((size_t)nr * sizeof(int64_t)));
-        PARTLS_HIP_CHECK(hipMemcpyAsync(c->pmRanks.p, ranks, (size_t)nr * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    }
-    auto run = [&]() -> partls_status {
-        const size_t esz = x_f32 ? sizeof(float) : sizeof(double);
-        const char *dX = static_cast<const char *>(X);
-        int64_t ld = ldX;
-        if (!x_on_device) {
-            PARTLS_HIP_CHECK(c->predX.ensure((size_t)N * M * esz));
-            const partls_status us = upload_matrix(c, c->predX.p, X, N, M, ldX, esz);
-            if (us != PARTLS_OK) return us;
-            dX = c->predX.as<char>(); ld = N;
-        }
-        const int64_t budget = c->knobs.contrib_bytes > 0 ? (int64_t)c->knobs.contrib_bytes : (int64_t)PARTLS_PREDICT_MANY_BYTES;
-        const int64_t rmax = contrib_rows_per_chunk(N, K, B, nr, budget), bmax = (rmax + 255) / 256;
-        const bool direct = x_on_device && contrib;              // the caller's device contrib is the intermediate
-        if (!direct) PARTLS_HIP_CHECK(c->ctC.ensure((size_t)rmax * cols * sizeof(double)));
-        if (!x_on_device && nr > 0) PARTLS_HIP_CHECK(c->ctStats.ensure((size_t)rmax * K * nr * sizeof(double)));
-        if (!x_on_device && mean) PARTLS_HIP_CHECK(c->ctMean.ensure((size_t)rmax * K * sizeof(double)));
-        double *dRun = nullptr, *dPart = nullptr;
-        if (sums) {
-            PARTLS_HIP_CHECK(c->ctSums.ensure((size_t)(3 * cols * (1 + bmax)) * sizeof(double)));
-            dRun = c->ctSums.as<double>(); dPart = dRun + 3 * cols;
-            PARTLS_HIP_CHECK(hipMemsetAsync(dRun, 0, (size_t)(3 * cols) * sizeof(double), c->stream));     // all bits zero: +0.0
-        }
-        for (int64_t r0 = 0; r0 < N; r0 += rmax) {
-            const int64_t rows = N - r0 < rmax ? N - r0 : rmax, blocks = (rows + 255) / 256;
-            double *Cc = direct ? contrib + r0 : c->ctC.as<double>();
-            const int64_t ldc = direct ? ldC : rows;
-            const dim3 grid((unsigned)blocks, (unsigned)nch, contrib_group_split(c, blocks, nch, K));
-            if (x_f32) hipLaunchKernelGGL(contrib_kernel<float>, grid, dim3(256), 0, c->stream, reinterpret_cast<const float *>(dX) + r0, rows, ld, (int)K, dPtr, dIdx, dW, B, Cc, ldc);
-            else hipLaunchKernelGGL(contrib_kernel<double>, grid, dim3(256), 0, c->stream, reinterpret_cast<const double *>(dX) + r0, rows, ld, (int)K, dPtr, dIdx, dW, B, Cc, ldc);
-            PARTLS_HIP_CHECK(hipGetLastError());
-            if (contrib && !direct)
-                PARTLS_HIP_CHECK(hipMemcpy2DAsync(contrib + r0, (size_t)ldC * sizeof(double), Cc, (size_t)rows * sizeof(double), (size_t)rows * sizeof(double),
-                                                  (size_t)cols, hipMemcpyDeviceToHost, c->stream));
-            // the (row, group) pairs of the chunk as the rows of a matrix with B columns, ld = ldc K: one matrix of rows K rows when the
-            // groups follow each other without a gap on both sides (ldc == rows, and so for the output), else one of `rows` rows per group
-            if (nr > 0) {
-                double *S = x_on_device ? stats + r0 : c->ctStats.as<double>();
-                const int64_t lds = x_on_device ? N : rows;
-                if (ldc == rows && lds == rows) PARTLS_HIP_CHECK(launch_row_select(Cc, rows * K, ldc * K, B, c->pmRanks.as<int64_t>(), nr, S, lds * K, c->stream));
-                else
-                    for (int64_t k = 0; k < K; ++k)
-                        PARTLS_HIP_CHECK(launch_row_select(Cc + ldc * k, rows, ldc * K, B, c->pmRanks.as<int64_t>(), nr, S + lds * k, lds * K, c->stream));
-                if (!x_on_device)
-                    PARTLS_HIP_CHECK(hipMemcpy2DAsync(stats + r0, (size_t)N * sizeof(double), S, (size_t)rows * sizeof(double), (size_t)rows * sizeof(double),
-                                                      (size_t)(K * nr), hipMemcpyDeviceToHost, c->stream));
-            }
-            if (mean) {
-                double *mu = x_on_device ? mean + r0 : c->ctMean.as<double>();
-                const int64_t ldm = x_on_device ? N : rows;
-                if (ldc == rows && ldm == rows) PARTLS_HIP_CHECK(launch_row_mean(Cc, rows * K, ldc * K, B, mu, c->stream));
-                else
-                    for (int64_t k = 0; k < K; ++k) PARTLS_HIP_CHECK(launch_row_mean(Cc + ldc * k, rows, ldc * K, B, mu + ldm * k, c->stream));
-                if (!x_on_device)
-                    PARTLS_HIP_CHECK(hipMemcpy2DAsync(mean + r0, (size_t)N * sizeof(double), mu, (size_t)rows * sizeof(double), (size_t)rows * sizeof(double),
-                                                      (size_t)K, hipMemcpyDeviceToHost, c->stream));
-            }
-            if (sums) {
-                const unsigned gy = (unsigned)(cols < 1024 ? cols : 1024);
-                hipLaunchKernelGGL(contrib_sums_kernel, dim3((unsigned)blocks, gy), dim3(256), 0, c->stream, Cc, rows, ldc, cols, dPart);
-                PARTLS_HIP_CHECK(hipGetLastError());
-                hipLaunchKernelGGL(contrib_sums_fold_kernel, dim3((unsigned)((3 * cols + 255) / 256)), dim3(256), 0, c->stream, dPart, blocks, cols, dRun);
-                PARTLS_HIP_CHECK(hipGetLastError());
-            }
-        }
-        if (sums) PARTLS_HIP_CHECK(hipMemcpyAsync(sums, dRun, (size_t)(3 * cols) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
-        return PARTLS_OK;
+    const int64_t budget = c->knobs.contrib_bytes > 0 ? (int64_t)c->knobs.contrib_bytes : (int64_t)PARTLS_PREDICT_MANY_BYTES;
+    mp.rmax = contrib_rows_per_chunk(N, K, B, nr, budget);
+    mp.produce = [&](const void *dX, int64_t ld, int64_t r0, int64_t rows, double *Cc, int64_t ldc) {
+        const int64_t blocks = (rows + 255) / 256;
+        const dim3 grid((unsigned)blocks, (unsigned)nch, contrib_group_split(c, blocks, nch, K));
+        if (x_f32) hipLaunchKernelGGL(contrib_kernel<float>, grid, dim3(256), 0, c->stream, static_cast<const float *>(dX) + r0, rows, ld, (int)K, dPtr, dIdx, dW, B, Cc, ldc);
+        else hipLaunchKernelGGL(contrib_kernel<double>, grid, dim3(256), 0, c->stream, static_cast<const double *>(dX) + r0, rows, ld, (int)K, dPtr, dIdx, dW, B, Cc, ldc);
+        return hipGetLastError();
     };
-    st = run();
-    if (!x_on_device) { c->predX.release(); c->ctC.release(); c->ctStats.release(); c->ctMean.release(); }    // a prediction set is not retained
-    return st;
+    if (sums) {
+        const int64_t bmax = (mp.rmax + 255) / 256;
+        PARTLS_HIP_CHECK(c->mmSums.ensure((size_t)(3 * cols * (1 + bmax)) * sizeof(double)));
+        double *dRun = c->mmSums.as<double>(), *dPart = dRun + 3 * cols;
+        PARTLS_HIP_CHECK(hipMemsetAsync(dRun, 0, (size_t)(3 * cols) * sizeof(double), c->stream));     // all bits zero: +0.0
+        mp.chunk_done = [=](const double *Cc, int64_t rows, int64_t ldc, bool last) -> partls_status {
+            const int64_t blocks = (rows + 255) / 256;
+            const unsigned gy = (unsigned)(cols < 1024 ? cols : 1024);
+            hipLaunchKernelGGL(contrib_sums_kernel, dim3((unsigned)blocks, gy), dim3(256), 0, c->stream, Cc, rows, ldc, cols, dPart);
+            PARTLS_HIP_CHECK(hipGetLastError());
+            PARTLS_HIP_CHECK(launch_fold_partials(dPart, blocks, 3 * cols, dRun, c->stream));
+            if (last) PARTLS_HIP_CHECK(hipMemcpyAsync(sums, dRun, (size_t)(3 * cols) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            return PARTLS_OK;
+        };
+    }
+    return many_model_pass(c, mp, X, N, M, ldX, x_on_device);
 }
 
 }  // namespace partls

@@ -17,17 +17,6 @@ namespace partls {
 namespace {
 constexpr int CSR_WPB = 4;                              // waves per workgroup of the row-walking and the Gram kernels (256 threads)
 
-__device__ __forceinline__ double csr_block_sum_256(double *red, double v)
-{
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 __device__ __forceinline__ bool csr_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN and Inf
 }  // namespace
 
@@ -150,19 +139,15 @@ template <bool WT>
 __global__ __launch_bounds__(256) void csr_corner_kernel(const double *__restrict__ y, const double *__restrict__ wt, int64_t N,
                                                          double *__restrict__ corner)
 {
-    __shared__ double red[256];
-    double s1 = 0.0, sy = 0.0, syy = 0.0;
+    __shared__ double red[3][256];
+    double v[3] = {0.0, 0.0, 0.0};                      // sums of w, w y, w y^2
     for (int64_t i = threadIdx.x; i < N; i += 256) {
         const double yi = y[i];
-        if constexpr (WT) { const double wi = wt[i], wy = wi * yi; s1 += wi; sy += wy; syy = fma(wy, yi, syy); }
-        else { s1 += 1.0; sy += yi; syy = fma(yi, yi, syy); }
+        if constexpr (WT) { const double wi = wt[i], wy = wi * yi; v[0] += wi; v[1] += wy; v[2] = fma(wy, yi, v[2]); }
+        else { v[0] += 1.0; v[1] += yi; v[2] = fma(yi, yi, v[2]); }
     }
-    s1 = csr_block_sum_256(red, s1);
-    __syncthreads();
-    sy = csr_block_sum_256(red, sy);
-    __syncthreads();
-    syy = csr_block_sum_256(red, syy);
-    if (threadIdx.x == 0) { corner[0] = s1; corner[1] = sy; corner[2] = syy; }
+    block_tree_256<3>(red, v);
+    if (threadIdx.x == 0) { corner[0] = v[0]; corner[1] = v[1]; corner[2] = v[2]; }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -277,7 +262,7 @@ __global__ __launch_bounds__(256) void csr_residual_kernel(const int64_t *__rest
         }
     }
     __shared__ double red[256];
-    acc2 = csr_block_sum_256(red, acc2);
+    acc2 = block_sum_256(red, acc2);
     if (threadIdx.x == 0 && partial) partial[blockIdx.x] = acc2;
 }
 
@@ -320,7 +305,7 @@ __global__ __launch_bounds__(256) void csr_xtr_kernel(const int64_t *__restrict_
         }
     }
     __shared__ double red[256];
-    const double g = csr_block_sum_256(red, acc);
+    const double g = block_sum_256(red, acc);
     if (threadIdx.x == 0) gpart[(size_t)r * (M + 1) + m] = g;
 }
 

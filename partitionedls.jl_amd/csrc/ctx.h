@@ -100,6 +100,13 @@ struct UploadStaging : NoCopy {
     }
 };
 
+// the N events of one call (timing its phases): created together, and whatever was created is destroyed on every way out
+template <int N> struct Events : NoCopy {
+    hipEvent_t e[N] = {};
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    hipError_t create() { for (hipEvent_t &x : e) { const hipError_t r = hipEventCreate(&x); if (r != hipSuccess) { x = nullptr; return r; } } return hipSuccess; }
+};
+
 }  // namespace partls
 
 // Tuning / diagnostic knobs, read from the environment ONCE at partls_create (never on the per-call path).
@@ -283,18 +290,15 @@ struct partls_ctx {
     // weight_prep_kernel and of oob_sse_kernel and their host copies; rsWv, the models of a chunk of problems as weight vectors
     partls::DevBuf rsW, rsS, rsPart, rsWv;
     partls::PinnedDoubles rsHost;
-    // partls_predict_many (predict_many.hip): pmW, the models of a call as chunk-blocked weight vectors and their
-    // intercepts; pmRanks, the ranks wanted; pmY, the N x B intermediate of a row chunk (at most PARTLS_PREDICT_MANY_BYTES); pmStats /
-    // pmMean, the device images of a host caller's stats (one row chunk) and mean
-    partls::DevBuf pmW, pmRanks, pmY, pmStats, pmMean;
-    // partls_contributions (contrib.hip) shares pmRanks and adds: ctW, the models of a call as chunk-blocked weights of
-    // the group lists, followed by the lists themselves (gptr[K + 1], feature indices; int32); ctC, the rows x K x B intermediate of a
-    // row chunk; ctStats / ctMean, the device images of a host caller's stats and mean for one row chunk; ctSums, the 3 K B running
-    // sums carried across the row chunks, followed by the per-block partial sums of one chunk
-    partls::DevBuf ctW, ctC, ctStats, ctMean, ctSums;
+    // partls_predict_many and partls_contributions (many_model_pass, predict_many.hip): mmW, the models of a call
+    // as the entry blocks them by chunk (predict_many: weight vectors and intercepts; contributions: weights of the group lists, then the
+    // lists themselves, gptr[K + 1] and feature indices, int32); mmRanks, the ranks wanted; mmY, the rows x K x B intermediate of a row
+    // chunk (K = 1: predictions); mmStats / mmMean, the device images of a host caller's stats and mean for one row chunk; mmSums
+    // (contributions), the 3 K B running sums carried across the row chunks, followed by the per-block partial sums of one chunk
+    partls::DevBuf mmW, mmRanks, mmY, mmStats, mmMean, mmSums;
     // partls_diagnostics (diag.hip): dgT, the packed tiles of T = L^-1, the index list of the active columns and the
     // prediction weights of the model; dgRow, yhat and the squared norms ||T x_iA||^2 of the rows, followed by the device images of a host
-    // caller's per-row outputs; dgSums, the four running sums and sigma2, followed by the per-block partial sums.  dg_ms: kernel /
+    // caller's per-row outputs; dgSums, the four running sums, followed by the per-block partial sums.  dg_ms: kernel /
     // factorisation / whole call of the last call (partls_get_diagnostics_timing)
     partls::DevBuf dgT, dgRow, dgSums;
     double dg_ms[3] = {0.0, 0.0, 0.0};
@@ -589,5 +593,33 @@ partls_status predict_weights(const int64_t *P, int64_t M, int64_t K, int64_t ld
 hipError_t launch_row_select(const double *Y, int64_t rows, int64_t ldY, int64_t B, const int64_t *ranks, int64_t nr, double *S, int64_t ldS,
                              hipStream_t stream);
 hipError_t launch_row_mean(const double *Y, int64_t rows, int64_t ldY, int64_t B, double *mean, hipStream_t stream);
+// run[q] += part[blk stride + q] for blk ascending, q < stride: the ONE device fold of per-block partial sums (the callers zero run)
+hipError_t launch_fold_partials(const double *part, int64_t blocks, int64_t stride, double *run, hipStream_t stream);
+// Shared by the post-fit entries (api.hip).  check_prepared_single: c is not NULL, not a context of a partls_multi and prepared (else
+// `unprepared`, which differs between the two robust entries; partls_diagnostics asks in another order and keeps its own lines).  check_models: alpha, beta and (unless NULL) t of B models are finite, else
+// PARTLS_ERR_BAD_ARG naming the first that is not ("model b" when the entry takes many).  stage_dense_x: a host X goes up into
+// c->predX (packed, ld N); *dX / *ld say where the pass reads X.
+partls_status check_prepared_single(const partls_ctx *c, const char *who, partls_status unprepared);
+partls_status check_models(const char *who, const double *alpha, int64_t ld_alpha, const double *beta, int64_t ld_beta, const double *t,
+                           int64_t M, int64_t K, int64_t B, bool many);
+partls_status stage_dense_x(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, int x_on_device, bool x_f32, const void **dX,
+                            int64_t *ld);
+// One pass of B models over X in row chunks (predict_many.hip), shared by partls_predict_many (K = 1) and partls_contributions (a row
+// of X is K rows of the intermediate).  The entry blocks its models into c->mmW and says how a chunk is produced; many_model_check
+// holds the rules of nr / stats / ranks and the caps; many_model_pass stages X, walks the chunks (a device caller's `out` is the
+// intermediate itself), selects, averages, copies back and releases.
+struct ManyModelPass {
+    const char *who, *ld_name, *slices;            // the entry, its name for ld_out, its advice at the cap
+    int64_t K = 1, B = 0, rmax = 0, ld_out = 0, nr = 0;   // rmax: rows per chunk, by the entry's own rule
+    bool x_f32 = false;
+    const int64_t *ranks = nullptr;
+    double *out = nullptr, *stats = nullptr, *mean = nullptr;   // optional: N x (K B), ld_out (yhat / contrib); N x (K nr) and N x K, ld N
+    // rows [r0, r0 + rows) of X (dX, ld: the staged or the caller's matrix, not yet offset) into Y (ld ldy): the entry's kernel
+    std::function<hipError_t(const void *dX, int64_t ld, int64_t r0, int64_t rows, double *Y, int64_t ldy)> produce;
+    // optional, after a chunk's statistics are queued (partls_contributions: its sums); last: no chunk follows
+    std::function<partls_status(const double *Y, int64_t rows, int64_t ldy, bool last)> chunk_done;
+};
+partls_status many_model_check(const ManyModelPass &mp, int64_t N);
+partls_status many_model_pass(partls_ctx *c, const ManyModelPass &mp, const void *X, int64_t N, int64_t M, int64_t ldX, int x_on_device);
 
 }  // namespace partls

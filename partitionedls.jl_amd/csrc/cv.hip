@@ -273,9 +273,9 @@ partls_status batch_sweep(partls_ctx *c, const ProblemBatch &pb)
     if (st != PARTLS_OK) return st;
     const bool want_sol = (sweep_reg_small(T) || sweep_reg_exports(T)) && !c->knobs.no_export;
     PARTLS_HIP_CHECK(c->scratch.ensure(64 * sizeof(double)));      // the register kernels' share (ensure_sweep_scratch goes by W, the prepared context)
-    hipEvent_t ev[4];
-    for (int i = 0; i < 4; ++i) PARTLS_HIP_CHECK(hipEventCreate(&ev[i]));
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; ++i) (void)hipEventDestroy(e[i]); } } evg{ev};
+    Events<4> evs;
+    PARTLS_HIP_CHECK(evs.create());
+    hipEvent_t *ev = evs.e;
     for (int64_t q0 = 0; q0 < B; q0 += bc_max) {
         const int bc = (int)std::min<int64_t>(bc_max, B - q0);
         int64_t chain_len = 0;

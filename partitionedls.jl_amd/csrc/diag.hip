@@ -124,51 +124,26 @@ __device__ __forceinline__ RowTerms row_terms(const double *__restrict__ y, cons
 __global__ __launch_bounds__(256) void diag_sums_kernel(const double *__restrict__ y, const double *__restrict__ yhat, const double *__restrict__ w,
                                                         const double *__restrict__ q, int64_t N, double *__restrict__ part)
 {
-    __shared__ double red[256];
+    __shared__ double red[4][256];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
     if (i < N) {
         const RowTerms r = row_terms(y, yhat, w, q, i);
-        v0 = r.h; v1 = (r.w * r.e) * r.e; v2 = (r.w * r.loo) * r.loo; v3 = r.w > 0.0 ? 1.0 : 0.0;
+        v[0] = r.h; v[1] = (r.w * r.e) * r.e; v[2] = (r.w * r.loo) * r.loo; v[3] = r.w > 0.0 ? 1.0 : 0.0;
     }
-    const double s0 = block_sum_256(red, v0);
-    __syncthreads();                                     // every thread has read red[0] before the next sum overwrites it
-    const double s1 = block_sum_256(red, v1);
-    __syncthreads();
-    const double s2 = block_sum_256(red, v2);
-    __syncthreads();
-    const double s3 = block_sum_256(red, v3);
+    block_tree_256<4>(red, v);
     if (threadIdx.x == 0) {
         double *p = part + (int64_t)blockIdx.x * 4;
-        p[0] = s0; p[1] = s1; p[2] = s2; p[3] = s3;
+        p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; p[3] = v[3];
     }
 }
 
-// ... and the block sums added in ascending block order from 0.0, one thread per sum (eight loads in flight): run[0 .. 3], then
-// run[4] = sigma2 = rss / (n+ - dof), NaN when n+ - dof <= 0
-__global__ __launch_bounds__(64) void diag_fold_kernel(const double *__restrict__ part, int64_t blocks, double *__restrict__ run)
+// ... launch_fold_partials adds them in ascending block order from 0.0 into run[0 .. 3]; sigma2 = rss / (n+ - dof), NaN when n+ - dof <= 0,
+// is formed from these where it is used, on the device and on the host: the same two operations on the same doubles
+__host__ __device__ inline double diag_sigma2(const double *run)
 {
-    __shared__ double tot[4];
-    if (threadIdx.x < 4) {
-        const double *p = part + threadIdx.x;
-        double s = 0.0;
-        int64_t blk = 0;
-        for (; blk + 8 <= blocks; blk += 8) {
-            double v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = p[(blk + k) * 4];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += v[k];
-        }
-        for (; blk < blocks; ++blk) s += p[blk * 4];
-        run[threadIdx.x] = s;
-        tot[threadIdx.x] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double df = tot[3] - tot[0];
-        run[4] = df > 0.0 ? tot[1] / df : __builtin_nan("");
-    }
+    const double df = run[3] - run[0];
+    return df > 0.0 ? run[1] / df : __builtin_nan("");
 }
 
 // (c) the one elementwise kernel: every per-row output that is wanted (a NULL pointer: not wanted)
@@ -181,7 +156,7 @@ __global__ __launch_bounds__(256) void diag_rows_kernel(const double *__restrict
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
     const RowTerms r = row_terms(y, yhat, w, q, i);
-    const double dof = run[0], sigma2 = run[4];
+    const double dof = run[0], sigma2 = diag_sigma2(run);
     const double om = 1.0 - r.h;
     const double st = (sqrt(r.w) * r.e) / sqrt(sigma2 * om);
     if (lev) lev[i] = r.h;
@@ -210,12 +185,6 @@ static hipError_t launch_leverage(const XT *X, int64_t N, int64_t ldX, const dou
     }
     return hipGetLastError();
 }
-
-// the two events around the leverage kernel: created per call, destroyed on every way out
-struct EventPair : NoCopy {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
 
 // T = L^-1 for the lower triangular L (both row-major, leading dimension p; T's upper triangle is left 0): row i is
 // -(sum_{k < i} L[i][k] T[k][:]) / L[i][i] with 1 / L[i][i] on the diagonal, the sum taken in ascending k over contiguous rows
@@ -320,14 +289,12 @@ static partls_status diag_common(partls_ctx *c, const double *alpha, const doubl
         return PARTLS_ERR_BAD_ARG;
     }
     const int64_t N = c->N, M = c->M, K = c->K;
-    bool fin = std::isfinite(t);
-    for (int64_t m = 0; m < M && fin; ++m) fin = std::isfinite(alpha[m]);
-    for (int64_t k = 0; k < K && fin; ++k) fin = std::isfinite(beta[k]);
-    if (!fin) { set_error("%s: the model has a NaN / Inf in alpha, beta or t", who); return PARTLS_ERR_BAD_ARG; }
+    partls_status st = check_models(who, alpha, M, beta, K, &t, M, K, 1, /*many=*/false);
+    if (st != PARTLS_OK) return st;
 
     // the weights the prediction applies (predict_weights: yhat is partls_predict's) and the model weights v that define the support
     std::vector<double> wp((size_t)M, 0.0), v((size_t)M + 1, 0.0);
-    partls_status st = predict_weights(c->P.data(), M, K, M, alpha, beta, wp.data());
+    st = predict_weights(c->P.data(), M, K, M, alpha, beta, wp.data());
     if (st != PARTLS_OK) return st;
     std::vector<int> A;
     for (int64_t m = 0; m < M; ++m) {
@@ -383,31 +350,30 @@ static partls_status diag_common(partls_ctx *c, const double *alpha, const doubl
     const int64_t blocks = (N + 255) / 256;
     PARTLS_HIP_CHECK(c->dgT.ensure(up.size() * sizeof(double)));
     PARTLS_HIP_CHECK(c->dgRow.ensure((size_t)N * (host_rows ? 7 : 2) * sizeof(double)));
-    PARTLS_HIP_CHECK(c->dgSums.ensure((size_t)(8 + 4 * blocks) * sizeof(double)));
-    EventPair ev;
-    PARTLS_HIP_CHECK(hipEventCreate(&ev.a));
-    PARTLS_HIP_CHECK(hipEventCreate(&ev.b));
+    PARTLS_HIP_CHECK(c->dgSums.ensure((size_t)(4 + 4 * blocks) * sizeof(double)));
+    Events<2> ev;                                        // around the leverage kernel
+    PARTLS_HIP_CHECK(ev.create());
     PARTLS_HIP_CHECK(hipMemcpyAsync(c->dgT.p, up.data(), up.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const double *dT = c->dgT.as<double>(), *dWp = dT + tdoubles;
     const int *dIdx = reinterpret_cast<const int *>(dWp + M);
-    double *dYh = c->dgRow.as<double>(), *dQ = dYh + N, *dRun = c->dgSums.as<double>(), *dPart = dRun + 8;
+    double *dYh = c->dgRow.as<double>(), *dQ = dYh + N, *dRun = c->dgSums.as<double>(), *dPart = dRun + 4;
     double *dev_out[5];
     for (int o = 0; o < 5; ++o) dev_out[o] = !rows_out[o] ? nullptr : (host_rows ? dQ + (int64_t)(o + 1) * N : rows_out[o]);
     PARTLS_HIP_CHECK(launch_residual(c->dX, N, M, c->ldX, nullptr, dWp, t, nullptr, 1024, dYh, c->stream, nullptr, c->x_f32));
-    PARTLS_HIP_CHECK(hipEventRecord(ev.a, c->stream));
+    PARTLS_HIP_CHECK(hipEventRecord(ev.e[0], c->stream));
     if (c->x_f32) PARTLS_HIP_CHECK(launch_leverage(static_cast<const float *>(c->dX), N, c->ldX, dT, dIdx, nt, dQ, c->stream));
     else PARTLS_HIP_CHECK(launch_leverage(static_cast<const double *>(c->dX), N, c->ldX, dT, dIdx, nt, dQ, c->stream));
-    PARTLS_HIP_CHECK(hipEventRecord(ev.b, c->stream));
+    PARTLS_HIP_CHECK(hipEventRecord(ev.e[1], c->stream));
+    PARTLS_HIP_CHECK(hipMemsetAsync(dRun, 0, 4 * sizeof(double), c->stream));                 // all bits zero: +0.0
     hipLaunchKernelGGL(diag_sums_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, c->dy, dYh, c->dw, dQ, N, dPart);
     PARTLS_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(diag_fold_kernel, dim3(1), dim3(64), 0, c->stream, dPart, blocks, dRun);
-    PARTLS_HIP_CHECK(hipGetLastError());
+    PARTLS_HIP_CHECK(launch_fold_partials(dPart, blocks, 4, dRun, c->stream));
     if (leverage || loo || studentized || cooks || residual) {
         hipLaunchKernelGGL(diag_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, c->dy, dYh, c->dw, dQ, N, dRun, dev_out[0],
                            dev_out[1], dev_out[2], dev_out[3], dev_out[4]);
         PARTLS_HIP_CHECK(hipGetLastError());
     }
-    double run[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    double run[4] = {0.0, 0.0, 0.0, 0.0};
     PARTLS_HIP_CHECK(hipMemcpyAsync(run, dRun, sizeof(run), hipMemcpyDeviceToHost, c->stream));
 
     // meanwhile, on the host: the standard errors before their factor sigma2, and the stationarity of the model on its support
@@ -442,8 +408,8 @@ static partls_status diag_common(partls_ctx *c, const double *alpha, const doubl
         for (int o = 0; o < 5; ++o)
             if (rows_out[o]) PARTLS_HIP_CHECK(hipMemcpy(rows_out[o], dev_out[o], (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
     float kms = 0.f;
-    if (hipEventElapsedTime(&kms, ev.a, ev.b) != hipSuccess) kms = 0.f;
-    const double dof = run[0], rss = run[1], press = run[2], nplus = run[3], sigma2 = run[4];
+    if (hipEventElapsedTime(&kms, ev.e[0], ev.e[1]) != hipSuccess) kms = 0.f;
+    const double dof = run[0], rss = run[1], press = run[2], nplus = run[3], sigma2 = diag_sigma2(run);
     if (summary) {
         const double tss = yy - sy * sy / sw;
         summary[PARTLS_DIAG_NPLUS] = nplus; summary[PARTLS_DIAG_P] = (double)p; summary[PARTLS_DIAG_DOF] = dof;
@@ -480,10 +446,11 @@ try {
 PARTLS_ABI_GUARD
 
 partls_status partls_get_diagnostics_timing(const partls_ctx *c, double *kernel_ms, double *factor_ms, double *call_ms)
-{
+try {
     if (!c || !kernel_ms || !factor_ms || !call_ms) { set_error("partls_get_diagnostics_timing: bad argument"); return PARTLS_ERR_BAD_ARG; }
     *kernel_ms = c->dg_ms[0]; *factor_ms = c->dg_ms[1]; *call_ms = c->dg_ms[2];
     return PARTLS_OK;
 }
+PARTLS_ABI_GUARD
 
 }

@@ -628,21 +628,11 @@ __global__ __launch_bounds__(256) void weight_prep_kernel(const double *__restri
         sum += fin ? v : 0.0;
         s[i] = (fin && v >= 0.0) ? sqrt(v) : 0.0;
     }
-    // the two flags: a max tree, written out (block_sum_256 adds); the two sums each have a row of red to themselves
-    red[0][threadIdx.x] = neg; red[1][threadIdx.x] = bad;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) {
-            red[0][threadIdx.x] = fmax(red[0][threadIdx.x], red[0][threadIdx.x + h]);
-            red[1][threadIdx.x] = fmax(red[1][threadIdx.x], red[1][threadIdx.x + h]);
-        }
-        __syncthreads();
-    }
-    sum = block_sum_256(red[2], sum);
-    zero = block_sum_256(red[3], zero);
+    double v[4] = {neg, bad, sum, zero};                // the two flags by max, the two sums by +: one tree
+    block_tree_256<4, 0x3u>(red, v);
     if (threadIdx.x == 0) {
         double *p = part + 4 * (b * gridDim.x + blockIdx.x);
-        p[0] = red[0][0]; p[1] = red[1][0]; p[2] = sum; p[3] = zero;
+        p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; p[3] = v[3];
     }
 }
 

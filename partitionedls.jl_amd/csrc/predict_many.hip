@@ -1,5 +1,6 @@
 // predict_many.hip — partls_predict_many(_f32): the predictions of B models in one pass over X per PARTLS_PREDICT_MANY_CHUNK models, and
-// per-row order statistics and mean of the B predictions.  Kernels first, then the host driver and the two entries.
+// per-row order statistics and mean of the B predictions.  Kernels first, then the host driver of a many-model
+// pass, which partls_contributions (contrib.hip) shares with the statistics kernels and the fold of partial sums, and the two entries.
 #include "ctx.h"
 #include <cmath>
 #include <vector>
@@ -118,6 +119,110 @@ hipError_t launch_row_mean(const double *Y, int64_t rows, int64_t ldY, int64_t B
     return hipGetLastError();
 }
 
+// run[q] += part[blk stride + q], blk ascending: one thread per q, eight loads in flight, the adds in block order
+__global__ __launch_bounds__(256) void fold_partials_kernel(const double *__restrict__ part, int64_t blocks, int64_t stride, double *__restrict__ run)
+{
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= stride) return;
+    const double *p = part + q;
+    double s = run[q];
+    int64_t blk = 0;
+    for (; blk + 8 <= blocks; blk += 8) {
+        double v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = p[(blk + k) * stride];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += v[k];
+    }
+    for (; blk < blocks; ++blk) s += p[blk * stride];
+    run[q] = s;
+}
+
+hipError_t launch_fold_partials(const double *part, int64_t blocks, int64_t stride, double *run, hipStream_t stream)
+{
+    hipLaunchKernelGGL(fold_partials_kernel, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, stream, part, blocks, stride, run);
+    return hipGetLastError();
+}
+
+// (c) the host driver of a many-model pass (ManyModelPass, ctx.h)
+partls_status many_model_check(const ManyModelPass &mp, int64_t N)
+{
+    const char *who = mp.who; const int64_t B = mp.B, nr = mp.nr;
+    if (nr < 0 || (nr == 0) != (mp.stats == nullptr) || (nr > 0 && !mp.ranks)) {
+        set_error("%s: stats must be NULL exactly when nr == 0, and ranks given when it is not (nr = %lld)", who, (long long)nr);
+        return PARTLS_ERR_BAD_ARG;
+    }
+    if (mp.out && mp.ld_out < N) { set_error("%s: %s = %lld is smaller than N = %lld", who, mp.ld_name, (long long)mp.ld_out, (long long)N); return PARTLS_ERR_BAD_ARG; }
+    if (B > PARTLS_PREDICT_MANY_MAX_B || nr > PARTLS_PREDICT_MANY_MAX_B) {
+        set_error("%s: B = %lld models, nr = %lld ranks: this build supports at most %d of either in one call (%s)", who, (long long)B,
+                  (long long)nr, PARTLS_PREDICT_MANY_MAX_B, mp.slices);
+        return PARTLS_ERR_UNSUPPORTED;
+    }
+    for (int64_t q = 0; q < nr; ++q)
+        if (mp.ranks[q] < 0 || mp.ranks[q] >= B) { set_error("%s: ranks[%lld] = %lld lies outside [0, B = %lld)", who, (long long)q, (long long)mp.ranks[q], (long long)B); return PARTLS_ERR_BAD_ARG; }
+    return PARTLS_OK;
+}
+
+partls_status many_model_pass(partls_ctx *c, const ManyModelPass &mp, const void *X, int64_t N, int64_t M, int64_t ldX, int x_on_device)
+{
+    const int64_t K = mp.K, B = mp.B, nr = mp.nr, rmax = mp.rmax;
+    // a chunk's rows of ncol columns to the host; one column is contiguous on both sides and goes as the plain copy predict_many's mean always was
+    auto to_host = [&](double *dst, int64_t ld_dst, const double *src, int64_t rows, int64_t ncol) {
+        if (ncol == 1) return hipMemcpyAsync(dst, src, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        return hipMemcpy2DAsync(dst, (size_t)ld_dst * sizeof(double), src, (size_t)rows * sizeof(double), (size_t)rows * sizeof(double), (size_t)ncol,
+                                hipMemcpyDeviceToHost, c->stream);
+    };
+    auto run = [&]() -> partls_status {
+        if (nr > 0) {
+            PARTLS_HIP_CHECK(c->mmRanks.ensure((size_t)nr * sizeof(int64_t)));
+            PARTLS_HIP_CHECK(hipMemcpyAsync(c->mmRanks.p, mp.ranks, (size_t)nr * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        }
+        const void *dX = nullptr; int64_t ld = 0;
+        const partls_status us = stage_dense_x(c, X, N, M, ldX, x_on_device, mp.x_f32, &dX, &ld);
+        if (us != PARTLS_OK) return us;
+        const bool direct = x_on_device && mp.out;               // the caller's device output is the intermediate
+        if (!direct) PARTLS_HIP_CHECK(c->mmY.ensure((size_t)rmax * K * B * sizeof(double)));
+        if (!x_on_device && nr > 0) PARTLS_HIP_CHECK(c->mmStats.ensure((size_t)rmax * K * nr * sizeof(double)));
+        if (!x_on_device && mp.mean) PARTLS_HIP_CHECK(c->mmMean.ensure((size_t)rmax * K * sizeof(double)));
+        const int64_t *dRanks = c->mmRanks.as<int64_t>();
+        for (int64_t r0 = 0; r0 < N; r0 += rmax) {
+            const int64_t rows = N - r0 < rmax ? N - r0 : rmax;
+            double *Y = direct ? mp.out + r0 : c->mmY.as<double>();
+            const int64_t ldy = direct ? mp.ld_out : rows;
+            PARTLS_HIP_CHECK(mp.produce(dX, ld, r0, rows, Y, ldy));
+            if (mp.out && !direct) PARTLS_HIP_CHECK(to_host(mp.out + r0, mp.ld_out, Y, rows, K * B));
+            // the (row, group) pairs of the chunk as the rows of a matrix with B columns, ld = ldy K: one matrix of rows K rows when the
+            // groups follow each other without a gap on both sides (ldy == rows, and so for the output), else one of `rows` rows per group
+            if (nr > 0) {
+                double *S = x_on_device ? mp.stats + r0 : c->mmStats.as<double>();
+                const int64_t lds = x_on_device ? N : rows;
+                if (ldy == rows && lds == rows) PARTLS_HIP_CHECK(launch_row_select(Y, rows * K, ldy * K, B, dRanks, nr, S, lds * K, c->stream));
+                else
+                    for (int64_t k = 0; k < K; ++k)
+                        PARTLS_HIP_CHECK(launch_row_select(Y + ldy * k, rows, ldy * K, B, dRanks, nr, S + lds * k, lds * K, c->stream));
+                if (!x_on_device) PARTLS_HIP_CHECK(to_host(mp.stats + r0, N, S, rows, K * nr));
+            }
+            if (mp.mean) {
+                double *mu = x_on_device ? mp.mean + r0 : c->mmMean.as<double>();
+                const int64_t ldm = x_on_device ? N : rows;
+                if (ldy == rows && ldm == rows) PARTLS_HIP_CHECK(launch_row_mean(Y, rows * K, ldy * K, B, mu, c->stream));
+                else
+                    for (int64_t k = 0; k < K; ++k) PARTLS_HIP_CHECK(launch_row_mean(Y + ldy * k, rows, ldy * K, B, mu + ldm * k, c->stream));
+                if (!x_on_device) PARTLS_HIP_CHECK(to_host(mp.mean + r0, N, mu, rows, K));
+            }
+            if (mp.chunk_done) {
+                const partls_status cs = mp.chunk_done(Y, rows, ldy, r0 + rows >= N);
+                if (cs != PARTLS_OK) return cs;
+            }
+        }
+        PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        return PARTLS_OK;
+    };
+    const partls_status st = run();
+    if (!x_on_device) { c->predX.release(); c->mmY.release(); c->mmStats.release(); c->mmMean.release(); }    // a prediction set is not retained
+    return st;
+}
+
 // rows of a chunk: the N x B intermediate (and a host caller's device image of stats) within PARTLS_PREDICT_MANY_BYTES
 static int64_t rows_per_chunk(int64_t N, int64_t B, int64_t nr)
 {
@@ -136,24 +241,11 @@ static partls_status predict_many_common(partls_ctx *c, const void *X, int64_t N
     if (B < 1) { set_error("%s: need B >= 1 (got %lld)", who, (long long)B); return PARTLS_ERR_BAD_ARG; }
     if (!alpha || !beta || !t) { set_error("%s: alpha, beta or t is NULL", who); return PARTLS_ERR_BAD_ARG; }
     if (!yhat && !stats && !mean) { set_error("%s: no output wanted (yhat, stats and mean are all NULL)", who); return PARTLS_ERR_BAD_ARG; }
-    if (nr < 0 || (nr == 0) != (stats == nullptr) || (nr > 0 && !ranks)) {
-        set_error("%s: stats must be NULL exactly when nr == 0, and ranks given when it is not (nr = %lld)", who, (long long)nr);
-        return PARTLS_ERR_BAD_ARG;
-    }
-    if (yhat && ldY < N) { set_error("%s: ldY = %lld is smaller than N = %lld", who, (long long)ldY, (long long)N); return PARTLS_ERR_BAD_ARG; }
-    if (B > PARTLS_PREDICT_MANY_MAX_B || nr > PARTLS_PREDICT_MANY_MAX_B) {
-        set_error("%s: B = %lld models, nr = %lld ranks: this build supports at most %d of either in one call (predict in slices of columns)", who,
-                  (long long)B, (long long)nr, PARTLS_PREDICT_MANY_MAX_B);
-        return PARTLS_ERR_UNSUPPORTED;
-    }
-    for (int64_t q = 0; q < nr; ++q)
-        if (ranks[q] < 0 || ranks[q] >= B) { set_error("%s: ranks[%lld] = %lld lies outside [0, B = %lld)", who, (long long)q, (long long)ranks[q], (long long)B); return PARTLS_ERR_BAD_ARG; }
-    for (int64_t b = 0; b < B; ++b) {
-        bool fin = std::isfinite(t[b]);
-        for (int64_t m = 0; m < M && fin; ++m) fin = std::isfinite(alpha[m + b * M]);
-        for (int64_t k = 0; k < K && fin; ++k) fin = std::isfinite(beta[k + b * K]);
-        if (!fin) { set_error("%s: model %lld has a NaN / Inf in alpha, beta or t", who, (long long)b); return PARTLS_ERR_BAD_ARG; }
-    }
+    ManyModelPass mp;
+    mp.who = who; mp.ld_name = "ldY"; mp.slices = "predict in slices of columns";
+    mp.B = B; mp.x_f32 = x_f32; mp.out = yhat; mp.ld_out = ldY; mp.nr = nr; mp.ranks = ranks; mp.stats = stats; mp.mean = mean;
+    if ((st = many_model_check(mp, N)) != PARTLS_OK) return st;
+    if ((st = check_models(who, alpha, M, beta, K, t, M, K, B, /*many=*/true)) != PARTLS_OK) return st;
     // the models as predict applies them, blocked by chunk: hw = [chunk][m][j] | intercepts, zero where a chunk runs past B
     const int64_t nch = (B + PM_C - 1) / PM_C, wcount = nch * M * PM_C;
     std::vector<double> hw((size_t)(wcount + nch * PM_C), 0.0), wb((size_t)M);
@@ -166,56 +258,17 @@ static partls_status predict_many_common(partls_ctx *c, const void *X, int64_t N
     }
 
     PARTLS_HIP_CHECK(hipSetDevice(c->device));
-    PARTLS_HIP_CHECK(c->pmW.ensure(hw.size() * sizeof(double)));
-    PARTLS_HIP_CHECK(hipMemcpyAsync(c->pmW.p, hw.data(), hw.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const double *dW = c->pmW.as<double>(), *dT = dW + wcount;
-    if (nr > 0) {
-        PARTLS_HIP_CHECK(c->pmRanks.ensure((size_t)nr * sizeof(int64_t)));
-        PARTLS_HIP_CHECK(hipMemcpyAsync(c->pmRanks.p, ranks, (size_t)nr * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    }
-    const size_t esz = x_f32 ? sizeof(float) : sizeof(double);
-    const char *dX = static_cast<const char *>(X);
-    int64_t ld = ldX;
-    if (!x_on_device) {
-        PARTLS_HIP_CHECK(c->predX.ensure((size_t)N * M * esz));
-        st = upload_matrix(c, c->predX.p, X, N, M, ldX, esz);
-        if (st != PARTLS_OK) return st;
-        dX = c->predX.as<char>(); ld = N;
-    }
-    const int64_t rmax = rows_per_chunk(N, B, nr);
-    const bool direct = x_on_device && yhat;                 // the caller's device yhat is the intermediate
-    if (!direct) PARTLS_HIP_CHECK(c->pmY.ensure((size_t)rmax * B * sizeof(double)));
-    if (!x_on_device && nr > 0) PARTLS_HIP_CHECK(c->pmStats.ensure((size_t)rmax * nr * sizeof(double)));
-    if (!x_on_device && mean) PARTLS_HIP_CHECK(c->pmMean.ensure((size_t)N * sizeof(double)));
-    for (int64_t r0 = 0; r0 < N; r0 += rmax) {
-        const int64_t rows = N - r0 < rmax ? N - r0 : rmax;
-        double *Y = direct ? yhat + r0 : c->pmY.as<double>();
-        const int64_t ldy = direct ? ldY : rows;
+    PARTLS_HIP_CHECK(c->mmW.ensure(hw.size() * sizeof(double)));
+    PARTLS_HIP_CHECK(hipMemcpyAsync(c->mmW.p, hw.data(), hw.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const double *dW = c->mmW.as<double>(), *dT = dW + wcount;
+    mp.rmax = rows_per_chunk(N, B, nr);
+    mp.produce = [&](const void *dX, int64_t ld, int64_t r0, int64_t rows, double *Y, int64_t ldy) {
         const dim3 grid((unsigned)((rows + 255) / 256), (unsigned)nch);
-        if (x_f32) hipLaunchKernelGGL(predict_many_kernel<float>, grid, dim3(256), 0, c->stream, reinterpret_cast<const float *>(dX) + r0, rows, M, ld, dW, dT, B, Y, ldy);
-        else hipLaunchKernelGGL(predict_many_kernel<double>, grid, dim3(256), 0, c->stream, reinterpret_cast<const double *>(dX) + r0, rows, M, ld, dW, dT, B, Y, ldy);
-        PARTLS_HIP_CHECK(hipGetLastError());
-        if (yhat && !direct)
-            PARTLS_HIP_CHECK(hipMemcpy2DAsync(yhat + r0, (size_t)ldY * sizeof(double), Y, (size_t)rows * sizeof(double), (size_t)rows * sizeof(double),
-                                              (size_t)B, hipMemcpyDeviceToHost, c->stream));
-        if (nr > 0) {
-            double *S = x_on_device ? stats + r0 : c->pmStats.as<double>();
-            const int64_t lds = x_on_device ? N : rows;
-            PARTLS_HIP_CHECK(launch_row_select(Y, rows, ldy, B, c->pmRanks.as<int64_t>(), nr, S, lds, c->stream));
-            if (!x_on_device)
-                PARTLS_HIP_CHECK(hipMemcpy2DAsync(stats + r0, (size_t)N * sizeof(double), S, (size_t)rows * sizeof(double), (size_t)rows * sizeof(double),
-                                                  (size_t)nr, hipMemcpyDeviceToHost, c->stream));
-        }
-        if (mean) {
-            double *mu = (x_on_device ? mean : c->pmMean.as<double>()) + r0;
-            PARTLS_HIP_CHECK(launch_row_mean(Y, rows, ldy, B, mu, c->stream));
-        }
-    }
-    if (!x_on_device && mean)
-        PARTLS_HIP_CHECK(hipMemcpyAsync(mean, c->pmMean.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    PARTLS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (!x_on_device) { c->predX.release(); c->pmY.release(); c->pmStats.release(); c->pmMean.release(); }    // a prediction set is not retained
-    return PARTLS_OK;
+        if (x_f32) hipLaunchKernelGGL(predict_many_kernel<float>, grid, dim3(256), 0, c->stream, static_cast<const float *>(dX) + r0, rows, M, ld, dW, dT, B, Y, ldy);
+        else hipLaunchKernelGGL(predict_many_kernel<double>, grid, dim3(256), 0, c->stream, static_cast<const double *>(dX) + r0, rows, M, ld, dW, dT, B, Y, ldy);
+        return hipGetLastError();
+    };
+    return many_model_pass(c, mp, X, N, M, ldX, x_on_device);
 }
 
 }  // namespace partls

@@ -121,10 +121,9 @@ static partls_status weightings_run(partls_ctx *c, const double *X, int64_t N, i
     PARTLS_HIP_CHECK(c->rsPart.ensure((size_t)std::max<int64_t>(oc_max, 4 * std::min<int64_t>(B, 65535)) * nb * sizeof(double)));
     PARTLS_HIP_CHECK(c->rsHost.resize((size_t)oc_max * (M + 1 + nb)));
     double *hwv = c->rsHost.data(), *hpart = hwv + (size_t)oc_max * (M + 1);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    PARTLS_HIP_CHECK(hipEventCreate(&e0));
-    PARTLS_HIP_CHECK(hipEventCreate(&e1));
-    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{e0, e1};
+    Events<2> ev;
+    PARTLS_HIP_CHECK(ev.create());
+    const hipEvent_t e0 = ev.e[0], e1 = ev.e[1];
     double ms_oob = 0.0;
     for (int64_t q0 = 0; q0 < B; q0 += oc_max) {
         const int oc = (int)std::min<int64_t>(oc_max, B - q0);

@@ -3,16 +3,16 @@
 //   1. yhat by the residual pass of the problem's storage kind (launch_residual / launch_csr_residual, the pass of partls_predict), then
 //      a_i = |yhat_i - y_i| in place;
 //   2. unless the scale is given: the order statistics a_(lo), a_(hi) of the median by a radix select, 8 bits a pass, most significant
-//      digit first, in the manner of topk.hip.  The bit pattern of a non-negative double orders as an unsigned integer, so the key is the
-//      value itself.  A pass is a histogram kernel (per-workgroup LDS histograms with integer LDS atomics — a wave whose lanes all hit
-//      one bin adds its lane count once — then one integer global add per non-empty bin and workgroup) and a one-workgroup scan that
-//      fixes the next digit of each threshold and the rank still to find below it.  Both statistics ride the same eight passes (two
-//      histograms while their prefixes agree, which is almost always all of them); after the last pass each threshold IS its
-//      statistic.  Integer counts do not depend on arrival order; nothing returns to the host between the passes;
+//      digit first, from the pieces of radix_select.h, which topk.hip shares.  The bit pattern of a non-negative double orders as an
+//      unsigned integer, so the key is the value itself.  A pass is a histogram kernel and a one-workgroup scan that fixes the next
+//      digit of each threshold and the rank still to find below it.  Both statistics ride the same eight passes (two histograms
+//      while their prefixes agree, which is almost always all of them); after the last pass each threshold IS its statistic.
+//      Integer counts do not depend on arrival order; nothing returns to the host between the passes;
 //   3. the weight kernel: w from (a, c, s), rho, |w - w_prev|, the two counts; per block of RB_ROWS rows the four partials by a fixed
 //      tree; w_prev is read from and w written to the same buffer, every row by its own thread.
 // The host adds the block partials in ascending order.  Kernels first, then the host driver and the entries.
 #include "ctx.h"
+#include "radix_select.h"
 #include <cmath>
 
 namespace partls {
@@ -64,37 +64,22 @@ __global__ __launch_bounds__(RB_THREADS) void robust_hist_kernel(const double *_
         if (in) key = (uint64_t)__double_as_longlong(a[i]);
         const uint64_t top = (key >> shift) >> 8;
         const int d = (int)((key >> shift) & 255ULL);
-        for (int j = 0; j < nsel; ++j) {
-            const bool part = in && top == (j ? top1 : top0);
-            const unsigned long long mask = __ballot(part);      // 64 lanes
-            if (mask) {
-                const int first = __ffsll((long long)mask) - 1;
-                const int d0 = __shfl(d, first);
-                const unsigned long long same = __ballot(part && d == d0);
-                if (same == mask) {                               // the usual case in the leading digits: one add for the wave
-                    if (lane == first) atomicAdd(&h[j][d0], (unsigned)__popcll(mask));
-                } else if (part) atomicAdd(&h[j][d], 1u);
-            }
-        }
+        for (int j = 0; j < nsel; ++j) radix_wave_add(h[j], in && top == (j ? top1 : top0), d, lane);
     }
     __syncthreads();
-    for (int i = tid; i < 256 * nsel; i += RB_THREADS)
-        if (h[i >> 8][i & 255]) atomicAdd(&st->hist[i >> 8][i & 255], h[i >> 8][i & 255]);
+    radix_flush(&h[0][0], &st->hist[0][0], 256 * nsel, tid, RB_THREADS);      // the histograms lie one behind the other on both sides
 }
 
 __global__ __launch_bounds__(RB_THREADS) void robust_scan_kernel(RobustState *st, int pass, int nsel)
 {
     __shared__ unsigned h[2][256];
     const int tid = threadIdx.x;
-    for (int i = tid; i < 512; i += RB_THREADS) { h[i >> 8][i & 255] = st->hist[i >> 8][i & 255]; st->hist[i >> 8][i & 255] = 0; }
+    radix_take(&h[0][0], &st->hist[0][0], 512, tid, RB_THREADS);
     __syncthreads();
     if (tid >= nsel) return;
-    uint64_t krem = st->k_rem[tid], cum = 0;
-    int d = 0;
-    for (; d < 255; ++d) {
-        if (cum + h[tid][d] >= krem) break;
-        cum += h[tid][d];
-    }
+    uint64_t cum = 0;
+    const uint64_t krem = st->k_rem[tid];
+    const int d = radix_digit(h[tid], krem, &cum);
     st->thr[tid] |= (uint64_t)d << (56 - 8 * pass);
     st->k_rem[tid] = krem - cum;
 }
@@ -126,18 +111,6 @@ template <int LOSS> __device__ __forceinline__ RobustRow robust_row(double a, do
     return r;
 }
 
-// the fixed tree of block_sum_256 with max in place of +
-__device__ __forceinline__ double block_max_256(double *red, double v)
-{
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + h]);
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // block b: rows [RB_ROWS b, RB_ROWS (b + 1)); thread t takes the row pairs 2 t and 512 + 2 t of the block (16-byte accesses: both buffers
 // are the context's own allocations) and adds its up to four rho in ascending row order; part[4 b ..] = (sum rho, max |w - w_prev|,
 // rows with w < 1, rows with w == 0).  have_prev == 0: w_prev is all ones and w is not read.  s == 0: nothing is written but the scale.
@@ -146,7 +119,7 @@ __global__ __launch_bounds__(RB_THREADS) void robust_weight_kernel(const double 
                                                                     double c, double scale_in, int nsel, int have_prev,
                                                                     double *__restrict__ part)
 {
-    __shared__ double red[RB_THREADS];
+    __shared__ double red[4][RB_THREADS];
     const double s = robust_scale(st, scale_in, nsel);
     if (blockIdx.x == 0 && threadIdx.x == 0) st->scale = s;
     if (s == 0.0) return;                                         // grid-uniform
@@ -176,44 +149,30 @@ __global__ __launch_bounds__(RB_THREADS) void robust_weight_kernel(const double 
             zero += r0.w == 0.0 ? 1.0 : 0.0;
         }
     }
-    const double s0 = block_sum_256(red, rho);
-    __syncthreads();                                              // every thread has read red[0] before the next fold overwrites it
-    const double s1 = block_max_256(red, dmax);
-    __syncthreads();
-    const double s2 = block_sum_256(red, down);
-    __syncthreads();
-    const double s3 = block_sum_256(red, zero);
+    double v[4] = {rho, dmax, down, zero};
+    block_tree_256<4, 0x2u>(red, v);                              // sum, max, sum, sum
     if (threadIdx.x == 0) {
         double *p = part + (int64_t)blockIdx.x * 4;
-        p[0] = s0; p[1] = s1; p[2] = s2; p[3] = s3;
+        p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; p[3] = v[3];
     }
 }
-
-// the events between the phases of a call: created per call, destroyed on every way out
-struct RobustEvents : NoCopy {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~RobustEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
 
 static partls_status robust_weights_common(partls_ctx *c, const double *alpha, const double *beta, double t, int loss, double cc,
                                            double scale_in, double *scale, double *rho_sum, double *max_dw, int64_t *n_down,
                                            int64_t *n_zero, double *w_out)
 {
     const char *who = "partls_robust_weights";
-    if (!c) { set_error("context is NULL"); return PARTLS_ERR_BAD_ARG; }
-    if (c->multi_rank || !c->peers.empty()) { set_error("%s: a context of a partls_multi is not supported", who); return PARTLS_ERR_UNSUPPORTED; }
-    if (!c->prepared) { set_error("%s: context not prepared", who); return PARTLS_ERR_BAD_ARG; }
+    partls_status st = check_prepared_single(c, who, PARTLS_ERR_BAD_ARG);
+    if (st != PARTLS_OK) return st;
     if (!alpha || !beta) { set_error("%s: alpha or beta is NULL", who); return PARTLS_ERR_BAD_ARG; }
     if (loss != PARTLS_ROBUST_HUBER && loss != PARTLS_ROBUST_BISQUARE) { set_error("%s: unknown loss %d", who, loss); return PARTLS_ERR_BAD_ARG; }
     if (!std::isfinite(cc) || !(cc > 0.0)) { set_error("%s: the tuning constant c must be finite and > 0", who); return PARTLS_ERR_BAD_ARG; }
     if (!std::isfinite(scale_in)) { set_error("%s: scale_in is NaN / Inf", who); return PARTLS_ERR_BAD_ARG; }
     const int64_t N = c->N, M = c->M, K = c->K;
-    bool fin = std::isfinite(t);
-    for (int64_t m = 0; m < M && fin; ++m) fin = std::isfinite(alpha[m]);
-    for (int64_t k = 0; k < K && fin; ++k) fin = std::isfinite(beta[k]);
-    if (!fin) { set_error("%s: the model has a NaN / Inf in alpha, beta or t", who); return PARTLS_ERR_BAD_ARG; }
+    st = check_models(who, alpha, M, beta, K, &t, M, K, 1, /*many=*/false);
+    if (st != PARTLS_OK) return st;
     std::vector<double> wp((size_t)M, 0.0);
-    partls_status st = predict_weights(c->P.data(), M, K, M, alpha, beta, wp.data());
+    st = predict_weights(c->P.data(), M, K, M, alpha, beta, wp.data());
     if (st != PARTLS_OK) return st;
 
     PARTLS_HIP_CHECK(hipSetDevice(c->device));
@@ -227,8 +186,8 @@ static partls_status robust_weights_common(partls_ctx *c, const double *alpha, c
     PARTLS_HIP_CHECK(c->rbState.ensure(RB_STATE_BYTES + (size_t)M * sizeof(double)));
     PARTLS_HIP_CHECK(c->rbPart.ensure((size_t)4 * blocks * sizeof(double)));
     PARTLS_HIP_CHECK(c->rbHost.resize((size_t)4 * blocks + 1));
-    RobustEvents ev;
-    for (hipEvent_t &x : ev.e) PARTLS_HIP_CHECK(hipEventCreate(&x));
+    Events<4> ev;                                                 // between the phases of the call
+    PARTLS_HIP_CHECK(ev.create());
     RobustState *dst = c->rbState.as<RobustState>();
     double *dWp = reinterpret_cast<double *>(c->rbState.as<char>() + RB_STATE_BYTES), *dA = c->rbA.as<double>(), *dW = c->rbW.as<double>();
     hipStream_t s = c->stream;
@@ -291,9 +250,8 @@ static partls_status robust_weights_common(partls_ctx *c, const double *alpha, c
 static partls_status reweight_common(partls_ctx *c, const double *w, int w_on_device)
 {
     const char *who = "partls_opt_reweight";
-    if (!c) { set_error("context is NULL"); return PARTLS_ERR_BAD_ARG; }
-    if (c->multi_rank || !c->peers.empty()) { set_error("%s: a context of a partls_multi is not supported", who); return PARTLS_ERR_UNSUPPORTED; }
-    if (!c->prepared) { set_error("%s: context not prepared", who); return PARTLS_ERR_STATE; }
+    const partls_status st = check_prepared_single(c, who, PARTLS_ERR_STATE);
+    if (st != PARTLS_OK) return st;
     if (!w) {
         if (!c->rb_have) { set_error("%s: w is NULL and no partls_robust_weights call has left weights since the last prepare", who); return PARTLS_ERR_STATE; }
         // the prepared problem gets a copy of its own: the next partls_robust_weights call updates rbW in place

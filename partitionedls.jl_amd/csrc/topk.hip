@@ -8,16 +8,16 @@
 //     lo = reference index b = g ^ (g >> 1) through the visiting order (as models_cleanup_kernel computes it)
 // which is unique, so "the k smallest" is a set.  All of it runs on one stream without a host round trip:
 //   1. radix select, 8 bits a pass, most significant digit first: 8 passes over hi, then ceil(kbits / 8) over lo among the entries whose
-//      hi equals the threshold's.  A pass is a histogram kernel (per-workgroup LDS histogram with integer LDS atomics, a wave whose
-//      lanes all hit one bin adds its lane count once; then one integer global add per non-empty bin and workgroup) and a one-workgroup
-//      scan that fixes the next digit of the threshold key, the k still to find below it, and `done` as soon as the threshold's bucket is
-//      taken whole — the remaining passes then return at once.  Integer counts do not depend on arrival order.
+//      hi equals the threshold's.  A pass is a histogram kernel (integer atomics only; its pieces are radix_select.h's, shared with
+//      robust.hip) and a one-workgroup scan that fixes the next digit of the threshold key, the k still to find below it, and `done` as
+//      soon as the threshold's bucket is taken whole — the remaining passes then return at once.  Counts do not depend on arrival order.
 //   2. compaction: every non-NaN entry with key <= threshold claims a slot by an integer atomic (any order: the next step sorts);
 //   3. a bitonic sort of the at most k survivors by the composite key in the LDS of one workgroup (4096 x 24 B = 96 KiB);
 //   4. gather: the survivors' scaled rows, objectives and Gray indices into a compact buffer in sorted order, one wave per row, 16-byte
 //      loads along the row when the rows are 16-byte aligned (n even).  Rows at and beyond the count get a NaN objective, which
 //      models_cleanup_kernel (run on the compact buffer with the Gray-index list) answers with NaN outputs that the host never reads.
 #include "sweep_rules.h"
+#include "radix_select.h"
 
 namespace partls {
 
@@ -87,19 +87,10 @@ __global__ __launch_bounds__(TK_THREADS) void topk_hist_kernel(const double *__r
                 }
             }
         }
-        const unsigned long long mask = __ballot(part);          // 64 lanes
-        if (mask) {
-            const int first = __ffsll((long long)mask) - 1;
-            const int d0 = __shfl(d, first);
-            const unsigned long long same = __ballot(part && d == d0);
-            if (same == mask) {                                   // the usual case in the leading digits: one add for the wave
-                if (lane == first) atomicAdd(&h[d0], (unsigned)__popcll(mask));
-            } else if (part) atomicAdd(&h[d], 1u);
-        }
+        radix_wave_add(h, part, d, lane);
     }
     __syncthreads();
-    for (int i = tid; i < TK_BINS; i += TK_THREADS)
-        if (h[i]) atomicAdd(&st->hist[i], h[i]);
+    radix_flush(h, st->hist, TK_BINS, tid, TK_THREADS);
 }
 
 __global__ __launch_bounds__(TK_THREADS) void topk_scan_kernel(TopState *st, int pass, int nlo)
@@ -107,7 +98,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_scan_kernel(TopState *st, int
     __shared__ unsigned h[TK_BINS];
     if (st->done) return;
     const int tid = threadIdx.x;
-    for (int i = tid; i < TK_BINS; i += TK_THREADS) { h[i] = st->hist[i]; st->hist[i] = 0; }
+    radix_take(h, st->hist, TK_BINS, tid, TK_THREADS);
     __syncthreads();
     if (tid != 0) return;
     uint64_t krem = st->k_rem;
@@ -119,11 +110,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_scan_kernel(TopState *st, int
         if (krem == 0) { st->k_rem = 0; st->done = 1; return; }
     }
     uint64_t cum = 0;
-    int d = 0;
-    for (; d < 255; ++d) {
-        if (cum + h[d] >= krem) break;
-        cum += h[d];
-    }
+    const int d = radix_digit(h, krem, &cum);
     krem -= cum;
     const bool on_hi = pass < 8;
     const int shift = on_hi ? 56 - 8 * pass : 8 * (nlo - 1 - (pass - 8));

@@ -163,7 +163,8 @@ def test_every_rank_and_the_mean_are_exact(partls, B):
 
 
 def test_row_chunks_join_without_a_seam(partls):
-    """B at the cap and the smallest N whose N x B doubles exceed the byte budget: two row chunks, the second of one row"""
+    """B at the cap and the smallest N whose N x B doubles exceed the byte budget: two row chunks, the second of one row; then B = 1000 and
+    three chunks (twice 8388 rows and three), every output compared with the single-chunk calls on the chunks' rows"""
     L = partls.lowlevel
     B, M = L.PREDICT_MANY_MAX_B, 2
     rows = L.PREDICT_MANY_BYTES // (8 * B)
@@ -191,6 +192,21 @@ def test_row_chunks_join_without_a_seam(partls):
     # the same statistics when no yhat is wanted (the intermediate never leaves the device)
     r2 = ctx.predict_many(X, P, a, b, t, ranks=ranks, want_yhat=False, want_mean=True)
     assert np.array_equal(r2["stats"], r["stats"]) and np.array_equal(r2["mean"], r["mean"])
+    # host arrays, yhat, stats and mean all wanted, three row chunks with an odd tail of three rows: each output goes back to the host
+    # chunk by chunk, and every chunk's rows are bit for bit those of the single-chunk call on that row range
+    B, M = 1000, 7
+    rows = L.PREDICT_MANY_BYTES // (8 * B)
+    N = 2 * rows + 3
+    P = _partition(M)
+    X = np.asfortranarray(rng.normal(size=(N, M)))
+    a, b, t = _models(rng, B, M, P.shape[1])
+    ranks = [0, B // 2, B - 1]
+    r = ctx.predict_many(X, P, a, b, t, ranks=ranks, want_mean=True)
+    for r0 in range(0, N, rows):
+        part = ctx.predict_many(np.asfortranarray(X[r0:r0 + rows]), P, a, b, t, ranks=ranks, want_mean=True)
+        assert part["yhat"].shape[0] * max(B, len(ranks)) * 8 <= L.PREDICT_MANY_BYTES       # the reference call is one chunk
+        for k in ("yhat", "stats", "mean"):
+            assert np.array_equal(r[k][r0:r0 + rows], part[k]), (r0, k)
 
 
 def test_bad_calls_are_refused_and_the_context_still_predicts(partls):
