@@ -195,10 +195,21 @@ def _index_ordered_mean(cube):
 def test_every_rank_and_the_mean_are_exact(partls, B):
     """B either side of a power of two (the sort pads to one); ties: models 1 and B - 1 duplicate model 0, the all-zero rows of X
     contribute 0 under every model, and so does the empty group; N K = 1200 (row, group) pairs: more than one workgroup sorts"""
+    _ranks_and_mean(partls, B, 300, _partitions(5)[-1][1])
+
+
+@pytest.mark.parametrize("B", [257, 1025])
+def test_group_shapes_of_the_row_sort_with_a_ragged_last_group(partls, B):
+    """the (row, group) pairs of a call are the rows of the sort: R = 8 of them per workgroup at B = 257 (n = 512) and 2 at B = 1025
+    (n = 2048).  One group per feature, K = 5, and N = 37: N K = 185 pairs, the last workgroup holds one"""
+    N, P = 37, _partitions(5)[1][1]
+    assert P.shape[1] == 5 and (N * P.shape[1]) % 8 == 1 and (N * P.shape[1]) % 2 == 1
+    _ranks_and_mean(partls, B, N, P)
+
+
+def _ranks_and_mean(partls, B, N, P):
     rng = np.random.default_rng(B)
-    N, M = 300, 5
-    P = _partitions(M)[-1][1]
-    K = P.shape[1]
+    M, K = P.shape
     X = np.asfortranarray(rng.normal(size=(N, M)))
     X[::7] = 0.0
     a, b = rng.normal(size=(B, M)), rng.normal(size=(B, K))
@@ -360,3 +371,73 @@ def test_bootstrap_band_and_group_importance_end_to_end(partls):
     assert np.allclose(rep.share.sum(1), 1.0, rtol=1e-14, atol=0)
     yhat = partls.predict(res.models[ok[0]], X)
     assert np.allclose(cube[:, :, 0].sum(1) + res.models[ok[0]].t, yhat, rtol=0, atol=1e-12 * (1 + np.abs(yhat).max()))
+
+
+@pytest.mark.parametrize("N", [257, 1000])
+def test_sums_past_1024_columns(partls, N):
+    """contrib_sums_kernel walks the columns blockIdx.y, blockIdx.y + gridDim.y, ... with gridDim.y = min(K B, 1024) and reuses the LDS
+    tree of its block sum from one column to the next.  K = 4 and B = 257 are 1028 columns: the workgroups of the columns 0 .. 3 make
+    a second trip, to the columns 1024 .. 1027 of model 256.  Integer data: all three sums exact in any order, equality.  Real data:
+    within (N + 1) u sum |term| (test_sums_are_exact_on_integers_and_within_the_summation_bound), and the same bits as the B
+    single-model calls, in which every column is the first trip of its workgroup"""
+    rng = np.random.default_rng(27 + N)
+    ctx = partls.default_context()
+    M, B = 5, 257
+    P = _partitions(M)[-1][1]
+    K = P.shape[1]
+    assert K == 4 and K * B == 1028
+    X = np.asfortranarray(rng.integers(-8, 9, size=(N, M)).astype(np.float64))
+    a, b = rng.integers(1, 5, size=(B, M)).astype(np.float64), rng.integers(-4, 5, size=(B, K)).astype(np.float64)
+    b[256] = [1.0, -2.0, 3.0, -4.0]                                                    # the model of the second trip: no zero sums
+    r = ctx.contributions(X, P, a, b, want_sums=True)
+    ci = r["contrib"].astype(np.int64)
+    assert np.array_equal(ci, r["contrib"]) and np.array_equal(ci, _chains(X, P, a, b)[0])
+    assert np.array_equal(r["sums"], np.stack([ci.sum(0), np.abs(ci).sum(0), (ci * ci).sum(0)]).astype(np.float64))
+    assert np.all(r["sums"][1, P.sum(0) > 0, 256] > 0.0)
+    X = np.asfortranarray(rng.normal(size=(N, M)))
+    a, b = rng.normal(size=(B, M)), rng.normal(size=(B, K))
+    r = ctx.contributions(X, P, a, b, want_sums=True)
+    cl = r["contrib"].astype(np.longdouble)
+    for s, term in enumerate((cl, np.abs(cl), cl * cl)):
+        err = np.abs(r["sums"][s].astype(np.longdouble) - term.sum(0))
+        bound = (N + 1) * U * np.abs(term).sum(0)
+        print("sums past 1024 columns", N, s, "max err / bound", float(np.max(err / np.maximum(bound, np.finfo(float).tiny))))
+        assert np.all(err <= bound), (N, s)
+    assert np.array_equal(ctx.contributions(X, P, a, b, want_contrib=False, want_sums=True)["sums"], r["sums"])
+    for j in range(B):
+        one = ctx.contributions(X, P, a[j:j + 1], b[j:j + 1], want_contrib=False, want_sums=True)["sums"]
+        assert np.array_equal(one[:, :, 0], r["sums"][:, :, j]), j
+
+
+def test_a_workgroup_that_walks_several_groups(partls):
+    """contrib_kernel deals the groups k = blockIdx.z, blockIdx.z + gridDim.z, ... to the workgroups of a (row block, model chunk), and
+    gridDim.z = ceil(32 ncu / waves) clamped to [1, K] with waves = 4 x row blocks x model chunks (contrib.hip: contrib_group_split).
+    6 ncu + 1 row blocks of one model (393 217 rows on 256 compute units, the last block of one row) give gridDim.z = 2 under K = 4:
+    each workgroup computes two groups, one after the other.  The rule is restated here from the device's compute units, so the test
+    cannot pass on another part without a partial split.  Entries: the chain restated in numpy, bit for bit; sums: exact integers"""
+    import torch
+    L = partls.lowlevel
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    blocks = 6 * ncu + 1
+    N, M, B = 256 * blocks - 255, 5, 1
+    P = _partitions(M)[-1][1]
+    K = P.shape[1]
+    assert (N + 255) // 256 == blocks and N % 256 == 1 and N * K * 8 <= L.PREDICT_MANY_BYTES         # one chunk of rows
+    waves, target = blocks * 4 * -(-B // _chunk(partls)), ncu * 4 * 8
+    z = min(max(-(-target // waves), 1), K)
+    assert 1 < z < K, (ncu, z)
+    rng = np.random.default_rng(28)
+    ctx = partls.default_context()
+    X, a, b = _exact_inputs(rng, N, M, K, B)
+    ref, _ = _chains(X, P, a, b)
+    got = ctx.contributions(X, P, a, b)["contrib"]
+    assert got.shape == ref.shape and np.array_equal(got, ref)
+    assert np.array_equal(ctx.contributions(X.astype(np.float32), P, a, b)["contrib"], ref)
+    X = np.asfortranarray(rng.integers(-8, 9, size=(N, M)).astype(np.float64))
+    a, b = rng.integers(1, 5, size=(B, M)).astype(np.float64), rng.integers(-4, 5, size=(B, K)).astype(np.float64)
+    b[0, np.flatnonzero(b[0] == 0)] = 3.0                                              # every group with features contributes
+    r = ctx.contributions(X, P, a, b, want_sums=True)
+    ci = r["contrib"].astype(np.int64)
+    assert np.array_equal(ci, r["contrib"]) and np.array_equal(ci, _chains(X, P, a, b)[0])
+    assert np.array_equal(r["sums"], np.stack([ci.sum(0), np.abs(ci).sum(0), (ci * ci).sum(0)]).astype(np.float64))
+    assert np.all(r["sums"][1, P.sum(0) > 0, 0] > 0.0)

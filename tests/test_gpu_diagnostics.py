@@ -118,6 +118,13 @@ class DeviceProblem:
 
 def check_case(partls, N, M, K, p, seed, mean, eta, weighted, want_se=True):
     X, y, P, w, S = make_data(N, M, K, p, seed, mean, weighted)
+    return check_problem(partls, X, y, P, w, S, eta, want_se)[0]
+
+
+def check_problem(partls, X, y, P, w, S, eta, want_se=True):
+    """every check of a case on given data (the support S has p - 1 features) -> (the outputs of the float64 device call, the model)"""
+    N, M = X.shape
+    p, weighted = len(S) + 1, w is not None
     model, _ = fit_on_support(partls, X, y, P, w, S, eta)
     href, R, kappa, smin, norms = reference(X, y, w, P, eta, S)
     assert kappa <= 50.0, kappa
@@ -161,7 +168,7 @@ def check_case(partls, N, M, K, p, seed, mean, eta, weighted, want_se=True):
     assert s[L.DIAG_STATIONARITY] <= 1e-12, (tag, s[L.DIAG_STATIONARITY])             # a fit(Opt) model is stationary on its support
     if want_se:
         check_standard_errors(d, X, y, w, P, eta, S, R, kappa, smin, norms, s[L.DIAG_SIGMA2], delta, s, L, tag)
-    return d
+    return d, model
 
 
 def _inverse_longdouble(H):

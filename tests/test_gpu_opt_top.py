@@ -394,3 +394,54 @@ def test_fit_with_top_weights_and_float32(partls):
     assert r32.best_index == r64.best_index and np.array_equal(m32.α, m64.α)
     for key in ("pattern", "opt", "alpha", "beta", "t"):
         assert np.array_equal(getattr(r32.top, key), getattr(r64.top, key)), key  # float32 X: the results of X.astype(float64), bit for bit
+
+
+# ---- 9. more entries than one trip of the capped grids --------------------------------------------------------------------------------
+def _wide_select_context(partls, monkeypatch, order):
+    """as _select_context with K = 18 groups, faithful: 2^19 patterns, twice the 1024 x 256 entries that the histogram and the
+    compaction grids cover in one trip.  The reference patterns of all Gray indices by numpy shifts on int64 (19 bits), checked against
+    wide_reference on a sample"""
+    X, y, P = wide_problem(1800, 26, 18)
+    ctx = _ctx(partls, monkeypatch, {"PARTLS_BIT_ORDER": order})
+    ctx.opt_prepare(X, y, P, 0.0, FAITHFUL)
+    n = 1 << 19
+    assert ctx.num_patterns() == n
+    gbit = [int(v) for v in ctx.bit_order()[0]]
+    assert sorted(gbit) == list(range(19))
+    if order == "identity":
+        assert gbit == list(range(19))
+    g = np.arange(n, dtype=np.int64)
+    q = g ^ (g >> 1)
+    pats = np.zeros(n, dtype=np.int64)
+    for k in range(19):
+        pats |= ((q >> gbit[k]) & 1) << k
+    for i in [0, 1, 2, 255, 256, 262143, 262144, 300000, n - 1] + [int(v) for v in np.random.default_rng(1).integers(0, n, 50)]:
+        assert pats[i] == reference_index(gray(i), gbit)
+    return ctx, pats
+
+
+@pytest.mark.parametrize("cnt", [300001, 524288])
+@pytest.mark.parametrize("order", ["identity", "calibrate"])
+def test_selection_beyond_one_trip_of_the_grid(partls, monkeypatch, order, cnt):
+    """cnt = 300 001: workgroups 0 .. 147 of topk_hist_kernel and topk_compact_kernel make a second trip, workgroup 147 a ragged one;
+    cnt = 524 288 = 2 x 1024 x 256: every workgroup makes two full trips.  Keys: blocks of about 750 exact ties, so that k = 1 and 100
+    end inside the first block and k = 4096 inside the sixth, decided by the reference index in the passes over lo; +-0.0 among a few
+    negative values and many ties; continuous values; 5 % NaN in each"""
+    ctx, pats = _wide_select_context(partls, monkeypatch, order)
+    rng = np.random.default_rng(cnt)
+    nan = rng.random(cnt) < 0.05
+    ties = rng.integers(0, cnt // 750, size=cnt).astype(np.float64)
+    zeros = rng.integers(0, 3, size=cnt).astype(np.float64)
+    zeros[(zeros == 0.0) & (rng.random(cnt) < 0.5)] = -0.0
+    zeros[rng.choice(cnt, 50, replace=False)] = -1.0
+    assert np.signbit(zeros[zeros == 0.0]).any() and not np.signbit(zeros[zeros == 0.0]).all()
+    smooth = rng.standard_normal(cnt)
+    for name, keys in (("tie blocks", ties), ("signed zeros", zeros), ("continuous", smooth)):
+        keys[nan] = np.nan
+        keys[0], keys[cnt - 1] = np.nan, -5.0                                   # the last entry of the last trip is the best of all
+        for g0 in (0, 5):
+            if g0 + cnt > len(pats):
+                continue
+            for k in (1, 100, 4096):
+                _check_select(ctx, pats, keys, g0, k, "%s cnt=%d g0=%d k=%d" % (name, cnt, g0, k))
+    ctx.close()

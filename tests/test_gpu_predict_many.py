@@ -141,8 +141,25 @@ def test_every_rank_and_the_mean_are_exact(partls, B):
     """B either side of a power of two (the sort pads to one), one and two models, more rows than one workgroup sorts at once (8 of
     them, 4 at B = 1000; N = 300 leaves the last workgroup of 8 half empty); ties: models 1 and B - 1 duplicate model 0, and the
     all-zero rows of X predict the intercepts, which take only three values"""
+    _ranks_and_mean(partls, B, 300)
+
+
+@pytest.mark.parametrize("B", [129, 256, 257, 512, 513, 1025, 2048, 2049])
+def test_every_group_shape_of_the_row_sort(partls, B):
+    """the sort pads a row to n = the power of two >= B and a workgroup sorts R = rows_per_group(n) rows at once: R = 8 at n = 256 and
+    512 (B = 129, 256 | 257, 512), 4 at n = 1024 (513), 2 at n = 2048 (1025, 2048: nothing padded) and 1 at n = 4096 with 2047 pads of
+    +inf (2049).  N = 37 leaves the last workgroup ragged for R = 8, 4 and 2.  Every rank, the duplicate models and the intercept-only
+    rows as above; np.sort and the index-ordered mean, exact"""
+    n = 1
+    while n < B:
+        n <<= 1
+    assert (n, 8 if n <= 512 else 4096 // n) in ((256, 8), (512, 8), (1024, 4), (2048, 2), (4096, 1))
+    _ranks_and_mean(partls, B, 37)
+
+
+def _ranks_and_mean(partls, B, N):
     rng = np.random.default_rng(B)
-    N, M = 300, 4
+    M = 4
     P = _partition(M)
     X = np.asfortranarray(rng.normal(size=(N, M)))
     X[::7] = 0.0

@@ -7,7 +7,9 @@ for operation) and the library's own weighted fits, never the code under test:
   2. partls_opt_reweight against a fresh weighted prepare, bit for bit (Gram, every pattern's objective, finish, Alt, BnB), with no
      upload, the statuses of a weighted prepare for bad weights, and its refusals;
   3. fit_robust against the same loop written around fit(..., weights=) with numpy weights, bit for bit; c = 1e300; the descent of
-     the loss under a fixed scale; planted outliers; running out of iterations; the default context afterwards."""
+     the loss under a fixed scale; planted outliers; running out of iterations; the default context afterwards;
+  4. the selection on residuals planted exactly (a one-column X, an all-zero model): thresholds that part in pass 0 and in pass 1, zero
+     and the smallest denormal under a normal value, an exact tie at the median, and N beyond one trip of the histogram's grid."""
 import warnings
 
 import numpy as np
@@ -529,3 +531,89 @@ def test_the_default_context_afterwards(partls, monkeypatch):
     fresh.close()
     for (mu, _, ru), (mf, _, rf) in zip(used, want):
         assert _same_bits(mu.α, mf.α) and _same_bits(mu.β, mf.β) and _same_bits(mu.t, mf.t) and not diff(flat(dict(ru)), flat(dict(rf)))
+
+
+# ---- 4. the selection on planted residuals: thresholds that part early, and more than one trip of the histogram loop ---------------------
+def _planted_residuals(a, seed):
+    """a problem whose absolute residuals at an all-zero model are exactly a: one column, beta = 0 and t = 0 predict 0, y = +-a"""
+    rng = np.random.default_rng(seed)
+    N = len(a)
+    X = np.asfortranarray(rng.normal(0.5, 1.0, (N, 1)))
+    y = a * rng.choice([-1.0, 1.0], N)
+    P = np.ones((1, 1), dtype=np.int64)
+    model = (np.ones(1), np.zeros(1), 0.0)
+    return X, y, P, model
+
+
+def _check_planted(ctx, a, seed, where):
+    """both losses on the planted residuals a, through _check: scale and weights bit for bit, counts exact, the loss within its bound"""
+    a = np.asarray(a, dtype=np.float64)
+    X, y, P, model = _planted_residuals(a, seed)
+    for loss in LOSSES:
+        ctx.opt_prepare(X, y, P)
+        if loss == LOSSES[0]:
+            assert _same_bits(_abs_res(ctx, X, y, P, model), a), where            # the residuals are the planted values
+        _check(ctx.robust_weights(*model, loss=loss), a, loss, where=" %s N=%d" % (where, len(a)))
+
+
+def _two_clusters(rng, N, lo, hi):
+    """N / 2 values in [lo, 2 lo] and N / 2 in [hi, 2 hi], shuffled: a_(lo) is the largest of the first cluster, a_(hi) the smallest
+    of the second"""
+    assert N % 2 == 0
+    a = np.concatenate([rng.uniform(lo, 2 * lo, N // 2), rng.uniform(hi, 2 * hi, N // 2)])
+    rng.shuffle(a)
+    return a
+
+
+def _middle_keys(a):
+    s = np.sort(a)
+    N = len(s)
+    return int(s[(N - 1) // 2:(N - 1) // 2 + 1].view(np.uint64)[0]), int(s[N // 2:N // 2 + 1].view(np.uint64)[0])
+
+
+@pytest.mark.parametrize("N", [2, 256, 4098])
+def test_thresholds_that_part_in_the_first_passes(partls, ctx, N):
+    """the two order statistics of an even N ride the same eight passes, each with its own prefix filter and its own rank inside its
+    own bucket from the pass in which their digits differ: pass 0 (another exponent byte) and pass 1 (the same top byte, another
+    second byte) here, against the last bytes on continuous residuals.  Then a_(lo) = 0 and a_(lo) = the smallest denormal under a
+    normal a_(hi) (keys 0 and 1 against 0x3f..), and an exact tie of the two inside a cluster of neighbours one ulp apart, where the
+    thresholds never part and both ranks fall into one bucket of the last pass"""
+    rng = np.random.default_rng(7000 + N)
+    a = _two_clusters(rng, N, 1e-3, 1e3)
+    klo, khi = _middle_keys(a)
+    assert klo >> 56 != khi >> 56
+    _check_planted(ctx, a, N, "split in pass 0")
+    a = _two_clusters(rng, N, 1e-2, 1.0)
+    klo, khi = _middle_keys(a)
+    assert klo >> 56 == khi >> 56 and klo >> 48 != khi >> 48
+    _check_planted(ctx, a, N + 1, "split in pass 1")
+    for tiny, name in ((0.0, "zero"), (5e-324, "denormal")):
+        a = np.concatenate([np.full(N // 2, tiny), rng.uniform(0.5, 4.0, N // 2)])
+        rng.shuffle(a)
+        klo, khi = _middle_keys(a)
+        assert klo == (0 if tiny == 0.0 else 1) and khi >> 56 in (0x3f, 0x40)
+        ref = R.robust_info(a, "huber")
+        assert ref["scale"] > 0.0
+        _check_planted(ctx, a, N + 2, name + " meets a normal")
+    # the tie: keys base + offset, offsets within the last byte; N / 2 - 1 below 0 (one of them -1), two zeros, N / 2 - 1 above (one +1)
+    base = int(np.array([1.5]).view(np.uint64)[0]) + 128
+    half = N // 2 - 1
+    off = np.concatenate([rng.integers(-100, 0, half), [0, 0], rng.integers(1, 101, half)])
+    if half:
+        off[0], off[-1] = -1, 1
+    a = (np.uint64(base) + off.astype(np.int64).astype(np.uint64)).view(np.float64)
+    rng.shuffle(a)
+    klo, khi = _middle_keys(a)
+    assert klo == khi == base and np.all(a.view(np.uint64) >> np.uint64(8) == np.uint64(base >> 8))
+    _check_planted(ctx, a, N + 3, "tie at the median")
+
+
+@pytest.mark.parametrize("N,split", [(262145, False), (262146, False), (262146, True), (600001, False)])
+def test_more_than_one_trip_of_the_histogram_loop(partls, ctx, N, split):
+    """the histogram grid is capped at 1024 workgroups of 256 rows: at N = 262 145 (odd: one statistic) and 262 146 (even: two)
+    workgroup 0 makes a second trip of one and of two rows, at N = 600 001 the workgroups make three trips, the last one by 296 of
+    them and ragged; continuous residuals, and at N = 262 146 also the two clusters that part the thresholds in pass 0"""
+    assert N > 1024 * 256
+    rng = np.random.default_rng(N + split)
+    a = _two_clusters(rng, N, 1e-3, 1e3) if split else np.abs(rng.standard_normal(N)) * 10.0 ** rng.uniform(-2.0, 2.0, N)
+    _check_planted(ctx, a, N, "split, second trip" if split else "trips")
