@@ -229,7 +229,8 @@ partls_status partls_opt_models(partls_ctx *ctx, int64_t g_begin, int64_t g_end,
  * return the same bits.  The models are the Gram-form models of partls_opt_models, bit for bit the rows it returns for the same
  * patterns when both run the same piece; accuracy and the meaning of *n_vetoes are partls_opt_models'.
  * The range is cut into equal pieces, ceil(total / npieces), whose scaled rows and objectives ((n + 1) doubles per pattern, n = M + 1)
- * stay below PARTLS_OPT_MODELS_PIECE_BYTES (PARTLS_TOP_PIECE, read at partls_create: patterns per piece instead); each piece is one
+ * stay below PARTLS_OPT_MODELS_PIECE_BYTES (PARTLS_TOP_PIECE, a test knob read at partls_create: patterns per piece instead, here, in
+ * partls_opt_models and in the second pass of a rescuing sweep); each piece is one
  * export sweep on the chain plan of partls_opt_sweep for its length, a selection, sort and gather of its k best rows on the device, the
  * cleanup of those rows and one copy back; the host merges the pieces' lists by the same order.
  * Leaves the state of the last partls_opt_sweep untouched, as partls_opt_models does. */

@@ -1,5 +1,5 @@
 // ctx.h — the context behind the opaque partls_ctx handle, the owning buffer types it is made of, and the host helpers the host
-// translation units share: api.hip (create / destroy / predict / getters), prepare.hip, sweep_setup.hip, opt.hip, refine.hip,
+// translation units share: api.hip (create / destroy / predict / getters), prepare.hip, sweep_setup.hip, opt.hip, opt_export.hip, refine.hip,
 // solvers.hip, multi.hip and the host halves of cv.hip, alt_multi.hip, predict_many.hip, contrib.hip, diag.hip and robust.hip.
 #pragma once
 #include "common.h"
@@ -148,7 +148,7 @@ struct partls_knobs {
     bool cv_serial = false;      // PARTLS_CV_SERIAL: partls_cv_opt sweeps its problems one after another through partls_opt_sweep (A/B tests, timing)
     bool resample_serial = false; // PARTLS_RESAMPLE_SERIAL: the same for partls_opt_weightings (resample.hip)
     int pair = -1;               // PARTLS_PAIR: 0 / 1 force the pair walk of the 512-thread register kernel off / on; -1 automatic (sweep_pairs, sweep_setup.hip)
-    long long top_piece = 0;     // PARTLS_TOP_PIECE: patterns per piece of partls_opt_top (0: what PARTLS_OPT_MODELS_PIECE_BYTES admits); tests
+    long long top_piece = 0;     // PARTLS_TOP_PIECE: patterns per piece of partls_opt_models, partls_opt_top and a sweep's second pass (0: what PARTLS_OPT_MODELS_PIECE_BYTES admits); tests
     int bit_order = 0;           // PARTLS_BIT_ORDER: 0 automatic (calibrate when the sweep is long enough to repay it), "identity" = 1
                                  // (group k on Gray bit k), "calibrate" = 2 (always measure; small problems in the tests)
     long long contrib_bytes = 0; // PARTLS_CONTRIB_BYTES: byte budget of a row chunk's intermediate in partls_contributions (0: PARTLS_PREDICT_MANY_BYTES);
@@ -316,6 +316,9 @@ struct partls_ctx {
     double rb_ms[3] = {0.0, 0.0, 0.0};
 };
 
+// propagate a partls_status that is not PARTLS_OK (the host code's counterpart of PARTLS_HIP_CHECK)
+#define PARTLS_CHECK(...) do { const partls_status _st = (__VA_ARGS__); if (_st != PARTLS_OK) return _st; } while (0)
+
 namespace partls {
 
 void t_begin(partls_ctx *c, int w);
@@ -398,7 +401,10 @@ void bind_sweep_block(SweepParams &p, double *base, int grid, bool runner_up);  
 hipError_t launch_any_sweep(partls_ctx *c, SweepParams &p, int grid, bool models = false);
 // the Opt sweep's pieces that partls_cv_opt shares
 partls_status calibrate_bit_order(partls_ctx *c);
-// What every entry that sweeps in chain mode does once per prepare (c->order_ready): calibrate_bit_order, then pair_relayout
+// fit(Opt) enumerates 2^K' patterns: false (error set, who: the entry's name) beyond K' = 40 (opt.hip)
+bool opt_range_ok(const partls_ctx *c, const char *who);
+// What every entry that sweeps in chain mode does once per prepare: calibrate_bit_order, then pair_relayout; nothing when the order
+// is ready (c->order_ready)
 partls_status prepare_sweep_order(partls_ctx *c);
 // Pair walk: where the rule of sweep_pairs holds for the whole enumeration, the live variables of the group on Gray bit 0 move into tile
 // column T - 2 (sweep_blk.hip prices twins from that column's fixed tile slots); every other variable keeps its relative order.  c->perm
@@ -409,6 +415,10 @@ bool sweep_pairs(const partls_ctx *c, int64_t total);   // does partls_opt_sweep
 int64_t reference_pattern(const partls_ctx *c, int64_t q);
 // sweep_out: the host copy of a result block with runner-up columns (sweep_block)
 void install_sweep_result(partls_ctx *c, const double *sweep_out, int grid, bool has_sol, double *bobj_out, int64_t *bpat_out);
+// winner (objective, reference pattern; pattern -1: none) and the list it is the best of -> cand, near_pat, near_for (near_tie.h)
+void install_candidates(partls_ctx *c, std::pair<double, int64_t> winner, std::vector<std::pair<double, int64_t>> others);
+// c->allOpt -> the caller's all_opt under the reference index (through allOptRef unless the order is the identity); queues, no wait
+partls_status deliver_all_opt(partls_ctx *c, double *all_opt);
 
 // ---- many problems over one (X, y, P) in one call (cv.hip): what partls_cv_opt, partls_opt_weightings (resample.hip) and partls_cv_alt
 // (cv_alt.hip) share.  The caller's context c keeps the upload and the Gram products (c->cvG) and holds no prepared problem
@@ -554,6 +564,11 @@ partls_status rescue_piece(partls_ctx *c, int64_t p0, int64_t cnt, double *rows,
 // obj[i], the objective of Gray index p0 + i -> all_opt[internal pattern of that index] (the second pass of a sweep)
 partls_status rescue_all_opt(partls_ctx *c, const double *obj, int64_t p0, int64_t cnt, double *all_opt);
 void rescue_collect(partls_ctx *c, unsigned long long *unconv, unsigned long long *vetoes);
+// The second pass of a partls_opt_sweep that reported capped patterns (opt_export.hip): the range again through the export pieces of
+// partls_opt_models with the rescue; installs its winner and near ties, fills all_opt (optional), *unconv_io = what stayed unsolved.
+// The caller has run rescue_begin_call.
+partls_status sweep_second_pass(partls_ctx *c, int64_t g_begin, int64_t g_end, double *all_opt, double *bobj_io, int64_t *bpat_io,
+                                unsigned long long *unconv_io);
 // one reference pattern, in the format of solve_nodes (sol: n scaled values, 0 for non-basic; obj2; *unconv = 1 when it failed)
 partls_status rescue_pattern(partls_ctx *c, uint64_t pattern, std::vector<double> &sol, double *obj2, unsigned long long *unconv);
 // node codes of one Opt sign pattern (Opt.jl:28-29): sign of the multiplier sum_k P[m,k] s_k of every tableau variable

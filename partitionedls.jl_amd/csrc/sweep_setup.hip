@@ -408,6 +408,7 @@ partls_status partls::pair_relayout(partls_ctx *c)
 
 partls_status partls::prepare_sweep_order(partls_ctx *c)
 {
+    if (c->order_ready) return PARTLS_OK;
     const partls_status st = calibrate_bit_order(c);
     return st != PARTLS_OK ? st : pair_relayout(c);
 }
@@ -482,21 +483,40 @@ void partls::install_sweep_result(partls_ctx *c, const double *sweep_out, int gr
         if (bpat < 0 || b.best_obj[i] < bobj || (b.best_obj[i] == bobj && bp[(size_t)i] < bpat)) { bobj = b.best_obj[i]; bpat = bp[(size_t)i]; best_wg = i; }
     }
     if (has_sol) c->export_wg = best_wg;                 // row of bestSol that holds the winner's solution (valid while near_for == winner)
-    // Near ties (near_tie.h): each workgroup reports its minimum and its runner-up; those within the Gram form's own error of the winner
-    // are remembered (at most 3, best first) and partls_opt_finish re-ranks them with the objective from the data.
-    c->near_pat.clear();
-    c->cand.clear();
-    c->near_for = bpat;
-    if (bpat >= 0) {
-        const double yy = h_reg(c, (int)c->M + 1, (int)c->M + 1);
-        const double lim2 = bobj * bobj + c->knobs.near_tie_rel * (yy > 0.0 ? yy : 0.0);
-        std::vector<std::pair<double, int64_t>> others;
-        for (int i = 0; i < grid; ++i) {
-            if (bp[(size_t)i] >= 0) others.emplace_back(b.best_obj[i], bp[(size_t)i]);
-            if (b.second_pat[i] >= 0) others.emplace_back(b.second_obj[i], reference_pattern(c, b.second_pat[i]));
-        }
-        install_near_ties({bobj, bpat}, std::move(others), lim2, 3, c->cand, c->near_pat, c->near_for);
+    // Near ties: each workgroup reports its minimum and its runner-up; partls_opt_finish re-ranks those install_candidates keeps.
+    std::vector<std::pair<double, int64_t>> others;
+    if (bpat >= 0) for (int i = 0; i < grid; ++i) {
+        if (bp[(size_t)i] >= 0) others.emplace_back(b.best_obj[i], bp[(size_t)i]);
+        if (b.second_pat[i] >= 0) others.emplace_back(b.second_obj[i], reference_pattern(c, b.second_pat[i]));
     }
+    install_candidates(c, {bobj, bpat}, std::move(others));
     *bobj_out = bobj;
     *bpat_out = bpat;
+}
+
+// The ONE install of a winner (pattern -1: none) and its near ties: of `others` those within near_tie_rel y'y of the winner's
+// objective^2 are kept, at most 3, best first (near_tie.h).  Replaces cand, near_pat and near_for; export_wg is the caller's.
+void partls::install_candidates(partls_ctx *c, std::pair<double, int64_t> winner, std::vector<std::pair<double, int64_t>> others)
+{
+    c->near_pat.clear();
+    c->cand.clear();
+    c->near_for = -1;
+    if (winner.second < 0) return;
+    const double yy = h_reg(c, (int)c->M + 1, (int)c->M + 1);
+    const double lim2 = winner.first * winner.first + c->knobs.near_tie_rel * (yy > 0.0 ? yy : 0.0);
+    install_near_ties(winner, std::move(others), lim2, 3, c->cand, c->near_pat, c->near_for);
+}
+
+// all_opt of a sweep (c->allOpt, indexed by the internal pattern) to the host under the reference index: queued on c->stream, no wait
+partls_status partls::deliver_all_opt(partls_ctx *c, double *all_opt)
+{
+    const int64_t npat = (int64_t)1 << c->kbits;
+    const void *src = c->allOpt.p;
+    if (!c->order_identity) {
+        PARTLS_HIP_CHECK(c->allOptRef.ensure((size_t)npat * sizeof(double)));
+        PARTLS_HIP_CHECK(launch_pattern_gather(c->allOpt.as<double>(), npat, c->kbits, c->order, c->allOptRef.as<double>(), c->stream));
+        src = c->allOptRef.p;
+    }
+    PARTLS_HIP_CHECK(hipMemcpyAsync(all_opt, src, (size_t)npat * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return PARTLS_OK;
 }

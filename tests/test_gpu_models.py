@@ -99,13 +99,8 @@ def test_ranges_errors_and_calibrated_order(partls, monkeypatch):
     fresh.close()
 
     # a calibrated (non-identity) visiting order: the same models under the reference's pattern index
-    rng = np.random.default_rng(11)
-    N, M, K = 400, 45, 9
-    X = np.asfortranarray(rng.standard_normal((N, M)))
-    P = np.zeros((M, K), dtype=np.int64)
-    P[np.arange(M), rng.integers(0, K, size=M)] = 1
-    w = rng.standard_normal(M) * (rng.random(M) < 0.6)
-    y = X @ w + 0.5 + 0.3 * rng.standard_normal(N)
+    X, y, P = _perm_problem()
+    K = P.shape[1]
     res = {}
     for mode in ("identity", "calibrate"):
         c = _ctx(partls, X, y, P, monkeypatch=monkeypatch, env={"PARTLS_BIT_ORDER": mode})
@@ -115,6 +110,63 @@ def test_ranges_errors_and_calibrated_order(partls, monkeypatch):
     assert list(res["calibrate"][0]) != list(range(K + 1))
     for k in ("opt", "alpha", "beta", "t"):
         _close(res["calibrate"][1][k], res["identity"][1][k], 1e-9)
+
+
+def _pieces(g0, g1, cap):
+    """the piece boundaries of the export walk for [g0, g1) under a cap of `cap` patterns (test_gpu_opt_top.py: _pieces)"""
+    total = g1 - g0
+    npieces = -(-total // cap)
+    piece = -(-total // npieces)
+    return [(p0, min(g1, p0 + piece)) for p0 in range(g0, g1, piece)]
+
+
+def _perm_problem():
+    """the calibrated-order problem of test_ranges_errors_and_calibrated_order: N = 400, M = 45, K = 9, 1024 patterns"""
+    rng = np.random.default_rng(11)
+    N, M, K = 400, 45, 9
+    X = np.asfortranarray(rng.standard_normal((N, M)))
+    P = np.zeros((M, K), dtype=np.int64)
+    P[np.arange(M), rng.integers(0, K, size=M)] = 1
+    w = rng.standard_normal(M) * (rng.random(M) < 0.6)
+    return X, X @ w + 0.5 + 0.3 * rng.standard_normal(N), P
+
+
+_EXPORT_KEYS = ("pattern", "opt", "alpha", "beta", "t", "raw_alpha")
+
+
+@pytest.mark.parametrize("name,env,caps,ranges", [
+    ("synth_b", {}, (7, 37), ((0, 64), (3, 37), (5, 62), (63, 64))),
+    ("perm", {"PARTLS_BIT_ORDER": "calibrate"}, (100,), ((0, 1024), (17, 900))),
+])
+def test_one_call_in_pieces(partls, monkeypatch, name, env, caps, ranges):
+    """PARTLS_TOP_PIECE caps the pieces of partls_opt_models: one call over several pieces is, bit for bit, the calls over its pieces
+    one by one, and its counters are their sums; against a context without the knob (other pieces, other chains) round-off apart"""
+    if name == "perm":
+        X, y, P = _perm_problem()
+    else:
+        g = load_golden(name)
+        X, y, P = g["X"], g["y"], g["P"]
+    plain = _ctx(partls, X, y, P, monkeypatch=monkeypatch, env=env or None)
+    npat = plain.num_patterns()
+    if name == "perm":
+        assert npat == 1024 and list(plain.bit_order()[0]) != list(range(P.shape[1] + 1))
+    whole = _scatter(plain.opt_models(raw=True), npat)
+    plain.close()
+    for cap in caps:
+        ctx = _ctx(partls, X, y, P, monkeypatch=monkeypatch, env=dict(env, PARTLS_TOP_PIECE=str(cap)))
+        for g0, g1 in ranges:
+            bounds = _pieces(g0, g1, cap)
+            assert all(b - a <= cap for a, b in bounds) and bounds[0][0] == g0 and bounds[-1][1] == g1
+            assert len(bounds) == -(-(g1 - g0) // cap)                     # several pieces wherever the range is longer than the cap
+            r = ctx.opt_models(g0, g1, raw=True)
+            parts = [ctx.opt_models(a, b, raw=True) for a, b in bounds]
+            for key in _EXPORT_KEYS:
+                assert np.array_equal(r[key], np.concatenate([p[key] for p in parts])), (cap, g0, g1, key)
+            assert r["n_unconverged"] == sum(p["n_unconverged"] for p in parts)
+            assert r["n_vetoes"] == sum(p["n_vetoes"] for p in parts)
+            for key in ("opt", "alpha", "beta", "t", "raw_alpha"):   # `whole` is indexed by the reference pattern
+                _close(r[key], whole[key][r["pattern"]], 1e-10)
+        ctx.close()
 
 
 def _big_problem(seed, N, D, K):

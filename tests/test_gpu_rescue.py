@@ -185,6 +185,62 @@ def test_capped_patterns_are_rescued(partls, oracle, monkeypatch, route, cap):
         ctx.close()
 
 
+@pytest.mark.parametrize("route", ["reg256-c40", "deferred-c40"])
+def test_second_pass_in_pieces(partls, oracle, monkeypatch, route):
+    """PARTLS_TOP_PIECE = 7 at a cap of 1: the second pass, opt_models and opt_top walk the 64 patterns of c40 in ten pieces, the last
+    one short; the second pass and the export cut the same pieces, so all_opt is the export's objectives bit for bit"""
+    name, env, flags, kernel = CHAIN_ROUTES[route]
+    ref = chain(oracle, name)
+    c, objs = ref["case"], ref["objs"]
+    g0, g1 = 0, ref["npat"]
+    assert g1 == 64
+    gs = np.arange(g0, g1)
+    pats = gs ^ (gs >> 1)
+    want = objs[pats]
+    knobs = dict(env, PARTLS_MAX_ROUNDS="1", **WALK)
+
+    def pieced(fl):
+        monkeypatch.setenv("PARTLS_TOP_PIECE", "7")
+        try:
+            ctx = ctx_with(partls, monkeypatch, knobs)
+        finally:
+            monkeypatch.delenv("PARTLS_TOP_PIECE")
+        ctx.opt_prepare(c["X"], c["y"], c["P"], c["eta"], c["flags"] | flags | fl)
+        assert ctx.sweep_route() == kernel, route
+        return ctx
+
+    plain = pieced(0)
+    try:
+        m0 = plain.opt_models(g0, g1, raw=True)
+        ncapped = int(np.isnan(m0["opt"]).sum())
+        assert ncapped > 0 and m0["n_unconverged"] == ncapped, route
+    finally:
+        plain.close()
+    ctx = pieced(RESCUE)
+    try:
+        bo, bp, allo, unconv = ctx.opt_sweep(g0, g1, want_all=True)
+        st = ctx.rescue_stats()
+        assert unconv == 0 and st.failed == 0, route
+        assert st.rescued == ncapped, "%s: %d rescued, the export of the plain context has %d NaN rows" % (route, st.rescued, ncapped)
+        got = allo[pats]
+        assert np.isfinite(got).all(), route
+        assert close_obj(got, want).all(), "%s: all_opt off by %.3g" % (route, (np.abs(got - want) / np.maximum(1.0, want)).max())
+        order = np.lexsort((pats, want))
+        if want[order[1]] - want[order[0]] > TOL_OBJ * max(1.0, want[order[0]]):
+            assert bp == int(pats[order[0]]), "%s: winner %d, the oracle's %d" % (route, bp, pats[order[0]])
+        assert close_obj(bo, objs[bp]), route
+        co, cp = ctx.opt_candidates()
+        assert len(cp) >= 1 and (co[0], cp[0]) == (bo, bp), route
+        m = ctx.opt_models(g0, g1, raw=True)
+        assert m["pattern"].tolist() == pats.tolist() and m["n_unconverged"] == 0, route
+        assert np.array_equal(m["opt"], allo[pats]), "%s: the second pass's all_opt is not its export's objective" % route
+        top = ctx.opt_top(8, g0, g1, raw=True)
+        assert top["n_unconverged"] == 0 and top["count"] == 8, route
+        same_as_host_sort(top, m, 8)
+    finally:
+        ctx.close()
+
+
 @pytest.mark.parametrize("cap", (1, 10))
 def test_duplicated_and_scaled_column(partls, oracle, monkeypatch, cap):
     """c40 with a duplicated and a scaled column inside one group: the oracle's objectives, no NaN"""
