@@ -555,6 +555,9 @@ partls_status partls_get_gram(const partls_ctx *ctx, double *G_aug);
 /* ---- robust fits: the Huber / bisquare row weights of a model on the prepared problem, formed on the device, and the re-prepare that
  * swaps the sample weights of a prepared problem without touching X. */
 #include "partls_robust.h"
+/* ---- generalised linear fits: the working rows of a logistic / Poisson family at a model on the prepared problem, formed on the device,
+ * the re-prepare that swaps sample weights and response without touching X, and the inverse link. */
+#include "partls_glm.h"
 
 #ifdef __cplusplus
 }

@@ -156,6 +156,16 @@ SYMBOLS_ROBUST = [
     ("partls_get_robust_timing", C.c_int, [C.c_void_p, _dp, _dp, _dp]),
 ]
 
+# ... and every symbol include/partls_glm.h declares (generalised linear fits: the working rows of a family on the prepared problem, the
+# re-prepare that swaps sample weights and response, the inverse link; row arrays are host arrays or device addresses, passed as addresses)
+GLM_BINOMIAL, GLM_POISSON = range(2)
+SYMBOLS_GLM = [
+    ("partls_glm_working", C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _ip, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("partls_opt_rework", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    ("partls_glm_mean", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    ("partls_get_glm_timing", C.c_int, [C.c_void_p, _dp, _dp]),
+]
+
 _lib = None
 
 
@@ -202,7 +212,7 @@ def lib():
                               f"(make -C '{CSRC}'); partitionedls.jl_amd has no CPU fallback")
         _preload_torch_hip_runtime()
         l = C.CDLL(SO_PATH)
-        for name, res, args in SYMBOLS + SYMBOLS_F32 + SYMBOLS_F32_MORE + SYMBOLS_CSR + SYMBOLS_CONTRIB + SYMBOLS_DIAG + SYMBOLS_ROBUST:
+        for name, res, args in SYMBOLS + SYMBOLS_F32 + SYMBOLS_F32_MORE + SYMBOLS_CSR + SYMBOLS_CONTRIB + SYMBOLS_DIAG + SYMBOLS_ROBUST + SYMBOLS_GLM:
             if os.environ.get("PARTLS_LIB") and not hasattr(l, name):
                 continue                   # diagnostic A/B builds of older sources may lack the newest entry points
             f = getattr(l, name)           # AttributeError here = header/library mismatch

@@ -912,6 +912,93 @@ class Context:
         _check(L.lib().partls_get_robust_timing(self._h, *(C.byref(m) for m in ms)))
         return tuple(m.value for m in ms)
 
+    # ---- generalised linear fits ----------------------------------------------------------------------
+    def glm_working(self, model=None, family="binomial", *, want_rows=True):
+        """The working rows of a family ("binomial": logit link; "poisson": log link) at a model on the problem this context is prepared
+        for, from HOST arrays (opt_prepare): partls_glm_working, DESIGN.md §4.19.  model: None for the start (eta from y alone, as
+        R's glm.fit), a (alpha[M], beta[K], t) triple or a fit result.  The response is the one the problem was prepared with, whatever
+        opt_rework installed since.  Returns a dict: deviance, max_abs_eta (before the clamp at +-30), n_clamped and (unless
+        want_rows is False) weights[N], working_response[N], mu[N].  The prepared problem is untouched."""
+        if getattr(self, "_on_device", False):
+            raise ValueError("Context.glm_working: the problem was prepared from device pointers; its rows are device arrays "
+                             "(glm_working_device)")
+        N = self._diag_shape("Context.glm_working")[0]
+        rows = [np.zeros(N) for _ in range(3)] if want_rows else [None] * 3
+        out = self._glm_working(model, family, *(None if r is None else r.ctypes.data for r in rows))
+        out.update(weights=rows[0], working_response=rows[1], mu=rows[2])
+        return out
+
+    def glm_working_device(self, model=None, family="binomial", *, dw_ptr=None, dz_ptr=None, dmu_ptr=None):
+        """the same on a problem prepared from DEVICE pointers (opt_prepare_device): dw_ptr, dz_ptr, dmu_ptr (each optional) are raw
+        device addresses of N doubles that receive the rows; returns the dict without rows"""
+        if not getattr(self, "_on_device", True):
+            raise ValueError("Context.glm_working_device: the problem was prepared from host arrays; its rows are host arrays "
+                             "(glm_working)")
+        self._diag_shape("Context.glm_working_device")
+        return self._glm_working(model, family, *(None if q is None else C.c_void_p(q) for q in (dw_ptr, dz_ptr, dmu_ptr)))
+
+    def _glm_working(self, model, family, w_out, z_out, mu_out):
+        """The one call behind glm_working and glm_working_device: the row outputs (or None) are addresses on the host or in HBM, as the
+        prepare was"""
+        _, M, K = self._shape
+        code = _glm_family(family, "glm_working")
+        a = b = None
+        t = 0.0
+        if model is not None:
+            alpha, beta, t = (model.α, model.β, model.t) if hasattr(model, "α") else model
+            a = np.ascontiguousarray(alpha, dtype=np.float64)
+            b = np.ascontiguousarray(beta, dtype=np.float64)
+            if a.shape != (M,) or b.shape != (K,):
+                raise ValueError("glm_working: expected alpha (%d,) and beta (%d,), got %s and %s" % (M, K, a.shape, b.shape))
+        dev, em, nc = C.c_double(), C.c_double(), C.c_int64()
+        _check(L.lib().partls_glm_working(self._h, None if a is None else _dp(a), None if b is None else _dp(b), float(t), code,
+                                          C.byref(dev), C.byref(em), C.byref(nc), w_out, z_out, mu_out))
+        return dict(deviance=dev.value, max_abs_eta=em.value, n_clamped=nc.value)
+
+    def opt_rework(self, w=None, z=None):
+        """New sample weights AND a new response for the prepared problem, X untouched (partls_opt_rework): w[N], z[N]
+        (host), or neither for the rows of the last glm_working call on this context; w alone is opt_reweight(w).  Afterwards the
+        context is in the state opt_prepare(X, z, ..., weights=w) would leave it in, bit for bit, except that glm_working still reads
+        the response of the first prepare; nothing but host w / z is uploaded.  A refusal leaves the context unprepared."""
+        N = self._diag_shape("Context.opt_rework")[0]
+        if w is None and z is not None:
+            raise ValueError("Context.opt_rework: z is given without w")
+        wv = _weights(w, N)
+        zv = None
+        if z is not None:
+            zv = np.ascontiguousarray(z, dtype=np.float64)
+            if zv.shape != (N,):
+                raise ValueError("Context.opt_rework: z must have %d entries, got %s" % (N, zv.shape))
+        self.generation += 1
+        _check(L.lib().partls_opt_rework(self._h, None if wv is None else wv.ctypes.data, None if zv is None else zv.ctypes.data, 0))
+
+    def opt_rework_device(self, dw_ptr, dz_ptr=None):
+        """the same with the rows in HBM: raw device addresses of N doubles each, which stay owned by the caller and must stay valid
+        while the context holds the problem"""
+        self._diag_shape("Context.opt_rework_device")
+        self.generation += 1
+        _check(L.lib().partls_opt_rework(self._h, C.c_void_p(dw_ptr), None if dz_ptr is None else C.c_void_p(dz_ptr), 1))
+
+    def glm_mean(self, family, eta):
+        """mu = the inverse link of the family at eta (host array), by the device function of the working rows, clamp included
+        (partls_glm_mean)"""
+        code = _glm_family(family, "glm_mean")
+        e = np.ascontiguousarray(eta, dtype=np.float64).reshape(-1)
+        mu = np.zeros(e.shape[0])
+        if e.shape[0]:
+            _check(L.lib().partls_glm_mean(self._h, code, e.ctypes.data, e.shape[0], 0, mu.ctypes.data))
+        return mu
+
+    def glm_mean_device(self, family, deta_ptr, N, dmu_ptr):
+        """the same with eta and mu (N doubles each) in HBM: raw device addresses"""
+        _check(L.lib().partls_glm_mean(self._h, _glm_family(family, "glm_mean_device"), C.c_void_p(deta_ptr), int(N), 1, C.c_void_p(dmu_ptr)))
+
+    def glm_timing(self):
+        """(residual pass, row kernel) of the last glm_working call on this context, in ms of device time"""
+        ms = [C.c_double() for _ in range(2)]
+        _check(L.lib().partls_get_glm_timing(self._h, *(C.byref(m) for m in ms)))
+        return tuple(m.value for m in ms)
+
     def _count(self, getter):
         n = C.c_int64()
         _check(getter(self._h, C.byref(n)))
@@ -1509,6 +1596,65 @@ def fit(alg, X, y, P, *, η=None, eta=None, ϵ=None, eps=None, T=100, nnlsalg="n
         return result(ctx, a, b, t, opt=o, nopen=no)
 
 
+def _irls_problem(who, what, alg, X, y, P, η, eta, ϵ, eps, T, rng, alpha0, beta0, faithful_intercept, generic_kernel, rescue, device,
+                  on_ill_conditioned):
+    """What the re-weighted fits (fit_robust, fit_glm) share from the option checks on: the marshalled inputs, the flags of the staged
+    prepare and staged(), the staged call of alg on whatever problem the context is prepared for.  Returns (ctx, Xf, yf, Pf, eta, flags,
+    staged, Pout); no device work but default_context.  who / what: the caller's name and its subject in the messages."""
+    if rescue and alg is not Opt:
+        raise ValueError("%s: rescue= is an option of Opt (the enumeration), not of %s" % (who, alg.__name__))
+    if on_ill_conditioned not in ("warn", "raise"):
+        raise ValueError('on_ill_conditioned must be "warn" or "raise"')
+    eta_v = _eta(η, eta)
+    eps_v = 1e-6 if (ϵ is None and eps is None) else float(ϵ if ϵ is not None else eps)
+    Xf, yf, Pf = _fit_inputs(X, y, P, f32=True)
+    N, M = Xf.shape
+    K = Pf.shape[1]
+    flags = L.OPT_FAITHFUL_INTERCEPT
+    if alg is Opt:
+        flags = (L.OPT_FAITHFUL_INTERCEPT if faithful_intercept else 0) | (L.OPT_GENERIC_KERNEL if generic_kernel else 0) | (L.OPT_RESCUE_CAPPED if rescue else 0)
+    if alg is Alt:
+        if np.ndim(alpha0) == 2 or np.ndim(beta0) == 2:
+            raise ValueError("%s: several starting points (restarts) are not supported together with %s" % (who, what))
+        if alpha0 is None or beta0 is None:
+            alpha0, beta0 = _draw_start(_generator(rng), M, K)
+        a0 = np.ascontiguousarray(alpha0, dtype=np.float64)
+        b0 = np.ascontiguousarray(beta0, dtype=np.float64)
+        if a0.shape != (M + 1,) or b0.shape != (K + 1,):
+            raise ValueError("alpha0 must have M+1 and beta0 K+1 entries")
+    ctx = default_context(device)
+    ctx.last_ill = False
+    Pout = np.array(Pf, dtype=np.int64, order="C")
+
+    def staged():
+        """the staged call of alg on the prepared problem -> (alpha, beta, t, the Report fields of this fit)"""
+        if alg is Opt:
+            _, bpat, _, unconv = ctx.opt_sweep(0, -1)
+            if unconv:
+                raise PartlsError(L.ERR_NOT_CONVERGED, f"{unconv} subproblems hit the pivot cap")
+            a, b, t, opt, bi = ctx.opt_finish(bpat)
+            kw = dict(opt=opt, best_index=bi)
+            if rescue:
+                kw.update(rescued=ctx.rescue_stats().rescued)
+            return a, b, t, kw
+        if alg is Alt:
+            a, b, t, o, it = ctx.alt_prepared(a0, b0, eps_v, int(T))
+            return a, b, t, dict(opt=o, iters=it)
+        a, b, t, o, no = ctx.bnb_prepared()
+        return a, b, t, dict(opt=o, nopen=no)
+
+    return ctx, Xf, yf, Pf, eta_v, flags, staged, Pout
+
+
+def _irls_ill(ctx, kw):
+    """the ill-conditioned ending of a re-weighted fit: fit's warning and report fields for the last staged fit"""
+    if ctx.last_ill:
+        warnings.warn("partitionedls: the model's KKT conditions do not hold in data space (X is too ill-conditioned for the fp64 "
+                      "Gram form); the returned model is the best Gram-form one — " + L.lib().partls_last_error().decode(),
+                      IllConditionedWarning, stacklevel=3)
+        kw.update(ill_conditioned=True, kkt_violation=ctx.kkt_violation())
+
+
 class RobustConvergenceWarning(UserWarning):
     """fit_robust ran out of iterations (max_iter) before the row weights settled within tol"""
 
@@ -1568,48 +1714,10 @@ def fit_robust(alg, X, y, P, *, loss="huber", c=None, scale="mad", max_iter=50, 
         raise ValueError("fit_robust: max_iter must be an integer >= 1, got %r" % (max_iter,))
     if isinstance(tol, (bool, str)) or not isinstance(tol, (int, float, np.integer, np.floating)) or not np.isfinite(tol) or tol < 0:
         raise ValueError("fit_robust: tol must be a finite number >= 0, got %r" % (tol,))
-    if rescue and alg is not Opt:
-        raise ValueError("fit_robust: rescue= is an option of Opt (the enumeration), not of %s" % alg.__name__)
-    if on_ill_conditioned not in ("warn", "raise"):
-        raise ValueError('on_ill_conditioned must be "warn" or "raise"')
-    eta_v = _eta(η, eta)
-    eps_v = 1e-6 if (ϵ is None and eps is None) else float(ϵ if ϵ is not None else eps)
-    Xf, yf, Pf = _fit_inputs(X, y, P, f32=True)
-    N, M = Xf.shape
-    K = Pf.shape[1]
-    flags = L.OPT_FAITHFUL_INTERCEPT
-    if alg is Opt:
-        flags = (L.OPT_FAITHFUL_INTERCEPT if faithful_intercept else 0) | (L.OPT_GENERIC_KERNEL if generic_kernel else 0) | (L.OPT_RESCUE_CAPPED if rescue else 0)
-    if alg is Alt:
-        if np.ndim(alpha0) == 2 or np.ndim(beta0) == 2:
-            raise ValueError("fit_robust: several starting points (restarts) are not supported together with a robust loss")
-        if alpha0 is None or beta0 is None:
-            alpha0, beta0 = _draw_start(_generator(rng), M, K)
-        a0 = np.ascontiguousarray(alpha0, dtype=np.float64)
-        b0 = np.ascontiguousarray(beta0, dtype=np.float64)
-        if a0.shape != (M + 1,) or b0.shape != (K + 1,):
-            raise ValueError("alpha0 must have M+1 and beta0 K+1 entries")
-    ctx = default_context(device)
-    ctx.last_ill = False
-    Pout = np.array(Pf, dtype=np.int64, order="C")
-
-    def staged():
-        """the staged call of alg on the prepared problem -> (alpha, beta, t, the Report fields of this fit)"""
-        if alg is Opt:
-            _, bpat, _, unconv = ctx.opt_sweep(0, -1)
-            if unconv:
-                raise PartlsError(L.ERR_NOT_CONVERGED, f"{unconv} subproblems hit the pivot cap")
-            a, b, t, opt, bi = ctx.opt_finish(bpat)
-            kw = dict(opt=opt, best_index=bi)
-            if rescue:
-                kw.update(rescued=ctx.rescue_stats().rescued)
-            return a, b, t, kw
-        if alg is Alt:
-            a, b, t, o, it = ctx.alt_prepared(a0, b0, eps_v, int(T))
-            return a, b, t, dict(opt=o, iters=it)
-        a, b, t, o, no = ctx.bnb_prepared()
-        return a, b, t, dict(opt=o, nopen=no)
-
+    ctx, Xf, yf, Pf, eta_v, flags, staged, Pout = _irls_problem(
+        "fit_robust", "a robust loss", alg, X, y, P, η, eta, ϵ, eps, T, rng, alpha0, beta0, faithful_intercept, generic_kernel, rescue,
+        device, on_ill_conditioned)
+    N = Xf.shape[0]
     rho_sums, max_dws, scales = [], [], []
     w_last = np.ones(N)                                       # the library writes the weights of every call that forms some into it
     iterations, converged, exact = 0, False, False
@@ -1628,17 +1736,123 @@ def fit_robust(alg, X, y, P, *, loss="huber", c=None, scale="mad", max_iter=50, 
             ctx.opt_reweight()
             a, b, t, kw = staged()
             iterations += 1
-        if ctx.last_ill:
-            warnings.warn("partitionedls: the model's KKT conditions do not hold in data space (X is too ill-conditioned for the fp64 "
-                          "Gram form); the returned model is the best Gram-form one — " + L.lib().partls_last_error().decode(),
-                          IllConditionedWarning, stacklevel=2)
-            kw.update(ill_conditioned=True, kkt_violation=ctx.kkt_violation())
+        _irls_ill(ctx, kw)
     if not converged:
         warnings.warn("partitionedls: fit_robust stopped after max_iter = %d re-weighted fits with the weights still moving "
                       "(max |dw| = %.3g > tol = %.3g)" % (int(max_iter), max_dws[-1], tol), RobustConvergenceWarning, stacklevel=2)
     kw["robust"] = Report(loss=loss, c=cv, scale=info["scale"], iterations=iterations, converged=converged, exact=exact, weights=w_last,
                           rho_sum=rho_sums, max_dw=max_dws, scales=scales, n_down=info["n_down"], n_zero=info["n_zero"])
     return PartLSFitResult(a, b, t, Pout), None, Report(**kw)
+
+
+class GLMConvergenceWarning(UserWarning):
+    """fit_glm ran out of iterations (max_iter) before the deviance settled within tol"""
+
+
+GLM_FAMILIES = ("binomial", "poisson")
+
+
+def _glm_family(family, who):
+    """the family code as partls_glm_working takes it; ValueError for anything else"""
+    if not isinstance(family, str) or family not in GLM_FAMILIES:
+        raise ValueError('%s: family must be "binomial" or "poisson", got %r' % (who, family))
+    return L.GLM_BINOMIAL if family == "binomial" else L.GLM_POISSON
+
+
+def _glm_null_deviance(y, family):
+    """the deviance of the intercept-only model (mu = mean(y) under both canonical links), in numpy"""
+    y = np.asarray(y, dtype=np.float64)
+    m = float(np.mean(y))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        xlogy = lambda a: np.where(a == 0.0, 0.0, a * np.log(np.where(a == 0.0, 1.0, a)))
+        if family == "binomial":
+            if m <= 0.0 or m >= 1.0:
+                return 0.0
+            d = (xlogy(y) + xlogy(1.0 - y)) - (y * np.log(m) + (1.0 - y) * np.log1p(-m))
+        else:
+            if m <= 0.0:
+                return 0.0
+            d = (xlogy(y) - y * np.log(m)) - (y - m)
+    return float(2.0 * np.sum(d))
+
+
+def fit_glm(alg, X, y, P, *, family="binomial", max_iter=25, tol=1e-8, η=None, eta=None, ϵ=None, eps=None, T=100, rng=None,
+            alpha0=None, beta0=None, faithful_intercept=False, generic_kernel=False, rescue=False, device=0,
+            on_ill_conditioned="warn", weights=None, restarts=None, top=None, returnAllSolutions=False, devices=None):
+    """fit_glm(Opt|Alt|BnB, X, y, P; family, ...) -> (PartLSFitResult, None, Report): the partitioned model under a logistic
+    (family="binomial", logit link, y in [0, 1]) or Poisson (family="poisson", log link, y >= 0) likelihood, by iteratively reweighted
+    least squares.  X is uploaded once; every iteration swaps the working weights and the working response into the
+    prepared problem on the device (Context.opt_rework), runs the staged fit of alg and forms the next working rows at its model
+    (Context.glm_working).  The loop, exactly:
+      1. prepare as fit_robust does: unweighted, on y (float32 stays float32, sparse stays CSR);
+      2. glm_working(None) -> dev_0 (the start: eta from y alone, as R's glm.fit);
+      3. for j = 1 .. max_iter: opt_rework(); the staged fit of alg (fit_robust's) -> model_j; glm_working(model_j) -> dev_j; stop,
+         converged, when |dev_j - dev_{j-1}| <= tol (|dev_j| + 0.1) (R's rule).
+    The model is on the link scale: predict(model, X) is eta; predict_mean(model, X, family) is the mean.  The linear predictor is
+    clamped to [-30, 30] inside the working rows, so a separable binomial problem ends (report.glm.n_clamped > 0).  IRLS without step
+    control need not be monotone: report.glm.deviance shows every iterate's.
+    Returns the last model; the report carries the last fit's fields (opt, best_index / iters / nopen, ill_conditioned ...) and
+    report.glm = Report(family, iterations, converged, deviance (list: dev_0 .. dev_iterations), null_deviance (the intercept-only
+    model's, in numpy), max_abs_eta, n_clamped (of the last working call), weights[N], working_response[N] (the last rows formed)).
+    Out of iterations: converged = False and a GLMConvergenceWarning.
+    ValueError before any device work: weights=, restarts=, top=, returnAllSolutions= (prior weights are not supported), a bad
+    family, max_iter or tol, a y with NaN / Inf or outside the family's domain; NotImplementedError: devices=."""
+    if alg not in (Opt, Alt, BnB):
+        raise TypeError("fit_glm: first argument must be Opt, Alt or BnB")
+    for name, given in (("weights", weights is not None), ("restarts", restarts is not None), ("top", top is not None),
+                        ("returnAllSolutions", bool(returnAllSolutions))):
+        if given:
+            raise ValueError("fit_glm: %s= is not supported together with a family" % name)
+    if devices is not None:
+        raise NotImplementedError("fit_glm: several devices (devices=) are not supported")
+    _glm_family(family, "fit_glm")
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or int(max_iter) < 1:
+        raise ValueError("fit_glm: max_iter must be an integer >= 1, got %r" % (max_iter,))
+    if isinstance(tol, (bool, str)) or not isinstance(tol, (int, float, np.integer, np.floating)) or not np.isfinite(tol) or tol < 0:
+        raise ValueError("fit_glm: tol must be a finite number >= 0, got %r" % (tol,))
+    yv = np.asarray(y)
+    if yv.ndim == 1 and np.issubdtype(yv.dtype, np.floating) and yv.size:
+        if not np.all(np.isfinite(yv)):
+            raise ValueError("fit_glm: y contains NaN / Inf")
+        if family == "binomial" and (yv.min() < 0 or yv.max() > 1):
+            raise ValueError("fit_glm: the binomial family needs 0 <= y <= 1")
+        if family == "poisson" and yv.min() < 0:
+            raise ValueError("fit_glm: the Poisson family needs y >= 0")
+    ctx, Xf, yf, Pf, eta_v, flags, staged, Pout = _irls_problem(
+        "fit_glm", "a family", alg, X, y, P, η, eta, ϵ, eps, T, rng, alpha0, beta0, faithful_intercept, generic_kernel, rescue, device,
+        on_ill_conditioned)
+    N = Xf.shape[0]
+    w_last, z_last = np.zeros(N), np.zeros(N)                 # the library writes the rows of every working call into them
+    devs = []
+    iterations, converged = 0, False
+    with _tolerating(on_ill_conditioned, ctx):
+        ctx.opt_prepare(Xf, yf, Pf, eta_v, flags)
+        info = ctx._glm_working(None, family, w_last.ctypes.data, z_last.ctypes.data, None)
+        devs.append(info["deviance"])
+        for _ in range(int(max_iter)):
+            ctx.opt_rework()
+            a, b, t, kw = staged()
+            iterations += 1
+            info = ctx._glm_working((a, b, t), family, w_last.ctypes.data, z_last.ctypes.data, None)
+            devs.append(info["deviance"])
+            if abs(devs[-1] - devs[-2]) <= tol * (abs(devs[-1]) + 0.1):
+                converged = True
+                break
+        _irls_ill(ctx, kw)
+    if not converged:
+        warnings.warn("partitionedls: fit_glm stopped after max_iter = %d re-weighted fits with the deviance still moving "
+                      "(|change| = %.3g)" % (int(max_iter), abs(devs[-1] - devs[-2])), GLMConvergenceWarning, stacklevel=2)
+    kw["glm"] = Report(family=family, iterations=iterations, converged=converged, deviance=devs,
+                       null_deviance=_glm_null_deviance(yf, family), max_abs_eta=info["max_abs_eta"], n_clamped=info["n_clamped"],
+                       weights=w_last, working_response=z_last)
+    return PartLSFitResult(a, b, t, Pout), None, Report(**kw)
+
+
+def predict_mean(model, X, family, *, device=0):
+    """predict_mean(model, X, family) -> the mean of a fit_glm model on the rows of X: predict(model, X), then the inverse link of the
+    family on the device, clamp included (partls_glm_mean) — on the training X, the mu of the fit's last working call bit for bit."""
+    _glm_family(family, "predict_mean")
+    return default_context(device).glm_mean(family, predict(model, X, device=device))
 
 
 def cv_folds(N, nfolds=5, shuffle=False, rng=None):

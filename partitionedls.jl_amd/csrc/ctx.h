@@ -168,7 +168,7 @@ struct partls_ctx {
 
     // Reset by forget_problem (prepare.hip), the one reset of ctx_prepare, batch_reset and batch_work_prepare — whatever below is derived
     // from a prepared problem or its last sweep or solve: prepared, peers; near_for, near_pat, cand, export_wg; sweep_vetoes, rescue_*,
-    // coop_state_valid, coop_fallback; tab_valid; order_ready, order_identity, flip_cost, pair_laid; dw, ds, x_f32, storage; last_upload_*; ms[CALIB], ms[OOB]; rb_have.
+    // coop_state_valid, coop_fallback; tab_valid; order_ready, order_identity, flip_cost, pair_laid; dw, ds, x_f32, storage; last_upload_*; ms[CALIB], ms[OOB]; rb_have; gl_y0, gl_have, gl_checked.
     // (Not last_kkt / last_min_loo: partls_get_kkt_violation reports them, for the last model returned, without a prepared problem.)
     // problem
     bool prepared = false;
@@ -314,6 +314,19 @@ struct partls_ctx {
     int64_t csr_seg = 0;
     int csr_S = 1;
     double rb_ms[3] = {0.0, 0.0, 0.0};
+    // partls_glm_working / partls_opt_rework (glm.hip): glEta, the linear predictor of the model; glW, glZ, glMu, the
+    // working weights, working response and mean of the last call; glPart / glHost, the row kernel's per-block partials (and the
+    // validation's error word) and their host copy; glMean, the staging of partls_glm_mean.  gl_y0: the response the problem was
+    // PREPARED with, once a rework has put another one into dy (nullptr: dy is still that response); ownZ: a reworked response the
+    // problem owns.  gl_have: glW / glZ hold the rows of a call since the last prepare; gl_checked: bit f set when that response passed
+    // the domain check of family f.  forget_problem clears the three, partls_opt_rework keeps them.  gl_ms: residual pass / row kernel
+    // of the last partls_glm_working call (partls_get_glm_timing)
+    partls::DevBuf glEta, glW, glZ, glMu, glPart, glMean, ownZ;
+    partls::PinnedDoubles glHost;
+    const double *gl_y0 = nullptr;
+    bool gl_have = false;
+    unsigned gl_checked = 0;
+    double gl_ms[2] = {0.0, 0.0};
 };
 
 // propagate a partls_status that is not PARTLS_OK (the host code's counterpart of PARTLS_HIP_CHECK)
@@ -356,10 +369,12 @@ partls_status adopt_or_upload(partls_ctx *c, const void *X, int64_t N, int64_t M
 // Sample weights w[N] (host, or device when on_device) -> c->dw, c->ds after one weight_prep_kernel pass, or the status of the first
 // failed check: NaN / Inf -> PARTLS_ERR_NONFINITE; a negative weight or a sum that is not > 0 -> PARTLS_ERR_BAD_ARG.
 partls_status prepare_weights(partls_ctx *c, const double *w, int64_t N, int on_device);
-// partls_opt_reweight: the prepared problem of c takes the sample weights w (prepare_weights' rules; never NULL) and
-// its Gram products and tableau are built again — forget_problem, prepare_weights, the storage kind's Gram launch and the ending of
-// every prepare, from the X, y, partition, eta and flags the context holds.  A refusal leaves the context unprepared.
-partls_status ctx_reweight(partls_ctx *c, const double *w, int on_device);
+// partls_opt_rework / partls_opt_reweight: the prepared problem of c takes the sample weights w
+// (prepare_weights' rules; never NULL) and, unless z is NULL, the response z (host: uploaded into ownZ; device: adopted), and its Gram
+// products and tableau are built again — forget_problem, prepare_weights, the storage kind's Gram launch and the ending of every
+// prepare, from the X, partition, eta and flags the context holds.  The records of the robust weights and of the GLM rows (with the
+// response the problem was first prepared with) survive.  A refusal leaves the context unprepared.
+partls_status ctx_rework(partls_ctx *c, const double *w, const double *z, int on_device);
 // The second half of ctx_prepare: from the Gram products in c->G (c->M, K, eta, flags, faithful and the partition already set) to the
 // tableau, the host copies and the tolerance.  partls_cv_opt calls it on a context whose G it filled itself.
 partls_status ctx_prepare_tableau(partls_ctx *c);

@@ -147,6 +147,7 @@ void forget_problem(partls_ctx *c)
     c->last_upload_ms = 0.0; c->last_upload_bytes = 0.0;
     c->ms[PARTLS_T_CALIB] = 0.0; c->ms[PARTLS_T_OOB] = 0.0;
     c->rb_have = false;
+    c->gl_y0 = nullptr; c->gl_have = false; c->gl_checked = 0;
 }
 
 partls_status adopt_or_upload(partls_ctx *c, const void *X, int64_t N, int64_t M, int64_t ldX, const double *y, int x_on_device, size_t esz)
@@ -200,7 +201,7 @@ static partls_status prepare_end(partls_ctx *c)
 }
 
 // The Gram launch of the problem c holds, queued on c->stream (no sync) — one definition per storage kind, shared by the prepare and by
-// ctx_reweight, so that a re-prepare builds exactly what a fresh prepare builds.  Dense (fp64 MFMA): X, y, ds = sqrt(w) -> c->G, timed
+// ctx_rework, so that a re-prepare builds exactly what a fresh prepare builds.  Dense (fp64 MFMA): X, y, ds = sqrt(w) -> c->G, timed
 // as PARTLS_T_GRAM (the launch alone, not the allocations in front of it).
 static partls_status queue_dense_gram(partls_ctx *c)
 {
@@ -360,15 +361,26 @@ partls_status ctx_prepare_csr(partls_ctx *c, const int64_t *indptr, const int32_
     return prepare_end(c);
 }
 
-// ---- partls_opt_reweight: new sample weights for the prepared problem, X untouched
-partls_status ctx_reweight(partls_ctx *c, const double *w, int on_device)
+// ---- partls_opt_rework / partls_opt_reweight: new sample weights and, unless z is NULL, a new response for the
+// prepared problem, X untouched
+partls_status ctx_rework(partls_ctx *c, const double *w, const double *z, int on_device)
 {
     const XStorage storage = c->storage;
-    const bool x_f32 = c->x_f32, had = c->rb_have;
+    const bool x_f32 = c->x_f32, had = c->rb_have, gl_had = c->gl_have;
+    const unsigned gl_checked = c->gl_checked;
+    const double *y0 = c->gl_y0 ? c->gl_y0 : c->dy;       // the response of the prepare, whatever reworks came since
     const int64_t N = c->N;
     forget_problem(c);
     c->storage = storage; c->x_f32 = x_f32;               // the kind of the X the context keeps holding
     PARTLS_HIP_CHECK(hipSetDevice(c->device));
+    if (z) {
+        if (!on_device) {
+            PARTLS_HIP_CHECK(c->ownZ.ensure((size_t)N * sizeof(double)));
+            PARTLS_HIP_CHECK(hipMemcpyAsync(c->ownZ.p, z, (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            z = c->ownZ.as<double>();
+        }
+        c->dy = z;
+    }
     partls_status st = prepare_weights(c, w, N, on_device);
     if (st != PARTLS_OK) return st;
     if (storage == XStorage::csr) {
@@ -378,7 +390,11 @@ partls_status ctx_reweight(partls_ctx *c, const double *w, int on_device)
     } else st = queue_dense_gram(c);
     if (st != PARTLS_OK) return st;
     st = prepare_end(c);
-    if (st == PARTLS_OK) c->rb_have = had;                // the record of the previous robust weights survives a re-prepare
+    if (st == PARTLS_OK) {                                // the records of the robust weights and of the GLM rows survive a re-prepare
+        c->rb_have = had;
+        c->gl_have = gl_had; c->gl_checked = gl_checked;
+        c->gl_y0 = c->dy == y0 ? nullptr : y0;
+    }
     return st;
 }
 

@@ -258,9 +258,9 @@ static partls_status reweight_common(partls_ctx *c, const double *w, int w_on_de
         PARTLS_HIP_CHECK(hipSetDevice(c->device));
         PARTLS_HIP_CHECK(c->ownW.ensure((size_t)c->N * sizeof(double)));
         PARTLS_HIP_CHECK(hipMemcpyAsync(c->ownW.p, c->rbW.p, (size_t)c->N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        return ctx_reweight(c, c->ownW.as<double>(), 1);
+        return ctx_rework(c, c->ownW.as<double>(), nullptr, 1);
     }
-    return ctx_reweight(c, w, w_on_device ? 1 : 0);
+    return ctx_rework(c, w, nullptr, w_on_device ? 1 : 0);
 }
 
 }  // namespace partls

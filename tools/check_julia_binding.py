@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """check_julia_binding.py — static check of the Julia patch in INTEGRATION.md against include/partls.h and the float32 headers
 (include/partls_f32.h, include/partls_f32_more.h) and the sparse, contributions, diagnostics and robust-fit headers (include/partls_csr.h, include/partls_contrib.h, include/partls_diag.h,
-include/partls_robust.h) it includes.
+include/partls_robust.h) and the generalised-linear-fit header (include/partls_glm.h) it includes.
 
 No Julia toolchain exists in this image, so the `ccall`s of the patch cannot be executed here.  What CAN be checked without
 one: every `ccall((:sym, _PARTLS_LIB), Ret, (ArgTypes...), args...)` in the fenced ```julia blocks names a symbol the header
@@ -97,12 +97,13 @@ CSR_HEADER = os.path.join(ROOT, "include", "partls_csr.h")
 CONTRIB_HEADER = os.path.join(ROOT, "include", "partls_contrib.h")
 DIAG_HEADER = os.path.join(ROOT, "include", "partls_diag.h")
 ROBUST_HEADER = os.path.join(ROOT, "include", "partls_robust.h")
+GLM_HEADER = os.path.join(ROOT, "include", "partls_glm.h")
 
 
 def parse_headers():
     """the whole ABI: include/partls.h and the entry points of the headers it includes — float32 (include/partls_f32.h,
     partls_f32_more.h), sparse (include/partls_csr.h), group contributions (include/partls_contrib.h), regression diagnostics
-    (include/partls_diag.h) and robust fits (include/partls_robust.h)"""
+    (include/partls_diag.h), robust fits (include/partls_robust.h) and generalised linear fits (include/partls_glm.h)"""
     protos = parse_header()
     protos.update(parse_header(F32_HEADER))
     protos.update(parse_header(F32_MORE_HEADER))
@@ -110,6 +111,7 @@ def parse_headers():
     protos.update(parse_header(CONTRIB_HEADER))
     protos.update(parse_header(DIAG_HEADER))
     protos.update(parse_header(ROBUST_HEADER))
+    protos.update(parse_header(GLM_HEADER))
     return protos
 
 
