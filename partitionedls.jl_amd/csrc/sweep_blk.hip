@@ -70,6 +70,7 @@ static constexpr int PAIR_PIV_MIN_HI = 0x3f1a36e2;   // ... and the smallest ent
                                                 // d >= 1.00000000055e-4: a scalar compare with a literal, where the double constant costs two VGPRs the
                                                 // compiler keeps live through the whole kernel.  The rounds' dependent-column rule, d <= 1e-11 max(1, cmax^2),
                                                 // needs the whole panel; a twin below the guard is left to the rounds
+static constexpr int PAIR_XCH = 40;             // ... and where, in doubles behind pair_solve's `out`, its 16 doubles of lane exchange lie (16-byte aligned)
 static constexpr int F64_EXP_HI = 0x7ff00000;   // the exponent bits of a double's high word: all set = inf or NaN (whose high word lies ABOVE the guard's)
 
 constexpr int nslots(int T) { return T * (T + 1) / 2; }
@@ -312,49 +313,75 @@ __device__ __forceinline__ int panel_block(double *P, double *Z, double *U, doub
 // Layout, DENSE: the panel holds ALL 16 columns of the pair column KC (sweep_body: the static gather), panel column k = variable 16 KC + k,
 // whose row position is k RS + KC.  Lane = r + 16 h holds row r of the four columns 4 h .. 4 h + 3 of that 16 x 16 block, loaded from
 // fixed addresses.  The steps run over k = 0 .. 15 in ascending order and a wave-uniform bit test of the violator mask `cm` skips every
-// column outside C: exactly |C| steps execute, in the order of the compacted solve.  The pivot column of step k is register k & 3 of
-// quarter k >> 2: four steps written out inside a rolled loop over the quarters keep the register indices static, only the source lane
-// of the shuffles moves.  Rows and columns outside C carry whatever the tableau holds there and are updated along with the rest; an
+// column outside C: exactly |C| steps execute, in the order of the compacted solve.  All 16 steps are written out, so the step, its
+// quarter k >> 2 and its register k & 3 are constants.  The pivot column of step k lies in the 16 lanes of quarter k >> 2: they store it
+// to a 16-double exchange in LDS (one masked ds_write_b64), and every lane reads its own row's entry (ds_read_b64) and the pivot row's
+// entries of its four columns (two broadcast ds_read_b128) from there — the same doubles ten ds_bpermute_b32 carried before.  The exchange
+// lies in U behind `out` (PAIR_XCH: in the first 64 KB, so its offsets are immediates; a field of its own would cost an address register).
+// Every lane does the step's five FMAs; the pivot column (quarter k >> 2) and the pivot row (the four lanes r == k) are then overwritten
+// under EXEC.  Rows and columns outside C carry whatever the tableau holds there and are updated along with the rest; an
 // entry (r, c) with r and c in C only ever takes its factors from rows r and c of a pivot column of C, so none of that reaches C, and the
-// guard tests the steps of C only.  8 VGPRs of matrix per lane: with a whole row per lane (32) the chain kernel of T = 16 spilled.
+// guard tests the steps of C only.  The guard takes no branch: the steps behind a bad pivot execute, on values nobody reads — the solve
+// writes nothing but `out`, and the caller reads nothing of `out` once the flag is set.  8 VGPRs of matrix per lane: with a whole row
+// per lane (32) the chain kernel of T = 16 spilled.
 // basm: the basis flags of the 16 variables (bit k: variable 16 KC + k is basic).
 // out, indexed by k: [0..16) a_k (0 outside C), [16..32) q'_k (meaningful on C), [33] != 0: an entering pivot at or below the guard, or a
-// pivot that is not finite (nothing else of `out` is then meaningful)
+// pivot that is not finite (nothing else of `out` is then meaningful); [PAIR_XCH, PAIR_XCH + 16): the exchange
+// The lanes of ONE wave exchange through LDS: the hardware executes a wave's LDS operations in order, so a store is seen by the loads
+// behind it without a wait; the fences only keep the compiler from moving a lane's load above another lane's store, or the next step's
+// store above this step's loads (they emit no s_waitcnt).  No __syncthreads() here: the barrier invariant above batch_select
+#define PAIR_XCH_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); \
+                             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 template <int CW, int RS, int KC>
 __device__ __forceinline__ void pair_solve(const double *P, unsigned cm, unsigned basm, int lane, int rhspos, double *out STAMP_PARAMS)
 {
+    typedef double d2 __attribute__((ext_vector_type(2)));
     const int r = lane & 15, h = lane >> 4;
     const int pos = r * RS + KC;
     double pv[4];
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) pv[jj] = P[(4 * h + jj) * CW + pos];
     double qc = P[r * CW + rhspos];
-    bool hard = false;
+    // the exchange's two addresses, opaque: one VGPR each through the steps (else the compiler forms them again at every use)
+    int xro = 8 * r, xuo = 32 * h;
+    asm volatile("" : "+v"(xro), "+v"(xuo));
+    double *const xr = reinterpret_cast<double *>(reinterpret_cast<char *>(out + PAIR_XCH) + xro);               // this row's entry of the pivot column
+    const d2 *const xu = reinterpret_cast<const d2 *>(reinterpret_cast<char *>(out + PAIR_XCH) + xuo);           // the pivot row's entries of this lane's four columns
+    // the guard, without a branch: the smallest high word of an entering pivot and the largest exponent field of any pivot, judged once
+    // behind the steps.  The steps behind a bad pivot compute on values nobody reads (`out` is not read once the flag is set)
+    int dlo = 0x7fffffff, dex = 0;
     STAMP(16);
-#pragma unroll 1
-    for (int hq = 0; hq < 4 && !hard; ++hq) {
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int s = 4 * hq + jj;
-            if (hard || !((cm >> s) & 1u)) continue;            // (wave-uniform: a scalar branch)
-            const double d = readlane_f64(pv[jj], 16 * hq + s);
-            const int dh = __double2hiint(d);                   // (wave-uniform: scalar compares)
-            if ((!((basm >> s) & 1u) && !(dh > PAIR_PIV_MIN_HI)) || (dh & F64_EXP_HI) == F64_EXP_HI) { hard = true; continue; }
-            const double inv = rcp_newton(d), ainv = fabs(inv);
-            const double pvs = __shfl(pv[jj], 16 * hq + r);     // this row's entry of the pivot column
-            const double fz = -pvs * inv;
-            const double qs = readlane_f64(qc, s);
-            double u[4];
+    for (int s = 0; s < PAIR_MAXC; ++s) {
+        const int hq = s >> 2, jj = s & 3;
+        if (!((cm >> s) & 1u)) continue;                        // (wave-uniform: a scalar branch)
+        const double d = readlane_f64(pv[jj], 16 * hq + s);
+        const int dh = __double2hiint(d);                       // (wave-uniform: scalar arithmetic)
+        dlo = min(dlo, ((basm >> s) & 1u) ? 0x7fffffff : dh);
+        dex = max(dex, dh & F64_EXP_HI);
+        if (h == hq) *xr = pv[jj];
+        PAIR_XCH_SYNC();
+        const double pvs = *xr;
+        const d2 u01 = xu[0], u23 = xu[1];                      // from the pivot COLUMN (panel_block's NUMERICS)
+        PAIR_XCH_SYNC();
+        const double u[4] = {u01.x, u01.y, u23.x, u23.y};
+        const double inv = rcp_newton(d), ainv = fabs(inv);
+        const double fz = -pvs * inv;
+        const double qs = readlane_f64(qc, s);
 #pragma unroll
-            for (int j2 = 0; j2 < 4; ++j2) u[j2] = __shfl(pv[jj], 16 * hq + 4 * h + j2);     // the pivot row's entry, from the pivot COLUMN (panel_block's NUMERICS)
+        for (int j2 = 0; j2 < 4; ++j2) pv[j2] = fma(fz, u[j2], pv[j2]);
+        qc = fma(fz, qs, qc);
+        // the pivot column and the pivot row, as fix-ups under EXEC (the empty asm keeps the compiler from turning them into selects)
+        if (h == hq) { asm volatile(""); pv[jj] = pvs * ainv; }
+        if (r == s) {
+            asm volatile("");
 #pragma unroll
-            for (int j2 = 0; j2 < 4; ++j2) {
-                const double v = (r == s) ? u[j2] * ainv : fma(fz, u[j2], pv[j2]);
-                pv[j2] = (j2 == jj && h == hq) ? ((r == s) ? -inv : pvs * ainv) : v;     // (... : the pivot column itself)
-            }
-            qc = (r == s) ? qs * ainv : fma(fz, qs, qc);
+            for (int j2 = 0; j2 < 4; ++j2) pv[j2] = u[j2] * ainv;
+            qc = qs * ainv;
+            if (h == hq) pv[jj] = -inv;
         }
     }
+    const bool hard = !(dlo > PAIR_PIV_MIN_HI) || dex == F64_EXP_HI;
     STAMP(17);
     if (lane < PAIR_MAXC) {
         const bool in_c = (cm >> lane) & 1u;
@@ -412,7 +439,8 @@ __device__ __forceinline__ void sweep_body(const SweepParams &p)
     [[maybe_unused]] int *const s_tw = reinterpret_cast<int *>(Dinv);
     [[maybe_unused]] int *const s_cm = s_tw + 8;
     static_assert(PAIR_MAXC == 16, "the pair column is one tile column: 16 variables, one mask bit each");
-    static_assert(2 * (MB + 64) >= 2 * PAIR_MAXC + 2, "pair_solve's `out` (doubles) fits U");
+    static_assert(2 * (MB + 64) >= PAIR_XCH + PAIR_MAXC && PAIR_XCH >= 2 * PAIR_MAXC + 2, "pair_solve's `out` and its exchange (doubles) fit U");
+    static_assert((sizeof(lds_image.Z) + PAIR_XCH * sizeof(double)) % 16 == 0, "the exchange is read 16 bytes at a time");
     static_assert(2 * (MB + 64) >= 9, "s_tw and s_cm (9 ints) fit Dinv (MB + 64 doubles)");
     for (int i = tid; i < 2 * MB * CW; i += THREADS) Pbase[i] = 0.0;                   // padding rows are never gathered
     for (int i = tid; i < MB * CW; i += THREADS) Z[i] = 0.0;
